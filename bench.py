@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s of the W4A16 hot path (the linears of one decode token) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload baseline-named|llama3-8b|llama2-13b]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload baseline-named|llama3-8b|llama2-13b] [--dump-outputs DIR] [--full]
 
 A "step" is one decode token: every W4A16 linear of every transformer block + lm_head (M = 1), issued through the
 C ABI of libtce_hip.so as ONE hipGraph replay (tinychatengine_amd.capi.Plan); weights are synthetic N(0, 0.02^2)
@@ -9,10 +9,15 @@ quantized with the reference's q4_6 recipe, all layers distinct (3.4 GB for the 
 from HBM, not from the 256 MB Infinity Cache) and resident in HBM before the timed region.  N > 1: one process per
 GPU (torch.distributed, backend nccl == RCCL), every linear column-sharded N-way, one all-gather per transformer block.
 
-Prints ONE JSON line (rank 0): metric/value/unit per the driver contract plus
+Prints ONE JSON line (rank 0): metric/value/unit/ms_per_step per the driver contract.  A plain run does only that: set up, warm up,
+time the K steps, write the outputs (--dump-outputs), print the line.  --full adds everything else the benchmark measures:
   "roofline":     the dominant kernel (the grouped gate+up GEMV launch), algorithmic bytes / HIP-event time, vs 8 TB/s
-  "cpu_baseline": the reference's own CPU path (oracle/_ref, built from /root/reference) timed on this host.
+  "cpu_baseline": the reference's own CPU path (oracle/_ref, built by oracle/Makefile) timed on this host, and the parity check
+  "other_configs" & co.: the other workloads, precisions and sizes (--no-extras / --no-cpu-baseline drop parts of it).
 Only the cpu_baseline leg touches oracle/; the measured path never does.
+
+--dump-outputs DIR: after the timed steps, every output buffer of the token as the last step left it (the last block's q/k/v, o, gate,
+up, down and the logits) as DIR/<name>.npy in float32.  Weights and activations are seeded, so the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -32,8 +37,11 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (decode tokens)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the roofline leg, the other workloads / precisions / sizes, the adapter path, "
+                                                         "the CPU baseline and the parity check (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--workload", default="llama3-8b", choices=["baseline-named", "llama3-8b", "llama2-13b", "tiny"],
                     help="the model whose decode token is the headline `value`.  Default: the model the metric names (Llama-3-8B's true shapes, llm/include/model.h:83); "
                          "the shape set BASELINE.json's configs[1] spells (4096x4096, 4096x11008: Llama-2-7B widths) is timed beside it and reported under `baseline_named_shapes` "
@@ -64,7 +72,10 @@ def parse_args():
     ap.add_argument("--cpu-worker", default="", choices=["", "avx", "avx_cold", "ref", "parity"], help=argparse.SUPPRESS)
     ap.add_argument("--threads", type=int, default=8, help=argparse.SUPPRESS)
     ap.add_argument("--parity-dir", default="", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 LINE_BUDGET = 6000  # bytes; the driver keeps the last 8 KB of stdout+stderr (BENCH_r04: a 21.7 KB line came back as parsed = null)
@@ -1001,6 +1012,25 @@ def cpu_baseline_leg(workload: str, shape):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+def dump_outputs(dl, dirname: str, rank: int = 0) -> None:
+    """What the timed step computed, as its last replay left it: the output buffer of every linear (the last block's, the buffers are reused block
+    after block) and the logits, as float32 .npy files (~0.7 MB for the default workload).  N > 1: rank 0's slices, plus the joined rows when the
+    run gathers them."""
+    import numpy as np
+    import torch
+    if rank != 0:
+        return
+    torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    bufs = {f"out_qkv{i}": t for i, t in enumerate(dl.out_qkv)}
+    bufs.update(out_o=dl.out_o, out_gate=dl.out_gate, out_up=dl.out_up, out_down=dl.out_down, logits=dl.logits)
+    if dl.world > 1 and hasattr(dl, "g_logits"):
+        bufs.update({f"gathered_qkv{i}": t for i, t in enumerate(dl.g_qkv)})
+        bufs.update(gathered_o=dl.g_o, gathered_gate=dl.g_gate, gathered_up=dl.g_up, gathered_down=dl.g_down, gathered_logits=dl.g_logits)
+    for name, t in bufs.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     args = parse_args()
     if args.cpu_worker:
@@ -1012,8 +1042,8 @@ def main():
     from tinychatengine_amd.decode import SHAPES, DecodeLinears
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1) and become that job --
-        # rank 0's JSON line is this command's last line of stdout, exactly as under `python -m torch.distributed.run ... bench.py --gpus N`
+        # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1) as a child job and exit
+        # with its status -- rank 0's JSON line is this command's last line of stdout, exactly as under `python -m torch.distributed.run ... bench.py --gpus N`
         import socket
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
@@ -1021,7 +1051,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.abspath(__file__), *sys.argv[1:]]
         print(f"[bench] --gpus {args.gpus} without WORLD_SIZE: starting the ranks: {' '.join(cmd)}", file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.exit(subprocess.call(cmd))
     if args.selftest_emit:
         return selftest_emit(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1369,6 +1400,8 @@ def main():
     llama13 = None
     if dist is None:
         wall, ev_ms_total = timed_run(step)
+        if args.dump_outputs:
+            dump_outputs(dl, args.dump_outputs)
     else:
         # Every way the ranks' slices can be joined, in ONE run (the first session on an 8-GPU node should not have to be repeated four
         # times): {peer-write kernel, RCCL} x {1 gather per block -- the north-star definition --, 4 -- the dependency-faithful form}.
@@ -1381,9 +1414,11 @@ def main():
         args.gathers_per_block, args.gather = gpb_h, gth_h
         n_launches = dl.n_layers * (4 if blk_h == "four" else 1) + 1  # (the gather kernels / collectives are not counted; "fused": there are none but the logits')
         gather_variants["headline"] = name_h
+        if args.dump_outputs:  # (every variant computes the same token; the last one timed left it in the buffers)
+            dump_outputs(dl, args.dump_outputs, rank)
         # BASELINE config 5 (Llama-2-13B column-sharded 8 ways) beside the headline workload when the run has its eight ranks (VERDICT r4 item 7 ii): same
         # variants, same timing; never takes the headline down with it
-        if world == 8 and args.workload != "llama2-13b" and not args.no_extras:
+        if world == 8 and args.workload != "llama2-13b" and args.full and not args.no_extras:
             try:
                 dl13 = DecodeLinears(SHAPES["llama2-13b"], device=dev, group_size=G, rank=rank, world=world, m=1, prepack=prepack)
                 if getattr(dl, "comm", None) is not None:
@@ -1416,12 +1451,14 @@ def main():
                            + [(shape.vocab, shape.hidden)])
     # the dominant kernel in isolation (at N > 1: this rank's row shard of it; purely local, every rank runs it so the ranks
     # stay in step for the teardown)
-    try:
-        roof = roofline_leg(dl, torch, args.roofline_launches, knobs=tuned_knobs)
-        if world > 1:
-            roof["kernel"] += f", rows sharded {world}-way (this rank's shard)"
-    except Exception as e:  # noqa: BLE001 -- never takes the headline number down with it
-        roof = None if world > 1 else {"error": f"{type(e).__name__}: {e}"}
+    roof = None
+    if args.full:
+        try:
+            roof = roofline_leg(dl, torch, args.roofline_launches, knobs=tuned_knobs)
+            if world > 1:
+                roof["kernel"] += f", rows sharded {world}-way (this rank's shard)"
+        except Exception as e:  # noqa: BLE001 -- never takes the headline number down with it
+            roof = None if world > 1 else {"error": f"{type(e).__name__}: {e}"}
     whole = {"achieved_GBs_per_gpu": round(token_bytes_rank / (ev_ms_per_step * 1e-3) / 1e9, 1),
              "frac_of_8TBs": round(token_bytes_rank / (ev_ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
              "algorithmic_bytes_per_token_per_gpu": token_bytes_rank, "launches_per_token": n_launches,
@@ -1429,7 +1466,7 @@ def main():
 
     extras = None
     secondary = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         try:
             extras = other_configs_leg(torch, dev)
         except Exception as e:  # noqa: BLE001 -- never takes the headline number down with it
@@ -1489,7 +1526,7 @@ def main():
                 secondary = {"error": f"{type(e).__name__}: {e}"}
 
     adapter = None
-    if rank == 0 and world == 1 and not args.no_extras and args.workload in ("baseline-named", "llama3-8b", "tiny"):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.workload in ("baseline-named", "llama3-8b", "tiny"):
         torch.cuda.synchronize()
         try:
             adapter = adapter_path_leg(args.workload)
@@ -1498,7 +1535,7 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline_leg(args.workload, shape)
         except Exception as e:  # noqa: BLE001 -- the baseline must never take the GPU number down with it

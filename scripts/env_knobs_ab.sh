@@ -1,7 +1,7 @@
 #!/bin/bash
 # Does any HIP runtime knob move the stream-ordered token (129 launches in one hipGraph)?  Same box, back to back, three runs each.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-run() { for i in 1 2 3; do env "$@" python bench.py --no-extras --no-cpu-baseline --issue graph --steps 200 --warmup 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['roofline']['avg_launch_us'])"; done | tr '\n' ' '; }
+run() { for i in 1 2 3; do env "$@" python bench.py --full --no-extras --no-cpu-baseline --issue graph --steps 200 --warmup 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['roofline']['avg_launch_us'])"; done | tr '\n' ' '; }
 echo "default: $(run X=1)"
 echo "DEBUG_CLR_GRAPH_PACKET_CAPTURE=1: $(run DEBUG_CLR_GRAPH_PACKET_CAPTURE=1)"
 echo "DEBUG_CLR_GRAPH_PACKET_CAPTURE=0: $(run DEBUG_CLR_GRAPH_PACKET_CAPTURE=0)"

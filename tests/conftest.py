@@ -9,6 +9,10 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 GOLDEN = os.path.join(REPO, "tests", "golden", "hotpath_golden.npz")
+REF_VECTORS = os.path.join(REPO, "tests", "golden", "reference_vectors.npz")
+RECORD_ENV = "TCE_RECORD_REFERENCE_VECTORS"
+_ref_store = None
+_ref_recorded = {}
 
 
 def pytest_configure(config):
@@ -39,11 +43,57 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    """The reference's own code (oracle/_ref/libtce_ref.so); skipped where that prebuilt file is absent."""
+    """The reference's own code (oracle/_ref/libtce_ref.so), or None where that build is absent: the tests then take its results from
+    tests/golden/reference_vectors.npz (reference_vectors below)."""
     from oracle import oracle as O
-    if not O.have_ref():
-        pytest.skip("oracle/_ref/libtce_ref.so not built (needs /root/reference at build time)")
-    return O.Reference()
+    return O.Reference() if O.have_ref() else None
+
+
+def _digest(inputs) -> np.ndarray:
+    import hashlib
+    h = hashlib.sha256()
+    for a in inputs:
+        a = np.ascontiguousarray(a)
+        h.update(f"{a.dtype.str}{a.shape}".encode())
+        h.update(a.tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def reference_vectors(key: str, inputs, live, available: bool) -> list:
+    """What the reference's own code (a build under oracle/_ref, made from the reference's sources by oracle/Makefile) returns for `inputs`.
+    available: that build is here -- live() runs it, and its result must equal the stored one (with TCE_RECORD_REFERENCE_VECTORS=1 it is
+    stored anew instead: tests/golden/make_reference_vectors.sh).  Elsewhere (a clean checkout, the GPU box) the stored result is returned,
+    after checking that `inputs` are still the ones it was recorded for.  The store is tests/golden/reference_vectors.npz."""
+    global _ref_store
+    if _ref_store is None:
+        _ref_store = dict(np.load(REF_VECTORS)) if os.path.exists(REF_VECTORS) else {}
+    key = "".join(c if c.isalnum() or c in "_-=" else "_" for c in key)
+    digest = _digest(inputs)
+    stored = key + ".sha256" in _ref_store
+    n = sum(1 for k in _ref_store if k.startswith(key + ".out"))
+    if available:
+        outs = [np.ascontiguousarray(o) for o in live()]
+        if os.environ.get(RECORD_ENV) == "1":
+            _ref_recorded[key + ".sha256"] = digest
+            _ref_recorded.update({f"{key}.out{i}": o for i, o in enumerate(outs)})
+        elif stored:
+            assert np.array_equal(_ref_store[key + ".sha256"], digest) and n == len(outs), f"{key}: inputs differ from the recorded ones (re-record)"
+            for i, o in enumerate(outs):
+                want = _ref_store[f"{key}.out{i}"]
+                assert want.dtype == o.dtype and want.shape == o.shape and want.tobytes() == o.tobytes(), f"{key}: the reference build's output {i} differs from the stored one"
+        return outs
+    assert stored, f"{key}: no stored reference vectors (record them where the reference build exists: tests/golden/make_reference_vectors.sh)"
+    assert np.array_equal(_ref_store[key + ".sha256"], digest), f"{key}: the test's inputs are not the ones its reference vectors were recorded for (re-record)"
+    return [_ref_store[f"{key}.out{i}"] for i in range(n)]
+
+
+def pytest_sessionfinish(session, exitstatus):
+    """TCE_RECORD_REFERENCE_VECTORS=1: merge what reference_vectors() recorded into tests/golden/reference_vectors.npz."""
+    if not _ref_recorded:
+        return
+    store = dict(np.load(REF_VECTORS)) if os.path.exists(REF_VECTORS) else {}
+    store.update(_ref_recorded)
+    np.savez_compressed(REF_VECTORS, **dict(sorted(store.items())))
 
 
 @pytest.fixture(scope="session")

@@ -117,3 +117,11 @@ def test_bench_gpus_n_starts_its_own_ranks():
     assert "needs torch.distributed.run" not in err
     assert err.count("bench.py needs an MI355X") >= 1, err[-2000:]  # the ranks ran bench.py's main() (both print it; the launcher may cut the second short)
     assert r.returncode != 0  # and the job fails loudly: no CPU fallback
+
+
+def test_plain_run_options():
+    """--full (everything beyond the headline) and --dump-outputs DIR are options of every run; --steps sets the timed steps and must be >= 1."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr

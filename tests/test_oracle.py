@@ -1,7 +1,14 @@
 """CPU: pin oracle/tce_oracle.c (the restatement) against (a) the committed golden vectors, which were produced by the
-reference's own code (tests/golden/make_golden.py), and (b) the reference build itself when oracle/_ref is present."""
+reference's own code (tests/golden/make_golden.py), and (b) the reference build itself: live where oracle/_ref is present, its
+stored results elsewhere (tests/golden/reference_vectors.npz, conftest.reference_vectors)."""
 import numpy as np
 import pytest
+from conftest import reference_vectors
+
+
+def _ref(reference, key, inputs, call):
+    """call(reference) on the reference build -- run live where oracle/_ref is built, its recorded result for `inputs` elsewhere."""
+    return reference_vectors(key, inputs, lambda: [call(reference)], reference is not None)[0]
 
 
 def _seq(codes):
@@ -78,7 +85,7 @@ def test_f16_conversions_match_numpy(oracle):
         assert oracle.lib.orc_f16_to_f32(bits) == float(np.uint16(bits).view(np.float16))
 
 
-# ---------------- live cross-check against the reference build (when present) ----------------
+# ---------------- cross-check against the reference build (live when present, its stored results elsewhere) ----------------
 @pytest.mark.parametrize("M,N,K,G", [(1, 64, 512, 128), (3, 40, 256, 32), (2, 24, 384, 64), (1, 16, 1408, 128)])
 def test_w4_against_reference_build(oracle, reference, M, N, K, G):
     rng = np.random.default_rng(M * 1000 + N + K + G)
@@ -87,17 +94,20 @@ def test_w4_against_reference_build(oracle, reference, M, N, K, G):
     a = rng.standard_normal((M, K)).astype(np.float16)
     s32 = sc[:, : K // G].astype(np.float32)
     a32 = a.astype(np.float32)
+    key = f"w4_{M}_{N}_{K}_{G}"
     assert np.array_equal(oracle.naive_mat_mul_int4(a32, _seq(codes), s32, 8.0, M, N, K, G),
-                          reference.naive_mat_mul_int4(a32, _seq(codes), s32, 8.0, M, N, K, G))
+                          _ref(reference, key + "_naive", [a32, _seq(codes), s32], lambda r: r.naive_mat_mul_int4(a32, _seq(codes), s32, 8.0, M, N, K, G)))
     off = (rng.standard_normal(s32.shape) * 0.01).astype(np.float32)
     assert np.array_equal(oracle.naive_mat_mul_int4_with_offset(a32, _seq(codes), s32, off, 8.0, M, N, K, G),
-                          reference.naive_mat_mul_int4_with_offset(a32, _seq(codes), s32, off, 8.0, M, N, K, G))
+                          _ref(reference, key + "_offset", [a32, _seq(codes), s32, off],
+                               lambda r: r.naive_mat_mul_int4_with_offset(a32, _seq(codes), s32, off, 8.0, M, N, K, G)))
     if G == 32:
-        assert np.array_equal(oracle.ref_int4_fast(a32, _seq(codes), s32, off, M, N, K), reference.ref_int4_fast(a32, _seq(codes), s32, off, M, N, K))
+        assert np.array_equal(oracle.ref_int4_fast(a32, _seq(codes), s32, off, M, N, K),
+                              _ref(reference, key + "_fast", [a32, _seq(codes), s32, off], lambda r: r.ref_int4_fast(a32, _seq(codes), s32, off, M, N, K)))
     if N % 8 == 0:
         q5, s5, _ = oracle.pack_q4_5(codes, d, N, K, G)
         assert np.array_equal(oracle.naive_mat_mul_fp16_int4(a, q5, s5, M, N, K, G).view(np.uint16),
-                              reference.naive_mat_mul_fp16_int4(a, q5, s5, M, N, K, G).view(np.uint16))
+                              _ref(reference, key + "_fp16", [a, q5, s5], lambda r: r.naive_mat_mul_fp16_int4(a, q5, s5, M, N, K, G)).view(np.uint16))
 
 
 @pytest.mark.parametrize("M,N,K", [(1, 32, 64), (17, 48, 96), (5, 8, 33)])
@@ -109,13 +119,21 @@ def test_int8_against_reference_build(oracle, reference, M, N, K):
     b8 = rng.integers(-128, 128, N, dtype=np.int8)
     bf = rng.standard_normal(N).astype(np.float32)
     for al, be in [(0.0005035400390625, 0.02130126953125), (0.0071, 0.13), (1.0, 1.0)]:
+        key = f"i8_{M}_{N}_{K}_{al}_{be}"
+        sc = np.array([al, be], np.float64)
         for qmin in (-128, 0):
-            assert np.array_equal(oracle.int8_matmul_bias_i8(A, B, b8, al, be, qmin, 127, M, N, K), reference.int8_matmul_bias_i8(A, B, b8, al, be, qmin, 127, M, N, K))
-            assert np.array_equal(oracle.int8_matmul_nobias_i8(A, B, al, qmin, 127, M, N, K), reference.int8_matmul_nobias_i8(A, B, al, qmin, 127, M, N, K))
-        assert np.array_equal(oracle.int8_matmul_nobias_i8(A, Bb, al, -128, 127, M, N, K, batch=True), reference.int8_matmul_nobias_i8(A, Bb, al, -128, 127, M, N, K, batch=True))
-        assert np.array_equal(oracle.int8_matmul_bias_f32(A, B, bf, al, M, N, K), reference.int8_matmul_bias_f32(A, B, bf, al, M, N, K))
-        assert np.array_equal(oracle.int8_matmul_nobias_f32(A, B, al, M, N, K), reference.int8_matmul_nobias_f32(A, B, al, M, N, K))
-        assert np.array_equal(oracle.int8_matmul_nobias_f32(A, Bb, al, M, N, K, batch=True), reference.int8_matmul_nobias_f32(A, Bb, al, M, N, K, batch=True))
+            assert np.array_equal(oracle.int8_matmul_bias_i8(A, B, b8, al, be, qmin, 127, M, N, K),
+                                  _ref(reference, f"{key}_bias_i8_{qmin}", [A, B, b8, sc], lambda r: r.int8_matmul_bias_i8(A, B, b8, al, be, qmin, 127, M, N, K)))
+            assert np.array_equal(oracle.int8_matmul_nobias_i8(A, B, al, qmin, 127, M, N, K),
+                                  _ref(reference, f"{key}_nobias_i8_{qmin}", [A, B, sc], lambda r: r.int8_matmul_nobias_i8(A, B, al, qmin, 127, M, N, K)))
+        assert np.array_equal(oracle.int8_matmul_nobias_i8(A, Bb, al, -128, 127, M, N, K, batch=True),
+                              _ref(reference, f"{key}_nobias_batch_i8", [A, Bb, sc], lambda r: r.int8_matmul_nobias_i8(A, Bb, al, -128, 127, M, N, K, batch=True)))
+        assert np.array_equal(oracle.int8_matmul_bias_f32(A, B, bf, al, M, N, K),
+                              _ref(reference, f"{key}_bias_f32", [A, B, bf, sc], lambda r: r.int8_matmul_bias_f32(A, B, bf, al, M, N, K)))
+        assert np.array_equal(oracle.int8_matmul_nobias_f32(A, B, al, M, N, K),
+                              _ref(reference, f"{key}_nobias_f32", [A, B, sc], lambda r: r.int8_matmul_nobias_f32(A, B, al, M, N, K)))
+        assert np.array_equal(oracle.int8_matmul_nobias_f32(A, Bb, al, M, N, K, batch=True),
+                              _ref(reference, f"{key}_nobias_batch_f32", [A, Bb, sc], lambda r: r.int8_matmul_nobias_f32(A, Bb, al, M, N, K, batch=True)))
 
 
 def test_config1_reference_shape_runs_on_cpu(oracle, reference):
@@ -125,7 +143,8 @@ def test_config1_reference_shape_runs_on_cpu(oracle, reference):
     w = (rng.standard_normal((N, K)) * 0.02).astype(np.float32)
     qw, sc, zp, codes, d = oracle.quantize_q4_6(w, 128)
     a = rng.standard_normal((1, K)).astype(np.float16)
-    ref = reference.naive_mat_mul_int4(a.astype(np.float32), _seq(codes), sc[:, :32].astype(np.float32), 8.0, 1, N, K, 128)
+    s32 = sc[:, :32].astype(np.float32)
+    ref = _ref(reference, "config1_4096", [a, _seq(codes), s32], lambda r: r.naive_mat_mul_int4(a.astype(np.float32), _seq(codes), s32, 8.0, 1, N, K, 128))
     c32, _ = oracle.w4a16_gemv_q4_6(a, qw, sc, zp, 1, N, K, 128)
     assert np.array_equal(c32, ref)
 
@@ -141,9 +160,6 @@ def test_x86_interleave_branch_and_avx_baseline_sanity(oracle):
     import ctypes as C
     import os
     from oracle import oracle as O
-    if not os.path.exists(O.REF_X86NAIVE_SO):
-        pytest.skip("oracle/_ref/libtce_ref_x86naive.so not built")
-    ref = C.CDLL(O.REF_X86NAIVE_SO)
     rng = np.random.default_rng(7)
     M, N, K = 2, 48, 512
     w = (rng.standard_normal((N, K)) * 0.02).astype(np.float32)
@@ -151,13 +167,13 @@ def test_x86_interleave_branch_and_avx_baseline_sanity(oracle):
     B = O.ReferenceAVX.pack_q4_3(codes)
     A = rng.standard_normal((M, K)).astype(np.float32)
     mine = O.naive_mat_mul_int4_x86(oracle.lib, "orc_", A, B, d, M, N, K)
-    theirs = O.naive_mat_mul_int4_x86(ref, "ref_", A, B, d, M, N, K)
+    (theirs,) = reference_vectors("x86naive", [A, B, d], lambda: [O.naive_mat_mul_int4_x86(C.CDLL(O.REF_X86NAIVE_SO), "ref_", A, B, d, M, N, K)],
+                                  os.path.exists(O.REF_X86NAIVE_SO))
     assert np.array_equal(mine, theirs)
     generic = oracle.naive_mat_mul_int4(A, oracle.pack_sequential(codes, N, K), d.reshape(N, -1), 8.0, M, N, K, 32)
     assert np.abs(mine - generic).max() < 1e-5  # same math, different summation order
-    if O.have_ref_avx():
-        avx = O.ReferenceAVX(num_thread=4).w4a8(A[:1], B, d.reshape(N, -1), 1, N, K)
-        assert float(np.mean((avx - mine[:1]) ** 2)) <= 7e-4
+    (avx,) = reference_vectors("avx_w4a8", [A[:1], B, d], lambda: [O.ReferenceAVX(num_thread=4).w4a8(A[:1], B, d.reshape(N, -1), 1, N, K)], O.have_ref_avx())
+    assert float(np.mean((avx - mine[:1]) ** 2)) <= 7e-4
 
 
 @pytest.mark.parametrize("isa,G", [("arm", 32), ("arm", 128), ("metal", 32), ("metal", 128)])
@@ -170,16 +186,14 @@ def test_arm_and_metal_nibble_orders_restated_and_pinned(oracle, isa, G):
     import os
     from oracle import oracle as O
     path = O.REF_ARMNAIVE_SO if isa == "arm" else O.REF_METALNAIVE_SO
-    if not os.path.exists(path):
-        pytest.skip(f"{os.path.basename(path)} not built")
-    ref = C.CDLL(path)
     rng = np.random.default_rng(17 + G)
     M, N, K = 3, 40, 512
     B = rng.integers(0, 256, (N, K // 2), dtype=np.uint8)
     d = (rng.random((N, K // G)).astype(np.float32) * 0.02 + 0.001)
     A = rng.standard_normal((M, K)).astype(np.float32)
     mine = O.naive_mat_mul_int4_isa(oracle.lib, "orc_", isa, A, B, d, M, N, K, G)
-    theirs = O.naive_mat_mul_int4_isa(ref, "ref_", isa, A, B, d, M, N, K, G)
+    (theirs,) = reference_vectors(f"{isa}naive_{G}", [A, B, d], lambda: [O.naive_mat_mul_int4_isa(C.CDLL(path), "ref_", isa, A, B, d, M, N, K, G)],
+                                  os.path.exists(path))
     assert np.array_equal(mine, theirs)
     if isa == "metal" or G == 32:  # the layouts as orders of codes along k (ARM with G > 32 overlaps its runs: not a permutation)
         lo, hi = (B & 0x0F).astype(np.int64), (B >> 4).astype(np.int64)

@@ -9,20 +9,31 @@ oracle/_ref/glue_harness, and this file compares orc_* with what they compute, b
 and order of operations; hexp is the same model on both sides (C library expf rounded to binary16), as tce_oracle.c says.
 generalT5LayerNorm (LlamaRMSNorm.cu:68-115) DOES use warp shuffles, a shared variable and __syncthreads: for it the emulation runs the
 threads of a block as concurrent OS threads (tce_emul::launch_concurrent: pthread barriers for __syncthreads and for each warp's
-shuffle), and orc_rmsnorm_half -- the hand-restated reduction tree -- is compared with it as well.  rsqrtf is 1 / sqrtf on both sides."""
+shuffle), and orc_rmsnorm_half -- the hand-restated reduction tree -- is compared with it as well.  rsqrtf is 1 / sqrtf on both sides.
+Where oracle/_ref/glue_harness is not built (a clean checkout, the GPU box) its results come from tests/golden/reference_vectors.npz, recorded
+from the same harness on the same inputs (conftest.reference_vectors)."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
+from conftest import reference_vectors
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HARNESS = os.path.join(REPO, "oracle", "_ref", "glue_harness")
 
-needs_harness = pytest.mark.skipif(not os.path.exists(HARNESS), reason="oracle/_ref/glue_harness not built (needs /root/reference at build time)")
+
+def _harness(key, inputs, live):
+    """live() runs glue_harness where it is built; elsewhere the outputs it recorded for these inputs."""
+    return reference_vectors("glue_" + key, inputs, live, os.path.exists(HARNESS))
 
 
 def _run(tmp_path, op, ints, inputs, n_out):
+    return _harness("_".join([op, *map(str, ints)]), [np.array(ints, np.int64), *[np.asarray(a, np.float16) for a in inputs]],
+                    lambda: _run_live(tmp_path, op, ints, inputs, n_out))
+
+
+def _run_live(tmp_path, op, ints, inputs, n_out):
     paths = []
     for i, a in enumerate(inputs):
         p = tmp_path / f"in{i}.bin"
@@ -42,7 +53,6 @@ def _halves(rng, shape, scale=1.0):
     return (rng.standard_normal(shape) * scale).astype(np.float16)
 
 
-@needs_harness
 @pytest.mark.parametrize("n", [1, 1023, 4096, 11008 + 5])
 def test_add_half_and_silu_mul_against_the_reference_kernels(tmp_path, oracle, n):
     rng = np.random.default_rng(n)
@@ -54,7 +64,6 @@ def test_add_half_and_silu_mul_against_the_reference_kernels(tmp_path, oracle, n
     assert np.array_equal(_bits(ref), _bits(oracle.silu_mul_half(a, b)))
 
 
-@needs_harness
 @pytest.mark.parametrize("x,y,z", [(32, 1, 129), (3, 5, 64), (2, 17, 1), (1, 1, 2048)])
 def test_softmax_against_the_reference_kernel(tmp_path, oracle, x, y, z):
     rng = np.random.default_rng(x * 100 + y * 10 + z)
@@ -64,7 +73,6 @@ def test_softmax_against_the_reference_kernel(tmp_path, oracle, x, y, z):
     assert np.array_equal(_bits(ref), _bits(oracle.softmax_half(s)).ravel())
 
 
-@needs_harness
 @pytest.mark.parametrize("batch,m,n,k", [(32, 1, 200, 128), (4, 7, 33, 64), (2, 3, 5, 300), (32, 1, 128, 257)])
 def test_bmm_f16t_against_the_reference_operator(tmp_path, oracle, batch, m, n, k):
     rng = np.random.default_rng(batch + m + n + k)
@@ -75,7 +83,6 @@ def test_bmm_f16t_against_the_reference_operator(tmp_path, oracle, batch, m, n, 
     assert np.array_equal(_bits(ref), _bits(oracle.bmm_f16t(a, w, alpha)).ravel())
 
 
-@needs_harness
 @pytest.mark.parametrize("heads,ln,hd,start", [(32, 1, 128, 77), (4, 9, 128, 0), (2, 3, 64, 5)])
 def test_rope_against_the_reference_kernel(tmp_path, oracle, heads, ln, hd, start):
     rng = np.random.default_rng(heads + ln + hd + start)
@@ -87,7 +94,6 @@ def test_rope_against_the_reference_kernel(tmp_path, oracle, heads, ln, hd, star
     assert np.array_equal(_bits(rq), _bits(oq).ravel()) and np.array_equal(_bits(rk), _bits(ok).ravel())
 
 
-@needs_harness
 @pytest.mark.parametrize("m,n", [(1, 4096), (3, 1024), (2, 520), (1, 11008), (2, 64)])
 def test_rmsnorm_against_the_reference_kernel(tmp_path, oracle, m, n):
     """LlamaRMSNorm_cuda::forward with its own grid / block (min(n, 1024) / 2 threads; 512 when n % 32 != 0): thread-strided partial sums,
@@ -102,13 +108,15 @@ def test_rmsnorm_against_the_reference_kernel(tmp_path, oracle, m, n):
     xin = tmp_path / "x.bin"
     x.tofile(xin)
     out = tmp_path / "out.bin"
-    r = subprocess.run([HARNESS, "rmsnorm", str(m), str(n), repr(eps), str(xin), str(gpath), str(out)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    ref = np.fromfile(out, np.float16)
+
+    def live():
+        r = subprocess.run([HARNESS, "rmsnorm", str(m), str(n), repr(eps), str(xin), str(gpath), str(out)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        return [np.fromfile(out, np.float16)]
+    (ref,) = _harness(f"rmsnorm_{m}_{n}", [x, gamma, np.array([eps])], live)
     assert np.array_equal(_bits(ref), _bits(oracle.rmsnorm_half(x, gamma, eps)).ravel())
 
 
-@needs_harness
 @pytest.mark.parametrize("m,n", [(1, 768), (5, 768), (2, 2048), (3, 100)])
 def test_layernorm_q_against_the_reference_source(tmp_path, oracle, m, n):
     """LayerNormQ::forward (llm/src/ops/LayerNormQ.cc:12-52) is host C++ in the reference: compiled as it is (-ffp-contract=off) and
@@ -123,13 +131,15 @@ def test_layernorm_q_against_the_reference_source(tmp_path, oracle, m, n):
         a.tofile(p)
         paths.append(str(p))
     out = tmp_path / "out.bin"
-    r = subprocess.run([HARNESS, "lnq", str(m), str(n), *paths, str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    ref = np.fromfile(out, np.int8).reshape(m, n)
+
+    def live():
+        r = subprocess.run([HARNESS, "lnq", str(m), str(n), *paths, str(out)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        return [np.fromfile(out, np.int8).reshape(m, n)]
+    (ref,) = _harness(f"lnq_{m}_{n}", [x, w, b], live)
     assert np.array_equal(ref, oracle.layernorm_q(x, w, b).reshape(m, n))
 
 
-@needs_harness
 @pytest.mark.parametrize("heads,sq,tgz", [(12, 1, 513), (3, 5, 40), (12, 64, 64), (2, 7, 1)])
 def test_opt_softmax_q_against_the_reference_sources(tmp_path, oracle, heads, sq, tgz):
     """batch_Add (llm/src/ops/batch_add.cc) and softmax (llm/src/ops/softmax.cc) are host C++ in the reference: compiled as they are, followed by
@@ -143,9 +153,12 @@ def test_opt_softmax_q_against_the_reference_sources(tmp_path, oracle, heads, sq
         mask[:, rng.integers(0, tgz, size=max(1, tgz // 5))] = np.finfo(np.float32).min
     sp, mp, out = tmp_path / "s.bin", tmp_path / "m.bin", tmp_path / "o.bin"
     scores.tofile(sp); mask.tofile(mp)
-    r = subprocess.run([HARNESS, "optsm", str(heads), str(sq), str(tgz), str(sp), str(mp), str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    ref = np.fromfile(out, np.int8).reshape(heads, sq, tgz)
+
+    def live():
+        r = subprocess.run([HARNESS, "optsm", str(heads), str(sq), str(tgz), str(sp), str(mp), str(out)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        return [np.fromfile(out, np.int8).reshape(heads, sq, tgz)]
+    (ref,) = _harness(f"optsm_{heads}_{sq}_{tgz}", [scores, mask], live)
     assert np.array_equal(ref, oracle.opt_softmax_q(scores, mask))
 
 
@@ -177,7 +190,6 @@ def _same_to_a_half_step(out_f16, ref32):
     assert int((d != 0).sum()) <= max(2, int(0.02 * d.size)), (int((d != 0).sum()), d.size)
 
 
-@needs_harness
 @pytest.mark.parametrize("M,N,K", [(1, 64, 1024), (2, 128, 4096), (1, 32, 11008), (3, 16, 256)])
 def test_reference_cuda_gemv_kernel_against_the_w4a16_oracle(tmp_path, oracle, M, N, K):
     """THE hot-path kernel of the reference -- gemv_forward_cuda -> gemv_kernel_g128, kernels/cuda/gemv_cuda.cu:140-260 -- from its own
@@ -185,7 +197,7 @@ def test_reference_cuda_gemv_kernel_against_the_w4a16_oracle(tmp_path, oracle, M
     fp32 (in different orders) and round to fp16 once, so the outputs agree to one binary16 step, and nearly all are identical."""
     mod, _ = _golden()
     a, qw, sc, zp = mod.gemv_case(oracle, M, N, K, seed=M * 1000 + N + K)
-    out = mod.run_reference_kernel(a, qw, sc, zp, M, N, K)
+    (out,) = _harness(f"cuda_gemv_{M}_{N}_{K}", [a, qw, sc, zp], lambda: [mod.run_reference_kernel(a, qw, sc, zp, M, N, K)])
     ref32, _ = oracle.w4a16_gemv_q4_6(a, qw, sc, zp, M, N, K, 128)
     _same_to_a_half_step(out, ref32)
 
