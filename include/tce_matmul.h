@@ -47,7 +47,7 @@ extern "C" {
 
 #define TCE_API __attribute__((visibility("default")))
 
-#define TCE_VERSION 113 /* 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
+#define TCE_VERSION 113 /* additive, unversioned: tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
 
 /* error codes (return values) */
 #define TCE_OK 0
@@ -218,6 +218,25 @@ TCE_API int tce_attention_decode_describe_gqa(int heads, int kv_heads, int keys,
 TCE_API int tce_attention_decode_step_pos_f16(const void *qkv, void *k_cache, void *v_cache, const void *cos_table, const void *sin_table, const void *mask,
                                               void *out, void *workspace, int heads, int kv_heads, int head_dim, int max_keys, const int32_t *pos_device,
                                               int pos_bound, unsigned short alpha_half_bits, void *stream);
+/* The same step for `batch` independent sequences in ONE launch (grid: query heads x chunk slots, batch).  Sequence b has
+ *   qkv        fp16 [batch][heads + 2 * kv_heads][head_dim]: row b is sequence b's fused projection row (what tce_w4a16_forward writes for M = batch)
+ *   k_cache, v_cache  fp16 [batch][kv_heads][max_keys][head_dim]: slot b is exactly a single-sequence cache
+ *   out        fp16 [batch][heads][head_dim]: row b is o_proj's input row b
+ *   pos_device int32 [batch], device memory: sequence b's position, read by the kernel (a captured launch is replayable token after token)
+ *   workspace  tce_attention_decode_batch_workspace_bytes(batch, heads, max_keys, head_dim) bytes -- `batch` single-step workspaces back to back --, zeroed once
+ * The RoPE tables (both or neither; row pos_device[b] for sequence b) and alpha are shared.  The cut is the fitted rule of the single step for pos_bound + 1 keys,
+ * one query head per workgroup, whatever the calling thread's attention tuning settings: every active row's `out` and appended cache rows are BIT-IDENTICAL to
+ * tce_attention_decode_step_pos_f16 on slot b with pos_device + b and the same pos_bound.  A row whose position is < 0 or > pos_bound is inactive: its `out` row is
+ * written with zeros (o_proj then adds exactly 0 to its residual) and its caches and workspace slice are not touched -- a fixed-batch captured graph is a slot pool,
+ * and a finished sequence is retired by writing -1.  No mask.  head_dim == 128, batch <= 65535, pointers 16-byte aligned.  New; the reference decodes one sequence.
+ * tce_attention_decode_batch_workspace_bytes returns 0 for an unsupported shape (head_dim != 128, batch <= 0).  tce_attention_decode_describe_batch is
+ * tce_attention_decode_describe_gqa(heads, kv_heads, pos_bound + 1) for the untuned rule with " batch=B" appended and workgroups B times the single step's; it makes no
+ * HIP call. */
+TCE_API size_t tce_attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int head_dim);
+TCE_API int tce_attention_decode_describe_batch(int batch, int heads, int kv_heads, int pos_bound, char *buf, int buf_len);
+TCE_API int tce_attention_decode_step_batch_f16(const void *qkv, void *k_cache, void *v_cache, const void *cos_table, const void *sin_table,
+                                                void *out, void *workspace, int batch, int heads, int kv_heads, int head_dim, int max_keys,
+                                                const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, void *stream);
 
 /* Round 5: the attention step WITHOUT its cross-workgroup combine, and the linear that consumes it (o_proj) doing the combine in its prologue.
  * A decode step over more than ~320 keys cuts every head's keys into 4 or 8 chunks; each chunk's workgroup ends with a partial online-softmax state (M, L, O[128]) and

@@ -1,0 +1,144 @@
+"""Batched decode: B independent sequences per decoder-block step, each at its own position.
+
+The linears already take a batch (tce_w4a16_forward streams the weights once for M rows); the attention step between q/k/v and o_proj is
+tce_attention_decode_step_batch_f16: ONE launch for B sequences, each with its own position word, cache slot, q/k/v and output rows and workspace
+slice.  Every active row computes, bit for bit, what tce_attention_decode_step_pos_f16 computes for that sequence alone with the same bound; a row
+whose position word is < 0 or > pos_bound is inactive (zero output row, caches and counters untouched), so a fixed-B captured graph is a slot pool
+in which a finished sequence is retired by writing -1.
+
+A layer is SEVEN launches for the B rows:
+
+    1  input_layernorm                           tce_rmsnorm_half over B rows (the fused RMSNorm prologue is an M = 1 form)
+    2  q/k/v projection                          tce_w4a16_forward, M = B
+    3  RoPE + KV append + attention              tce_attention_decode_step_batch_f16
+    4  o_proj + residual add                     tce_w4a16_forward, M = B, TCE_W4_ADD_TO_C (an inactive row adds exactly 0)
+    5  post_attention_layernorm                  tce_rmsnorm_half
+    6  gate/up + SiLU*mul                        tce_w4a16_forward, M = B, TCE_W4_SILU_MUL_PAIRS (gate, up and tce_silu_mul_half where the pairs are refused)
+    7  down_proj + residual add                  tce_w4a16_forward, M = B, TCE_W4_ADD_TO_C
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import capi
+from .attention_ops import DecodeAttention
+from .decoder_block import DecoderBlock
+from .linear import _stream, rmsnorm_half
+
+
+class _SlotAttention(DecodeAttention):
+    """DecodeAttention over one slot of a BatchDecodeAttention: the slot's caches and workspace slice (views, no copies)."""
+
+    def __init__(self, parent: "BatchDecodeAttention", b: int):  # (no DecodeAttention.__init__: it would allocate caches of its own)
+        self.heads, self.hd, self.max_keys, self.kv_heads = parent.heads, parent.hd, parent.max_keys, parent.kv_heads
+        self.k_cache, self.v_cache = parent.k_cache[b], parent.v_cache[b]
+        self.workspace = parent.workspace[b * parent.slot_workspace_bytes:(b + 1) * parent.slot_workspace_bytes]
+        self.cos, self.sin, self.alpha_bits = parent.cos, parent.sin, parent.alpha_bits
+
+
+class BatchDecodeAttention:
+    """The attention step for `batch` sequences: caches [batch][kv_heads][max_keys][128] (slot b is exactly a single-sequence cache), a workspace of
+    `batch` single-step workspaces zeroed once, shared RoPE tables."""
+
+    def __init__(self, batch: int, heads: int, max_keys: int, device, cos: torch.Tensor | None = None, sin: torch.Tensor | None = None,
+                 kv_heads: int | None = None, head_dim: int = 128):
+        self.batch, self.heads, self.hd, self.max_keys = batch, heads, head_dim, max_keys
+        self.kv_heads = heads if kv_heads is None else kv_heads
+        need = int(capi.lib().tce_attention_decode_batch_workspace_bytes(batch, heads, max_keys, head_dim))
+        if need == 0:
+            raise ValueError("unsupported batched attention shape (head_dim must be 128, batch > 0)")
+        self.slot_workspace_bytes = need // batch
+        self.k_cache = torch.zeros((batch, self.kv_heads, max_keys, head_dim), dtype=torch.float16, device=device)
+        self.v_cache = torch.zeros((batch, self.kv_heads, max_keys, head_dim), dtype=torch.float16, device=device)
+        self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)  # zeroed once: the per-(sequence, head) arrival counters
+        self.cos, self.sin = cos, sin
+        self.alpha_bits = int(np.array([1.0 / np.sqrt(head_dim)], np.float16).view(np.uint16)[0])
+
+    def step(self, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """qkv fp16 [batch][(heads + 2 kv_heads) * 128] (the q/k/v linear's output at M = batch), pos_device int32 [batch] on the device (read when the
+        kernel runs; every value that is to be active <= pos_bound), out fp16 [batch][heads * 128] (o_proj's input rows)."""
+        rw = (self.heads + 2 * self.kv_heads) * self.hd
+        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == self.batch * rw
+        assert pos_device.dtype == torch.int32 and pos_device.is_cuda and pos_device.is_contiguous() and pos_device.numel() == self.batch
+        if out is None:
+            out = torch.empty((self.batch, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == self.batch * self.heads * self.hd
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        capi.check(capi.lib().tce_attention_decode_step_batch_f16(p(qkv), p(self.k_cache), p(self.v_cache), p(self.cos), p(self.sin), p(out), p(self.workspace),
+                                                                  self.batch, self.heads, self.kv_heads, self.hd, self.max_keys, p(pos_device), int(pos_bound),
+                                                                  self.alpha_bits, C.c_void_p(_stream())))
+        return out
+
+    def slot(self, b: int) -> DecodeAttention:
+        """A DecodeAttention over slot b's caches and workspace slice: its prefill() admits a sequence into the slot, its step() is the single-sequence yardstick."""
+        if not 0 <= b < self.batch:
+            raise IndexError(f"slot {b} of {self.batch}")
+        return _SlotAttention(self, b)
+
+
+class BatchedDecoder:
+    """`batch` sequences through one decoder block: the linears and gammas of `block` (nothing in the block changes), caches of its own."""
+
+    LAUNCHES = 7  # per layer and step, with the SiLU*mul pairs accepted (9 otherwise)
+
+    def __init__(self, block: DecoderBlock, batch: int):
+        self.block, self.batch = block, batch
+        dev = block.gamma1.device
+        self.attention = BatchDecodeAttention(batch, block.heads, block.attention.max_keys, dev, block.attention.cos, block.attention.sin, kv_heads=block.kv_heads)
+        e = lambda n: torch.empty((batch, n), dtype=torch.float16, device=dev)
+        self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
+        self.act = e(block.ffn)
+        self._up = None  # gate / up / SiLU*mul as three launches: up's output rows (only where the dispatcher refuses the pairs at M = batch)
+
+    def step(self, hidden: torch.Tensor, pos_device: torch.Tensor, pos_bound: int) -> None:
+        """hidden fp16 [batch][hidden], updated in place (each row is its sequence's residual stream); pos_device int32 [batch], -1 for an inactive slot: its
+        attention row is zero and its caches are untouched (its hidden row still passes through the MLP and means nothing).  Capturable in one
+        torch.cuda.graph and replayable token after token with pos_device advanced on the device."""
+        blk = self.block
+        assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.batch, blk.hidden)
+        st = _stream()
+        rmsnorm_half(hidden, blk.gamma1, blk.eps, out=self.xn)
+        capi.check(capi.w4a16_forward(blk.qkv.desc(self.xn, self.qkv_out), st))
+        self.attention.step(self.qkv_out, pos_device, pos_bound, out=self.attn_out)
+        capi.check(capi.w4a16_forward(blk.o.desc(self.attn_out, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+        rmsnorm_half(hidden, blk.gamma2, blk.eps, out=self.xn)
+        self._gate_up(self.xn, st)
+        capi.check(capi.w4a16_forward(blk.down.desc(self.act, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+
+    def _gate_up(self, xn: torch.Tensor, st: int) -> None:
+        blk = self.block
+        if self._up is None:
+            rc = capi.w4a16_forward(blk.gate_up.desc(xn, self.act, flags=capi.TCE_W4_SILU_MUL_PAIRS), st)
+            if rc == capi.TCE_OK:
+                return
+            if rc == capi.TCE_ERR_HIP:
+                capi.check(rc)
+            self._up = torch.empty_like(self.act)  # refused before any launch: the three-launch form from now on
+        capi.check(capi.w4a16_forward(blk.gate.desc(xn, self.act), st))
+        capi.check(capi.w4a16_forward(blk.up.desc(xn, self._up), st))
+        capi.check(capi.lib().tce_silu_mul_half(self.act.data_ptr(), self._up.data_ptr(), self.act.numel(), st))
+
+    def prefill(self, slot: int, rows: torch.Tensor, pos: int) -> None:
+        """Admit a sequence into `slot`: rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated in place -- DecoderBlock.prefill's launches on the
+        slot's caches."""
+        blk = self.block
+        m = rows.shape[0]
+        assert rows.dtype == torch.float16 and rows.is_contiguous() and rows.shape[1] == blk.hidden
+        st = _stream()
+        e = lambda n: torch.empty((m, n), dtype=torch.float16, device=rows.device)
+        xn, qkv, attn, g, u = e(blk.hidden), e((blk.heads + 2 * blk.kv_heads) * 128), e(blk.hidden), e(blk.ffn), e(blk.ffn)
+        rmsnorm_half(rows, blk.gamma1, blk.eps, out=xn)
+        capi.check(capi.w4a16_forward(blk.qkv.desc(xn, qkv), st))
+        self.attention.slot(slot).prefill(qkv, pos, out=attn, causal=True)
+        capi.check(capi.w4a16_forward(blk.o.desc(attn, rows, flags=capi.TCE_W4_ADD_TO_C), st))
+        rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
+        if m > 128 and blk.gate_up.packed is not None:
+            capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, g, flags=capi.TCE_W4_SILU_MUL_PAIRS), st))
+        else:
+            capi.check(capi.w4a16_forward(blk.gate.desc(xn, g), st))
+            capi.check(capi.w4a16_forward(blk.up.desc(xn, u), st))
+            capi.check(capi.lib().tce_silu_mul_half(g.data_ptr(), u.data_ptr(), g.numel(), st))
+        capi.check(capi.w4a16_forward(blk.down.desc(g, rows, flags=capi.TCE_W4_ADD_TO_C), st))

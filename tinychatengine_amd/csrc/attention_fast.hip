@@ -90,23 +90,45 @@ constexpr int kHD = 128;
 constexpr float kNegBig = -1.0e30f;
 constexpr int kDeferStride = 4 + kHD;  // floats per deferred partial state: M, L, two unused, O[128] (16-byte aligned rows of O)
 
+// one step's workspace in 4-byte words: the arrival counters (a 256-byte multiple), then the partial states for the smallest chunk (64 keys)
+__host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) {
+    return (((size_t)heads * 4 + 255) & ~(size_t)255) / 4 + (size_t)heads * ((max_keys + 63) / 64) * kDeferStride;
+}
+
 // MASK: the caller gave a mask row (a compile-time form: a branch inside the fetch block makes hipcc drain the load queue at the loop head)
 // NW: waves per workgroup (4; 8 and 16 exist for the sweep that ruled them out, see pick_chunk).
 // R: query heads per key / value head (grouped-query attention, llm/src/nn_modules/non_cuda/Int4llamaAttention.cc:166-185: query head i reads
 //    key / value head i / R; Llama-3-8B: 32 / 8, llm/include/model.h:83).  A workgroup is (key / value head, chunk of keys): it streams the
 //    chunk's cache rows ONCE and keeps R online-softmax states per lane, so the R query heads cost one pass over the cache, not R.
-template <bool MASK, int NW, int R>
+// BATCH: the batched step (launch_attention_decode_batch): grid.y = sequences, sequence blockIdx.y's q/k/v row, cache slot, output row, workspace slice and
+// position word; a position outside [0, a.pos] marks the row inactive.  Every offset below is a constant 0 in the single step's form (BATCH == false).
+template <bool MASK, int NW, int R, bool BATCH = false>
 __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAttnArgs a) {
     constexpr int NT = 64 * NW, NS = 4 * NW;
     __shared__ __attribute__((aligned(16))) float st[NS][R][2 + kHD];  // the (wave, slot) states per query head: m, l, o[hd]
     __shared__ __attribute__((aligned(16))) half_t newrow[2][kHD];  // the token's own (rotated) key and value
     __shared__ unsigned last_flag;
+    // the sequence's offsets into the batched arrays, in elements / words (BATCH == false: 0)
+    const unsigned seq = BATCH ? blockIdx.y : 0u;
+    const size_t seq_qkv = (size_t)seq * (a.heads + 2 * a.kv_heads) * kHD, seq_cache = (size_t)seq * a.kv_heads * a.max_keys * kHD;
+    const size_t seq_out = (size_t)seq * a.heads * kHD, seq_ws = BATCH ? seq * attn_workspace_words(a.heads, a.max_keys) : 0;
     // grp: this workgroup's group of R consecutive query heads (R == rep: all the query heads of a key / value head, its cache rows streamed
     // once for all of them; R < rep: rep / R workgroups read the same cache rows -- from HBM once, the others from the memory-side cache)
     const int grp = blockIdx.x / a.chunks, c = blockIdx.x - grp * a.chunks;
     // the position: by value, or from a device word (wave-uniform scalar load) -- then chunks past the context have nothing to do and the
     // head's combine expects only the chunks that exist
-    const int pos = a.pos_dev ? __builtin_amdgcn_readfirstlane(*a.pos_dev) : a.pos;
+    const int pos = a.pos_dev ? __builtin_amdgcn_readfirstlane(*(a.pos_dev + seq)) : a.pos;
+    if constexpr (BATCH) {
+        // an inactive row (a retired slot: -1; or any word outside the bound the grid was cut for): zeros for o_proj, and nothing else -- no cache row, no
+        // partial state, no counter.  The first chunk slot of each query-head group writes them.
+        if (pos < 0 || pos > a.pos) {
+            if (c == 0 && threadIdx.x < kHD) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) a.out[seq_out + (size_t)grp * R * kHD + r * kHD + threadIdx.x] = (half_t)0;
+            }
+            return;
+        }
+    }
     const int keys = pos + 1;
     const int chunks = a.pos_dev ? (keys + a.chunk - 1) / a.chunk : a.chunks;  // active chunks (<= the grid's chunk slots)
     if (c >= chunks) return;
@@ -124,7 +146,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     const int per_wave = a.chunk / NW;  // (the host made the chunk a multiple of 4 * NW)
     const int kw0 = key0 + wave * per_wave;
     const int kw1 = kw0 + per_wave < key1 ? kw0 + per_wave : key1;  // a block is 16 keys, a wave's run any multiple of 4: the rest weighs nothing
-    const half_t *kbase = a.kc + (size_t)head * a.max_keys * kHD, *vbase = a.vc + (size_t)head * a.max_keys * kHD;
+    const half_t *kbase = a.kc + seq_cache + (size_t)head * a.max_keys * kHD, *vbase = a.vc + seq_cache + (size_t)head * a.max_keys * kHD;
     // blocks of 4 steps (16 keys per wave): the 8 loads of the next block are in flight while this block's scores and
     // exponentials are computed (the online-softmax state is the only loop-carried dependence; without the explicit double
     // buffer every step paid a full memory round trip: 20 us at 2048 keys, profiles/r2/attention_decode_step.jsonl)
@@ -145,7 +167,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     // ---- every piece the prologue needs, requested together: q, k (with their partner halves), v, cos, sin.  All four
     //      waves fetch the k / v pieces (L2 hits, 3 instructions) so that nobody waits for a second batch; wave 0 uses them ----
     const bool rope = cosr != nullptr;
-    const half_t *xq = a.qkv + (size_t)grp * R * kHD, *xk = a.qkv + (size_t)a.heads * kHD + hoff, *xv = a.qkv + (size_t)(a.heads + a.kv_heads) * kHD + hoff;
+    const half_t *xq = a.qkv + seq_qkv + (size_t)grp * R * kHD, *xk = a.qkv + seq_qkv + (size_t)a.heads * kHD + hoff,
+                 *xv = a.qkv + seq_qkv + (size_t)(a.heads + a.kv_heads) * kHD + hoff;
     const half_t *cp = rope ? cosr : xq, *sp = rope ? sinr : xq;  // no rotation: harmless repeats of the q piece, not used
     auto ld8 = [](const half_t *ptr) { return *reinterpret_cast<const half8_t *>(ptr); };
     half8_t q_v[R], q_p[R];
@@ -175,8 +198,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
             *reinterpret_cast<half8_t *>(&newrow[0][piece * 8]) = kh;
             *reinterpret_cast<half8_t *>(&newrow[1][piece * 8]) = vh;
             if (appends && pos >= key0 && pos < key1) {
-                *reinterpret_cast<half8_t *>(a.kc + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = kh;
-                *reinterpret_cast<half8_t *>(a.vc + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = vh;
+                *reinterpret_cast<half8_t *>(a.kc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = kh;
+                *reinterpret_cast<half8_t *>(a.vc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = vh;
             }
         }
     }
@@ -301,7 +324,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     if (chunks == 1) {
         if (tid < kHD) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) a.out[qoff + r * kHD + tid] = (half_t)(O[r] / Lq[r]);
+            for (int r = 0; r < R; ++r) a.out[seq_out + qoff + r * kHD + tid] = (half_t)(O[r] / Lq[r]);
         }
         return;
     }
@@ -337,7 +360,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     if (tid < kHD) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            float *mine = a.part + ((size_t)(grp * R + r) * chunks + c) * (2 + kHD);
+            float *mine = a.part + seq_ws + ((size_t)(grp * R + r) * chunks + c) * (2 + kHD);
             __hip_atomic_store(mine + 2 + tid, O[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through (sc1) stores
             if (tid == 0) {
                 __hip_atomic_store(mine, M[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -348,9 +371,9 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores are acknowledged before the workgroup arrives
     __syncthreads();
     if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(a.cnt + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned old = __hip_atomic_fetch_add(a.cnt + seq_ws + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         last_flag = old == (unsigned)chunks - 1 ? 1u : 0u;
-        if (last_flag) __hip_atomic_store(a.cnt + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+        if (last_flag) __hip_atomic_store(a.cnt + seq_ws + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
     }
     __syncthreads();
     if (!last_flag) return;
@@ -360,7 +383,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     constexpr int kMaxChunksUnrolled = 16;
     float *ml = &st[0][0][0];  // [R][chunks][2], reuses the state area
     const int stride = (2 + kHD) * 4;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (size_t)grp * R * chunks * (2 + kHD), 0, (int)((size_t)R * chunks * stride), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + seq_ws + (size_t)grp * R * chunks * (2 + kHD), 0, (int)((size_t)R * chunks * stride), 0x00020000);
     for (int i = tid; i < R * chunks; i += NT) {
         ml[2 * i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, i * stride, 0, /*sc0|sc1*/ 17));
         ml[2 * i + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, i * stride + 4, 0, 17));
@@ -394,7 +417,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
                 Lx += mlr[2 * i + 1] * w;
                 Ox += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (r * chunks + i) * stride + (2 + tid) * 4, 0, 17)) * w;
             }
-            a.out[qoff + r * kHD + tid] = (half_t)(Ox / Lx);
+            a.out[seq_out + qoff + r * kHD + tid] = (half_t)(Ox / Lx);
         }
     }
 }
@@ -428,9 +451,10 @@ static thread_local int g_attn_fuse = 0;  // tuning: query heads per workgroup f
 void set_attention_fast_fuse(int r) { g_attn_fuse = (r == 1 || r == 2 || r == 4) ? r : 0; }
 
 // `heads` here = workgroup groups (query heads / heads per workgroup)
-static void pick_chunk(int heads, int keys, int rep, int *chunk_out, int *waves_out) {
+// tuned = false: the fitted rule alone, whatever the calling thread's tuning settings (the batched step)
+static void pick_chunk(int heads, int keys, int rep, int *chunk_out, int *waves_out, bool tuned = true) {
     int chunk;
-    if (g_attn_target_wgs > 0) {
+    if (tuned && g_attn_target_wgs > 0) {
         const int target_chunks = heads >= g_attn_target_wgs ? 1 : g_attn_target_wgs / heads;
         chunk = (keys + target_chunks - 1) / target_chunks;
         if (chunk < 64) chunk = 64;
@@ -449,7 +473,7 @@ static void pick_chunk(int heads, int keys, int rep, int *chunk_out, int *waves_
     // (profiles/r2/attention_step_waves_sweep.jsonl): the launch is at the floor of a dependent load -> compute -> store launch
     // (4.5 us; the 8 MiB GEMV's is 4.1) plus ~2 us for the combine plus the keys at 6.4 TB/s, and wider workgroups only add to the
     // fixed part (prologue loads per wave, barriers, the workgroup's own merge over 4 x waves states).
-    int nw = g_attn_waves ? g_attn_waves : 4;
+    int nw = tuned && g_attn_waves ? g_attn_waves : 4;
     chunk = (chunk + 4 * nw - 1) / (4 * nw) * (4 * nw);
     *chunk_out = chunk;
     *waves_out = nw;
@@ -473,10 +497,7 @@ void describe_attention_decode_fast(int heads, int keys, int *chunk, int *chunks
 
 size_t attention_decode_workspace_bytes(int heads, int max_keys, int hd) {
     if (heads <= 0 || max_keys <= 0 || hd != kHD) return 0;
-    const int chunk = 64;  // the smallest chunk bounds the number of partials
-    const size_t chunks = (size_t)(max_keys + chunk - 1) / chunk;
-    const size_t cnt_bytes = ((size_t)heads * 4 + 255) & ~(size_t)255;
-    return cnt_bytes + (size_t)heads * chunks * kDeferStride * 4;  // (the deferred layout's stride; the combined form's 2 + hd fits inside)
+    return attn_workspace_words(heads, max_keys) * 4;  // (the deferred layout's stride; the combined form's 2 + hd fits inside)
 }
 
 int launch_attention_decode_fast(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace,
@@ -533,6 +554,54 @@ int launch_attention_decode_fast(const void *qkv, void *kc, void *vc, const void
     };
     if (a.mask) go(std::true_type{});
     else go(std::false_type{});
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+// the batched step's cut: the single step's fitted rule for pos_bound + 1 keys, one query head per workgroup (no HIP call)
+void describe_attention_decode_batch(int heads, int kv_heads, int pos_bound, int *chunk, int *chunks, int *waves) {
+    pick_chunk(heads, pos_bound + 1, heads / kv_heads, chunk, waves, false);
+    *chunks = (pos_bound + 1 + *chunk - 1) / *chunk;
+}
+
+size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int hd) {
+    if (batch <= 0) return 0;
+    return (size_t)batch * attention_decode_workspace_bytes(heads, max_keys, hd);
+}
+
+int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
+                                  int kv_heads, int hd, int max_keys, const int *pos_dev, int pos_bound, unsigned short alpha_bits, hipStream_t stream,
+                                  hipError_t *hip_err) {
+    if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !pos_dev) return TCE_ERR_UNSUPPORTED_SHAPE;
+    FastAttnArgs a{};
+    a.qkv = static_cast<const half_t *>(qkv);
+    a.kc = static_cast<half_t *>(kc);
+    a.vc = static_cast<half_t *>(vc);
+    a.cosv = static_cast<const half_t *>(cosv);
+    a.sinv = static_cast<const half_t *>(sinv);
+    a.out = static_cast<half_t *>(out);
+    const size_t cnt_bytes = ((size_t)heads * 4 + 255) & ~(size_t)255;  // (one sequence's slice: the single step's layout)
+    a.cnt = static_cast<unsigned *>(workspace);
+    a.part = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + cnt_bytes);
+    a.heads = heads;
+    a.kv_heads = kv_heads;
+    a.rep = heads / kv_heads;
+    a.hd = hd;
+    a.max_keys = max_keys;
+    a.pos = pos_bound;
+    a.keys = pos_bound + 1;
+    a.pos_dev = pos_dev;
+    int nw = 4;
+    describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
+    if (a.chunks > 1024 || nw != 4) return TCE_ERR_UNSUPPORTED_SHAPE;
+    half_t ah;
+    __builtin_memcpy(&ah, &alpha_bits, 2);
+    a.alpha = (float)ah;
+    hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;

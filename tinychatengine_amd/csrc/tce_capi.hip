@@ -1164,6 +1164,36 @@ int tce_attention_decode_step_pos_f16(const void *qkv, void *kc, void *vc, const
     return rc == TCE_ERR_HIP ? hip_fail(he, "attention decode step launch") : rc;
 }
 
+size_t tce_attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int hd) { return tce::attention_decode_batch_workspace_bytes(batch, heads, max_keys, hd); }
+
+int tce_attention_decode_describe_batch(int batch, int heads, int kv_heads, int pos_bound, char *buf, int buf_len) {
+    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0)
+        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_batch: bad argument");
+    int chunk = 0, chunks = 0, waves = 0;
+    tce::describe_attention_decode_batch(heads, kv_heads, pos_bound, &chunk, &chunks, &waves);
+    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d", chunks, chunk, waves, (long long)batch * heads * chunks,
+                  chunks > 1 ? "yes" : "no", batch);
+    return TCE_OK;
+}
+
+int tce_attention_decode_step_batch_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
+                                        int kv_heads, int hd, int max_keys, const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
+    if (!qkv || !kc || !vc || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: null pointer");
+    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: cos and sin tables come together");
+    if (batch <= 0 || heads <= 0 || max_keys <= 0 || pos_bound < 0 || pos_bound >= max_keys)
+        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: need batch, heads > 0 and 0 <= pos_bound < max_keys");
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: %d query heads do not divide over %d key / value heads", heads, kv_heads);
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: head_dim %d (128 only: Llama's)", hd);
+    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: batch %d (at most 65535: the grid's second dimension)", batch);
+    for (const void *p : {qkv, (const void *)kc, (const void *)vc, cosv, sinv})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: 16-byte aligned pointers");
+    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: pos_device must be int32-aligned");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_attention_decode_batch(qkv, kc, vc, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, max_keys, pos_device, pos_bound, alpha_bits,
+                                                      static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "batched attention decode step launch") : rc;
+}
+
 int tce_attention_decode_step_deferred_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace, int heads,
                                            int kv_heads, int hd, int max_keys, const int32_t *pos_device, int pos, unsigned short alpha_bits, tce_attention_deferred *info, void *stream) {
     if (!qkv || !kc || !vc || !out || !workspace || !info) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_deferred_f16: null pointer");

@@ -262,6 +262,12 @@ constexpr int kAttnDeferMaxSlots = 8;
 int launch_attention_decode_fast(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace,
                                  int heads, int kv_heads, int hd, int max_keys, int pos, unsigned short alpha_bits, hipStream_t stream, hipError_t *hip_err,
                                  const int *pos_dev = nullptr, AttnDeferred *deferred = nullptr);
+// the batched step: `batch` sequences in one launch, each with its own position word, cache slot, q/k/v and output rows and workspace slice
+void describe_attention_decode_batch(int heads, int kv_heads, int pos_bound, int *chunk, int *chunks, int *waves);
+size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int hd);
+int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
+                                  int kv_heads, int hd, int max_keys, const int *pos_dev, int pos_bound, unsigned short alpha_bits, hipStream_t stream,
+                                  hipError_t *hip_err);
 int launch_rope_half(void *q, void *k, const void *cosv, const void *sinv, int heads, int len, int hd, int start_idx, hipStream_t stream, hipError_t *hip_err);
 int launch_softmax_half(const void *x, void *out, long long rows, int n, hipStream_t stream, hipError_t *hip_err);
 int launch_prefetch(const void *ptr, long long bytes, int workgroups, hipStream_t stream, hipError_t *hip_err);
