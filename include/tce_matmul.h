@@ -47,7 +47,7 @@ extern "C" {
 
 #define TCE_API __attribute__((visibility("default")))
 
-#define TCE_VERSION 113 /* additive, unversioned: tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
+#define TCE_VERSION 113 /* additive, unversioned: tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
 
 /* error codes (return values) */
 #define TCE_OK 0
@@ -237,6 +237,38 @@ TCE_API int tce_attention_decode_describe_batch(int batch, int heads, int kv_hea
 TCE_API int tce_attention_decode_step_batch_f16(const void *qkv, void *k_cache, void *v_cache, const void *cos_table, const void *sin_table,
                                                 void *out, void *workspace, int batch, int heads, int kv_heads, int head_dim, int max_keys,
                                                 const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, void *stream);
+
+/* The batched step on a PAGED cache: keys and values live in fixed-size pages drawn from one pool, a per-sequence block table maps logical key index to page.
+ *   k_pool, v_pool  fp16 [num_pages][kv_heads][page_keys][head_dim] each; page_keys a power of two from 16 to 256; one page number addresses both pools
+ *   block_table     int32 [batch][table_stride], device memory, read when the kernel runs: logical key j of sequence b, key / value head h is row j % page_keys of
+ *                   page p = block_table[b][j / page_keys], at element ((p * kv_heads + h) * page_keys + j % page_keys) * head_dim of either pool
+ *   workspace       tce_attention_decode_batch_workspace_bytes(batch, heads, table_stride * page_keys, head_dim) bytes, zeroed once (the batched step's layout)
+ * Everything else is tce_attention_decode_step_batch_f16: the grid, the untuned fitted cut for pos_bound + 1 keys, one query head per workgroup, pos_device, inactive
+ * rows (position < 0 or > pos_bound: a zero `out` row, nothing else of theirs written), the new key / value rows appended -- to the page that holds index pos.  Every
+ * active row's `out` and appended rows are BIT-IDENTICAL to the batched step on contiguous caches with the same contents; the arithmetic is the same instructions.
+ * TRUST: for an active row only words 0 .. pos / page_keys of its table row become addresses (rows read past the range and not weighted stay inside those pages);
+ * words beyond them and every word of an inactive row may hold anything.  The step does NOT validate page numbers -- a word it follows must lie in [0, num_pages) --;
+ * tce_kv_block_table_check is the check to run first where a table is not known to be sound.  pos_bound < table_stride * page_keys.
+ * tce_kv_pages_pool_bytes: the bytes of ONE pool, 0 for an unsupported shape (head_dim != 128, page_keys outside the rule, a count <= 0).
+ * tce_attention_decode_describe_paged: tce_attention_decode_describe_batch's text with " page-keys=P" appended; no HIP call.
+ * tce_kv_pages_scatter_f16: rows [key0, key0 + nkeys) of every head of a contiguous single-sequence pair [kv_heads][src_max_keys][head_dim] (what
+ * tce_attention_prefill_f16 and the single steps write) into the pages ONE table row names (`table_row` = block_table + b * table_stride); tce_kv_pages_gather_f16 is
+ * the reverse.  One launch of 16-byte copies each; key0 and nkeys need not be page-aligned; no other row of either side is written; a table word outside
+ * [0, num_pages) copies nothing.  Admission: prefill on a contiguous staging pair (after a gather, on top of cached keys), then scatter the new rows.
+ * tce_kv_block_table_check (asynchronous, one small launch): *violations (a device-visible word) = the number of words an active row (0 <= pos_device[b] <= pos_bound)
+ * would follow -- 0 .. pos / page_keys -- that lie outside [0, num_pages), plus the active rows with pos / page_keys >= table_stride.  Words past the needed range and
+ * inactive rows are not looked at.  The word is written, not accumulated. */
+TCE_API size_t tce_kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int head_dim);
+TCE_API int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int pos_bound, int page_keys, char *buf, int buf_len);
+TCE_API int tce_attention_decode_step_paged_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
+                                                int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, void *stream);
+TCE_API int tce_kv_pages_scatter_f16(const void *k_src, const void *v_src, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
+                                     int num_pages, int kv_heads, int head_dim, int src_max_keys, int key0, int nkeys, void *stream);
+TCE_API int tce_kv_pages_gather_f16(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys,
+                                    int num_pages, int kv_heads, int head_dim, int dst_max_keys, int key0, int nkeys, void *stream);
+TCE_API int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                                     uint32_t *violations, void *stream);
 
 /* Round 5: the attention step WITHOUT its cross-workgroup combine, and the linear that consumes it (o_proj) doing the combine in its prologue.
  * A decode step over more than ~320 keys cuts every head's keys into 4 or 8 chunks; each chunk's workgroup ends with a partial online-softmax state (M, L, O[128]) and

@@ -49,6 +49,13 @@ struct FastAttnArgs {
     int probe_no_combine;  // timing experiment (tce_w4a16_set_debug_mode(2931)): the partial states are stored plainly and the launch ends -- `out` is NOT written
 };
 
+// the paged step's arguments: the batched step's, with the caches replaced by two pools of pages and a block table (kc / vc = the pools, max_keys =
+// table_stride << page_shift: the bound of a sequence's logical key index, what the workspace slices are sized for)
+struct PagedAttnArgs : FastAttnArgs {
+    const int *table;  // int32 [batch][table_stride]: logical key j of sequence b lives in page table[b][j >> page_shift], row j & (page_keys - 1)
+    int table_stride, page_shift;  // page_keys = 1 << page_shift (16 .. 256)
+};
+
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
     auto dpp = [](float x, auto ctrl) {
         return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, false));
@@ -102,19 +109,34 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 //    chunk's cache rows ONCE and keeps R online-softmax states per lane, so the R query heads cost one pass over the cache, not R.
 // BATCH: the batched step (launch_attention_decode_batch): grid.y = sequences, sequence blockIdx.y's q/k/v row, cache slot, output row, workspace slice and
 // position word; a position outside [0, a.pos] marks the row inactive.  Every offset below is a constant 0 in the single step's form (BATCH == false).
-template <bool MASK, int NW, int R, bool BATCH = false>
-__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAttnArgs a) {
+// PAGED (with BATCH): the caches are pools of pages [num_pages][kv_heads][page_keys][hd] addressed through a block table (PagedAttnArgs).  Only the base of a
+// cache row changes: a wave-instruction of the cache stream covers four consecutive keys from a multiple of four, which never cross a page, so the request stays
+// 1 KiB contiguous.  Which table words a wave can need depends on the grid alone (its keys kw0 .. kw0 + per_wave - 1), so they are requested BEFORE the position
+// word is waited for -- one word per lane, plain ints inside the table -- and a cache request picks its page with v_readlane: no round trip is added to the
+// chain position word -> cache rows.  Only words 0 .. pos / page_keys of an active row become addresses (see page_of below); of an inactive row, none.
+template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false>
+__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs> a) {
+    static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
     constexpr int NT = 64 * NW, NS = 4 * NW;
     __shared__ __attribute__((aligned(16))) float st[NS][R][2 + kHD];  // the (wave, slot) states per query head: m, l, o[hd]
     __shared__ __attribute__((aligned(16))) half_t newrow[2][kHD];  // the token's own (rotated) key and value
     __shared__ unsigned last_flag;
     // the sequence's offsets into the batched arrays, in elements / words (BATCH == false: 0)
     const unsigned seq = BATCH ? blockIdx.y : 0u;
-    const size_t seq_qkv = (size_t)seq * (a.heads + 2 * a.kv_heads) * kHD, seq_cache = (size_t)seq * a.kv_heads * a.max_keys * kHD;
+    const size_t seq_qkv = (size_t)seq * (a.heads + 2 * a.kv_heads) * kHD, seq_cache = PAGED ? 0 : (size_t)seq * a.kv_heads * a.max_keys * kHD;
     const size_t seq_out = (size_t)seq * a.heads * kHD, seq_ws = BATCH ? seq * attn_workspace_words(a.heads, a.max_keys) : 0;
     // grp: this workgroup's group of R consecutive query heads (R == rep: all the query heads of a key / value head, its cache rows streamed
     // once for all of them; R < rep: rep / R workgroups read the same cache rows -- from HBM once, the others from the memory-side cache)
     const int grp = blockIdx.x / a.chunks, c = blockIdx.x - grp * a.chunks;
+    // PAGED: lane i's table word kw0 / page_keys + i of this sequence's row (clamped into the row; lane 63: word 0, which every active row owns -- the page that
+    // wholly invalid groups of four are read from).  Requested here, in front of the position word's wait: a load of an int inside the table, whatever it holds.
+    int tabw = 0, tab_e0 = 0;
+    if constexpr (PAGED) {
+        const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l_ = threadIdx.x & 63;
+        tab_e0 = (c * a.chunk + w_ * (a.chunk / NW)) >> a.page_shift;
+        const int e = l_ == 63 ? 0 : (tab_e0 + l_ < a.table_stride ? tab_e0 + l_ : a.table_stride - 1);
+        tabw = a.table[(size_t)seq * a.table_stride + e];
+    }
     // the position: by value, or from a device word (wave-uniform scalar load) -- then chunks past the context have nothing to do and the
     // head's combine expects only the chunks that exist
     const int pos = a.pos_dev ? __builtin_amdgcn_readfirstlane(*(a.pos_dev + seq)) : a.pos;
@@ -147,6 +169,11 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
     const int kw0 = key0 + wave * per_wave;
     const int kw1 = kw0 + per_wave < key1 ? kw0 + per_wave : key1;  // a block is 16 keys, a wave's run any multiple of 4: the rest weighs nothing
     const half_t *kbase = a.kc + seq_cache + (size_t)head * a.max_keys * kHD, *vbase = a.vc + seq_cache + (size_t)head * a.max_keys * kHD;
+    // PAGED: the element offset of (page, this key / value head, row) in either pool
+    [[maybe_unused]] auto page_row = [&](int page, int row) -> size_t {
+        if constexpr (PAGED) return ((((size_t)page * a.kv_heads + head) << a.page_shift) + row) * kHD;
+        else return 0;
+    };
     // blocks of 4 steps (16 keys per wave): the 8 loads of the next block are in flight while this block's scores and
     // exponentials are computed (the online-softmax state is the only loop-carried dependence; without the explicit double
     // buffer every step paid a full memory round trip: 20 us at 2048 keys, profiles/r2/attention_decode_step.jsonl)
@@ -158,6 +185,20 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
         for (int u = 0; u < BLK; ++u) {
             const int key = kw0 + it0 + u * 4 + slot;
             const int kk = key < kw1 ? key : (keys - 1);  // clamped: rows past the range are read (harmlessly) and weigh nothing
+            if constexpr (PAGED) {
+                // the group of four keys g .. g + 3 (g a multiple of 4, wave-uniform).  g < kw1: at least key g is in the range, so g <= pos, its table word
+                // g / page_keys <= pos / page_keys is one the row owns and one of this wave's (lane g / page_keys - tab_e0 < 63 holds it); a slot past the range
+                // is clamped to keys - 1, which then lies in the same group (kw1 is a multiple of 4 or keys itself) and so in the same page.  g >= kw1: nothing of
+                // the group is weighted; it is read from rows 0 .. 3 of word 0's page (lane 63) -- never from a word past pos / page_keys.
+                const int g = kw0 + it0 + u * 4;
+                const bool live = g < kw1;
+                const int page = __builtin_amdgcn_readlane(tabw, __builtin_amdgcn_readfirstlane(live ? (g >> a.page_shift) - tab_e0 : 63));
+                const size_t off = page_row(page, live ? (kk & ((1 << a.page_shift) - 1)) : slot) + piece * 8;
+                kd[u] = *reinterpret_cast<const half8_t *>(a.kc + off);
+                vd[u] = *reinterpret_cast<const half8_t *>(a.vc + off);
+                md[u] = (half_t)0;
+                continue;
+            }
             kd[u] = *reinterpret_cast<const half8_t *>(kbase + (size_t)kk * kHD + piece * 8);
             vd[u] = *reinterpret_cast<const half8_t *>(vbase + (size_t)kk * kHD + piece * 8);
             if constexpr (MASK) md[u] = a.mask[kk];
@@ -198,8 +239,17 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const FastAtt
             *reinterpret_cast<half8_t *>(&newrow[0][piece * 8]) = kh;
             *reinterpret_cast<half8_t *>(&newrow[1][piece * 8]) = vh;
             if (appends && pos >= key0 && pos < key1) {
-                *reinterpret_cast<half8_t *>(a.kc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = kh;
-                *reinterpret_cast<half8_t *>(a.vc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = vh;
+                if constexpr (PAGED) {
+                    // the page that holds index pos: word pos / page_keys, the last one the row owns (a wave-uniform load that depends on the position word, beside
+                    // the cos / sin pieces which do too: it delays this store, not the cache requests)
+                    const int page = __builtin_amdgcn_readfirstlane(a.table[(size_t)seq * a.table_stride + (pos >> a.page_shift)]);
+                    const size_t off = page_row(page, pos & ((1 << a.page_shift) - 1)) + piece * 8;
+                    *reinterpret_cast<half8_t *>(a.kc + off) = kh;
+                    *reinterpret_cast<half8_t *>(a.vc + off) = vh;
+                } else {
+                    *reinterpret_cast<half8_t *>(a.kc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = kh;
+                    *reinterpret_cast<half8_t *>(a.vc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = vh;
+                }
             }
         }
     }
@@ -602,6 +652,140 @@ int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const voi
     __builtin_memcpy(&ah, &alpha_bits, 2);
     a.alpha = (float)ah;
     hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+// ---- pages <-> a contiguous single-sequence cache pair, and the block-table check (the paged step's companions) ----
+namespace {
+
+// Rows [key0, key0 + nkeys) of every key / value head between a contiguous pair [kv_heads][lin_max_keys][hd] and the pages one table row names; GATHER: pages ->
+// contiguous, else contiguous -> pages.  One thread per 16 bytes, grid.y: K / V.  A table word outside [0, num_pages) copies nothing (no address is formed from it).
+template <bool GATHER>
+__global__ __launch_bounds__(256) void kv_pages_copy_kernel(half_t *k_lin, half_t *v_lin, half_t *k_pool, half_t *v_pool, const int *table_row, int page_shift,
+                                                            int num_pages, int kv_heads, int lin_max_keys, int key0, int nkeys) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int piece = (int)(i & 15);
+    const long long r = i >> 4;  // (head, key of the range)
+    if (r >= (long long)kv_heads * nkeys) return;
+    const int head = (int)(r / nkeys), key = key0 + (int)(r % nkeys);
+    const int page = table_row[key >> page_shift];
+    if (page < 0 || page >= num_pages) return;
+    const size_t po = ((((size_t)page * kv_heads + head) << page_shift) + (key & ((1 << page_shift) - 1))) * kHD + piece * 8;
+    const size_t lo = ((size_t)head * lin_max_keys + key) * kHD + piece * 8;
+    half_t *lin = blockIdx.y ? v_lin : k_lin, *pool = blockIdx.y ? v_pool : k_pool;
+    if constexpr (GATHER) *reinterpret_cast<half8_t *>(lin + lo) = *reinterpret_cast<const half8_t *>(pool + po);
+    else *reinterpret_cast<half8_t *>(pool + po) = *reinterpret_cast<const half8_t *>(lin + lo);
+}
+
+// *violations = the number of table words an active row would follow that are not page numbers, plus the active rows whose position needs a word past the row
+// (one workgroup: the tables are a few thousand words)
+__global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *table, int table_stride, int page_shift, int num_pages, int batch, const int *pos_dev,
+                                                                    int pos_bound, unsigned *violations) {
+    __shared__ unsigned bad;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    unsigned mine = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int pos = pos_dev[b];
+        if (pos < 0 || pos > pos_bound) continue;
+        int last = pos >> page_shift;
+        if (last >= table_stride) {
+            if (threadIdx.x == 0) ++mine;
+            last = table_stride - 1;
+        }
+        for (int e = threadIdx.x; e <= last; e += 1024) {
+            const int page = table[(size_t)b * table_stride + e];
+            if (page < 0 || page >= num_pages) ++mine;
+        }
+    }
+    if (mine) atomicAdd(&bad, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) *violations = bad;
+}
+
+}  // namespace
+
+// ---- the paged step: the batched step on pools of pages.  The cut, the grid, the workspace layout and every row's arithmetic are the batched step's ----
+static int page_shift_of(int page_keys) {  // log2 of a power of two in [16, 256], or -1
+    for (int s = 4; s <= 8; ++s)
+        if (page_keys == 1 << s) return s;
+    return -1;
+}
+
+size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) {
+    if (num_pages <= 0 || kv_heads <= 0 || hd != kHD || page_shift_of(page_keys) < 0) return 0;
+    return (size_t)num_pages * kv_heads * page_keys * kHD * sizeof(half_t);
+}
+
+int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
+                                  void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
+                                  hipStream_t stream, hipError_t *hip_err) {
+    const int shift = page_shift_of(page_keys);
+    if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !pos_dev || !table || shift < 0 || table_stride < 1 ||
+        (long long)pos_bound >= ((long long)table_stride << shift))
+        return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedAttnArgs a{};
+    a.qkv = static_cast<const half_t *>(qkv);
+    a.kc = static_cast<half_t *>(k_pool);
+    a.vc = static_cast<half_t *>(v_pool);
+    a.cosv = static_cast<const half_t *>(cosv);
+    a.sinv = static_cast<const half_t *>(sinv);
+    a.out = static_cast<half_t *>(out);
+    const size_t cnt_bytes = ((size_t)heads * 4 + 255) & ~(size_t)255;
+    a.cnt = static_cast<unsigned *>(workspace);
+    a.part = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + cnt_bytes);
+    a.heads = heads;
+    a.kv_heads = kv_heads;
+    a.rep = heads / kv_heads;
+    a.hd = hd;
+    a.max_keys = table_stride << shift;  // (the workspace slices' size; no cache address is formed from it)
+    a.pos = pos_bound;
+    a.keys = pos_bound + 1;
+    a.pos_dev = pos_dev;
+    a.table = table;
+    a.table_stride = table_stride;
+    a.page_shift = shift;
+    int nw = 4;
+    describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
+    if (a.chunks > 1024 || nw != 4) return TCE_ERR_UNSUPPORTED_SHAPE;
+    half_t ah;
+    __builtin_memcpy(&ah, &alpha_bits, 2);
+    a.alpha = (float)ah;
+    hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
+                         int lin_max_keys, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err) {
+    const int shift = page_shift_of(page_keys);
+    if (shift < 0 || kv_heads <= 0 || nkeys <= 0 || key0 < 0 || (long long)key0 + nkeys > lin_max_keys) return TCE_ERR_UNSUPPORTED_SHAPE;
+    const dim3 grid((unsigned)(((long long)kv_heads * nkeys * 16 + 255) / 256), 2);
+    auto h = [](void *p) { return static_cast<half_t *>(p); };
+    if (gather) hipLaunchKernelGGL(kv_pages_copy_kernel<true>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), h(k_pool), h(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys);
+    else hipLaunchKernelGGL(kv_pages_copy_kernel<false>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), h(k_pool), h(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_kv_block_table_check(const int *table, int table_stride, int page_keys, int num_pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations,
+                                hipStream_t stream, hipError_t *hip_err) {
+    const int shift = page_shift_of(page_keys);
+    if (shift < 0 || table_stride < 1 || batch < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
+    hipLaunchKernelGGL(kv_block_table_check_kernel, dim3(1), dim3(1024), 0, stream, table, table_stride, shift, num_pages, batch, pos_dev, pos_bound, violations);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;

@@ -1194,6 +1194,86 @@ int tce_attention_decode_step_batch_f16(const void *qkv, void *kc, void *vc, con
     return rc == TCE_ERR_HIP ? hip_fail(he, "batched attention decode step launch") : rc;
 }
 
+// ---- the paged step and its companions (csrc/attention_fast.hip): every refusal below happens before any HIP call ----
+size_t tce_kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes(num_pages, kv_heads, page_keys, hd); }
+
+static bool page_keys_ok(int page_keys) { return page_keys >= 16 && page_keys <= 256 && (page_keys & (page_keys - 1)) == 0; }
+
+int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int pos_bound, int page_keys, char *buf, int buf_len) {
+    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys))
+        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_paged: bad argument");
+    int chunk = 0, chunks = 0, waves = 0;
+    tce::describe_attention_decode_batch(heads, kv_heads, pos_bound, &chunk, &chunks, &waves);
+    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
+                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
+    return TCE_OK;
+}
+
+int tce_attention_decode_step_paged_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                        const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                        const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
+    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: null pointer");
+    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: cos and sin tables come together");
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: page_keys %d (a power of two from 16 to 256)", page_keys);
+    if (table_stride < 1 || num_pages < 1) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: need table_stride, num_pages >= 1");
+    if (batch <= 0 || heads <= 0 || pos_bound < 0 || (long long)pos_bound >= (long long)table_stride * page_keys)
+        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: need batch, heads > 0 and 0 <= pos_bound < table_stride * page_keys");
+    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: table_stride * page_keys overflows int");
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: %d query heads do not divide over %d key / value heads", heads, kv_heads);
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: head_dim %d (128 only: Llama's)", hd);
+    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: batch %d (at most 65535: the grid's second dimension)", batch);
+    for (const void *p : {qkv, (const void *)k_pool, (const void *)v_pool, cosv, sinv})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: 16-byte aligned pointers");
+    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: pos_device must be int32-aligned");
+    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: block_table must be int32-aligned");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_attention_decode_paged(qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd,
+                                                      pos_device, pos_bound, alpha_bits, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "paged attention decode step launch") : rc;
+}
+
+static int kv_pages_copy(const char *who, bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
+                         int num_pages, int kv_heads, int hd, int lin_max_keys, int key0, int nkeys, void *stream) {
+    if (!k_lin || !v_lin || !k_pool || !v_pool || !table_row) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
+    if (table_stride < 1 || num_pages < 1 || kv_heads < 1 || lin_max_keys < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages, kv_heads, max_keys >= 1", who);
+    if (key0 < 0 || nkeys < 1 || (long long)key0 + nkeys > lin_max_keys || (long long)key0 + nkeys > (long long)table_stride * page_keys)
+        return fail(TCE_ERR_BAD_ARG, "%s: rows [%d, %d + %d) must lie inside the contiguous cache (%d keys) and the table row (%d pages of %d)", who, key0, key0, nkeys,
+                    lin_max_keys, table_stride, page_keys);
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
+    for (const void *p : {(const void *)k_lin, (const void *)v_lin, (const void *)k_pool, (const void *)v_pool})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned pointers", who);
+    if (reinterpret_cast<uintptr_t>(table_row) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: the table row must be int32-aligned", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_kv_pages_copy(gather, k_lin, v_lin, k_pool, v_pool, table_row, page_keys, num_pages, kv_heads, lin_max_keys, key0, nkeys,
+                                             static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, who) : rc;
+}
+
+int tce_kv_pages_scatter_f16(const void *k_src, const void *v_src, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
+                             int kv_heads, int hd, int src_max_keys, int key0, int nkeys, void *stream) {
+    return kv_pages_copy("tce_kv_pages_scatter_f16", false, const_cast<void *>(k_src), const_cast<void *>(v_src), k_pool, v_pool, table_row, table_stride, page_keys, num_pages,
+                         kv_heads, hd, src_max_keys, key0, nkeys, stream);
+}
+
+int tce_kv_pages_gather_f16(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
+                            int kv_heads, int hd, int dst_max_keys, int key0, int nkeys, void *stream) {
+    return kv_pages_copy("tce_kv_pages_gather_f16", true, k_dst, v_dst, const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, table_stride, page_keys, num_pages,
+                         kv_heads, hd, dst_max_keys, key0, nkeys, stream);
+}
+
+int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                             uint32_t *violations, void *stream) {
+    if (!block_table || !pos_device || !violations) return fail(TCE_ERR_BAD_ARG, "tce_kv_block_table_check: null pointer");
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "tce_kv_block_table_check: page_keys %d (a power of two from 16 to 256)", page_keys);
+    if (table_stride < 1 || num_pages < 1 || batch < 1 || pos_bound < 0) return fail(TCE_ERR_BAD_ARG, "tce_kv_block_table_check: need table_stride, num_pages, batch >= 1 and pos_bound >= 0");
+    if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(pos_device) | reinterpret_cast<uintptr_t>(violations)) & 3)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_kv_block_table_check: int32-aligned pointers");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_kv_block_table_check(block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "block table check launch") : rc;
+}
+
 int tce_attention_decode_step_deferred_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace, int heads,
                                            int kv_heads, int hd, int max_keys, const int32_t *pos_device, int pos, unsigned short alpha_bits, tce_attention_deferred *info, void *stream) {
     if (!qkv || !kc || !vc || !out || !workspace || !info) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_deferred_f16: null pointer");

@@ -268,6 +268,16 @@ size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys
 int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
                                   int kv_heads, int hd, int max_keys, const int *pos_dev, int pos_bound, unsigned short alpha_bits, hipStream_t stream,
                                   hipError_t *hip_err);
+// the paged step: the batched step with the caches in pools of pages [num_pages][kv_heads][page_keys][hd] behind a block table int32 [batch][table_stride]; its
+// companions: rows of a contiguous single-sequence pair <-> the pages of one table row (gather: pages -> contiguous), and the table check (*violations = count)
+size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd);
+int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
+                                  void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
+                                  hipStream_t stream, hipError_t *hip_err);
+int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
+                         int lin_max_keys, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err);
+int launch_kv_block_table_check(const int *table, int table_stride, int page_keys, int num_pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations,
+                                hipStream_t stream, hipError_t *hip_err);
 int launch_rope_half(void *q, void *k, const void *cosv, const void *sinv, int heads, int len, int hd, int start_idx, hipStream_t stream, hipError_t *hip_err);
 int launch_softmax_half(const void *x, void *out, long long rows, int n, hipStream_t stream, hipError_t *hip_err);
 int launch_prefetch(const void *ptr, long long bytes, int workgroups, hipStream_t stream, hipError_t *hip_err);

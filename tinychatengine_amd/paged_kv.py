@@ -1,0 +1,281 @@
+"""Paged KV cache for batched decode: keys and values in fixed-size pages drawn from one pool, a block table per sequence.
+
+BatchDecodeAttention reserves [batch][kv_heads][max_keys][128] per K and V and layer: every slot holds max_keys rows for its whole life.  Here a layer holds two
+pools [num_pages][kv_heads][page_keys][128] and the attention step (tce_attention_decode_step_paged_f16, csrc/attention_fast.hip) finds logical key j of
+sequence b in row j % page_keys of page table[b][j // page_keys].  Memory follows the tokens that exist, a retired sequence's pages go back to the pool, and full
+pages can be shared read-only between sequences (a common prompt).  The step is the batched step with another row base: every active row's output and appended
+rows are bit-identical to tce_attention_decode_step_batch_f16 on contiguous caches with the same contents.
+
+    PageAllocator              host bookkeeping (free list, reference counts, a page list per slot) + the device block table; ONE for all layers: every layer
+                               uses the same page numbers in its own pools
+    PagedBatchDecodeAttention  one layer's pools and workspace: step (one launch), admit (scatter from a contiguous cache), read_back (gather), copy_rows
+    PagedBatchedDecoder        BatchedDecoder's seven launches with the paged step as launch 3; prefill runs on a contiguous staging cache and scatters
+
+Trust: the step follows only table words 0 .. pos // page_keys of an active row; everything else in the table may hold anything (a released slot's words stay as
+they were).  It does not validate page numbers: PageAllocator writes only numbers in [0, num_pages), and PagedBatchDecodeAttention.table_violations runs
+tce_kv_block_table_check for a caller who wants the table checked on the device before a launch.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import capi
+from .attention_ops import DecodeAttention
+from .batch_decode import BatchedDecoder
+from .decoder_block import DecoderBlock
+from .linear import _stream
+
+
+class PagePoolExhausted(MemoryError):
+    """The pool has fewer free pages than the operation needs; nothing was changed."""
+
+
+class PageAllocator:
+    """`num_pages` pages of `page_keys` keys for `batch` slots of at most `max_pages_per_seq` pages each.  Works with device="cpu" (the table is then a host tensor)."""
+
+    def __init__(self, num_pages: int, page_keys: int, batch: int, max_pages_per_seq: int, device, free_order=None):
+        """free_order: the page numbers in the order they are handed out first (default 0, 1, 2, ...) -- a permutation of range(num_pages)."""
+        if page_keys not in (16, 32, 64, 128, 256):
+            raise ValueError(f"page_keys {page_keys}: a power of two from 16 to 256")
+        if num_pages < 1 or batch < 1 or max_pages_per_seq < 1:
+            raise ValueError("num_pages, batch and max_pages_per_seq must be positive")
+        order = list(range(num_pages)) if free_order is None else [int(p) for p in free_order]
+        if sorted(order) != list(range(num_pages)):
+            raise ValueError("free_order must be a permutation of range(num_pages)")
+        self.num_pages, self.page_keys, self.batch, self.max_pages_per_seq = num_pages, page_keys, batch, max_pages_per_seq
+        self.free = order[::-1]  # a stack: pop() hands out order[0] first, and a released page is the next one handed out
+        self.refcount = [0] * num_pages
+        self.pages: list[list[int]] = [[] for _ in range(batch)]
+        self.frozen = [0] * batch  # leading pages of a slot that are (or were) shared: read-only for it, never the target of an append
+        self.table = torch.zeros((batch, max_pages_per_seq), dtype=torch.int32, device=device)
+
+    # ---- queries ----
+    @property
+    def max_keys(self) -> int:
+        return self.max_pages_per_seq * self.page_keys
+
+    def pages_in_use(self) -> int:
+        return self.num_pages - len(self.free)
+
+    def appendable_pages(self, slot: int) -> list[int]:
+        """The pages of `slot` that an append may write: those behind its shared prefix."""
+        return self.pages[slot][self.frozen[slot]:]
+
+    # ---- operations ----
+    def reserve(self, slot: int, upto_pos: int) -> list[int]:
+        """Add pages to `slot` until key index `upto_pos` is covered; returns the pages added.  Only the changed table words are written (stream-ordered)."""
+        self._slot(slot)
+        need = upto_pos // self.page_keys + 1
+        if upto_pos < 0 or need > self.max_pages_per_seq:
+            raise ValueError(f"key index {upto_pos} outside a slot's {self.max_keys} keys")
+        have = len(self.pages[slot])
+        if need - have > len(self.free):
+            raise PagePoolExhausted(f"{need - have} pages needed for slot {slot}, {len(self.free)} free")
+        added = [self.free.pop() for _ in range(need - have)]
+        for p in added:
+            assert self.refcount[p] == 0
+            self.refcount[p] = 1
+        self.pages[slot] += added
+        if added:
+            self._write(slot, have, added)
+        target = self.pages[slot][upto_pos // self.page_keys]
+        assert self.refcount[target] == 1 and upto_pos // self.page_keys >= self.frozen[slot], f"slot {slot}: key {upto_pos} lies in a shared page ({target})"
+        return added
+
+    def release(self, slot: int) -> list[int]:
+        """Drop the slot's references; returns the pages that went back to the free list.  The slot's table words are left as they are (an inactive row's words are
+        never followed)."""
+        self._slot(slot)
+        freed = []
+        for p in self.pages[slot]:
+            assert self.refcount[p] > 0
+            self.refcount[p] -= 1
+            if self.refcount[p] == 0:
+                freed.append(p)
+        self.free += freed[::-1]  # (the slot's first page is the next one handed out)
+        self.pages[slot] = []
+        self.frozen[slot] = 0
+        return freed
+
+    def fork(self, src_slot: int, dst_slot: int, keys: int) -> list[tuple[int, int, int]]:
+        """`dst_slot` (empty) starts as a copy of the first `keys` keys of `src_slot`: the full pages among them are shared (reference counts raised), a partial last
+        page gets a fresh page of dst's own.  Returns the copies the caller must carry out in every layer: [(src page, dst page, rows)] (empty when keys is a
+        multiple of page_keys)."""
+        self._slot(src_slot)
+        self._slot(dst_slot)
+        if src_slot == dst_slot or self.pages[dst_slot]:
+            raise ValueError("fork needs an empty destination slot other than the source")
+        if keys < 0 or keys > len(self.pages[src_slot]) * self.page_keys:
+            raise ValueError(f"slot {src_slot} does not hold {keys} keys")
+        full, rows = divmod(keys, self.page_keys)
+        if rows and not self.free:
+            raise PagePoolExhausted(f"1 page needed for slot {dst_slot}, 0 free")
+        shared = self.pages[src_slot][:full]
+        for p in shared:
+            self.refcount[p] += 1
+        mine, copies = list(shared), []
+        if rows:
+            fresh = self.free.pop()
+            assert self.refcount[fresh] == 0
+            self.refcount[fresh] = 1
+            mine.append(fresh)
+            copies.append((self.pages[src_slot][full], fresh, rows))
+        self.pages[dst_slot] = mine
+        self.frozen[dst_slot] = full
+        self.frozen[src_slot] = max(self.frozen[src_slot], full)
+        if mine:
+            self._write(dst_slot, 0, mine)
+        return copies
+
+    def check_invariants(self) -> None:
+        """No page both free and referenced, counts equal to the slot lists, no shared page appendable, the table's live words equal to the slot lists."""
+        counts = [0] * self.num_pages
+        for ps in self.pages:
+            assert len(ps) <= self.max_pages_per_seq and len(set(ps)) == len(ps)
+            for p in ps:
+                counts[p] += 1
+        assert counts == self.refcount
+        assert len(set(self.free)) == len(self.free) and all(self.refcount[p] == 0 for p in self.free)
+        assert len(self.free) + sum(1 for c in counts if c) == self.num_pages
+        host = self.table.cpu().numpy()
+        for s, ps in enumerate(self.pages):
+            assert all(self.refcount[p] == 1 for p in self.appendable_pages(s))
+            assert host[s, :len(ps)].tolist() == ps
+
+    # ---- internals ----
+    def _slot(self, slot: int) -> None:
+        if not 0 <= slot < self.batch:
+            raise IndexError(f"slot {slot} of {self.batch}")
+
+    def _write(self, slot: int, first: int, pages: list[int]) -> None:
+        # a copy on the current stream: ordered after the launches already issued that read the old words, before the ones issued next
+        self.table[slot, first:first + len(pages)].copy_(torch.tensor(pages, dtype=torch.int32))
+
+
+class PagedBatchDecodeAttention:
+    """One layer's K and V pools and the step's workspace, over a PageAllocator's table."""
+
+    def __init__(self, allocator: PageAllocator, heads: int, kv_heads: int | None, device, cos: torch.Tensor | None = None, sin: torch.Tensor | None = None):
+        self.allocator, self.batch, self.heads, self.hd = allocator, allocator.batch, heads, 128
+        self.kv_heads = heads if kv_heads is None else kv_heads
+        self.page_keys, self.num_pages, self.max_keys = allocator.page_keys, allocator.num_pages, allocator.max_keys
+        L = capi.lib()
+        if int(L.tce_kv_pages_pool_bytes(self.num_pages, self.kv_heads, self.page_keys, self.hd)) == 0:
+            raise ValueError("unsupported page pool shape")
+        need = int(L.tce_attention_decode_batch_workspace_bytes(self.batch, heads, self.max_keys, self.hd))
+        if need == 0:
+            raise ValueError("unsupported batched attention shape")
+        self.k_pool = torch.zeros((self.num_pages, self.kv_heads, self.page_keys, self.hd), dtype=torch.float16, device=device)
+        self.v_pool = torch.zeros_like(self.k_pool)
+        self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)  # zeroed once: the per-(sequence, head) arrival counters
+        self.slot_workspace_bytes = need // self.batch
+        self.cos, self.sin = cos, sin
+        self.alpha_bits = int(np.array([1.0 / np.sqrt(self.hd)], np.float16).view(np.uint16)[0])
+        self._staging: DecodeAttention | None = None
+        self._violations = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _table_args(self):
+        t = self.allocator.table
+        assert t.is_cuda and t.device == self.k_pool.device
+        return C.c_void_p(t.data_ptr()), t.shape[1], self.page_keys, self.num_pages
+
+    def step(self, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """BatchDecodeAttention.step on the pages: one launch; the table is read when the kernel runs."""
+        rw = (self.heads + 2 * self.kv_heads) * self.hd
+        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == self.batch * rw
+        assert pos_device.dtype == torch.int32 and pos_device.is_cuda and pos_device.is_contiguous() and pos_device.numel() == self.batch
+        if out is None:
+            out = torch.empty((self.batch, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == self.batch * self.heads * self.hd
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        capi.check(capi.lib().tce_attention_decode_step_paged_f16(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out),
+                                                                  p(self.workspace), self.batch, self.heads, self.kv_heads, self.hd, p(pos_device), int(pos_bound),
+                                                                  self.alpha_bits, C.c_void_p(_stream())))
+        return out
+
+    def table_violations(self, pos_device: torch.Tensor, pos_bound: int) -> int:
+        """tce_kv_block_table_check on the allocator's table, waited for: the number of words the step would follow that are not page numbers (0: sound)."""
+        tab, stride, pk, n = self._table_args()
+        capi.check(capi.lib().tce_kv_block_table_check(tab, stride, pk, n, self.batch, C.c_void_p(pos_device.data_ptr()), int(pos_bound),
+                                                       C.c_void_p(self._violations.data_ptr()), C.c_void_p(_stream())))
+        return int(self._violations.item())
+
+    def _row(self, slot: int) -> C.c_void_p:
+        t = self.allocator.table
+        if not 0 <= slot < self.batch:
+            raise IndexError(f"slot {slot} of {self.batch}")
+        return C.c_void_p(t.data_ptr() + slot * t.shape[1] * 4)
+
+    def admit(self, slot: int, contiguous_attention, key0: int, nkeys: int) -> None:
+        """Scatter rows [key0, key0 + nkeys) of a contiguous single-sequence cache pair (a DecodeAttention's k_cache / v_cache) into the slot's pages (reserved
+        before: PageAllocator.reserve(slot, key0 + nkeys - 1))."""
+        k, v = contiguous_attention.k_cache, contiguous_attention.v_cache
+        assert k.dtype == v.dtype == torch.float16 and k.is_contiguous() and v.is_contiguous() and tuple(k.shape) == tuple(v.shape) and k.shape[0] == self.kv_heads
+        assert (key0 + nkeys - 1) // self.page_keys < len(self.allocator.pages[slot]), "reserve the slot's pages first"
+        p = lambda t: C.c_void_p(t.data_ptr())
+        capi.check(capi.lib().tce_kv_pages_scatter_f16(p(k), p(v), p(self.k_pool), p(self.v_pool), self._row(slot), self.allocator.table.shape[1], self.page_keys,
+                                                       self.num_pages, self.kv_heads, self.hd, k.shape[1], int(key0), int(nkeys), C.c_void_p(_stream())))
+
+    def gather_into(self, slot: int, contiguous_attention, key0: int, nkeys: int) -> None:
+        """The reverse of admit: the slot's rows [key0, key0 + nkeys) into a contiguous cache pair."""
+        k, v = contiguous_attention.k_cache, contiguous_attention.v_cache
+        assert k.dtype == v.dtype == torch.float16 and k.is_contiguous() and v.is_contiguous() and tuple(k.shape) == tuple(v.shape) and k.shape[0] == self.kv_heads
+        assert (key0 + nkeys - 1) // self.page_keys < len(self.allocator.pages[slot]), "the slot does not hold these keys"
+        p = lambda t: C.c_void_p(t.data_ptr())
+        capi.check(capi.lib().tce_kv_pages_gather_f16(p(self.k_pool), p(self.v_pool), p(k), p(v), self._row(slot), self.allocator.table.shape[1], self.page_keys,
+                                                      self.num_pages, self.kv_heads, self.hd, k.shape[1], int(key0), int(nkeys), C.c_void_p(_stream())))
+
+    def read_back(self, slot: int, keys: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """The slot's first `keys` keys as a fresh contiguous pair [kv_heads][keys][128]."""
+        class _Pair:
+            pass
+        pair = _Pair()
+        pair.k_cache = torch.zeros((self.kv_heads, keys, self.hd), dtype=torch.float16, device=self.k_pool.device)
+        pair.v_cache = torch.zeros_like(pair.k_cache)
+        self.gather_into(slot, pair, 0, keys)
+        return pair.k_cache, pair.v_cache
+
+    def copy_rows(self, src_page: int, dst_page: int, rows: int) -> None:
+        """PageAllocator.fork's copy for this layer: the first `rows` rows of every head of src_page into dst_page."""
+        assert 0 <= src_page < self.num_pages and 0 <= dst_page < self.num_pages and src_page != dst_page and 0 < rows <= self.page_keys
+        self.k_pool[dst_page, :, :rows].copy_(self.k_pool[src_page, :, :rows])
+        self.v_pool[dst_page, :, :rows].copy_(self.v_pool[src_page, :, :rows])
+
+    def staging(self) -> DecodeAttention:
+        """The contiguous single-sequence cache that prefill runs on (one per layer, max_keys rows, made on first use)."""
+        if self._staging is None:
+            self._staging = DecodeAttention(self.heads, self.hd, self.max_keys, self.k_pool.device, self.cos, self.sin, kv_heads=self.kv_heads)
+        return self._staging
+
+    def slot(self, b: int) -> DecodeAttention:
+        """What BatchedDecoder.prefill runs a slot's prefill on: the staging cache (PagedBatchedDecoder.prefill gathers before and scatters after)."""
+        if not 0 <= b < self.batch:
+            raise IndexError(f"slot {b} of {self.batch}")
+        return self.staging()
+
+
+class PagedBatchedDecoder(BatchedDecoder):
+    """BatchedDecoder on a paged cache: the same seven launches per layer (BatchedDecoder.step itself, with PagedBatchDecodeAttention.step as launch 3), the same
+    prefill launches on a contiguous staging cache.  One PageAllocator serves the decoders of all layers."""
+
+    def __init__(self, block: DecoderBlock, allocator: PageAllocator):  # (no BatchedDecoder.__init__: it would allocate the contiguous caches)
+        self.block, self.batch, self.allocator = block, allocator.batch, allocator
+        dev = block.gamma1.device
+        self.attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, dev, block.attention.cos, block.attention.sin)
+        e = lambda n: torch.empty((self.batch, n), dtype=torch.float16, device=dev)
+        self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
+        self.act = e(block.ffn)
+        self._up = None
+
+    def prefill(self, slot: int, rows: torch.Tensor, pos: int) -> None:
+        """Admit a sequence into `slot`: BatchedDecoder.prefill's launches on the staging cache -- on top of the slot's `pos` cached keys, gathered first -- and the
+        new rows pos .. pos + m - 1 scattered into the slot's pages (reserved here; the allocator is shared, so the first layer's call reserves for all)."""
+        m = rows.shape[0]
+        self.allocator.reserve(slot, pos + m - 1)
+        if pos > 0:
+            self.attention.gather_into(slot, self.attention.staging(), 0, pos)
+        super().prefill(slot, rows, pos)
+        self.attention.admit(slot, self.attention.staging(), pos, m)
