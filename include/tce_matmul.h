@@ -308,6 +308,31 @@ TCE_API size_t tce_attention_prefill_workspace_bytes(int heads, int m, int head_
 TCE_API int tce_attention_prefill_f16(const void *qkv, int ld_qkv, void *k_cache, void *v_cache, const void *cos_table, const void *sin_table, const void *mask,
                                       int ld_mask, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, int head_dim, int max_keys,
                                       int pos, int m, unsigned short alpha_half_bits, void *stream);
+/* The PAGED prefill: the two launches above on the paged step's pools and block table (k_pool / v_pool [num_pages][kv_heads][page_keys][head_dim], block_table int32
+ * [table_rows][table_stride], as for tce_attention_decode_step_paged_f16), for up to TCE_PREFILL_MAX_SEGMENTS sequences at once.  No staging cache, no gather, no
+ * scatter: appended rows go straight into their pages, key tiles are read through the table.
+ *   segments   a HOST array, read at the call: segment i is m new rows -- rows row0 .. row0 + m - 1 of qkv and out -- on top of pos cached keys of table row `slot`.
+ *              Distinct slots, disjoint row ranges inside [0, total_rows); rows of qkv that belong to no segment are skipped.
+ *   qkv, out   fp16 [total_rows][ld_qkv] / [total_rows][ld_out] as for tce_attention_prefill_f16; workspace: tce_attention_prefill_paged_workspace_bytes(heads,
+ *              total_rows, head_dim) bytes (the rotated queries [heads][total_rows][head_dim])
+ *   causal     0 or non-zero, as above; the paged form takes no additive mask
+ * Every segment's output rows and appended cache rows are bit-identical to tce_attention_prefill_f16 (mask NULL) for that sequence alone on a contiguous cache with the
+ * same contents.  Trust, as for the paged step: of a segment's table row only words 0 .. (pos + m - 1) / page_keys ever become addresses; rows of the last page at and
+ * beyond pos + m may hold anything; no pool row other than rows pos .. pos + m - 1 of each segment is written; page numbers are NOT validated
+ * (tce_kv_block_table_check).  A launch lists at most 1024 query blocks (of 64 rows, or 128 once the launch has 512 of those over all heads):
+ * TCE_ERR_UNSUPPORTED_SHAPE beyond -- several calls.  Every other refusal happens before any HIP call and tce_last_error() names the segment.
+ * tce_attention_prefill_describe_paged: "form=F rows-per-block=R pair=yes|no blocks=B workgroups=W segments=S" for such a launch (a thread-local buffer; NULL and
+ * tce_last_error() for a refused list; no HIP call).  With one segment, form and pairing are what tce_attention_prefill_f16 chooses for the same heads, m, causal. */
+#define TCE_PREFILL_MAX_SEGMENTS 16
+typedef struct tce_prefill_segment {
+    int32_t slot, pos, m, row0;
+} tce_prefill_segment;
+TCE_API size_t tce_attention_prefill_paged_workspace_bytes(int heads, int total_rows, int head_dim);
+TCE_API int tce_attention_prefill_paged_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                            int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out, void *workspace,
+                                            int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments, int total_rows,
+                                            unsigned short alpha_half_bits, void *stream);
+TCE_API const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int causal, const tce_prefill_segment *segments, int num_segments);
 /* Reads [ptr, ptr + bytes) with at most `workgroups` workgroups (0 = as many as the range needs) and discards the data: the
  * range then sits in the memory-side cache (256 MiB) for the launch that needs it.  Meant for a side stream / graph branch
  * next to the launch BEFORE that one (no reference counterpart: cudaMallocManaged prefetching is the closest idea). */

@@ -124,6 +124,10 @@ class BatchedDecoder:
     def prefill(self, slot: int, rows: torch.Tensor, pos: int) -> None:
         """Admit a sequence into `slot`: rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated in place -- DecoderBlock.prefill's launches on the
         slot's caches."""
+        self._prefill_rows(rows, lambda qkv, attn: self.attention.slot(slot).prefill(qkv, pos, out=attn, causal=True))
+
+    def _prefill_rows(self, rows: torch.Tensor, attend) -> None:
+        """prefill's launches over `rows`; attend(qkv, attn) is the attention in the middle (the paged decoder's serves several sequences' rows at once)."""
         blk = self.block
         m = rows.shape[0]
         assert rows.dtype == torch.float16 and rows.is_contiguous() and rows.shape[1] == blk.hidden
@@ -132,7 +136,7 @@ class BatchedDecoder:
         xn, qkv, attn, g, u = e(blk.hidden), e((blk.heads + 2 * blk.kv_heads) * 128), e(blk.hidden), e(blk.ffn), e(blk.ffn)
         rmsnorm_half(rows, blk.gamma1, blk.eps, out=xn)
         capi.check(capi.w4a16_forward(blk.qkv.desc(xn, qkv), st))
-        self.attention.slot(slot).prefill(qkv, pos, out=attn, causal=True)
+        attend(qkv, attn)
         capi.check(capi.w4a16_forward(blk.o.desc(attn, rows, flags=capi.TCE_W4_ADD_TO_C), st))
         rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
         if m > 128 and blk.gate_up.packed is not None:

@@ -30,6 +30,14 @@
 //     row per lane -- and ran 158 us at 2048 rows; this one 130.)
 // Grouped-query attention: query head i reads key / value head i / (heads / kv_heads); the workgroups of a group stage the same tiles (L2).
 // Rows of the caches at and beyond pos + m may hold anything (uninitialised memory): staged as zeros, and their scores are cut.
+//
+// The PAGED form of both launches (tce_attention_prefill_paged_f16): the caches are the paged step's pools [num_pages][kv_heads][page_keys][hd] behind a block table
+// (attention_fast.hip), and one launch serves up to kMaxSegments sequences -- a segment is {slot, pos, m, row0}: m new rows, rows row0 .. row0 + m - 1 of qkv / out, on
+// top of pos cached keys of table row `slot`.  Only a row's ADDRESS changes: what is appended and what comes out is bit-identical to the contiguous launch of each
+// segment alone.  Trust, as for the paged step: of a segment's table row only words 0 .. (pos + m - 1) / page_keys become addresses, no page number is validated, and no
+// pool row other than rows pos .. pos + m - 1 of each segment is written.
+#include <algorithm>
+
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
 
@@ -52,19 +60,60 @@ struct PrepareArgs {
     int heads, kv_heads, max_keys, pos, m;
 };
 
+// tce_prefill_segment's layout (include/tce_matmul.h)
+struct PrefillSegment {
+    int slot, pos, m, row0;
+};
+constexpr int kMaxSegments = 16;          // TCE_PREFILL_MAX_SEGMENTS
+constexpr int kMaxListedBlocks = 1024;    // query blocks of one paged launch (their order travels in the kernel arguments)
+
+// the paged prepare's arguments: the rows of every segment in one launch
+struct PagedPrepareArgs {
+    const half_t *qkv;  // [total_rows][ld_qkv]
+    int ld_qkv;
+    half_t *qrot;       // [heads][total_rows][hd]
+    half_t *kc, *vc;    // the pools [num_pages][kv_heads][page_keys][hd]
+    const half_t *cosv, *sinv;
+    const int *table;   // int32 [table_rows][table_stride]
+    int table_stride, page_shift;
+    int heads, kv_heads, total_rows, nseg;
+    PrefillSegment seg[kMaxSegments];
+};
+
 // one thread per 16-byte piece of a (row, head slot): rotation as RotaryPosEmb_cuda_forward (hd = 128: the partner half is piece ^ 8)
-__global__ __launch_bounds__(256) void attn_prefill_prepare_kernel(const PrepareArgs a) {
+// PAGED: row r belongs to the segment whose row range holds it (a row in none is skipped), its position is that segment's pos + (r - row0), and the appended row goes
+// to the page the segment's table row names for that position.
+template <bool PAGED = false>
+__global__ __launch_bounds__(256) void attn_prefill_prepare_kernel(const std::conditional_t<PAGED, PagedPrepareArgs, PrepareArgs> a) {
     const int slots = a.heads + 2 * a.kv_heads;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)a.m * slots * 16) return;
+    int rows;
+    if constexpr (PAGED) rows = a.total_rows;
+    else rows = a.m;
+    if (idx >= (long long)rows * slots * 16) return;
     const int piece = (int)(idx & 15);
     const int hs = (int)((idx >> 4) % slots), r = (int)((idx >> 4) / slots);
+    int key;            // the row's position: its key index in the cache
+    int slot = 0;
+    if constexpr (PAGED) {
+        key = -1;
+        for (int s = 0; s < a.nseg; ++s) {
+            const int d = r - a.seg[s].row0;
+            if (d >= 0 && d < a.seg[s].m) {
+                key = a.seg[s].pos + d;
+                slot = a.seg[s].slot;
+            }
+        }
+        if (key < 0) return;
+    } else {
+        key = a.pos + r;
+    }
     const half_t *src = a.qkv + (size_t)r * a.ld_qkv + (size_t)hs * kHD;
     half8_t v = *reinterpret_cast<const half8_t *>(src + piece * 8);
     if (hs < a.heads + a.kv_heads && a.cosv) {
         const half8_t p = *reinterpret_cast<const half8_t *>(src + (piece ^ 8) * 8);
-        const half8_t c = *reinterpret_cast<const half8_t *>(a.cosv + (size_t)(a.pos + r) * kHD + piece * 8);
-        const half8_t s = *reinterpret_cast<const half8_t *>(a.sinv + (size_t)(a.pos + r) * kHD + piece * 8);
+        const half8_t c = *reinterpret_cast<const half8_t *>(a.cosv + (size_t)key * kHD + piece * 8);
+        const half8_t s = *reinterpret_cast<const half8_t *>(a.sinv + (size_t)key * kHD + piece * 8);
         half8_t o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -75,9 +124,20 @@ __global__ __launch_bounds__(256) void attn_prefill_prepare_kernel(const Prepare
         v = o;
     }
     half_t *dst;
-    if (hs < a.heads) dst = a.qrot + ((size_t)hs * a.m + r) * kHD;
-    else if (hs < a.heads + a.kv_heads) dst = a.kc + ((size_t)(hs - a.heads) * a.max_keys + a.pos + r) * kHD;
-    else dst = a.vc + ((size_t)(hs - a.heads - a.kv_heads) * a.max_keys + a.pos + r) * kHD;
+    if constexpr (PAGED) {
+        if (hs < a.heads) {
+            dst = a.qrot + ((size_t)hs * a.total_rows + r) * kHD;
+        } else {
+            const int page = a.table[(size_t)slot * a.table_stride + (key >> a.page_shift)];
+            const int h = hs < a.heads + a.kv_heads ? hs - a.heads : hs - a.heads - a.kv_heads;
+            const size_t off = ((((size_t)page * a.kv_heads + h) << a.page_shift) + (key & ((1 << a.page_shift) - 1))) * kHD;
+            dst = (hs < a.heads + a.kv_heads ? a.kc : a.vc) + off;
+        }
+    } else {
+        if (hs < a.heads) dst = a.qrot + ((size_t)hs * a.m + r) * kHD;
+        else if (hs < a.heads + a.kv_heads) dst = a.kc + ((size_t)(hs - a.heads) * a.max_keys + a.pos + r) * kHD;
+        else dst = a.vc + ((size_t)(hs - a.heads - a.kv_heads) * a.max_keys + a.pos + r) * kHD;
+    }
     *reinterpret_cast<half8_t *>(dst + piece * 8) = v;
 }
 
@@ -90,6 +150,22 @@ struct PrefillArgs {
     int heads, rep, max_keys, pos, m, causal;
     int pair;  // a workgroup takes two query blocks (see attn_prefill_kernel)
     float alpha;
+};
+
+// the paged attention launch's arguments.  `order` lists the launch's query blocks, heaviest (most key tiles) first: entry i = segment << 12 | query block, two
+// entries per word; workgroup i takes entry i and, paired, entry nblocks - 1 - i after it.
+struct PagedPrefillArgs {
+    const half_t *qrot;      // [heads][total_rows][hd]
+    const half_t *kc, *vc;   // the pools
+    half_t *out;             // [total_rows][ld_out]
+    const int *table;        // int32 [table_rows][table_stride]
+    int ld_out;
+    int heads, rep, kv_heads, total_rows, causal;
+    int pair;
+    int table_stride, page_shift, nblocks;
+    float alpha;
+    PrefillSegment seg[kMaxSegments];
+    unsigned order[kMaxListedBlocks / 2];
 };
 
 template <int CTRL>
@@ -138,8 +214,53 @@ __device__ __forceinline__ float quad_sum(float v) {
     return v;
 }
 
-template <bool MASK, int NW, int RT>
-__device__ __forceinline__ void attn_prefill_block(const PrefillArgs &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+// PAGED: query block qb of one segment of a paged launch (PagedBlockArgs).  The rows of qrot / out are the segment's (row0 + ...), and a key row's address comes
+// from the segment's table row: a tile of 64 keys is four runs of 16 keys, each inside one page (page_keys is a power of two >= 16), so a tile needs four table
+// words -- one load per tile and wave, requested a whole tile ahead of the row requests that use them (TileWords), so that no row request ever waits for a table
+// word.  Everything behind the fetch is the contiguous kernel's.
+// (The paged kernel hands the block a PagedBlockArgs: the launch's arguments with one segment's pos / m / row0 / table row filled in, so that the statements both forms
+// share read a.pos and a.m as they always did -- the contiguous instantiations compile to the instructions they compiled to before the flag existed.)
+struct PagedBlockArgs {
+    const half_t *qrot, *kc, *vc;
+    half_t *out;
+    const int *trow;  // the segment's table row
+    int ld_out, rep, kv_heads, total_rows, row0, pos, m, causal, page_shift;
+    float alpha;
+};
+
+// what differs between the forms in the statements they share: the row count and first row of the segment inside qrot / out, and a key / value head's base
+__device__ __forceinline__ int qrows(const PrefillArgs &a) { return a.m; }
+__device__ __forceinline__ int qrows(const PagedBlockArgs &a) { return a.total_rows; }
+__device__ __forceinline__ int qrow0(const PrefillArgs &) { return 0; }
+__device__ __forceinline__ int qrow0(const PagedBlockArgs &a) { return a.row0; }
+__device__ __forceinline__ int head_keys(const PrefillArgs &a) { return a.max_keys; }
+__device__ __forceinline__ int head_keys(const PagedBlockArgs &) { return 0; }  // (the head is part of a page's address: both bases are the pools')
+
+// The table words of the four 16-key runs of one tile: lane l holds the word of run l % 4, fetched with ONE vector load whose request follows the row requests
+// of the tile before -- vector loads return in order, so the word is there when those rows are (the wait in front of the LDS writes).  latch() moves the four words
+// to scalars right behind that wait, unconditionally and outside the row requests' branches: no wait of its own, ever, and the compiler can see that the register is
+// free again when the next request is issued.  (Measured first: scalar loads in front of the tile's first barrier -- the barrier's s_waitcnt lgkmcnt(0) waited for
+// them at every tile, 6-16 % of the launch; then v_readlane inside the `key < kend` branches -- the compiler waited for ALL outstanding rows before each one.)
+// Word indices are clamped to the last word the block may follow, (kend - 1) / page_keys: a run wholly at or beyond kend requests no row.
+template <bool PAGED>
+struct TileWords {};
+template <>
+struct TileWords<true> {
+    int v, w[4];
+    __device__ __forceinline__ void request(const PagedBlockArgs &a, int kt, int kend, int lane) {
+        const int lastw = (kend - 1) >> a.page_shift;
+        const int e = (kt * kBK + 16 * (lane & 3)) >> a.page_shift;
+        v = a.trow[e < lastw ? e : lastw];
+    }
+    __device__ __forceinline__ void latch() {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = __builtin_amdgcn_readlane(v, r);
+    }
+};
+
+template <bool MASK, int NW, int RT, bool PAGED = false>
+__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+    static_assert(!PAGED || !MASK, "the paged form takes no additive mask");
     constexpr int kBQ = 16 * RT * NW, NT = 64 * NW, KI = 1024 / NT;
     constexpr float kLog2e = 1.4426950408889634f;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -161,7 +282,7 @@ __device__ __forceinline__ void attn_prefill_block(const PrefillArgs &a, const i
     for (int t = 0; t < RT; ++t) {
         const int row = r0 + 16 * t + n16;
         rowc[t] = row < a.m ? row : a.m - 1;
-        const half_t *qrow = a.qrot + ((size_t)head * a.m + rowc[t]) * kHD;
+        const half_t *qrow = a.qrot + ((size_t)head * qrows(a) + qrow0(a) + rowc[t]) * kHD;
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[t][s] = *reinterpret_cast<const half8_t *>(qrow + 32 * s + 8 * quad);
     }
@@ -174,7 +295,8 @@ __device__ __forceinline__ void attn_prefill_block(const PrefillArgs &a, const i
         m_i[t] = kNegBig;
         l_i[t] = 0.f;
     }
-    const half_t *kbase = a.kc + (size_t)kvh * a.max_keys * kHD, *vbase = a.vc + (size_t)kvh * a.max_keys * kHD;
+    const half_t *kbase = a.kc + (size_t)kvh * head_keys(a) * kHD, *vbase = a.vc + (size_t)kvh * head_keys(a) * kHD;
+    TileWords<PAGED> tw;  // PAGED: the table words of the tile that is fetched next
 
     // a tile's global loads, K and V alike: piece idx = tid + NT i -> key idx / 16, piece idx % 16 (coalesced rows).  The loads of tile kt + 1 are requested
     // before tile kt is multiplied (registers) and written to LDS once every wave is done with tile kt.  (A ring of 3-4 register sets, tiles requested that
@@ -188,12 +310,28 @@ __device__ __forceinline__ void attn_prefill_block(const PrefillArgs &a, const i
             kreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
             vreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
             if (gk < kend) {
-                kreg[i] = *reinterpret_cast<const half8_t *>(kbase + (size_t)gk * kHD + (idx & 15) * 8);
-                vreg[i] = *reinterpret_cast<const half8_t *>(vbase + (size_t)gk * kHD + (idx & 15) * 8);
+                if constexpr (PAGED) {
+                    // the piece's run of the tile: i with 4 waves (a pass of 256 pieces is 16 keys), 2 i + wave / 4 with 8 -- wave-uniform, so the page is a scalar
+                    const int page = NT == 256 ? tw.w[i] : (wave >= 4 ? tw.w[(2 * i + 1) & 3] : tw.w[(2 * i) & 3]);
+                    const int run0 = key0 + 16 * (NT == 256 ? i : 2 * i + (wave >> 2));
+                    const size_t off = ((((size_t)page * a.kv_heads + kvh) << a.page_shift) + (run0 & ((1 << a.page_shift) - 1))) * kHD;
+                    // (the lane's offset inside a 16-key run: row (tid / 16) % 16, its 16-byte piece -- the same for every tile)
+                    const unsigned lane_off = (unsigned)(((tid >> 4) & 15) * kHD + (tid & 15) * 8);
+                    kreg[i] = *reinterpret_cast<const half8_t *>(kbase + off + lane_off);
+                    vreg[i] = *reinterpret_cast<const half8_t *>(vbase + off + lane_off);
+                } else {
+                    kreg[i] = *reinterpret_cast<const half8_t *>(kbase + (size_t)gk * kHD + (idx & 15) * 8);
+                    vreg[i] = *reinterpret_cast<const half8_t *>(vbase + (size_t)gk * kHD + (idx & 15) * 8);
+                }
             }
         }
     };
+    if constexpr (PAGED) {
+        tw.request(a, 0, kend, lane);  // (the one table round trip a block waits for)
+        tw.latch();
+    }
     fetch_tile(0);
+    if constexpr (PAGED) tw.request(a, 1, kend, lane);
     // this lane's piece of a [4 keys][16 head dimensions] block for the transpose read: key 4 quad + n16 / 4, head dimensions 4 (n16 % 4) ..
     const unsigned char *vfrag = vs + (4 * quad + (n16 >> 2)) * kVStride + (n16 & 3) * 8;
     for (int kt = 0; kt < ntiles; ++kt) {
@@ -206,8 +344,10 @@ __device__ __forceinline__ void attn_prefill_block(const PrefillArgs &a, const i
             *reinterpret_cast<half8_t *>(ks + (idx >> 4) * kKStride + (idx & 15) * 16) = kreg[i];
             *reinterpret_cast<half8_t *>(vs + (idx >> 4) * kVStride + (idx & 15) * 16) = vreg[i];
         }
+        if constexpr (PAGED) tw.latch();  // tile kt + 1's words arrived with tile kt's rows
         __syncthreads();
         if (kt + 1 < ntiles) fetch_tile(kt + 1);
+        if constexpr (PAGED) tw.request(a, kt + 2, kend, lane);  // behind tile kt + 1's row requests, for the fetch a tile from now
         // ---- S^T = K Q^T (64 keys x this wave's 16 RT rows): a K fragment feeds the RT row tiles ----
         float4_t sacc[RT][4];
 #pragma unroll
@@ -298,7 +438,7 @@ __device__ __forceinline__ void attn_prefill_block(const PrefillArgs &a, const i
         const float inv = l > 0.f ? 1.0f / l : 0.f;
         const int row = r0 + 16 * t + n16;
         if (row >= a.m) continue;
-        half_t *orow = a.out + (size_t)row * a.ld_out + (size_t)head * kHD;
+        half_t *orow = a.out + (size_t)(qrow0(a) + row) * a.ld_out + (size_t)head * kHD;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const half4_t v = half4_t{(half_t)(o[t][c][0] * inv), (half_t)(o[t][c][1] * inv), (half_t)(o[t][c][2] * inv), (half_t)(o[t][c][3] * inv)};
@@ -327,6 +467,48 @@ __global__ __launch_bounds__(64 * NW) void attn_prefill_kernel(const PrefillArgs
     }
 }
 
+// The paged launch: workgroup i takes entry i of the launch's block list (heaviest first) and, when `pair` is set, entry nblocks - 1 - i after it.  With one
+// segment the list is that segment's blocks nb - 1 .. 0: the contiguous launch's order and pairs.
+__device__ __forceinline__ PagedBlockArgs paged_block_args(const PagedPrefillArgs &a, const PrefillSegment sg) {
+    PagedBlockArgs b;
+    b.qrot = a.qrot;
+    b.kc = a.kc;
+    b.vc = a.vc;
+    b.out = a.out;
+    b.trow = a.table + (size_t)sg.slot * a.table_stride;
+    b.ld_out = a.ld_out;
+    b.rep = a.rep;
+    b.kv_heads = a.kv_heads;
+    b.total_rows = a.total_rows;
+    b.row0 = sg.row0;
+    b.pos = sg.pos;
+    b.m = sg.m;
+    b.causal = a.causal;
+    b.page_shift = a.page_shift;
+    b.alpha = a.alpha;
+    return b;
+}
+
+// (waves per SIMD: the paired 8-wave form is pinned to the 3 its contiguous counterpart has.  Left alone it fits 126 registers, the compiler then keeps the schedule
+//  it made for a fourth wave -- two K fragments read ahead of the MFMAs instead of six -- and the launch at 2048 rows took 108 us against the contiguous 93, though a
+//  paired launch is one such workgroup per CU whatever its registers.  Every other form lands on its counterpart's occupancy by itself: 1 .. 8 leaves it alone.)
+template <int NW, int RT, bool PAIR>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((PAIR && NW == 8 && RT == 1) ? 3 : 1, (PAIR && NW == 8 && RT == 1) ? 3 : 8)))
+void attn_prefill_paged_kernel(const PagedPrefillArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile
+    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
+    const int i = (int)blockIdx.x;
+    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
+    attn_prefill_block<false, NW, RT, true>(paged_block_args(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
+    if constexpr (PAIR) {
+        const int j = a.nblocks - 1 - i;
+        if (i < j) {
+            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
+            attn_prefill_block<false, NW, RT, true>(paged_block_args(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
+        }
+    }
+}
+
 thread_local int g_prefill_pair = 0;   // 0: by the rule; 1 / 2: pairing forced on / off
 thread_local int g_prefill_waves = 0;  // 0: by the rule in launch_attention_prefill; forced (tests, sweeps): 4 / 8 waves with one row tile per wave, 14 / 18: with two
 
@@ -342,6 +524,24 @@ size_t attention_prefill_workspace_bytes(int heads, int m, int hd) {
     if (hd != kHD || heads <= 0 || m <= 0) return 0;
     return (size_t)heads * m * kHD * sizeof(half_t);
 }
+
+namespace {
+
+// The block form (4 / 8 waves x 1 row tile; 14 / 18: x 2, forced only) and the pairing of a launch whose query blocks number blocks(rows) at `rows` rows per block
+// (all heads counted) -- ONE rule for the contiguous and the paged launch.
+template <class F>
+void prefill_form_rule(F blocks, int causal, int *form_out, int *pair_out) {
+    // the block: 128 rows (8 waves) while that leaves two workgroups per CU, else 64 rows (forced: g_prefill_waves)
+    int form = g_prefill_waves;
+    if (form == 0) form = blocks(128) >= 512 ? 8 : 4;
+    // causal prompts: pair a heavy block with a light one while the pairs still fill the chip
+    *pair_out = g_prefill_pair == 1 || (g_prefill_pair == 0 && causal && blocks(form == 8 || form == 18 ? (form == 18 ? 256 : 128) : (form == 14 ? 128 : 64)) >= 512) ? 1 : 0;  // (two row tiles per wave -- forms 14 / 18 -- cost more in occupancy than the shared fragments give: 147 vs 130 us at 2048 rows)
+    *form_out = form;
+}
+
+int form_rows(int form) { return form == 18 ? 256 : (form == 8 || form == 14 ? 128 : 64); }
+
+}  // namespace
 
 int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, int ld_mask, int causal,
                              void *out, int ld_out, void *workspace, int heads, int kv_heads, int max_keys, int pos, int m, float alpha, hipStream_t stream,
@@ -360,7 +560,7 @@ int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, co
     p.pos = pos;
     p.m = m;
     const long long pieces = (long long)m * (heads + 2 * kv_heads) * 16;
-    hipLaunchKernelGGL(attn_prefill_prepare_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(attn_prefill_prepare_kernel<false>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, p);
     PrefillArgs a{};
     a.qrot = p.qrot;
     a.kc = p.kc;
@@ -376,12 +576,9 @@ int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, co
     a.m = m;
     a.causal = causal;
     a.alpha = alpha;
-    // the block: 128 rows (8 waves) while that leaves two workgroups per CU, else 64 rows (forced: g_prefill_waves)
     auto blocks = [&](int rows) { return (long long)((m + rows - 1) / rows) * heads; };
-    int form = g_prefill_waves;
-    if (form == 0) form = blocks(128) >= 512 ? 8 : 4;
-    // causal prompts: pair a heavy block with a light one while the pairs still fill the chip
-    a.pair = g_prefill_pair == 1 || (g_prefill_pair == 0 && causal && blocks(form == 8 || form == 18 ? (form == 18 ? 256 : 128) : (form == 14 ? 128 : 64)) >= 512) ? 1 : 0;  // (two row tiles per wave -- forms 14 / 18 -- cost more in occupancy than the shared fragments give: 147 vs 130 us at 2048 rows)
+    int form = 0;
+    prefill_form_rule(blocks, causal, &form, &a.pair);
     auto go = [&](auto nw_c, auto rt_c) {
         constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
         const int nb = (m + 16 * RT * NW - 1) / (16 * RT * NW);
@@ -393,6 +590,129 @@ int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, co
             if (mask) hipLaunchKernelGGL((attn_prefill_kernel<true, NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
             else hipLaunchKernelGGL((attn_prefill_kernel<false, NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
         }
+    };
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using I4 = std::integral_constant<int, 4>;
+    using I8 = std::integral_constant<int, 8>;
+    if (form == 18) go(I8{}, I2{});
+    else if (form == 14) go(I4{}, I2{});
+    else if (form == 8) go(I8{}, I1{});
+    else go(I4{}, I1{});
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+// ---- the paged launch ----
+namespace {
+
+int prefill_page_shift(int page_keys) {  // log2 of a power of two in [16, 256], or -1
+    for (int s = 4; s <= 8; ++s)
+        if (page_keys == (1 << s)) return s;
+    return -1;
+}
+
+// form, pairing and the block list (heaviest first; ties: in segment order, a segment's later blocks first) of a paged launch; false: more blocks than the list holds
+bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int nseg, int *form_out, int *pair_out, int *nblocks_out, unsigned short *order) {
+    auto blocks = [&](int rows) {
+        long long n = 0;
+        for (int s = 0; s < nseg; ++s) n += (seg[s].m + rows - 1) / rows;
+        return n * heads;
+    };
+    int form = 0, pair = 0;
+    prefill_form_rule(blocks, causal, &form, &pair);
+    const int rows = form_rows(form);
+    const long long nb = blocks(rows) / heads;
+    *form_out = form;
+    *pair_out = pair;
+    *nblocks_out = (int)(nb < 0x7fffffff ? nb : 0x7fffffff);
+    if (nb > kMaxListedBlocks) return false;
+    if (!order) return true;
+    int tiles[kMaxListedBlocks];
+    int n = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const int nbs = (seg[s].m + rows - 1) / rows;
+        for (int qb = nbs - 1; qb >= 0; --qb) {
+            const int last_row = (qb * rows + rows < seg[s].m ? qb * rows + rows : seg[s].m) - 1;
+            const int kend = causal ? seg[s].pos + last_row + 1 : seg[s].pos + seg[s].m;
+            tiles[n] = (kend + kBK - 1) / kBK;
+            order[n++] = (unsigned short)(s << 12 | qb);
+        }
+    }
+    int idx[kMaxListedBlocks];
+    for (int i = 0; i < n; ++i) idx[i] = i;
+    std::stable_sort(idx, idx + n, [&](int x, int y) { return tiles[x] > tiles[y]; });
+    unsigned short sorted[kMaxListedBlocks];
+    for (int i = 0; i < n; ++i) sorted[i] = order[idx[i]];
+    for (int i = 0; i < n; ++i) order[i] = sorted[i];
+    return true;
+}
+
+}  // namespace
+
+size_t attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd) { return attention_prefill_workspace_bytes(heads, total_rows, hd); }
+
+int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups) {
+    PrefillSegment seg[kMaxSegments];
+    if (nseg < 1 || nseg > kMaxSegments || heads < 1) return TCE_ERR_BAD_ARG;
+    __builtin_memcpy(seg, segments, sizeof(PrefillSegment) * nseg);
+    if (!plan_paged_prefill(heads, causal, seg, nseg, form, pair, nblocks, nullptr)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    *workgroups = (*pair ? (*nblocks + 1) / 2 : *nblocks) * heads;
+    return TCE_OK;
+}
+
+int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                   const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
+                                   int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err) {
+    const int shift = prefill_page_shift(page_keys);
+    if (shift < 0 || nseg < 1 || nseg > kMaxSegments || !table || table_stride < 1 || kv_heads <= 0 || heads % kv_heads != 0 || total_rows < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedPrefillArgs a{};
+    __builtin_memcpy(a.seg, segments, sizeof(PrefillSegment) * nseg);
+    int form = 0;
+    unsigned short order[kMaxListedBlocks] = {};
+    if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    for (int i = 0; i < a.nblocks; ++i) a.order[i >> 1] |= (unsigned)order[i] << ((i & 1) * 16);
+    PagedPrepareArgs p{};
+    p.qkv = static_cast<const half_t *>(qkv);
+    p.ld_qkv = ld_qkv;
+    p.qrot = static_cast<half_t *>(workspace);
+    p.kc = static_cast<half_t *>(k_pool);
+    p.vc = static_cast<half_t *>(v_pool);
+    p.cosv = static_cast<const half_t *>(cosv);
+    p.sinv = static_cast<const half_t *>(sinv);
+    p.table = table;
+    p.table_stride = table_stride;
+    p.page_shift = shift;
+    p.heads = heads;
+    p.kv_heads = kv_heads;
+    p.total_rows = total_rows;
+    p.nseg = nseg;
+    __builtin_memcpy(p.seg, a.seg, sizeof(p.seg));
+    const long long pieces = (long long)total_rows * (heads + 2 * kv_heads) * 16;
+    hipLaunchKernelGGL(attn_prefill_prepare_kernel<true>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, p);
+    a.qrot = p.qrot;
+    a.kc = p.kc;
+    a.vc = p.vc;
+    a.out = static_cast<half_t *>(out);
+    a.table = table;
+    a.ld_out = ld_out;
+    a.heads = heads;
+    a.rep = heads / kv_heads;
+    a.kv_heads = kv_heads;
+    a.total_rows = total_rows;
+    a.causal = causal;
+    a.table_stride = table_stride;
+    a.page_shift = shift;
+    a.alpha = alpha;
+    auto go = [&](auto nw_c, auto rt_c) {
+        constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
+        const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
+        if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, a);
+        else hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
     };
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;

@@ -1356,6 +1356,86 @@ int tce_attention_prefill_f16(const void *qkv, int ld_qkv, void *kc, void *vc, c
     return rc == TCE_ERR_HIP ? hip_fail(he, "attention prefill launch") : rc;
 }
 
+// ---- the paged prefill (csrc/attention_prefill.hip): every refusal below happens before any HIP call ----
+size_t tce_attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd) { return tce::attention_prefill_paged_workspace_bytes(heads, total_rows, hd); }
+
+// the segment list's own rules (shared by the launch and describe); table_rows / table_stride / page_keys / total_rows <= 0: that bound is not checked (describe)
+static int check_prefill_segments(const char *who, const tce_prefill_segment *seg, int n, int table_rows, long long max_keys, int total_rows) {
+    if (!seg) return fail(TCE_ERR_BAD_ARG, "%s: null segment list", who);
+    if (n < 1 || n > TCE_PREFILL_MAX_SEGMENTS) return fail(TCE_ERR_BAD_ARG, "%s: num_segments %d outside 1 .. %d", who, n, TCE_PREFILL_MAX_SEGMENTS);
+    for (int i = 0; i < n; ++i) {
+        const tce_prefill_segment &s = seg[i];
+        if (s.m < 1 || s.pos < 0) return fail(TCE_ERR_BAD_ARG, "%s: segment %d: need m >= 1 and pos >= 0 (m %d, pos %d)", who, i, s.m, s.pos);
+        if (max_keys > 0 && (long long)s.pos + s.m > max_keys)
+            return fail(TCE_ERR_BAD_ARG, "%s: segment %d: pos + m = %lld keys do not fit a table row (%lld keys)", who, i, (long long)s.pos + s.m, max_keys);
+        if (max_keys <= 0 && (long long)s.pos + s.m > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: segment %d: pos + m overflows int", who, i);
+        if (table_rows > 0 && (s.slot < 0 || s.slot >= table_rows)) return fail(TCE_ERR_BAD_ARG, "%s: segment %d: slot %d outside [0, %d)", who, i, s.slot, table_rows);
+        if (total_rows > 0 && (s.row0 < 0 || (long long)s.row0 + s.m > total_rows))
+            return fail(TCE_ERR_BAD_ARG, "%s: segment %d: rows [%d, %d + %d) outside [0, %d)", who, i, s.row0, s.row0, s.m, total_rows);
+        for (int j = 0; j < i; ++j) {
+            if (table_rows > 0 && seg[j].slot == s.slot) return fail(TCE_ERR_BAD_ARG, "%s: segment %d: slot %d is segment %d's too (their appends would race)", who, i, s.slot, j);
+            if (total_rows > 0 && s.row0 < seg[j].row0 + seg[j].m && seg[j].row0 < s.row0 + s.m)
+                return fail(TCE_ERR_BAD_ARG, "%s: segment %d: its rows overlap segment %d's", who, i, j);
+        }
+    }
+    return TCE_OK;
+}
+
+const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int causal, const tce_prefill_segment *segments, int num_segments) {
+    static thread_local char buf[192];
+    static const char *who = "tce_attention_prefill_describe_paged";
+    if (heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0) {
+        fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
+        return nullptr;
+    }
+    if (check_prefill_segments(who, segments, num_segments, 0, 0, 0) != TCE_OK) return nullptr;
+    static_assert(sizeof(tce_prefill_segment) == 16, "four int32");
+    int form = 0, pair = 0, blocks = 0, wgs = 0;
+    const int rc = tce::describe_attention_prefill_paged(heads, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, &form, &pair, &blocks, &wgs);
+    if (rc != TCE_OK) {
+        fail(rc, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
+        return nullptr;
+    }
+    std::snprintf(buf, sizeof(buf), "form=%d rows-per-block=%d pair=%s blocks=%d workgroups=%d segments=%d", form, form == 18 ? 256 : (form == 8 || form == 14 ? 128 : 64),
+                  pair ? "yes" : "no", blocks, wgs, num_segments);
+    return buf;
+}
+
+int tce_attention_prefill_paged_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride, int page_keys,
+                                    int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, int hd,
+                                    const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, void *stream) {
+    static const char *who = "tce_attention_prefill_paged_f16";
+    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
+    if (table_stride < 1 || num_pages < 1 || table_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_rows, table_stride, num_pages >= 1", who);
+    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
+    if (heads <= 0 || total_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need heads, total_rows > 0", who);
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
+    const int rcs = check_prefill_segments(who, segments, num_segments, table_rows, (long long)table_stride * page_keys, total_rows);
+    if (rcs != TCE_OK) return rcs;
+    const int width = (heads + 2 * kv_heads) * hd;
+    if (ld_qkv == 0) ld_qkv = width;
+    if (ld_out == 0) ld_out = heads * hd;
+    if (ld_qkv < width || ld_out < heads * hd) return fail(TCE_ERR_BAD_ARG, "%s: a leading dimension is shorter than its row", who);
+    if (ld_qkv % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_qkv must be a multiple of 8 (16-byte pieces)", who);
+    if (ld_out % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 7)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_out must be a multiple of 4 and out 8-byte aligned (8-byte stores)", who);
+    for (const void *p : {qkv, (const void *)k_pool, (const void *)v_pool, cosv, sinv, (const void *)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned pointers", who);
+    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
+    int form = 0, pair = 0, blocks = 0, wgs = 0;
+    if (tce::describe_attention_prefill_paged(heads, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, &form, &pair, &blocks, &wgs) != TCE_OK)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
+    tce::half_t ah;
+    __builtin_memcpy(&ah, &alpha_bits, 2);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_attention_prefill_paged(qkv, ld_qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, causal ? 1 : 0, out, ld_out, workspace, heads,
+                                                       kv_heads, reinterpret_cast<const int *>(segments), num_segments, total_rows, (float)ah, static_cast<hipStream_t>(stream), &he);
+    if (rc == TCE_ERR_HIP) return hip_fail(he, "paged attention prefill launch");
+    return rc == TCE_OK ? TCE_OK : fail(rc, "%s: unsupported shape", who);
+}
+
 int tce_layernorm_q_w8a8_group(const float *x, const float *ln_weight, const float *ln_bias, int m, int k, const tce_w8a8_desc *lin, int count,
                                void *ln_out, void *stream) {
     if (!x || !ln_weight || !ln_bias || !lin) return fail(TCE_ERR_BAD_ARG, "tce_layernorm_q_w8a8_group: null pointer");

@@ -250,6 +250,13 @@ void set_attention_prefill_waves(int w);  // 0 automatic, 4 / 8 forced
 int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, int ld_mask, int causal,
                              void *out, int ld_out, void *workspace, int heads, int kv_heads, int max_keys, int pos, int m, float alpha, hipStream_t stream,
                              hipError_t *hip_err);
+// the paged prefill: both launches on the paged step's pools and block table, up to 16 segments {slot, pos, m, row0} (int32 x 4 each: tce_prefill_segment) per
+// launch; UNSUPPORTED_SHAPE: more query blocks than one launch lists (1024).  describe: the form (4 / 8 / 14 / 18), pairing, query blocks and workgroups; no HIP call.
+size_t attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd);
+int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups);
+int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                   const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
+                                   int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err);
 // what a deferred attention step leaves for its consumer (tce_attention_deferred of the C ABI, field for field)
 struct AttnDeferred {
     int slots;   // chunk slots of the launch's grid: 1 = nothing deferred (`out` is final); 2 .. kAttnDeferMaxSlots = partial states per (query head, slot)

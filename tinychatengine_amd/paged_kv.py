@@ -8,8 +8,10 @@ rows are bit-identical to tce_attention_decode_step_batch_f16 on contiguous cach
 
     PageAllocator              host bookkeeping (free list, reference counts, a page list per slot) + the device block table; ONE for all layers: every layer
                                uses the same page numbers in its own pools
-    PagedBatchDecodeAttention  one layer's pools and workspace: step (one launch), admit (scatter from a contiguous cache), read_back (gather), copy_rows
-    PagedBatchedDecoder        BatchedDecoder's seven launches with the paged step as launch 3; prefill runs on a contiguous staging cache and scatters
+    PagedBatchDecodeAttention  one layer's pools and workspace: step (one launch), prefill (tce_attention_prefill_paged_f16: the new rows of up to 16 sequences
+                               straight into their pages, two launches), admit (scatter from a contiguous cache), read_back (gather), copy_rows
+    PagedBatchedDecoder        BatchedDecoder's seven launches with the paged step as launch 3; prefill / prefill_many: BatchedDecoder.prefill's launches once for
+                               the rows of all admitted sequences, the paged prefill in the middle (no staging cache, no gather, no scatter)
 
 Trust: the step follows only table words 0 .. pos // page_keys of an active row; everything else in the table may hold anything (a released slot's words stay as
 they were).  It does not validate page numbers: PageAllocator writes only numbers in [0, num_pages), and PagedBatchDecodeAttention.table_violations runs
@@ -64,7 +66,34 @@ class PageAllocator:
         """The pages of `slot` that an append may write: those behind its shared prefix."""
         return self.pages[slot][self.frozen[slot]:]
 
+    def writable(self, slot: int, key0: int, nkeys: int) -> bool:
+        """May an append write rows [key0, key0 + nkeys) of `slot`: every page they fall in exists, is held by this slot alone and lies behind its frozen prefix."""
+        self._slot(slot)
+        if key0 < 0 or nkeys < 1:
+            return False
+        first, last = key0 // self.page_keys, (key0 + nkeys - 1) // self.page_keys
+        if first < self.frozen[slot] or last >= len(self.pages[slot]):
+            return False
+        return all(self.refcount[p] == 1 for p in self.pages[slot][first:last + 1])
+
     # ---- operations ----
+    def reserve_many(self, wanted: list[tuple[int, int]]) -> list[list[int]]:
+        """reserve() for several slots, all or nothing: [(slot, upto_pos)] with distinct slots.  Every argument is checked and the pages are counted before anything
+        changes; on PagePoolExhausted (or a bad argument) no slot, page or table word has changed.  Returns the pages added per entry."""
+        slots = [s for s, _ in wanted]
+        if len(set(slots)) != len(slots):
+            raise ValueError("reserve_many: a slot is named twice")
+        short = 0
+        for slot, upto_pos in wanted:
+            self._slot(slot)
+            need = upto_pos // self.page_keys + 1
+            if upto_pos < 0 or need > self.max_pages_per_seq:
+                raise ValueError(f"key index {upto_pos} outside a slot's {self.max_keys} keys")
+            short += max(0, need - len(self.pages[slot]))
+        if short > len(self.free):
+            raise PagePoolExhausted(f"{short} pages needed for slots {slots}, {len(self.free)} free")
+        return [self.reserve(slot, upto_pos) for slot, upto_pos in wanted]
+
     def reserve(self, slot: int, upto_pos: int) -> list[int]:
         """Add pages to `slot` until key index `upto_pos` is covered; returns the pages added.  Only the changed table words are written (stream-ordered)."""
         self._slot(slot)
@@ -174,7 +203,8 @@ class PagedBatchDecodeAttention:
         self.slot_workspace_bytes = need // self.batch
         self.cos, self.sin = cos, sin
         self.alpha_bits = int(np.array([1.0 / np.sqrt(self.hd)], np.float16).view(np.uint16)[0])
-        self._staging: DecodeAttention | None = None
+        self._staging: DecodeAttention | None = None  # made on first use of staging(): nothing in this module asks for it
+        self._prefill_ws: torch.Tensor | None = None
         self._violations = torch.zeros(1, dtype=torch.int32, device=device)
 
     def _table_args(self):
@@ -194,6 +224,29 @@ class PagedBatchDecodeAttention:
         capi.check(capi.lib().tce_attention_decode_step_paged_f16(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out),
                                                                   p(self.workspace), self.batch, self.heads, self.kv_heads, self.hd, p(pos_device), int(pos_bound),
                                                                   self.alpha_bits, C.c_void_p(_stream())))
+        return out
+
+    def prefill(self, segments, qkv: torch.Tensor, out: torch.Tensor | None = None, causal: bool = True) -> torch.Tensor:
+        """tce_attention_prefill_paged_f16: segments [(slot, pos, m)] (at most 16, distinct slots, pages reserved before), qkv fp16 [sum m][(heads + 2 kv_heads) * 128]
+        with the segments' rows packed in that order.  ONE call, two launches: rows pos .. pos + m - 1 of every segment are appended to its pages and out
+        [sum m][heads * 128] (o_proj's input rows) is returned -- each segment bit-identical to DecodeAttention.prefill of that sequence alone."""
+        segs, total = capi.prefill_segments(segments)
+        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.dim() == 2 and qkv.is_cuda and tuple(qkv.shape) == (total, (self.heads + 2 * self.kv_heads) * self.hd)
+        for slot, pos, m in segments:
+            assert self.allocator.writable(slot, pos, m), f"slot {slot}: rows [{pos}, {pos} + {m}) are not all in pages of its own (reserve them; a shared page is read-only)"
+        if out is None:
+            out = torch.empty((total, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and tuple(out.shape) == (total, self.heads * self.hd)
+        L = capi.lib()
+        need = int(L.tce_attention_prefill_paged_workspace_bytes(self.heads, total, self.hd))
+        if self._prefill_ws is None or self._prefill_ws.numel() < need:
+            self._prefill_ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
+        t = self.allocator.table
+        assert t.is_cuda and t.device == self.k_pool.device
+        p = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        capi.check(L.tce_attention_prefill_paged_f16(p(qkv), 0, p(self.k_pool), p(self.v_pool), p(t), t.shape[0], t.shape[1], self.page_keys, self.num_pages, p(self.cos),
+                                                     p(self.sin), 1 if causal else 0, p(out), 0, p(self._prefill_ws), self.heads, self.kv_heads, self.hd,
+                                                     C.cast(segs, C.c_void_p), len(segments), total, self.alpha_bits, C.c_void_p(_stream())))
         return out
 
     def table_violations(self, pos_device: torch.Tensor, pos_bound: int) -> int:
@@ -245,13 +298,14 @@ class PagedBatchDecodeAttention:
         self.v_pool[dst_page, :, :rows].copy_(self.v_pool[src_page, :, :rows])
 
     def staging(self) -> DecodeAttention:
-        """The contiguous single-sequence cache that prefill runs on (one per layer, max_keys rows, made on first use)."""
+        """A contiguous single-sequence cache of max_keys rows for a caller that wants one beside the pages (admit / gather_into; made on first use).  Prefill does
+        not use it: PagedBatchDecodeAttention.prefill writes the pages directly."""
         if self._staging is None:
             self._staging = DecodeAttention(self.heads, self.hd, self.max_keys, self.k_pool.device, self.cos, self.sin, kv_heads=self.kv_heads)
         return self._staging
 
     def slot(self, b: int) -> DecodeAttention:
-        """What BatchedDecoder.prefill runs a slot's prefill on: the staging cache (PagedBatchedDecoder.prefill gathers before and scatters after)."""
+        """A DecodeAttention for slot b: the staging cache (the caller gathers before and scatters after: gather_into / admit)."""
         if not 0 <= b < self.batch:
             raise IndexError(f"slot {b} of {self.batch}")
         return self.staging()
@@ -259,7 +313,7 @@ class PagedBatchDecodeAttention:
 
 class PagedBatchedDecoder(BatchedDecoder):
     """BatchedDecoder on a paged cache: the same seven launches per layer (BatchedDecoder.step itself, with PagedBatchDecodeAttention.step as launch 3), the same
-    prefill launches on a contiguous staging cache.  One PageAllocator serves the decoders of all layers."""
+    prefill launches with the paged prefill in the middle.  One PageAllocator serves the decoders of all layers."""
 
     def __init__(self, block: DecoderBlock, allocator: PageAllocator):  # (no BatchedDecoder.__init__: it would allocate the contiguous caches)
         self.block, self.batch, self.allocator = block, allocator.batch, allocator
@@ -270,12 +324,27 @@ class PagedBatchedDecoder(BatchedDecoder):
         self.act = e(block.ffn)
         self._up = None
 
+    def prefill_many(self, admissions) -> None:
+        """Admit several sequences at once: admissions [(slot, rows, pos)], at most 16, distinct slots; rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated
+        in place.  Pages are reserved for every sequence first, all or nothing (PagePoolExhausted: no slot changed; the allocator is shared, so the first layer's call
+        reserves for all); then BatchedDecoder.prefill's launches run ONCE at M = all rows -- the weights are streamed once -- with the paged prefill in the middle."""
+        blk = self.block
+        if not 1 <= len(admissions) <= capi.TCE_PREFILL_MAX_SEGMENTS:
+            raise ValueError(f"{len(admissions)} sequences: 1 .. {capi.TCE_PREFILL_MAX_SEGMENTS} per call")
+        for _, rows, _ in admissions:
+            assert rows.dtype == torch.float16 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == blk.hidden and rows.shape[0] >= 1
+        self.allocator.reserve_many([(slot, pos + rows.shape[0] - 1) for slot, rows, pos in admissions])
+        segments = [(slot, pos, rows.shape[0]) for slot, rows, pos in admissions]
+        for slot, pos, m in segments:
+            assert self.allocator.writable(slot, pos, m), f"slot {slot}: a chunk at key {pos} starts inside a shared page"
+        packed = admissions[0][1] if len(admissions) == 1 else torch.cat([rows for _, rows, _ in admissions])
+        self._prefill_rows(packed, lambda qkv, attn: self.attention.prefill(segments, qkv, out=attn, causal=True))
+        if len(admissions) > 1:
+            row0 = 0
+            for _, rows, _ in admissions:
+                rows.copy_(packed[row0:row0 + rows.shape[0]])
+                row0 += rows.shape[0]
+
     def prefill(self, slot: int, rows: torch.Tensor, pos: int) -> None:
-        """Admit a sequence into `slot`: BatchedDecoder.prefill's launches on the staging cache -- on top of the slot's `pos` cached keys, gathered first -- and the
-        new rows pos .. pos + m - 1 scattered into the slot's pages (reserved here; the allocator is shared, so the first layer's call reserves for all)."""
-        m = rows.shape[0]
-        self.allocator.reserve(slot, pos + m - 1)
-        if pos > 0:
-            self.attention.gather_into(slot, self.attention.staging(), 0, pos)
-        super().prefill(slot, rows, pos)
-        self.attention.admit(slot, self.attention.staging(), pos, m)
+        """Admit a sequence into `slot`: prefill_many with one sequence.  The new rows pos .. pos + m - 1 go straight into the slot's pages (reserved here)."""
+        self.prefill_many([(slot, rows, pos)])
