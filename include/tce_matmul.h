@@ -47,7 +47,7 @@ extern "C" {
 
 #define TCE_API __attribute__((visibility("default")))
 
-#define TCE_VERSION 113 /* additive, unversioned: tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
+#define TCE_VERSION 113 /* additive, unversioned: tce_sample_workspace_bytes, tce_sample_f16, tce_embed_rows_f16 (device-side sampling and the embedding lookup: one graph replay is one token); tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
 
 /* error codes (return values) */
 #define TCE_OK 0
@@ -333,6 +333,77 @@ TCE_API int tce_attention_prefill_paged_f16(const void *qkv, int ld_qkv, void *k
                                             int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments, int total_rows,
                                             unsigned short alpha_half_bits, void *stream);
 TCE_API const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int causal, const tce_prefill_segment *segments, int num_segments);
+
+/* Device-side sampling: what the reference does on the host between Int4LlamaForCausalLM::forward and the next token's Embedding (llm/src/Generate.cc driven by
+ * LLaMA3Generate.cc:127-198), for `batch` rows of fp16 logits [batch][ld] (lm_head's output at M = batch; vocab <= ld) in TWO launches (csrc/sampling.hip), so that a
+ * captured decode graph yields one token per replay for every sequence with no host round trip.  Per ACTIVE row (0 <= pos_device[b] <= pos_bound, the project's rule;
+ * an inactive row has nothing read and nothing written: token, log, ring, counters and position stay as they are), in fp32 on the exact value of each fp16 word:
+ *   1. sample_repetition_penalty over the last repeat_last_n (<= 64) tokens of the row's ring (x <= 0 ? x * penalty : x / penalty, once per distinct id), then
+ *      sample_frequency_and_presence_penalties (x -= float(count) * alpha_frequency + float(count > 0) * alpha_presence); IEEE operations, no contraction.
+ *   2. temp <= 0: greedy -- the LOWEST id among the maxima (std::max_element returns the first maximum).
+ *   3. otherwise top_k (1 .. top_k_bound <= 256) -> softmax over the k in descending order (subtract the maximum, expf, a SEQUENTIAL fp32 sum, divide) -> top_p
+ *      (with cum the running sum of p, n = the first i >= 1 with cum_i > top_p; candidates [0, n) are kept: the one that crosses the threshold is dropped -- the
+ *      reference's behaviour --, top_p >= 1 keeps all k) -> logit / temp -> softmax over the n -> inverse-CDF draw on a uniform u in [0, 1): the first i with u < cdf_i
+ *      (the last candidate if rounding leaves none).
+ *   ORDER (std::partial_sort leaves it open and fp16 logits tie constantly): descending penalised logit, ASCENDING token id among equals, inside the top-k and at
+ *   its boundary.  -0 and +0 are one value and come back as +0.
+ *   u = (Philox4x32-10(counter = (rows[b].generated, 0, 0, 0), key = (seed_lo, seed_hi)) word 0 >> 8) * 2^-24: keyed by the sequence's seed and the index of the token
+ *   within its sequence, never by slot, batch or launch; uniform_override ([batch] fp32, may be NULL) replaces it (tests).
+ *   The tail, same launch: next_token[b] = token; out_log[b][generated] = token; the token is pushed into the ring; generated += 1; then pos_device[b] += 1 -- or = -1
+ *   (retired) when the token is one of the n_stop (<= 4) stop_ids or generated has reached rows[b].max_new (or log_stride).
+ * rows: DEVICE array [batch] of tce_sample_row (304 bytes): the row's parameters and its state -- a slot changes hands by one copy of its row, a captured graph needs
+ * no recapture.  A fresh row has generated = ring_pushed = 0 and ring = 64 zeros, as the reference's last_n_tokens starts (token 0 is penalised until 64 tokens have
+ * passed); prompt tokens are pushed by the host at admission (ring[ring_pushed % 64], ring_pushed += 1).  A row's top_k outside [1, top_k_bound] is clamped (it lives
+ * on the device: the host cannot refuse it at the call).
+ * NOT BUILT: tfs_z, typical_p, mirostat (the call accepts only their disabled values 1.0, 1.0, 0), top_k <= 0 = "whole vocabulary", k > 256: TCE_ERR_UNSUPPORTED_SHAPE
+ * before any launch.  Also refused there: vocab > ld (TCE_ERR_BAD_ARG), vocab > 2^20, logits not 16-byte aligned or ld % 8 != 0, and ceil(vocab / 4096) * top_k_bound
+ * > 8192 (the second launch holds the chunks' survivors in registers: 131072 entries at k = 256, 838k at k = 40).
+ * workspace: tce_sample_workspace_bytes(batch, vocab) bytes (0 for a bad shape), zeroed once; word 0 counts the ids tce_embed_rows_f16 refused, the rest carries the
+ * first launch's survivors to the second -- the kernel boundary is the only ordering, there is no counter to reset.  The logits are not modified.
+ * debug (may be NULL): [batch] records of the row's sorted candidates for tests. */
+typedef struct tce_sample_row {
+    float temp;              /* <= 0: greedy */
+    int32_t top_k;
+    float top_p;
+    float repeat_penalty;    /* 1.0: off */
+    float alpha_frequency, alpha_presence;
+    int32_t repeat_last_n;   /* 0 .. 64 */
+    int32_t max_new;         /* the row retires when `generated` reaches it */
+    uint32_t seed_lo, seed_hi;
+    uint32_t generated;      /* tokens sampled for this sequence so far = the generator's counter */
+    uint32_t ring_pushed;    /* tokens pushed into the ring (prompt + generated) */
+    int32_t ring[64];
+} tce_sample_row;
+typedef struct tce_sample_debug {
+    int32_t n, k;            /* candidates kept after top-p; candidates after top-k */
+    float u;
+    int32_t choice;          /* the index drawn */
+    int32_t ids[256];
+    float logit[256], p[256], final_p[256]; /* sorted penalised logits, p of the first softmax, p after temperature (n entries) */
+} tce_sample_debug;
+typedef struct tce_sample_call {
+    const void *logits;
+    int32_t ld, vocab, batch, top_k_bound;
+    tce_sample_row *rows;
+    int32_t *pos_device;
+    int32_t pos_bound, log_stride;
+    int32_t *next_token;     /* [batch] */
+    int32_t *out_log;        /* [batch][log_stride] */
+    const float *uniform_override;
+    tce_sample_debug *debug;
+    void *workspace;
+    int32_t stop_ids[4];
+    int32_t n_stop, mirostat;
+    float tfs_z, typical_p;
+} tce_sample_call;
+TCE_API size_t tce_sample_workspace_bytes(int batch, int vocab);
+TCE_API int tce_sample_f16(const tce_sample_call *call, void *stream);
+/* The next step's input rows, one launch: row token[b] of an fp16 table [vocab][hidden] into out[b] ([batch][hidden]) for every active row (pos_device / pos_bound as
+ * above; inactive rows are left as they are).  The reference looks an fp32 table up and rounds with float2half (Int4llamaDecoder: Embedding + float2half); a table
+ * rounded once to fp16 gives the same bits.  A token outside [0, vocab) is not followed: the row is written as zeros and word 0 of `workspace` (tce_sample_f16's, or
+ * any zeroed uint32) is incremented.  hidden % 8 == 0, 16-byte aligned table and out. */
+TCE_API int tce_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos_device, int pos_bound,
+                               void *workspace, void *stream);
 /* Reads [ptr, ptr + bytes) with at most `workgroups` workgroups (0 = as many as the range needs) and discards the data: the
  * range then sits in the memory-side cache (256 MiB) for the launch that needs it.  Meant for a side stream / graph branch
  * next to the launch BEFORE that one (no reference counterpart: cudaMallocManaged prefetching is the closest idea). */

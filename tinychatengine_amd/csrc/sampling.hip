@@ -1,0 +1,385 @@
+// sampling.hip -- the piece between lm_head's output and the next step's input, on the device (include/tce_matmul.h: tce_sample_f16, tce_embed_rows_f16).
+//
+// The reference samples on the host (llm/src/Generate.cc driven by LLaMA3Generate.cc:127-198): penalties over the recent-token window, then greedy, or
+// top-k -> softmax -> top-p -> temperature -> softmax -> draw, all in fp32 on the half2float'ed logits.  Here the same chain runs for B rows in TWO launches, so that
+// a captured decode graph produces a token per replay without a host round trip:
+//
+//   1  sample_select_kernel   grid (vocab chunks of 4096, B): 16-byte loads, 16 logits per thread in registers; the <= 64 penalised ids of the row are patched in
+//                             through a per-thread bit mask (no membership test per vocabulary entry); every logit becomes an order-preserving 32-bit key and
+//                             (key, 4095 - index) a 44-bit number that is DISTINCT per element, so "the chunk's k largest, lowest id first among equals" is one
+//                             bitwise threshold search (44 counting rounds: ballots + one barrier each; no atomics on the data, no sort).  The k survivors of
+//                             each chunk go to the workspace.
+//   2  sample_draw_kernel     grid (B): the chunks' survivors (chunks x k <= 8192, in registers) through the same search with (key, ~id), a rank sort of the k
+//                             winners, then the reference's arithmetic in the reference's order -- expf, SEQUENTIAL fp32 sums, IEEE divisions -- top-p with the
+//                             reference's quirk, temperature, the second softmax, the inverse-CDF draw; and the tail that closes the loop: token, log, ring,
+//                             counters, position (or retirement).
+//
+// The kernel boundary is the only ordering between the two: no counters, no flags, nothing to reset -- launch 200 of a workspace is launch 1.
+// A row whose position word is < 0 or > pos_bound is skipped by both kernels before it reads anything of the row.
+#include "tce_common.hpp"
+
+namespace tce {
+
+namespace {
+
+constexpr int kChunk = 4096;  // logits per workgroup of the select launch: 256 threads x 16
+constexpr int kThreads = 256;
+constexpr int kMaxK = 256;
+constexpr int kMergePerThread = 32;  // the draw launch holds chunks x k <= 256 x 32 survivors in registers
+
+typedef unsigned long long u64;
+
+// fp32 -> 32-bit integer with the same order (-0 and +0 are one value for the reference's comparisons: both map to +0's key).  0 is kept for "no element".
+__device__ __forceinline__ unsigned order_key(float x) {
+    x = x == 0.0f ? 0.0f : x;
+    unsigned u = __builtin_bit_cast(unsigned, x);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return u ? u : 1u;
+}
+__device__ __forceinline__ float key_value(unsigned k) {
+    const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    return __builtin_bit_cast(float, u);
+}
+
+__device__ __forceinline__ bool row_active(const int32_t *pos, int b, int pos_bound) {
+    const int p = pos[b];
+    return p >= 0 && p <= pos_bound;
+}
+
+__device__ __forceinline__ int row_k(const tce_sample_row &r, int kbound) {
+    if (r.temp <= 0.0f) return 1;  // greedy: the first maximum = the largest (key, lowest id)
+    const int k = r.top_k < 1 ? 1 : r.top_k;
+    return k > kbound ? kbound : k;
+}
+
+// the number of threads of the workgroup (4 waves) whose `pred` holds, summed over `n` predicates per thread by the caller: per wave a ballot and a scalar
+// population count per predicate, across waves two alternating LDS rows (one barrier per round)
+__device__ __forceinline__ int block_total(int wave_count, int (*cnt)[4], int round, int wave, int lane) {
+    if (lane == 0) cnt[round & 1][wave] = wave_count;
+    __syncthreads();
+    return cnt[round & 1][0] + cnt[round & 1][1] + cnt[round & 1][2] + cnt[round & 1][3];
+}
+
+__global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *logits, int ld, int vocab, const tce_sample_row *rows, const int32_t *pos, int pos_bound,
+                                                                  int kbound, uint2_t *entries, int nchunks) {
+    const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!row_active(pos, b, pos_bound)) return;
+    __shared__ int win_id[64], pen_id[64];
+    __shared__ float pen_val[64];
+    __shared__ unsigned mask[kThreads];
+    __shared__ int cnt[2][4];
+    __shared__ int nsel;
+    const tce_sample_row &r = rows[b];
+    const int k = row_k(r, kbound);
+    const half_t *row = logits + (size_t)b * ld;
+    const int base = c * kChunk, i0 = base + tid * 16;
+
+    float x[16];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        half8_t v = {};
+        if (i0 + 8 * h < vocab) v = *reinterpret_cast<const half8_t *>(row + i0 + 8 * h);  // (a piece across `vocab` stays inside the row: vocab <= ld, ld % 8 == 0)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[8 * h + j] = (float)v[j];
+    }
+
+    // ---- penalties: window slot t < nwin is the t-th most recent token of the ring; the first occurrence of an id that lies in this chunk patches its logit ----
+    const float rp = r.repeat_penalty, af = r.alpha_frequency, ap = r.alpha_presence;
+    const bool freq_on = !(af == 0.0f && ap == 0.0f);
+    const int nwin = r.repeat_last_n < 0 ? 0 : (r.repeat_last_n > 64 ? 64 : r.repeat_last_n);
+    mask[tid] = 0;
+    if (tid == 0) nsel = 0;
+    if (tid < 64) {
+        win_id[tid] = tid < nwin ? r.ring[(r.ring_pushed - 1u - (unsigned)tid) & 63u] : -1;
+        pen_id[tid] = -1;
+    }
+    __syncthreads();
+    if ((rp != 1.0f || freq_on) && tid < nwin) {
+        const int id = win_id[tid];
+        if (id >= base && id < base + kChunk && id < vocab) {
+            int count = 0;
+            bool first = true;
+            for (int j = 0; j < nwin; ++j) {
+                const bool same = win_id[j] == id;
+                count += same ? 1 : 0;
+                first = first && !(same && j < tid);
+            }
+            if (first) {
+                float v = (float)row[id];
+                if (rp != 1.0f) v = v <= 0.0f ? v * rp : v / rp;                   // sample_repetition_penalty (Generate.cc:26-30)
+                if (freq_on) v = v - ((float)count * af + 1.0f * ap);             // sample_frequency_and_presence_penalties (:56)
+                pen_id[tid] = id;
+                pen_val[tid] = v;
+                atomicOr(&mask[(id - base) >> 4], 1u << ((id - base) & 15));
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned m = mask[tid];
+    if (m) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            if ((m >> e) & 1u) {
+                for (int j = 0; j < 64; ++j)
+                    if (pen_id[j] == i0 + e) x[e] = pen_val[j];
+            }
+        }
+    }
+
+    // ---- the chunk's k largest (key, lowest index first): a bitwise search for the k-th largest of 4096 distinct 44-bit numbers ----
+    u64 comp[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const unsigned key = i0 + e < vocab ? order_key(x[e]) : 0u;
+        comp[e] = ((u64)key << 12) | (u64)(0xFFF - (tid * 16 + e));
+    }
+    u64 T = 0;
+    for (int bit = 43; bit >= 0; --bit) {
+        const u64 cand = T | (1ull << bit);
+        int cw = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) cw += __builtin_popcountll(__ballot(comp[e] >= cand));
+        if (block_total(cw, cnt, bit, wave, lane) >= k) T = cand;
+    }
+    // exactly k numbers are >= T (they are distinct and there are 4096 >= k of them); those past the vocabulary (key 0) are dropped
+    uint2_t *out = entries + ((size_t)b * nchunks + c) * kMaxK;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const unsigned key = (unsigned)(comp[e] >> 12);
+        if (comp[e] >= T && key != 0u) {
+            const int slot = atomicAdd(&nsel, 1);
+            if (slot < kMaxK) {
+                uint2_t ent;
+                ent.x = key;
+                ent.y = (unsigned)(i0 + e);
+                out[slot] = ent;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid >= nsel && tid < k) {
+        uint2_t ent;
+        ent.x = 0u;
+        ent.y = 0u;
+        out[tid] = ent;  // "no element": the draw launch reads k entries of every chunk
+    }
+}
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (c0, 0, 0, 0), key (k0, k1); the first output word.
+__device__ __forceinline__ unsigned philox4x32_10_first(unsigned c0, unsigned k0, unsigned k1) {
+    unsigned c[4] = {c0, 0u, 0u, 0u};
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const u64 p0 = (u64)0xD2511F53u * c[0], p1 = (u64)0xCD9E8D57u * c[2];
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c[0];
+}
+
+struct DrawArgs {
+    const uint2_t *entries;
+    int nchunks, kbound, pos_bound, log_stride;
+    tce_sample_row *rows;
+    int32_t *pos, *next_token, *out_log;
+    const float *uniform_override;
+    tce_sample_debug *debug;
+    int32_t stop_ids[4];
+    int n_stop;
+};
+
+__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!row_active(a.pos, b, a.pos_bound)) return;
+    __shared__ u64 sel[kMaxK];
+    __shared__ float lg[kMaxK + 8], ex[kMaxK + 8], pr[kMaxK + 8], fp[kMaxK + 8];
+    __shared__ int ids[kMaxK];
+    __shared__ int cnt[2][4];
+    __shared__ int nsel;
+    tce_sample_row &r = a.rows[b];
+    const int k = row_k(r, a.kbound);
+    const int E = a.nchunks * k;  // <= 8192 (checked by the host)
+
+    // ---- the k largest (key, lowest id first) of the chunks' survivors ----
+    u64 comp[kMergePerThread];
+    int valid = 0;
+#pragma unroll
+    for (int j = 0; j < kMergePerThread; ++j) {
+        const int idx = j * kThreads + tid;
+        comp[j] = 0;
+        if (idx < E) {
+            const int ch = idx / k, s = idx - ch * k;
+            const uint2_t ent = a.entries[((size_t)b * a.nchunks + ch) * kMaxK + s];
+            if (ent.x != 0u) comp[j] = ((u64)ent.x << 20) | (u64)(0xFFFFFu - ent.y);
+        }
+        valid += __builtin_popcountll(__ballot(comp[j] != 0));
+    }
+    if (tid == 0) nsel = 0;
+    const int V = block_total(valid, cnt, 0, wave, lane);
+    const int kk = V < k ? V : k;  // (>= 1: the vocabulary is not empty)
+    const int nj = (E + kThreads - 1) / kThreads;
+    u64 T = 0;
+    for (int bit = 51; bit >= 0; --bit) {
+        const u64 cand = T | (1ull << bit);
+        int cw = 0;
+#pragma unroll
+        for (int j = 0; j < kMergePerThread; ++j)
+            if (j < nj) cw += __builtin_popcountll(__ballot(comp[j] >= cand));
+        if (block_total(cw, cnt, bit, wave, lane) >= kk) T = cand;  // (rounds 51, 50, ...: the LDS row alternates with the count above, round 0)
+    }
+#pragma unroll
+    for (int j = 0; j < kMergePerThread; ++j) {
+        if (comp[j] != 0 && comp[j] >= T) {
+            const int slot = atomicAdd(&nsel, 1);
+            if (slot < kMaxK) sel[slot] = comp[j];
+        }
+    }
+    __syncthreads();
+    // rank sort of the kk distinct winners: descending key, ascending id among equal keys
+    if (tid < kk) {
+        const u64 mine = sel[tid];
+        int rank = 0;
+        for (int j = 0; j < kk; ++j) rank += sel[j] > mine ? 1 : 0;
+        lg[rank] = key_value((unsigned)(mine >> 20));
+        ids[rank] = (int)(0xFFFFFu - (unsigned)(mine & 0xFFFFFu));
+    }
+    __syncthreads();
+
+    const unsigned gen = r.generated;
+    float u = 0.0f;
+    int n = 1, choice = 0;
+    if (r.temp > 0.0f) {
+        // sample_top_p's softmax over the k candidates (Generate.cc:81-100): every thread walks the sums itself (broadcast LDS reads), in sorted order
+        const float l0 = lg[0];
+        if (tid < kk) ex[tid] = expf(lg[tid] - l0);
+        __syncthreads();
+        float sum = 0.0f;
+        for (int i = 0; i < kk; ++i) sum += ex[i];
+        if (tid < kk) pr[tid] = ex[tid] / sum;
+        __syncthreads();
+        n = kk;
+        if (r.top_p < 1.0f) {  // sample_top_p (:304-327) with min_keep 1: the candidate that crosses the threshold is dropped
+            float cum = 0.0f;
+            for (int i = 0; i < kk; ++i) {
+                cum += pr[i];
+                if (cum > r.top_p && i >= 1) {
+                    n = i;
+                    break;
+                }
+            }
+        }
+        // sample_temperature (:72-76), then sample_token's softmax over the n kept (:103-118)
+        const float t0 = lg[0] / r.temp;
+        if (tid < n) ex[tid] = expf(lg[tid] / r.temp - t0);
+        __syncthreads();
+        float sum2 = 0.0f;
+        for (int i = 0; i < n; ++i) sum2 += ex[i];
+        if (tid < n) fp[tid] = ex[tid] / sum2;
+        __syncthreads();
+        u = a.uniform_override ? a.uniform_override[b] : (float)(philox4x32_10_first(gen, r.seed_lo, r.seed_hi) >> 8) * 0x1p-24f;
+        choice = n - 1;
+        float cdf = 0.0f;
+        for (int i = 0; i < n; ++i) {
+            cdf += fp[i];
+            if (u < cdf) {
+                choice = i;
+                break;
+            }
+        }
+    }
+    if (a.debug) {
+        tce_sample_debug &d = a.debug[b];
+        if (tid < kMaxK) {
+            const bool in_k = tid < kk, in_n = tid < n && r.temp > 0.0f;
+            d.ids[tid] = in_k ? ids[tid] : -1;
+            d.logit[tid] = in_k ? lg[tid] : 0.0f;
+            d.p[tid] = in_k && r.temp > 0.0f ? pr[tid] : 0.0f;
+            d.final_p[tid] = in_n ? fp[tid] : 0.0f;
+        }
+        if (tid == 0) {
+            d.n = n;
+            d.k = kk;
+            d.u = u;
+            d.choice = choice;
+        }
+    }
+    // ---- the tail: the token, the log, the ring, the counters, the position ----
+    if (tid == 0) {
+        const int tok = ids[choice];
+        a.next_token[b] = tok;
+        if (gen < (unsigned)a.log_stride) a.out_log[(size_t)b * a.log_stride + gen] = tok;
+        r.ring[r.ring_pushed & 63u] = tok;
+        r.ring_pushed = r.ring_pushed + 1u;
+        r.generated = gen + 1u;
+        bool stop = (int)(gen + 1u) >= r.max_new || gen + 1u >= (unsigned)a.log_stride;
+        for (int i = 0; i < a.n_stop; ++i) stop = stop || tok == a.stop_ids[i];
+        a.pos[b] = stop ? -1 : a.pos[b] + 1;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void embed_rows_kernel(const uint4_t *table, int vocab, int pieces, const int32_t *token, uint4_t *out, const int32_t *pos, int pos_bound,
+                                                               unsigned *violations) {
+    const int b = blockIdx.x;
+    if (!row_active(pos, b, pos_bound)) return;
+    const int tok = token[b];
+    const bool ok = tok >= 0 && tok < vocab;
+    uint4_t zero = {0u, 0u, 0u, 0u};
+    for (int p = threadIdx.x; p < pieces; p += kThreads) out[(size_t)b * pieces + p] = ok ? table[(size_t)tok * pieces + p] : zero;
+    if (!ok && threadIdx.x == 0) atomicAdd(violations, 1u);
+}
+
+}  // namespace
+
+int sample_chunks(int vocab) { return (vocab + kChunk - 1) / kChunk; }
+
+size_t sample_workspace_bytes(int batch, int vocab) {
+    if (batch < 1 || vocab < 1) return 0;
+    return 256 + (size_t)batch * sample_chunks(vocab) * kMaxK * sizeof(uint2_t);  // 256 bytes of counters (word 0: tce_embed_rows_f16's refused ids), then the survivors
+}
+
+int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *hip_err) {
+    const int nchunks = sample_chunks(c.vocab);
+    uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
+    hipLaunchKernelGGL(sample_select_kernel, dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows, c.pos_device,
+                       c.pos_bound, c.top_k_bound, entries, nchunks);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        DrawArgs a;
+        a.entries = entries;
+        a.nchunks = nchunks;
+        a.kbound = c.top_k_bound;
+        a.pos_bound = c.pos_bound;
+        a.log_stride = c.log_stride;
+        a.rows = c.rows;
+        a.pos = c.pos_device;
+        a.next_token = c.next_token;
+        a.out_log = c.out_log;
+        a.uniform_override = c.uniform_override;
+        a.debug = c.debug;
+        for (int i = 0; i < 4; ++i) a.stop_ids[i] = c.stop_ids[i];
+        a.n_stop = c.n_stop;
+        hipLaunchKernelGGL(sample_draw_kernel, dim3(c.batch), dim3(kThreads), 0, stream, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos, int pos_bound, void *workspace,
+                          hipStream_t stream, hipError_t *hip_err) {
+    hipLaunchKernelGGL(embed_rows_kernel, dim3(batch), dim3(kThreads), 0, stream, static_cast<const uint4_t *>(table), vocab, hidden / 8, token, static_cast<uint4_t *>(out), pos,
+                       pos_bound, static_cast<unsigned *>(workspace));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+}  // namespace tce

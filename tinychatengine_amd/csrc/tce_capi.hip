@@ -18,6 +18,11 @@ namespace tce {
 int launch_w8a8(const tce_w8a8_desc &d, hipStream_t stream, hipError_t *hip_err, void *scratch = nullptr, char *describe = nullptr, int describe_len = 0);
 size_t w8a8_scratch_bytes();
 void set_w8a8_xsplit(int xs);
+int sample_chunks(int vocab);
+size_t sample_workspace_bytes(int batch, int vocab);
+int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *hip_err);
+int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos, int pos_bound, void *workspace,
+                          hipStream_t stream, hipError_t *hip_err);
 }
 
 namespace {
@@ -1272,6 +1277,44 @@ int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int p
     hipError_t he = hipSuccess;
     const int rc = tce::launch_kv_block_table_check(block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "block table check launch") : rc;
+}
+
+size_t tce_sample_workspace_bytes(int batch, int vocab) { return batch < 1 || batch > 65535 || vocab < 1 || vocab > (1 << 20) ? 0 : tce::sample_workspace_bytes(batch, vocab); }
+
+int tce_sample_f16(const tce_sample_call *c, void *stream) {
+    if (!c) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: null call");
+    if (!c->logits || !c->rows || !c->pos_device || !c->next_token || !c->out_log || !c->workspace) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: null pointer");
+    if (c->batch < 1 || c->vocab < 1 || c->pos_bound < 0 || c->log_stride < 1) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: need batch, vocab, log_stride >= 1 and pos_bound >= 0");
+    if (c->vocab > c->ld) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: vocab %d > ld %d", c->vocab, c->ld);
+    if (c->n_stop < 0 || c->n_stop > 4) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: n_stop %d (0 .. 4)", c->n_stop);
+    if (c->tfs_z != 1.0f || c->typical_p != 1.0f || c->mirostat != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: tail-free, typical and mirostat sampling are not built (tfs_z 1.0, typical_p 1.0, mirostat 0 only)");
+    if (c->top_k_bound < 1 || c->top_k_bound > 256)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: top_k_bound %d (1 .. 256; top_k <= 0 = the whole vocabulary is not built)", c->top_k_bound);
+    if (c->batch > 65535 || c->vocab > (1 << 20)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: batch <= 65535 and vocab <= 2^20");
+    if (c->ld % 8 != 0 || reinterpret_cast<uintptr_t>(c->logits) % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: logits 16-byte aligned with ld %% 8 == 0");
+    if ((reinterpret_cast<uintptr_t>(c->rows) | reinterpret_cast<uintptr_t>(c->workspace)) % 8 != 0 ||
+        (reinterpret_cast<uintptr_t>(c->pos_device) | reinterpret_cast<uintptr_t>(c->next_token) | reinterpret_cast<uintptr_t>(c->out_log) | reinterpret_cast<uintptr_t>(c->uniform_override) |
+         reinterpret_cast<uintptr_t>(c->debug)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: rows / workspace 8-byte aligned, the int32 / fp32 arrays 4-byte aligned");
+    if ((long long)tce::sample_chunks(c->vocab) * c->top_k_bound > 8192)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: %d chunks of 4096 logits x top_k_bound %d > 8192 survivors", tce::sample_chunks(c->vocab), c->top_k_bound);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_f16(*c, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+int tce_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos_device, int pos_bound, void *workspace,
+                       void *stream) {
+    if (!table || !token || !out || !pos_device || !workspace) return fail(TCE_ERR_BAD_ARG, "tce_embed_rows_f16: null pointer");
+    if (vocab < 1 || hidden < 1 || batch < 1 || pos_bound < 0) return fail(TCE_ERR_BAD_ARG, "tce_embed_rows_f16: need vocab, hidden, batch >= 1 and pos_bound >= 0");
+    if (hidden % 8 != 0 || (reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(out)) % 16 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_embed_rows_f16: hidden %% 8 == 0 and 16-byte aligned table / out");
+    if ((reinterpret_cast<uintptr_t>(token) | reinterpret_cast<uintptr_t>(pos_device) | reinterpret_cast<uintptr_t>(workspace)) % 4 != 0 || batch > 65535)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_embed_rows_f16: int32-aligned token / pos_device / workspace, batch <= 65535");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_embed_rows_f16(table, vocab, hidden, token, out, batch, pos_device, pos_bound, workspace, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "embedding launch") : rc;
 }
 
 int tce_attention_decode_step_deferred_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace, int heads,

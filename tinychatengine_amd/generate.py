@@ -1,0 +1,534 @@
+"""Generation: the piece between lm_head's output and the next step's input, on the device, and a front that admits prompts and returns token ids.
+
+The batched / paged decoders (batch_decode.py, paged_kv.py) run a "step" = the layers, fed a hidden row per sequence.  Here a TOKEN step is
+
+    1        tce_embed_rows_f16      row next_token[b] of the fp16 embedding table -> hidden[b]            (active rows)
+    7 x L    the layers              BatchedDecoder.step / PagedBatchedDecoder.step, unchanged
+    1        tce_rmsnorm_half        the final norm, B rows
+    1        tce_w4a16_forward       lm_head at M = B -> logits fp16 [B][vocab]
+    2        tce_sample_f16          penalties, top-k, softmax, top-p, temperature, draw; token -> next_token, log, ring; pos += 1 or -1 (retired)
+
+7 L + 5 launches, captured once in one torch.cuda.graph: ONE REPLAY IS ONE TOKEN for all B sequences, with no host round trip.  Everything a replay needs lives
+on the device (positions, sampling parameters, recent-token rings, generator counters, output logs), so a slot changes hands without recapture.
+
+    sample_reference      the sampling chain restated in numpy (fp32 throughout, sequential sums, the ordering rule): the CPU-side yardstick of tce_sample_f16
+    philox4x32_10, uniform   the counter-based generator restated in numpy; the device matches it bit for bit
+    Sampler               the per-row device state + workspace; step(logits, pos_device, pos_bound)
+    SlotBook              host bookkeeping of live slots (positions, budgets): which pages run(n) must reserve.  No device, no launch.
+    BatchedGenerator      admit / run / tokens / release over a list of PagedBatchedDecoder (one PageAllocator) or BatchedDecoder
+    HostDrivenLoop        the same decoders driven from the host -- logits copied back, numpy argmax, the row looked up and copied over: what a caller had to do
+                          before this module, kept as the yardstick for tests and scripts/generate_time.py
+
+Reference: llm/src/Generate.cc (sample_*), llm/src/nn_modules/non_cuda/LLaMA3Generate.cc:127-198 (the order of the chain, min_keep 1, last_n_tokens).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import capi
+
+RING = capi.TCE_SAMPLE_RING
+MAX_K = capi.TCE_SAMPLE_MAX_K
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the generator: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), counter (index, 0, 0, 0), key (seed_lo, seed_hi)
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_MASK = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key) -> tuple[int, int, int, int]:
+    """counter: four 32-bit words, key: two -> four 32-bit words (ten rounds, the key bumped by the Weyl constants between rounds)."""
+    c0, c1, c2, c3 = (int(v) & _MASK for v in counter)
+    k0, k1 = (int(v) & _MASK for v in key)
+    for _ in range(10):
+        p0, p1 = _M0 * c0, _M1 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & _MASK, p1 & _MASK, ((p0 >> 32) ^ c3 ^ k1) & _MASK, p0 & _MASK
+        k0, k1 = (k0 + _W0) & _MASK, (k1 + _W1) & _MASK
+    return c0, c1, c2, c3
+
+
+def uniform(seed: int, index: int) -> np.float32:
+    """The uniform in [0, 1) that draws token `index` of the sequence seeded `seed` (64 bits): the top 24 bits of the first output word.  It depends on nothing
+    else -- not the slot, the batch or the number of launches."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10((index, 0, 0, 0), (seed & _MASK, seed >> 32))[0]
+    return np.float32(w >> 8) * np.float32(2.0 ** -24)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the sampling chain in numpy
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class SamplingParams:
+    """opt_params' sampling fields with the reference's defaults (llm/include/Generate.h:60-69).  temp <= 0: greedy."""
+    temp: float = 0.8
+    top_k: int = 40
+    top_p: float = 0.95
+    repeat_penalty: float = 1.1
+    alpha_frequency: float = 0.0
+    alpha_presence: float = 0.0
+    repeat_last_n: int = 64
+    tfs_z: float = 1.0
+    typical_p: float = 1.0
+    mirostat: int = 0
+
+    def check(self, top_k_bound: int = MAX_K) -> None:
+        if self.tfs_z != 1.0 or self.typical_p != 1.0 or self.mirostat != 0:
+            raise ValueError("tail-free, typical and mirostat sampling are not built (tfs_z 1.0, typical_p 1.0, mirostat 0 only)")
+        if self.temp > 0 and not 1 <= self.top_k <= top_k_bound:
+            raise ValueError(f"top_k {self.top_k}: 1 .. {top_k_bound} (top_k <= 0 = the whole vocabulary is not built)")
+        if not 0 <= self.repeat_last_n <= RING:
+            raise ValueError(f"repeat_last_n {self.repeat_last_n}: 0 .. {RING}")
+
+
+def penalised_logits(logits_f16_row: np.ndarray, recent, params: SamplingParams) -> np.ndarray:
+    """fp32 logits after sample_repetition_penalty and sample_frequency_and_presence_penalties over the window `recent` (Generate.cc:14-60)."""
+    assert logits_f16_row.dtype == np.float16 and logits_f16_row.ndim == 1
+    x = logits_f16_row.astype(np.float32)  # half2float: exact
+    recent = np.asarray(recent, dtype=np.int64).reshape(-1)
+    recent = recent[(recent >= 0) & (recent < x.size)]
+    if recent.size == 0:
+        return x
+    ids, counts = np.unique(recent, return_counts=True)
+    rp, af, ap = np.float32(params.repeat_penalty), np.float32(params.alpha_frequency), np.float32(params.alpha_presence)
+    v = x[ids]
+    if rp != np.float32(1.0):
+        v = np.where(v <= 0, v * rp, v / rp).astype(np.float32)
+    if not (af == 0 and ap == 0):
+        v = (v - (counts.astype(np.float32) * af + np.float32(1.0) * ap)).astype(np.float32)
+    x[ids] = v
+    return x
+
+
+def _softmax_sorted(l: np.ndarray) -> np.ndarray:
+    """sample_softmax on sorted candidates (Generate.cc:91-100): subtract the maximum, expf, a SEQUENTIAL fp32 sum, divide."""
+    e = np.exp((l - l[0]).astype(np.float32)).astype(np.float32)
+    s = np.cumsum(e, dtype=np.float32)[-1]  # cumsum accumulates in order
+    return (e / s).astype(np.float32)
+
+
+def top_p_cut(p: np.ndarray, top_p) -> int:
+    """sample_top_p with min_keep 1 (Generate.cc:304-327): the first i >= 1 whose running sum exceeds top_p; candidates [0, i) stay (the one that crosses is dropped)."""
+    if np.float32(top_p) >= np.float32(1.0):
+        return int(p.size)
+    cum = np.cumsum(p, dtype=np.float32)
+    hit = np.nonzero(cum[1:] > np.float32(top_p))[0]
+    return int(hit[0]) + 1 if hit.size else int(p.size)
+
+
+def draw_reference(final_p: np.ndarray, u) -> int:
+    """Inverse CDF on the sequential fp32 running sum of final_p: the first i with u < cdf_i, the last candidate if rounding leaves none."""
+    cdf = np.cumsum(final_p, dtype=np.float32)
+    hit = np.nonzero(np.float32(u) < cdf)[0]
+    return int(hit[0]) if hit.size else int(final_p.size) - 1
+
+
+def sample_reference(logits_f16_row: np.ndarray, recent, params: SamplingParams, u) -> dict:
+    """One row through the chain tce_sample_f16 implements.  recent: the penalty window (the last repeat_last_n ids of the ring, initial zeros included).
+    Ordering rule: descending penalised logit, ascending id among equals.  Returns ids / logits (the k sorted candidates), p (first softmax), n (kept by top-p),
+    final_p (after temperature, n entries), choice and token."""
+    x = penalised_logits(logits_f16_row, recent, params)
+    V = x.size
+    if params.temp <= 0:
+        tok = int(np.argmax(x))  # the first maximum: std::max_element
+        return {"ids": np.array([tok], np.int32), "logits": x[tok:tok + 1].copy(), "p": np.zeros(1, np.float32), "n": 1, "final_p": np.zeros(1, np.float32),
+                "choice": 0, "token": tok}
+    k = min(max(int(params.top_k), 1), V)
+    if k < V:
+        kth = np.partition(x, V - k)[V - k]
+        gt = np.nonzero(x > kth)[0]
+        eq = np.nonzero(x == kth)[0][:k - gt.size]  # the lowest ids of the boundary's tie class
+        cand = np.concatenate([gt, eq])
+    else:
+        cand = np.arange(V)
+    order = np.lexsort((cand, -x[cand].astype(np.float64)))
+    ids = cand[order].astype(np.int32)
+    l = (x[ids] + np.float32(0.0)).astype(np.float32)  # (-0 -> +0, as the device returns it)
+    p = _softmax_sorted(l)
+    n = top_p_cut(p, params.top_p)
+    lt = (l[:n] / np.float32(params.temp)).astype(np.float32)
+    fp = _softmax_sorted(lt)
+    choice = draw_reference(fp, u)
+    return {"ids": ids, "logits": l, "p": p, "n": n, "final_p": fp, "choice": choice, "token": int(ids[choice])}
+
+
+def ring_window(ring: np.ndarray, pushed: int, repeat_last_n: int) -> np.ndarray:
+    """The penalty window of a ring [64] after `pushed` pushes: its last repeat_last_n entries (zeros where fewer tokens have been pushed)."""
+    n = min(max(int(repeat_last_n), 0), RING)
+    return np.array([ring[(pushed - 1 - t) % RING] for t in range(n)], np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# device state
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+_ROW_WORDS = C.sizeof(capi.SampleRow) // 4
+_DEBUG_WORDS = C.sizeof(capi.SampleDebug) // 4
+
+
+def make_row(params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> capi.SampleRow:
+    """A fresh tce_sample_row: the ring starts as 64 zeros (the reference's last_n_tokens) and takes the prompt's tokens in order."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    r = capi.SampleRow(temp=params.temp, top_k=params.top_k, top_p=params.top_p, repeat_penalty=params.repeat_penalty, alpha_frequency=params.alpha_frequency,
+                       alpha_presence=params.alpha_presence, repeat_last_n=params.repeat_last_n, max_new=int(max_new), seed_lo=seed & _MASK, seed_hi=seed >> 32,
+                       generated=0, ring_pushed=0)
+    for t in prompt_ids:
+        r.ring[r.ring_pushed % RING] = int(t)
+        r.ring_pushed += 1
+    return r
+
+
+class Sampler:
+    """The per-row device state of tce_sample_f16 for `batch` rows: rows (parameters, ring, counters), next_token, the output log [batch][log_stride], the workspace
+    (zeroed once).  debug=True keeps the sorted candidates of the last call (tests)."""
+
+    def __init__(self, batch: int, vocab: int, log_stride: int, device, top_k_bound: int = 40, stop_ids=(), debug: bool = False, tfs_z: float = 1.0,
+                 typical_p: float = 1.0, mirostat: int = 0):
+        import torch
+        if len(stop_ids) > 4:
+            raise ValueError("at most 4 stop ids")
+        self.batch, self.vocab, self.log_stride, self.top_k_bound, self.stop_ids = batch, vocab, int(log_stride), int(top_k_bound), [int(s) for s in stop_ids]
+        self.tfs_z, self.typical_p, self.mirostat = tfs_z, typical_p, mirostat
+        need = int(capi.lib().tce_sample_workspace_bytes(batch, vocab))
+        if need == 0:
+            raise ValueError("unsupported sampling shape (batch 1 .. 65535, vocab 1 .. 2^20)")
+        self.rows = torch.zeros((batch, _ROW_WORDS), dtype=torch.int32, device=device)
+        self.next_token = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.out_log = torch.full((batch, self.log_stride), -1, dtype=torch.int32, device=device)
+        self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)
+        self.uniform_override = None  # fp32 [batch] on the device: replaces the generator (tests)
+        self.debug = torch.zeros((batch, _DEBUG_WORDS), dtype=torch.int32, device=device) if debug else None
+
+    def set_row(self, slot: int, params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> None:
+        """The slot changes hands: one stream-ordered copy of its row (parameters, a fresh ring with the prompt pushed, counters at zero)."""
+        import torch
+        params.check(self.top_k_bound)
+        if not 1 <= max_new <= self.log_stride:
+            raise ValueError(f"max_new {max_new}: 1 .. {self.log_stride}")
+        row = make_row(params, seed, max_new, prompt_ids)
+        host = torch.from_numpy(np.frombuffer(bytes(row), dtype=np.int32).copy())
+        self.rows[slot].copy_(host)
+
+    def step(self, logits, pos_device, pos_bound: int) -> None:
+        """tce_sample_f16 on logits fp16 [batch][ld] (two launches on the current stream).  pos_device int32 [batch] is READ (activity) and WRITTEN (+1, or -1)."""
+        import torch
+        from .linear import _stream
+        assert logits.dtype == torch.float16 and logits.is_contiguous() and logits.dim() == 2 and logits.shape[0] == self.batch and logits.shape[1] >= self.vocab
+        assert pos_device.dtype == torch.int32 and pos_device.is_contiguous() and pos_device.numel() == self.batch
+        assert logits.is_cuda and pos_device.is_cuda
+        capi.check(capi.sample_f16(self.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound), _stream()))
+
+    def call(self, logits_ptr: int, ld: int, pos_ptr: int, pos_bound: int) -> capi.SampleCall:
+        c = capi.SampleCall(logits=logits_ptr, ld=ld, vocab=self.vocab, batch=self.batch, top_k_bound=self.top_k_bound, rows=self.rows.data_ptr(), pos_device=pos_ptr,
+                            pos_bound=int(pos_bound), log_stride=self.log_stride, next_token=self.next_token.data_ptr(), out_log=self.out_log.data_ptr(),
+                            uniform_override=self.uniform_override.data_ptr() if self.uniform_override is not None else None,
+                            debug=self.debug.data_ptr() if self.debug is not None else None, workspace=self.workspace.data_ptr(), n_stop=len(self.stop_ids),
+                            mirostat=self.mirostat, tfs_z=self.tfs_z, typical_p=self.typical_p)
+        for i, s in enumerate(self.stop_ids):
+            c.stop_ids[i] = s
+        return c
+
+    # ---- reading state back (each synchronises) ----
+    def row(self, slot: int) -> capi.SampleRow:
+        return capi.SampleRow.from_buffer_copy(self.rows[slot].cpu().numpy().tobytes())
+
+    def debug_row(self, slot: int) -> capi.SampleDebug:
+        return capi.SampleDebug.from_buffer_copy(self.debug[slot].cpu().numpy().tobytes())
+
+    def generated(self) -> np.ndarray:
+        return self.rows[:, 10].cpu().numpy().astype(np.int64)  # word 10: tce_sample_row.generated
+
+
+def embed_rows(table, token, out, pos_device, pos_bound: int, workspace) -> None:
+    """tce_embed_rows_f16: out[b] = table[token[b]] for every active row (one launch on the current stream)."""
+    import torch
+    from .linear import _stream
+    assert table.dtype == torch.float16 and table.is_contiguous() and table.dim() == 2 and out.dtype == torch.float16 and out.is_contiguous()
+    assert token.dtype == torch.int32 and pos_device.dtype == torch.int32 and token.numel() == pos_device.numel() and out.numel() == token.numel() * table.shape[1]
+    capi.check(capi.lib().tce_embed_rows_f16(table.data_ptr(), table.shape[0], table.shape[1], token.data_ptr(), out.data_ptr(), token.numel(), pos_device.data_ptr(),
+                                             int(pos_bound), workspace.data_ptr(), _stream()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# host bookkeeping
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+class SlotBook:
+    """What the host knows about the slots between synchronisations: the position of the next token each live slot will process and how many tokens it may still
+    produce.  run(n) asks it which key indices the next n replays can touch, so that pages are reserved BEFORE the replays and nothing is copied in between."""
+
+    def __init__(self, batch: int, max_keys: int):
+        self.batch, self.max_keys = batch, max_keys
+        self.pos = [-1] * batch        # -1: free or retired
+        self.generated = [0] * batch
+        self.max_new = [0] * batch
+
+    def live(self) -> list[int]:
+        return [s for s in range(self.batch) if self.pos[s] >= 0]
+
+    def admit(self, slot: int, prompt_len: int, max_new: int) -> None:
+        if self.pos[slot] >= 0:
+            raise ValueError(f"slot {slot} is live")
+        if prompt_len < 1 or prompt_len >= self.max_keys or max_new < 1:
+            raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new >= 1")
+        self.pos[slot], self.generated[slot], self.max_new[slot] = prompt_len, 1, max_new  # (admission samples the first token)
+        if max_new == 1:
+            self.pos[slot] = -1
+
+    def wanted(self, n: int) -> list[tuple[int, int]]:
+        """[(slot, highest key index)] the next n replays may append: a live slot at position p with r tokens left processes positions p .. p + min(n, r) - 1,
+        and never beyond the cache's last key (a row past it is inactive by the position rule)."""
+        out = []
+        for s in self.live():
+            steps = min(n, self.max_new[s] - self.generated[s])
+            if steps >= 1:
+                out.append((s, min(self.pos[s] + steps - 1, self.max_keys - 1)))
+        return out
+
+    def reserve(self, allocator, n: int) -> list[list[int]]:
+        """PageAllocator.reserve_many for the next n replays, all or nothing (PagePoolExhausted: nothing changed)."""
+        w = self.wanted(n)
+        return allocator.reserve_many(w) if w else []
+
+    def update(self, pos_host, generated_host) -> list[int]:
+        """After a synchronise: take the device's positions and counts; returns the slots that retired since the last update."""
+        retired = []
+        for s in range(self.batch):
+            if self.pos[s] >= 0:
+                self.generated[s] = int(generated_host[s])
+                p = int(pos_host[s])
+                if p < 0 or p >= self.max_keys:
+                    retired.append(s)
+                    p = -1
+                self.pos[s] = p
+        return retired
+
+    def clear(self, slot: int) -> None:
+        self.pos[slot], self.generated[slot], self.max_new[slot] = -1, 0, 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the front
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+class BatchedGenerator:
+    """decoders: one PagedBatchedDecoder per layer over ONE PageAllocator, or one BatchedDecoder per layer.  final_gamma fp32 [hidden], lm_head a Linear_half_int4
+    [vocab][hidden], embed_table fp16 [vocab][hidden] (the reference's fp32 table rounded once).  graph=True captures the token step once (at construction, every row
+    inactive) and run() replays it."""
+
+    def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
+                 debug: bool = False):
+        import torch
+        self.decoders = list(decoders)
+        d0 = self.decoders[0]
+        self.batch, self.hidden_size = d0.batch, d0.block.hidden
+        self.allocator = getattr(d0, "allocator", None)
+        assert all(getattr(d, "allocator", None) is self.allocator and d.batch == self.batch for d in self.decoders), "one allocator, one batch size"
+        self.max_keys = d0.attention.max_keys
+        self.pos_bound = self.max_keys - 1
+        self.final_gamma, self.lm_head, self.embed_table = final_gamma, lm_head, embed_table
+        self.eps = d0.block.eps if eps is None else eps
+        self.vocab = embed_table.shape[0]
+        assert embed_table.dtype == torch.float16 and embed_table.shape[1] == self.hidden_size and lm_head.in_features == self.hidden_size and lm_head.out_features >= self.vocab
+        dev = embed_table.device
+        self.device = dev
+        self.sampler = Sampler(self.batch, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, debug=debug)
+        self.book = SlotBook(self.batch, self.max_keys)
+        self.pos = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
+        self.hidden = torch.zeros((self.batch, self.hidden_size), dtype=torch.float16, device=dev)
+        self.xn = torch.zeros_like(self.hidden)
+        self.logits = torch.zeros((self.batch, lm_head.out_features), dtype=torch.float16, device=dev)
+        self._adm_pos = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
+        self._adm_hidden = torch.zeros_like(self.hidden)
+        self.launches_per_token = 1 + d0.LAUNCHES * len(self.decoders) + 1 + 1 + 2
+        self._graph = None
+        if graph:
+            self.token_step()  # the warm-up: every row inactive -- nothing is embedded, appended or sampled; the gate/up form is settled
+            torch.cuda.synchronize()
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                self.token_step()
+
+    # ---- one token for every live row ----
+    def token_step(self) -> None:
+        embed_rows(self.embed_table, self.sampler.next_token, self.hidden, self.pos, self.pos_bound, self.sampler.workspace)
+        for d in self.decoders:
+            d.step(self.hidden, self.pos, self.pos_bound)
+        self._head(self.hidden, self.pos)
+
+    def _head(self, hidden, pos) -> None:
+        """final norm -> lm_head at M = batch -> sampling (which advances or retires `pos`)"""
+        from .linear import _stream, rmsnorm_half
+        rmsnorm_half(hidden, self.final_gamma, self.eps, out=self.xn)
+        capi.check(capi.w4a16_forward(self.lm_head.desc(self.xn, self.logits), _stream()))
+        self.sampler.step(self.logits, pos, self.pos_bound)
+
+    # ---- admission ----
+    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None) -> list[int]:
+        """admit(slot, prompt_ids, params, seed, max_new), or admit([(slot, prompt_ids, params, seed, max_new), ...]) for several sequences through ONE prefill_many.
+        The prompt is embedded, prefilled through every layer, the final norm and lm_head run on its last row and the first token is sampled; the slot's position
+        becomes the prompt length.  Synchronises.  Returns the slots that retired on their first token."""
+        import torch
+        adm = slot if prompt_ids is None else [(slot, prompt_ids, params, seed, max_new)]
+        adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(self.sampler.log_stride if mn is None else mn)) for s, ids, p, sd, mn in adm]
+        if len({s for s, *_ in adm}) != len(adm):
+            raise ValueError("admit: a slot is named twice")
+        for s, ids, p, sd, mn in adm:
+            if not 0 <= s < self.batch:
+                raise IndexError(f"slot {s} of {self.batch}")
+            if self.book.pos[s] >= 0:
+                raise ValueError(f"slot {s} is live")
+            if any(not 0 <= t < self.vocab for t in ids):
+                raise ValueError("a prompt token lies outside the vocabulary")
+            p.check(self.sampler.top_k_bound)
+            if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
+                raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new 1 .. {self.sampler.log_stride}")
+        if self.allocator is not None:  # all or nothing, before anything changes
+            if any(self.allocator.pages[s] for s, *_ in adm):
+                raise ValueError("admit: a slot still holds pages (release it first)")
+            self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])
+        rows = []
+        for s, ids, p, sd, mn in adm:
+            tok = torch.tensor(ids, dtype=torch.int32).to(self.device)
+            r = torch.empty((len(ids), self.hidden_size), dtype=torch.float16, device=self.device)
+            embed_rows(self.embed_table, tok, r, torch.zeros(len(ids), dtype=torch.int32, device=self.device), 0, self.sampler.workspace)
+            rows.append(r)
+        for d in self.decoders:
+            if self.allocator is not None:
+                d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
+            else:
+                for (s, *_), r in zip(adm, rows):
+                    d.prefill(s, r, 0)
+        self._adm_pos.fill_(-1)
+        for (s, ids, p, sd, mn), r in zip(adm, rows):
+            self.sampler.set_row(s, p, sd, mn, ids)
+            self.sampler.out_log[s].fill_(-1)
+            self._adm_hidden[s].copy_(r[-1])
+            self._adm_pos[s] = len(ids) - 1
+        self._head(self._adm_hidden, self._adm_pos)  # the first token: the sampler leaves len(ids) -- or -1 -- in the admitted slots' words
+        slots = torch.tensor([s for s, *_ in adm], dtype=torch.int64, device=self.device)
+        self.pos.index_copy_(0, slots, self._adm_pos.index_select(0, slots))
+        for s, ids, p, sd, mn in adm:
+            self.book.admit(s, len(ids), mn)
+        return self._sync()
+
+    # ---- running ----
+    def run(self, n: int) -> list[int]:
+        """n tokens for every live slot: pages for the next n positions are reserved first (all or nothing), then the step is replayed n times with no host
+        synchronisation and no host-to-device copy in between, then ONE synchronise.  Returns the slots that retired (a stop id, or their budget)."""
+        if n < 1:
+            raise ValueError("run: n >= 1")
+        if self.allocator is not None:
+            self.book.reserve(self.allocator, n)
+        for _ in range(n):
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self.token_step()
+        return self._sync()
+
+    def _sync(self) -> list[int]:
+        return self.book.update(self.pos.cpu().numpy(), self.sampler.generated())
+
+    def tokens(self, slot: int) -> list[int]:
+        """The token ids the slot's sequence has produced so far (since its admission)."""
+        n = int(self.sampler.generated()[slot])
+        return self.sampler.out_log[slot, :n].cpu().numpy().tolist()
+
+    def release(self, slot: int) -> list[int]:
+        """The slot is free again: its position word is -1 and (paged) its pages go back to the pool; returns them."""
+        self.pos[slot] = -1
+        self.book.clear(slot)
+        return self.allocator.release(slot) if self.allocator is not None else []
+
+    def embed_violations(self) -> int:
+        """Token ids tce_embed_rows_f16 refused since the workspace was made (0 unless something wrote next_token from outside)."""
+        return int(self.sampler.workspace[:4].view(self.sampler.workspace.dtype).cpu().numpy().view(np.uint32)[0])
+
+
+class HostDrivenLoop:
+    """The same decoders driven from the host, greedy: every token the logits [B][vocab] are copied to the host, the lowest-id argmax is taken in numpy, the row is
+    looked up in a host copy of the table and copied back.  A device synchronise and two copies per token -- what a caller had to do before tce_sample_f16 /
+    tce_embed_rows_f16; the yardstick of tests/test_gpu_generate.py and scripts/generate_time.py."""
+
+    def __init__(self, decoders, final_gamma, lm_head, embed_table, eps: float | None = None, stop_ids=()):
+        import torch
+        self.decoders = list(decoders)
+        d0 = self.decoders[0]
+        self.batch, self.allocator = d0.batch, getattr(d0, "allocator", None)
+        self.max_keys = d0.attention.max_keys
+        self.pos_bound = self.max_keys - 1
+        self.final_gamma, self.lm_head = final_gamma, lm_head
+        self.eps = d0.block.eps if eps is None else eps
+        self.table_host = embed_table.cpu()
+        self.vocab = embed_table.shape[0]
+        dev = embed_table.device
+        self.device = dev
+        self.hidden = torch.zeros((self.batch, d0.block.hidden), dtype=torch.float16, device=dev)
+        self.xn = torch.zeros_like(self.hidden)
+        self.logits = torch.zeros((self.batch, lm_head.out_features), dtype=torch.float16, device=dev)
+        self.pos_host = np.full(self.batch, -1, np.int32)
+        self.pos = torch.from_numpy(self.pos_host.copy()).to(dev)
+        self.next_token = np.zeros(self.batch, np.int64)
+        self.out: list[list[int]] = [[] for _ in range(self.batch)]
+        self.max_new = [0] * self.batch
+        self.stop_ids = set(int(s) for s in stop_ids)
+
+    def _argmax(self, rows_hidden) -> np.ndarray:
+        from .linear import _stream, rmsnorm_half
+        rmsnorm_half(rows_hidden, self.final_gamma, self.eps, out=self.xn)
+        capi.check(capi.w4a16_forward(self.lm_head.desc(self.xn, self.logits), _stream()))
+        lg = self.logits.cpu().numpy()[:, :self.vocab].astype(np.float32)  # (synchronises)
+        return np.argmax(lg, axis=1)  # the first maximum = the lowest id
+
+    def _take(self, slot: int, tok: int) -> None:
+        self.out[slot].append(tok)
+        self.next_token[slot] = tok
+        if tok in self.stop_ids or len(self.out[slot]) >= self.max_new[slot]:
+            self.pos_host[slot] = -1
+        else:
+            self.pos_host[slot] += 1
+
+    def admit(self, slot, prompt_ids=None, max_new: int | None = None) -> None:
+        """admit(slot, prompt_ids, max_new) or admit([(slot, prompt_ids, max_new), ...]): the prefill launches BatchedGenerator.admit makes for the same call (several
+        sequences of a paged cache through one prefill_many), the first token chosen on the host."""
+        import torch
+        adm = slot if prompt_ids is None else [(slot, prompt_ids, max_new)]
+        adm = [(int(s), [int(t) for t in ids], int(mn)) for s, ids, mn in adm]
+        rows = [self.table_host[torch.tensor(ids, dtype=torch.int64)].to(self.device).contiguous() for _, ids, _ in adm]
+        for d in self.decoders:
+            if self.allocator is not None:
+                d.prefill_many([(s, r, 0) for (s, _, _), r in zip(adm, rows)])
+            else:
+                for (s, _, _), r in zip(adm, rows):
+                    d.prefill(s, r, 0)
+        last = torch.zeros_like(self.hidden)
+        for (s, _, _), r in zip(adm, rows):
+            last[s].copy_(r[-1])
+        tok = self._argmax(last)
+        for s, ids, mn in adm:
+            self.out[s], self.max_new[s] = [], mn
+            self.pos_host[s] = len(ids) - 1
+            self._take(s, int(tok[s]))
+
+    def step(self) -> None:
+        import torch
+        live = [s for s in range(self.batch) if self.pos_host[s] >= 0]
+        if self.allocator is not None:
+            for s in live:
+                self.allocator.reserve(s, int(self.pos_host[s]))
+        self.pos.copy_(torch.from_numpy(self.pos_host))
+        rows = self.table_host[torch.from_numpy(self.next_token)]
+        self.hidden.copy_(rows)  # host -> device
+        for d in self.decoders:
+            d.step(self.hidden, self.pos, self.pos_bound)
+        tok = self._argmax(self.hidden)
+        for s in live:
+            self._take(s, int(tok[s]))
+
+    def release(self, slot: int) -> None:
+        self.pos_host[slot] = -1
+        if self.allocator is not None:
+            self.allocator.release(slot)
