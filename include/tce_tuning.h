@@ -54,6 +54,7 @@ TCE_API int tce_w4a16_set_gemv_i8(int mode, int tiles_per_wave);
  *   2600+a, 26000+a                     the 256-row / wide form with parts of the loop switched off (as 600+a; 128 / 256: where the refill is issued); outputs meaningless
  *   7700 / 7701, 7702 / 7703, 7710+u    TCE_PLAN_TAGGED on packed copies: the int8 token kernel where the list allows (7700, default) / never (7701); plans built from now on record per-stage
  *                                       wall-clock stamps in the debug buffer (7702) / stop (7703); a stage with more than u units per workgroup ends the prefix the kernel takes (7710: 512)
+ *   7704 / 7705                         the int8 decode kernel (plain M = 1 launches): wave 0 of every workgroup records its clock readings [workgroup][8] in the debug buffer (7704, lab build) / stop (7705)
  *   (6262 / 6263 of round 5 are gone: the two-quartet forms are offered for every group size again -- isa_lint.py RULE 1, profiles/r6/pk_lost_lanes_rule.md)
  *   170..179, 180..188                  W8A8: the 64 x 64 tile with 8 k-steps in flight (quartets forced / off); a tile's k-steps cut across workgroups (180 the rule, 181 off, 182.. runs)
  *   190..192, 19000 / 19001 / 19304..   W8A8: 32 x 64 tiles (190 the rule, 191 forced, 192 off); the whole tile in every wave, the k-steps dealt to the waves (round 6: 19000 the rule,

@@ -29,7 +29,10 @@ HIPCC_FLAGS = [
     "-Wall", "-Wno-unused-function",
 ]
 # per-file additions (experiments land here first)
-EXTRA_FLAGS: dict[str, list[str]] = {}  # (-fno-slp-vectorize on the GEMM: no packed fp32 fma beside the MFMAs -- measured neutral)
+# (-fno-slp-vectorize on the GEMM: no packed fp32 fma beside the MFMAs -- measured neutral)
+# w4a16_gemv_i8.hip: the decode kernels' leading scalar / pointer parameters arrive in SGPRs with the wave (kernel descriptor: kernarg_preload_length 14) -- no scalar-memory
+# round trip in front of the first weight request; a machine that does not preload runs the compiler's compatible prologue (tests/test_decode_head_isa.py)
+EXTRA_FLAGS: dict[str, list[str]] = {"w4a16_gemv_i8.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 # Kernels that must not spill a vector register: lnq_w8a8_wide_kernel keeps 16 requested weight pieces per lane in flight through its sums; ONE spilled register
 # makes the compiler wait for all of them at the spill (measured: the OPT-6.7B layer 94 -> 103 us, found only by accident).  The build fails instead.
 NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_kernel"],
@@ -39,7 +42,7 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         "w4a16_gemv_i8_token.hip": ["w4a16_gemv_i8_token_kernelILb0E"],  # (ILb1E: the lab build's instantiation with wall-clock stamps)
                                         # round 5: EVERY instantiation of the decode kernel, the general-zero-point forms included (round 4 let four of them spill 3-19 registers: each
                                         # spilled scale / zero-point load became load -> wait -> scratch store, i.e. the wave's requests went out one at a time)
-                                        "w4a16_gemv_i8.hip": ["w4a16_gemv_i8_kernel"],
+                                        "w4a16_gemv_i8.hip": ["w4a16_gemv_i8_kernel", "w4a16_gemv_i8_mixed_kernel"],
                                         # the 256-row prefill GEMM lands asm loads in ordinary variables that become valid at a counted wait: a spill of one of them in
                                         # between would store stale data (the product instantiation only; its timing-experiment variants may spill)
                                         "w4a16_gemm_pk.hip": ["w4a16_gemm_pk256_kernelILi7ELi0E", "w4a16_gemm_pk256x2_kernelILi7ELi0E", "w4a16_gemm_pkw_kernelILi7ELi0E", "w4a16_gemm_pkwx2_kernelILi7ELi0E", "w4a16_gemm_pkw3_kernelILi7ELi0E", "w4a16_gemm_pkw3x2_kernelILi7ELi0E", "w4a16_gemm_pkw512_kernelILi7ELi0E"]}  # (round 3: four forms spilled 3-34 registers under __launch_bounds__(1024))

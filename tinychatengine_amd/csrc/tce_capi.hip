@@ -213,6 +213,13 @@ int tce_w4a16_set_debug_mode(int mode) {
         }
         return TCE_OK;
     }
+    if (mode == 7704 || mode == 7705) {  // the int8 decode kernel's time budget: plain launches from now on record wave 0's clock readings per workgroup in the debug buffer (7704) / stop (7705)
+#ifndef TCE_LAB
+        if (mode == 7704) return fail(TCE_ERR_BAD_ARG, "debug mode 7704 (stamps of the int8 decode kernel) needs the lab build (python -m tinychatengine_amd.build --lab, TCE_LIB_PATH)");
+#endif
+        tce::set_gemv_i8_stamps(mode == 7704 ? g_dbg_buf_capi : nullptr);
+        return TCE_OK;
+    }
     if (mode >= 19000 && mode <= 19999) {  // W8A8, the whole tile in every wave (round 6): 19000 the rule, 19001 off, 19304 / 19404 / 19904 the 32 x 48 / 32 x 64 / 64 x 64 tile forced wherever the 64 x 64 kernel would run
         tce::set_w8a8_kslice(mode - 19000);
         return TCE_OK;

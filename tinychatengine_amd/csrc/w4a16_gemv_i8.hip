@@ -17,6 +17,8 @@
 //              (fp16 scale) per output register then serve FOUR groups; M = 2 / 4 rows of A take the columns instead (2 / 1 units per pass).
 //   * STREAM   a wave owns ROWS tiles x UW units: every weight byte it will use is requested at once (after the few x / scale bytes: loads retire in order,
 //              a wait for x must not be a wait for the weights), 1 KiB of consecutive memory per load instruction, non-temporal.
+//   * HEAD     nothing stands between wave entry and those requests: the arguments they need are flat leading parameters that arrive preloaded in SGPRs (I8SegHead
+//              below); everything else -- the store's fields, the residual's old values -- is asked for behind them.
 //   * K        the waves of a workgroup split K (UW depends on K only: a row's bits do not depend on N, so column shards are bit-identical to the whole);
 //              partial rows meet in LDS and are added in wave order.
 // Numerics: integer part exact; the roundings are one fp32 fma per (row, group), the plane / group / wave additions in a fixed order, the fp16 store.
@@ -29,26 +31,41 @@ namespace tce {
 
 namespace {
 
-struct I8Seg {
-    const void *words;       // u32 [NT16][U][64][4]
-    const half_t *dscales;   // fp16 [NT16][NG][16]
-    const unsigned *dzeros;  // u32 [NT16][NG][2]
-    half_t *C;               // fp16 [M][ldc]
-    int N, ldc, epilogue;
-    int bytes_w, bytes_s, bytes_z;
+// ---- the ordinary launch's arguments: FLAT, in the order the wave needs them (decode-head round; profiles/decode_head/).
+// A kernel argument struct passed by value cannot be preloaded; scalar and pointer parameters can: with -mllvm -amdgpu-kernarg-preload-count the first 14 dwords below
+// arrive in SGPRs with the wave (kernel descriptor: kernarg_preload_length 14 -- the 16 user SGPRs less the kernarg pointer), so x, the scales and all weight requests of a
+// single-linear launch issue without ONE scalar-memory round trip (before: header + block_begin words -> wait -> the chosen segment's fields at a computed offset + the
+// hidden blockDim word -> wait -> first request).  Hardware or firmware that does not preload enters 256 bytes earlier, through the compiler's compatible prologue: one
+// batch of scalar loads and one wait.
+//     dword  0- 1  words      linear 0's packed words          8- 9  dscales    linear 0's tile-major scales
+//            2     bytes_w    their byte count                10     bytes_s
+//            3     U          K / 128                          11     N          linear 0's rows
+//            4- 5  A          activations                      12     M
+//            6     lda                                         13     geom       waves that split K (the workgroup's width / 64; not read from the hidden
+//            7     K                                                             arguments any more) | linears of the launch << 8
+// Everything else -- what is used BEHIND the weight requests (C, ldc, epilogue flags, zero points), linears 1.. of a grouped launch, gamma, the RNORM / COMB fields -- is the
+// tail struct: ordinary scalar loads, issued with the wave's first instructions and waited for where first used (a grouped launch: ONE batch holding every further
+// linear's addressing fields, chosen by scalar selects -- at most one wait in front of the weight requests; nothing behind the K reduction's barrier).
+struct I8SegHead {  // what the requests need, linears 1.. of a grouped launch (linear 0: the leading parameters)
+    const void *words;
+    const half_t *dscales;
+    int bytes_w, bytes_s, N;
     int block_begin;  // first blockIdx.x of this linear
 };
-
-struct I8Args {
-    const half_t *A;  // fp16 [M][lda]
-    int lda, M, K, U, NG;  // U = K / 128 units, NG = K / G groups
-    int nseg;
+struct I8SegRest {  // what the epilogue (and the general-zero-point forms) need
+    half_t *C;               // fp16 [M][ldc]
+    const unsigned *dzeros;  // u32 [NT16][NG][2]
+    int ldc, epilogue, bytes_z, pad_;
+};
+struct I8Tail {
+    I8SegRest rest[TCE_MAX_GROUP];
+    I8SegHead head[TCE_MAX_GROUP - 1];
     const float *gamma;  // non-null: the activation is the UN-normalised hidden state; the conversion stages RMSNorm(A) * gamma (generalT5LayerNorm arithmetic; M = 1)
     float eps;
     // RNORM (tce_w4a16_forward_residual_rmsnorm): the residual epilogue also produces the NEXT RMSNorm of the updated row -- out_gamma fp32 [N], xn_out fp16 [N],
     // ws = float slots[2048] (the row's piece sums) + unsigned counter at word 2048 (zero between launches)
-    const float *out_gamma;
     float out_eps;
+    const float *out_gamma;
     half_t *xn_out;
     float *ws;
     // COMB (tce_w4a16_forward_deferred_attention, round 5): the activation row is the output of a deferred attention step -- per query head `comb_slots` partial
@@ -57,7 +74,25 @@ struct I8Args {
     const float *comb_part;
     const int *comb_pos_dev;
     int comb_pos, comb_slots, comb_chunk, comb_stride, comb_heads;
-    I8Seg seg[TCE_MAX_GROUP];
+    unsigned long long *dbg;  // the lab build's stamped form only (null otherwise): [workgroup][8] clock readings of wave 0, see I8Stamps
+};
+
+// The time budget of a launch (lab build, debug mode 7704; scripts/decode_head_timeline.py): wave 0 of every workgroup reads the 100 MHz clock (s_memrealtime) at
+// [0] wave entry, [1] the last weight request issued, [2] x converted and staged (its loads have arrived), [3] the contraction done (the last weight has arrived and
+// been used), [4] the output stored; [5] / [6]: the shader clock (s_memtime) at [0] / [1], for the head in cycles.  The readings stay in scalar registers until the end.
+struct I8Stamps {
+    unsigned long long t[7];
+};
+
+// one linear as the body uses it (the mixed launch passes it in this form)
+struct I8Seg {
+    const void *words;       // u32 [NT16][U][64][4]
+    const half_t *dscales;   // fp16 [NT16][NG][16]
+    const unsigned *dzeros;  // u32 [NT16][NG][2]
+    half_t *C;               // fp16 [M][ldc]
+    int N, ldc, epilogue;
+    int bytes_w, bytes_s, bytes_z;
+    int block_begin;  // first blockIdx.x of this linear
 };
 
 // ---- the MIXED launch (round 6): up to kI8MixMax decode linears that share NOTHING -- own activation, own K -- as one launch.
@@ -75,7 +110,7 @@ struct I8MixSeg {
 };
 struct I8MixArgs {
     int nseg, M;
-    // (what the body reads from I8Args whatever the form; the prologues / epilogues that use them are not compiled into the mixed form)
+    // (what the body reads from the launch's arguments whatever the form; the prologues / epilogues that use them are not compiled into the mixed form)
     const float *gamma = nullptr;
     float eps = 0.f;
     const float *out_gamma = nullptr;
@@ -118,10 +153,18 @@ __device__ __forceinline__ float dpp_add_f32(float v) {
 // gate/up launches; the next launch is then the plain kernel).  Bits: C as TCE_W4_ADD_TO_C, xn as tce_rmsnorm_half on the updated row.
 // MEASURED (round 4): correct and SLOWER than the prologue it replaces -- the write-through stores must be acknowledged before a workgroup may count itself in and the last
 // workgroup's pass is serial: +3.8 us per producer launch, a whole token 1.65 against 1.41 ms.  Kept as an entry point (tests pin its bits); DecoderBlock.step does not use it.
-// ARGS = I8MixArgs: the mixed launch (above) -- the linear, its activation and k range per WORKGROUP, the tile per wave group
-template <int MB, int GPU, int ROWS, int UW, bool Z8, int MAXT, bool NORM = false, bool RNORM = false, int COMB = 0, typename ARGS = I8Args>
-__global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
-    constexpr bool MIX = std::is_same<ARGS, I8MixArgs>::value;
+// a scalar the compiler must keep in its register from here on: kernel arguments are invariant loads, which the register allocator re-loads at the use rather than
+// keep (the parent's `args.M` was fetched again, with its own wait, between the final LDS sum and the store)
+template <typename T>
+__device__ __forceinline__ void keep_scalar(T &v) {
+    asm volatile("" : "+s"(v));
+}
+
+// The body: everything behind the choice of the workgroup's linear.  `seg`, `A_` ... are VALUES (registers, or scalar loads still in flight: waited for at the first use);
+// `args` is the launch's tail (I8Tail) or the mixed launch's struct, for the prologue / epilogue fields.
+template <int MB, int GPU, int ROWS, int UW, bool Z8, bool NORM, bool RNORM, int COMB, bool MIX, typename ARGS, bool STAMPS = false>
+__device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned char *smem, int tid, const int WK, const int U, const int K_, const int lda_, int M_, const half_t *A_,
+                                                   I8Seg seg, const int tile0, const bool gathers, const unsigned g_epoch, I8Stamps *st = nullptr) {
     static_assert(!MIX || (MB == 1 && GPU == 1 && ROWS == 1 && UW == 8 && !NORM && !RNORM && !COMB), "the mixed launch: one decode row, groups of 128, one tile per wave group");
     static_assert(!COMB || (MB == 1 && ROWS == 1 && GPU == 1 && UW == 8 && !NORM && !RNORM), "the deferred-attention prologue: one decode row, groups of 128, K a multiple of 1024");
     static_assert(MB * GPU <= 4, "sixteen output columns: rows x groups-per-unit x 4 planes");
@@ -132,49 +175,7 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
     constexpr int NP = UW / UPP;         // passes
     constexpr int XC = UW / 4;           // 8-element activation chunks per lane and row (64 lanes x 8 = 4 units)
     constexpr int SPG = 4 / GPU;         // dwords of a lane's B operand that belong to one group
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_wg[];
-    unsigned char *smem = smem_wg;
-    int tid = threadIdx.x;
-    int WK = blockDim.x >> 6;
-    int U, NG, K_, lda_, tile0;
-    const half_t *A_;
-    I8Seg seg;
-    bool gathers = false;   // MIX: this workgroup's linear is the one whose slice is exchanged inside the launch
-    unsigned g_epoch = 0;   // the exchange's epoch: the slot's count of completed exchanges + 1 (the same on every rank: they all run the same sequence per slot)
-    if constexpr (MIX) {
-        int si = 0;
-#pragma unroll
-        for (int s = 1; s < kI8MixMax; ++s)
-            if (s < args.nseg && (int)blockIdx.x >= args.s[s].seg.block_begin) si = s;
-        A_ = args.s[si].A;
-        lda_ = args.s[si].lda;
-        K_ = args.s[si].K;
-        seg = args.s[si].seg;
-        U = NG = K_ >> 7;
-        const int wl = WK;                               // waves of the launch's workgroups
-        WK = (U + UW - 1) / UW;                          // waves that split THIS linear's K
-        const int nsub = wl / WK;                        // its tiles per workgroup
-        const int sub = __builtin_amdgcn_readfirstlane(tid >> 6) / WK;
-        tile0 = ((int)blockIdx.x - seg.block_begin) * nsub + sub;
-        if (sub >= nsub || tile0 >= ((seg.N + 15) >> 4)) return;  // (whole wave groups: the barrier below counts the surviving waves)
-        tid -= sub * WK * 64;
-        smem += (size_t)sub * ((size_t)WK * UW * 512 + (size_t)WK * 16 * sizeof(float));
-        gathers = si == args.g_seg;
-        // (read before any tile of this launch can have counted itself in: the word changes only after ALL of them have)
-        if (gathers) g_epoch = __hip_atomic_load(args.g.epochs + args.g.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-    } else {
-        U = args.U;
-        NG = args.NG;
-        K_ = args.K;
-        lda_ = args.lda;
-        A_ = args.A;
-        int si = 0;
-#pragma unroll
-        for (int s = 1; s < TCE_MAX_GROUP; ++s)
-            if (s < args.nseg && (int)blockIdx.x >= args.seg[s].block_begin) si = s;
-        seg = args.seg[si];
-        tile0 = ((int)blockIdx.x - seg.block_begin) * ROWS;
-    }
+    const int NG = U * GPU;              // groups of a row
     const int lane = tid & 63;
     const int wk = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int u0 = wk * UW;
@@ -230,21 +231,11 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
     for (int m = 0; m < MB; ++m) {
         if (COMB && nact > 1) break;
         int mrow = m0 + m;
-        mrow = mrow < args.M ? mrow : args.M - 1;
+        mrow = mrow < M_ ? mrow : M_ - 1;
         // a descriptor per row, K halves long: chunks past K (a ragged last wave) read as zeros
         const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t *>(A_ + (size_t)mrow * lda_), 0, K_ * 2, 0x00020000);
 #pragma unroll
         for (int c = 0; c < XC; ++c) xv[m][c] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, u0 * 256 + (lane + 64 * c) * 16, 0, 0);  // (the scalar offset of a buffer load is NOT range-checked: everything that may run past K sits in the vector offset)
-    }
-    // the residual epilogue's old values (TCE_W4_ADD_TO_C): requested HERE, by the lanes that will add to them -- behind the barrier of the K reduction the load was a
-    // memory round trip at the very end of every o_proj / down_proj launch (the row was written by another launch, possibly on another XCD: no cache holds it)
-    half_t c_old = (half_t)0.0f;
-    if constexpr (!RNORM) {
-        if (wk == 0 && (seg.epilogue & TCE_W4_ADD_TO_C) && tid < ROWS * MB * 16) {
-            const int i16 = tid & 15, m = (tid >> 4) % MB, r = tid / (16 * MB);
-            const int row = (tile0 + r) * 16 + i16;
-            if (m0 + m < args.M && row < seg.N) c_old = seg.C[(size_t)(m0 + m) * seg.ldc + row];
-        }
     }
     float4_t gm[NORM ? XC : 1][2];  // gamma of the lane's 8 columns per chunk
     if constexpr (NORM) {
@@ -279,6 +270,11 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
             w[r][t] = __builtin_amdgcn_raw_buffer_load_b128(u0 + t < U ? rs_w : rs_none, lane * 16, (tile_of(r) * U + u0 + t) * 1024, /*nt*/ 2);
         }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (STAMPS) {
+        st->t[1] = __builtin_amdgcn_s_memrealtime();
+        st->t[6] = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
 
     if constexpr (COMB) {
         if (nact > 1) {
@@ -416,6 +412,19 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    if constexpr (STAMPS) st->t[2] = __builtin_amdgcn_s_memrealtime();
+
+    // the residual epilogue's old values (TCE_W4_ADD_TO_C): requested by the lanes that will add to them, BEHIND the weight requests and the conversion (the flags, C and
+    // ldc are tail arguments: asking here, not in front of the weights, keeps every scalar wait out of the head; loads return in order, and the value is needed behind
+    // the K reduction's barrier only -- where a load issued there was a memory round trip at the very end of every o_proj / down_proj launch)
+    half_t c_old = (half_t)0.0f;
+    if constexpr (!RNORM) {
+        if (wk == 0 && (seg.epilogue & TCE_W4_ADD_TO_C) && tid < ROWS * MB * 16) {
+            const int i16 = tid & 15, m = (tid >> 4) % MB, r = tid / (16 * MB);
+            const int row = (tile0 + r) * 16 + i16;
+            if (m0 + m < M_ && row < seg.N) c_old = seg.C[(size_t)(m0 + m) * seg.ldc + row];
+        }
+    }
 
     // ---- 3. contraction.  B set uu: the operand of unit uu of the pass in the lanes of ITS columns, zeros in the others (never written) ----
     int4_t B[UPP][2];
@@ -504,6 +513,11 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
     }
 
     // ---- 4. planes and groups -> the wave's partial rows (fixed lane order), waves -> rows (wave order), store ----
+    if constexpr (STAMPS) {
+        // (behind the last accumulator: the reading must not be taken before the contraction's results exist)
+        asm volatile("" ::"v"(acc[ROWS - 1][3]));
+        st->t[3] = __builtin_amdgcn_s_memrealtime();
+    }
     int sh_l = sh[0];
     bool bad_l = bad[0];
 #pragma unroll
@@ -525,6 +539,27 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
             if constexpr (MB == 1) v = dpp_add_f32<0x124>(v);  // row_ror 4
             if (p_l == 0 && (j >> 2) < MB) red[((wk * ROWS + r) * MB + m_l) * 16 + kq * 4 + q] = v;
         }
+    // nothing behind the barrier waits on scalar memory: what the store needs is in registers by now
+    keep_scalar(seg.C);
+    keep_scalar(seg.ldc);
+    keep_scalar(seg.epilogue);
+    keep_scalar(seg.N);
+    keep_scalar(M_);
+    float *ws_ = nullptr, *out_gamma_ = nullptr;
+    half_t *xn_out_ = nullptr;
+    unsigned out_eps_ = 0, last_wg_ = 0;
+    if constexpr (RNORM) {
+        ws_ = args.ws;
+        out_gamma_ = const_cast<float *>(args.out_gamma);
+        xn_out_ = args.xn_out;
+        out_eps_ = __builtin_bit_cast(unsigned, args.out_eps);
+        last_wg_ = gridDim.x - 1;
+        keep_scalar(ws_);
+        keep_scalar(out_gamma_);
+        keep_scalar(xn_out_);
+        keep_scalar(out_eps_);
+        keep_scalar(last_wg_);
+    }
     __syncthreads();
     if (tid < ROWS * MB * 16) {
         float part[16];
@@ -540,7 +575,7 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
         const half_t y_other = __builtin_bit_cast(half_t, (unsigned short)__builtin_amdgcn_update_dpp(0, (int)__builtin_bit_cast(unsigned short, y), 0xB1, 0xF, 0xF, false));
         half_t hnew = (half_t)0.0f;
         (void)hnew;
-        if (m0 + m < args.M && row < seg.N) {
+        if (m0 + m < M_ && row < seg.N) {
             half_t *crow = seg.C + (size_t)(m0 + m) * seg.ldc;
             if (seg.epilogue & TCE_W4_SILU_MUL_PAIRS) {
                 if ((i16 & 1) == 0) crow[row >> 1] = silu_mul_half(y, y_other);
@@ -574,7 +609,16 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
                 s0 = __builtin_fmaf(v0, v0, s0);
                 s1 = __builtin_fmaf(v1, v1, s1);
             }
-            if (tid < 2) __hip_atomic_store(args.ws + 2 * tile0 + tid, tid == 0 ? s0 : s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (tid < 2) __hip_atomic_store(ws_ + 2 * tile0 + tid, tid == 0 ? s0 : s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    if constexpr (STAMPS) {
+        if (tid < 64 && args.dbg) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores have been acknowledged
+            st->t[4] = __builtin_amdgcn_s_memrealtime();
+#pragma unroll
+            for (int i = 0; i < 7; ++i)
+                if (tid == i) args.dbg[(size_t)blockIdx.x * 8 + i] = st->t[i];
         }
     }
     if constexpr (MIX) {
@@ -635,14 +679,14 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
         if (tid < 64) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores above have left this wave before it counts itself in
             if (tid == 0) {
-                const unsigned old = __hip_atomic_fetch_add(reinterpret_cast<unsigned *>(args.ws) + 2048, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                flag[0] = old == gridDim.x - 1 ? 1u : 0u;
+                const unsigned old = __hip_atomic_fetch_add(reinterpret_cast<unsigned *>(ws_) + 2048, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                flag[0] = old == last_wg_ ? 1u : 0u;
             }
         }
         __syncthreads();
         if (flag[0] == 0u) return;
         // ---- the last workgroup: rs, then the normalised row ----
-        if (tid == 0) reinterpret_cast<unsigned *>(args.ws)[2048] = 0u;  // for the next launch on this workspace (ordered by the kernel boundary)
+        if (tid == 0) reinterpret_cast<unsigned *>(ws_)[2048] = 0u;  // for the next launch on this workspace (ordered by the kernel boundary)
         const int n = seg.N, pieces = n >> 3;
         auto sys_load_f32 = [](const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
         float tot = 0.f;
@@ -650,43 +694,124 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const ARGS args) {
         for (int c = 0; c < 16; ++c) {
             const int q = c * 64 + lane;
             float slot = 0.f;
-            slot += q < pieces ? sys_load_f32(args.ws + q) : 0.f;
-            if (q + 1024 < pieces) slot += sys_load_f32(args.ws + q + 1024);
+            slot += q < pieces ? sys_load_f32(ws_ + q) : 0.f;
+            if (q + 1024 < pieces) slot += sys_load_f32(ws_ + q + 1024);
             tot += slot;
         }
         tot = wave_sum_dpp_lane63(tot);
         tot = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tot), 63));
-        const float rs = 1.0f / sqrtf(tot / (float)n + args.out_eps);
+        const float rs = 1.0f / sqrtf(tot / (float)n + __builtin_bit_cast(float, out_eps_));
         const half_t *hrow = seg.C;
-        for (int p = tid; p < pieces; p += (int)blockDim.x) {
+        for (int p = tid; p < pieces; p += WK * 64) {
             uint4_t raw;
             asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(raw) : "v"(hrow + p * 8) : "memory");
             const half8_t hv = __builtin_bit_cast(half8_t, raw);
-            const float4_t g0 = *reinterpret_cast<const float4_t *>(args.out_gamma + p * 8), g1 = *reinterpret_cast<const float4_t *>(args.out_gamma + p * 8 + 4);
+            const float4_t g0 = *reinterpret_cast<const float4_t *>(out_gamma_ + p * 8), g1 = *reinterpret_cast<const float4_t *>(out_gamma_ + p * 8 + 4);
             half8_t o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 o[e] = rmsnorm_out(hv[e], rs, g0[e]);
                 o[4 + e] = rmsnorm_out(hv[4 + e], rs, g1[e]);
             }
-            *reinterpret_cast<half8_t *>(args.xn_out + p * 8) = o;
+            *reinterpret_cast<half8_t *>(xn_out_ + p * 8) = o;
         }
     }
+}
+
+// The ordinary launch: flat arguments (the layout and the reason: above I8SegHead).  MB rows per pass ... as the body.
+template <int MB, int GPU, int ROWS, int UW, bool Z8, int MAXT, bool NORM = false, bool RNORM = false, int COMB = 0, bool STAMPS = false>
+__global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const void *words, int bytes_w, int U, const void *A_, int lda, int K, const void *dscales_, int bytes_s, int N, int M,
+                                                            int geom, const I8Tail t) {
+    // (A, dscales: fp16; untyped in the signature so that every demangler in use can print the kernel's name)
+    const half_t *A = static_cast<const half_t *>(A_), *dscales = static_cast<const half_t *>(dscales_);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_wg[];
+    I8Stamps st;
+    if constexpr (STAMPS) {
+        st.t[0] = __builtin_amdgcn_s_memrealtime();
+        st.t[5] = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const int WK = geom & 0xFF, nseg = geom >> 8;
+    int si = 0, block_begin = 0;
+    if (nseg > 1) {
+        // a grouped launch (q/k/v, gate+up): every further linear's addressing fields in ONE batch of scalar loads, the workgroup's own by scalar selects
+        static_assert(TCE_MAX_GROUP == 4, "the batch below names three further linears");
+        I8SegHead h[TCE_MAX_GROUP - 1] = {t.head[0], t.head[1], t.head[2]};
+        // (all 24 dwords requested before the first select: left alone the compiler asks for the third linear's behind the wait for the first two -- a second round trip)
+        asm volatile("" : "+s"(h[0].words), "+s"(h[0].dscales), "+s"(h[0].bytes_w), "+s"(h[0].bytes_s), "+s"(h[0].N), "+s"(h[0].block_begin),
+                          "+s"(h[1].words), "+s"(h[1].dscales), "+s"(h[1].bytes_w), "+s"(h[1].bytes_s), "+s"(h[1].N), "+s"(h[1].block_begin),
+                          "+s"(h[2].words), "+s"(h[2].dscales), "+s"(h[2].bytes_w), "+s"(h[2].bytes_s), "+s"(h[2].N), "+s"(h[2].block_begin));
+#pragma unroll
+        for (int s = 1; s < TCE_MAX_GROUP; ++s) {
+            const bool mine = s < nseg && (int)blockIdx.x >= h[s - 1].block_begin;
+            si = mine ? s : si;
+            words = mine ? h[s - 1].words : words;
+            dscales = mine ? h[s - 1].dscales : dscales;
+            bytes_w = mine ? h[s - 1].bytes_w : bytes_w;
+            bytes_s = mine ? h[s - 1].bytes_s : bytes_s;
+            N = mine ? h[s - 1].N : N;
+            block_begin = mine ? h[s - 1].block_begin : block_begin;
+        }
+    }
+    const I8SegRest &r = t.rest[si];
+    const I8Seg seg{words, dscales, r.dzeros, r.C, N, r.ldc, r.epilogue, bytes_w, bytes_s, r.bytes_z, block_begin};
+    w4a16_gemv_i8_body<MB, GPU, ROWS, UW, Z8, NORM, RNORM, COMB, false, I8Tail, STAMPS>(t, smem_wg, (int)threadIdx.x, WK, U, K, lda, M, A, seg, ((int)blockIdx.x - block_begin) * ROWS, false, 0u, &st);
+}
+
+// The mixed launch (I8MixArgs, above): the linear, its activation and k range per WORKGROUP, the tile per wave group.  Its arguments stay one struct by value (P > 1
+// plans only; not on the single-GPU token's path).
+template <bool Z8>
+__global__ __launch_bounds__(1024) void w4a16_gemv_i8_mixed_kernel(const I8MixArgs args) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_wg[];
+    unsigned char *smem = smem_wg;
+    int tid = threadIdx.x;
+    int si = 0;
+#pragma unroll
+    for (int s = 1; s < kI8MixMax; ++s)
+        if (s < args.nseg && (int)blockIdx.x >= args.s[s].seg.block_begin) si = s;
+    const half_t *A_ = args.s[si].A;
+    const int lda_ = args.s[si].lda;
+    const int K_ = args.s[si].K;
+    const I8Seg seg = args.s[si].seg;
+    const int U = K_ >> 7;
+    const int wl = blockDim.x >> 6;                  // waves of the launch's workgroups
+    const int WK = (U + 8 - 1) / 8;                  // waves that split THIS linear's K
+    const int nsub = wl / WK;                        // its tiles per workgroup
+    const int sub = __builtin_amdgcn_readfirstlane(tid >> 6) / WK;
+    const int tile0 = ((int)blockIdx.x - seg.block_begin) * nsub + sub;
+    if (sub >= nsub || tile0 >= ((seg.N + 15) >> 4)) return;  // (whole wave groups: the barrier of the K reduction counts the surviving waves)
+    tid -= sub * WK * 64;
+    smem += (size_t)sub * ((size_t)WK * 8 * 512 + (size_t)WK * 16 * sizeof(float));
+    const bool gathers = si == args.g_seg;  // this workgroup's linear is the one whose slice is exchanged inside the launch
+    // the exchange's epoch: the slot's count of completed exchanges + 1 (the same on every rank: they all run the same sequence per slot)
+    // (read before any tile of this launch can have counted itself in: the word changes only after ALL of them have)
+    unsigned g_epoch = 0;
+    if (gathers) g_epoch = __hip_atomic_load(args.g.epochs + args.g.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    w4a16_gemv_i8_body<1, 1, 1, 8, Z8, false, false, 0, true>(args, smem, tid, WK, U, K_, lda_, args.M, A_, seg, tile0, gathers, g_epoch);
 }
 
 static int i8_units_per_wave(int U) { return U <= 128 ? 8 : (U <= 256 ? 16 : 0); }
 thread_local int g_i8_mode = 0;  // 0 automatic (wherever the shape allows and a packed copy is given), 1 off
 thread_local int g_i8_rows = 0;  // 0 the rule, 1 / 2 forced tiles per wave
+thread_local unsigned long long *g_i8_stamps = nullptr;  // lab build: the plain M = 1 / G = 128 / zero-point-8 launches run the stamped form and write [workgroup][8] readings here
 
-template <int MB, int GPU, int ROWS, int UW, bool Z8, int MAXT, bool NORM = false, bool RNORM = false, int COMB = 0>
-hipError_t launch_i8(const I8Args &a, int blocks, int m_blocks, int wk, hipStream_t stream) {
+// host side: the leading parameters of a launch and its tail
+struct I8Launch {
+    const void *words;
+    const half_t *dscales, *A;
+    int bytes_w, bytes_s, U, lda, K, N, M, nseg;
+    I8Tail t;
+};
+
+template <int MB, int GPU, int ROWS, int UW, bool Z8, int MAXT, bool NORM = false, bool RNORM = false, int COMB = 0, bool STAMPS = false>
+hipError_t launch_i8(const I8Launch &a, int blocks, int m_blocks, int wk, hipStream_t stream) {
     const size_t lds = (size_t)wk * UW * MB * 512 + (size_t)wk * ROWS * MB * 16 * sizeof(float) + (NORM ? (size_t)(a.K >> 3) * sizeof(float) + 1024 : 0);  // the row's piece sums (+ the ragged last wave's zero pieces)
-    auto kfn = w4a16_gemv_i8_kernel<MB, GPU, ROWS, UW, Z8, MAXT, NORM, RNORM, COMB>;
+    auto kfn = w4a16_gemv_i8_kernel<MB, GPU, ROWS, UW, Z8, MAXT, NORM, RNORM, COMB, STAMPS>;
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kfn, dim3(blocks, m_blocks, 1), dim3(64 * wk, 1, 1), lds, stream, a);
+    hipLaunchKernelGGL(kfn, dim3(blocks, m_blocks, 1), dim3(64 * wk, 1, 1), lds, stream, a.words, a.bytes_w, a.U, static_cast<const void *>(a.A), a.lda, a.K, static_cast<const void *>(a.dscales), a.bytes_s, a.N, a.M, wk | (a.nseg << 8), a.t);
     return hipGetLastError();
 }
 
@@ -702,6 +827,8 @@ int gemv_i8_rows_per_pass(int M, int K, int group_size) {
     while (mb > 1 && (mb * gpu > 4 || (size_t)wk * uw * mb * 512 > 72 * 1024)) mb >>= 1;
     return mb;
 }
+
+void set_gemv_i8_stamps(void *buf) { g_i8_stamps = static_cast<unsigned long long *>(buf); }
 
 void set_gemv_i8_mode(int mode, int rows) {
     g_i8_mode = mode == 1 ? 1 : 0;
@@ -734,15 +861,14 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
         gamma = static_cast<const float *>(d0.rmsnorm_gamma);
         eps = d0.rmsnorm_eps;
     }
-    I8Args a{};
-    a.gamma = gamma;
-    a.eps = eps;
+    I8Launch a{};
+    a.t.gamma = gamma;
+    a.t.eps = eps;
     a.A = static_cast<const half_t *>(d0.A);
     a.lda = d0.lda ? d0.lda : d0.K;
     a.M = d0.M;
     a.K = d0.K;
     a.U = d0.K / 128;
-    a.NG = d0.K / d0.group_size;
     a.nseg = count;
     const int gpu = 128 / d0.group_size;
     const int uw = i8_units_per_wave(a.U);
@@ -770,29 +896,42 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
     int blocks = 0;
     for (int i = 0; i < count; ++i) {
         const tce_w4a16_desc &d = descs[i];
-        I8Seg &s = a.seg[i];
         const unsigned char *base = static_cast<const unsigned char *>(d.prepacked);
-        s.words = base;
-        s.dscales = reinterpret_cast<const half_t *>(base + pk::dscales_offset(d.N, d.K, d.group_size));
-        s.dzeros = reinterpret_cast<const unsigned *>(base + pk::dzeros_offset(d.N, d.K, d.group_size));
-        s.C = static_cast<half_t *>(d.C);
-        s.N = d.N;
-        s.epilogue = d.flags & (TCE_W4_SILU_MUL_PAIRS | TCE_W4_ADD_TO_C);
-        s.ldc = d.ldc ? d.ldc : ((s.epilogue & TCE_W4_SILU_MUL_PAIRS) ? d.N / 2 : d.N);
-        s.bytes_w = (int)pk::words_bytes(d.N, d.K);
-        s.bytes_s = (int)pk::dscales_bytes(d.N, d.K, d.group_size);
-        s.bytes_z = (int)pk::dzeros_bytes(d.N, d.K, d.group_size);
-        s.block_begin = blocks;
+        I8SegHead h{};
+        h.words = base;
+        h.dscales = reinterpret_cast<const half_t *>(base + pk::dscales_offset(d.N, d.K, d.group_size));
+        h.bytes_w = (int)pk::words_bytes(d.N, d.K);
+        h.bytes_s = (int)pk::dscales_bytes(d.N, d.K, d.group_size);
+        h.N = d.N;
+        h.block_begin = blocks;
+        if (i == 0) {  // linear 0: the leading (preloaded) parameters
+            a.words = h.words;
+            a.dscales = h.dscales;
+            a.bytes_w = h.bytes_w;
+            a.bytes_s = h.bytes_s;
+            a.N = h.N;
+        } else {
+            a.t.head[i - 1] = h;
+        }
+        I8SegRest &r = a.t.rest[i];
+        r.C = static_cast<half_t *>(d.C);
+        r.dzeros = reinterpret_cast<const unsigned *>(base + pk::dzeros_offset(d.N, d.K, d.group_size));
+        r.epilogue = d.flags & (TCE_W4_SILU_MUL_PAIRS | TCE_W4_ADD_TO_C);
+        r.ldc = d.ldc ? d.ldc : ((r.epilogue & TCE_W4_SILU_MUL_PAIRS) ? d.N / 2 : d.N);
+        r.bytes_z = (int)pk::dzeros_bytes(d.N, d.K, d.group_size);
         blocks += (pk::nt16(d.N) + rows - 1) / rows;
     }
-    for (int i = count; i < TCE_MAX_GROUP; ++i) a.seg[i] = a.seg[0];
+    for (int i = count; i < TCE_MAX_GROUP; ++i) {  // (never chosen: the kernel's selects stop at the launch's count)
+        a.t.rest[i] = a.t.rest[0];
+        a.t.head[i - 1] = I8SegHead{a.words, a.dscales, a.bytes_w, a.bytes_s, a.N, 0};
+    }
     hipError_t e = hipErrorInvalidConfiguration;
     if (rn) {  // residual add + the next RMSNorm: one decode row, one linear, groups of 128, N <= 16384 (the 2048 slots of the order)
         if (count != 1 || gamma || mb != 1 || gpu != 1 || d0.M != 1 || !(d0.flags & TCE_W4_ADD_TO_C) || d0.N > 16384 || d0.N % 8 != 0) return TCE_ERR_UNSUPPORTED_SHAPE;
-        a.out_gamma = rn->gamma;
-        a.out_eps = rn->eps;
-        a.xn_out = static_cast<half_t *>(rn->xn_out);
-        a.ws = static_cast<float *>(rn->workspace);
+        a.t.out_gamma = rn->gamma;
+        a.t.out_eps = rn->eps;
+        a.t.xn_out = static_cast<half_t *>(rn->xn_out);
+        a.t.ws = static_cast<float *>(rn->workspace);
         if (uw == 8) e = z8 ? launch_i8<1, 1, 1, 8, true, 1024, false, true>(a, blocks, m_blocks, wk, stream) : launch_i8<1, 1, 1, 8, false, 1024, false, true>(a, blocks, m_blocks, wk, stream);
         else if (z8) e = launch_i8<1, 1, 1, 16, true, 1024, false, true>(a, blocks, m_blocks, wk, stream);
         else return TCE_ERR_UNSUPPORTED_SHAPE;  // K > 16384 with general zero points: the epilogue's registers on top of 16 KiB of weights per wave and the zero-point chain do not fit 128 (the form spilled; no instantiation spills: build.py NO_VGPR_SPILL)
@@ -805,13 +944,13 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
     if (comb && comb->slots > 1) {  // the activation row = a deferred attention step's partial states (one decode row, one linear, groups of 128, K = heads x 128 in whole 1024-k waves)
         if (count != 1 || gamma || mb != 1 || gpu != 1 || uw != 8 || d0.M != 1 || d0.K != comb->heads * 128 || d0.K % 1024 != 0 || comb->slots > kAttnDeferMaxSlots || comb->stride != 132)
             return TCE_ERR_UNSUPPORTED_SHAPE;
-        a.comb_part = comb->part;
-        a.comb_pos_dev = comb_pos_dev;
-        a.comb_pos = comb_pos;
-        a.comb_slots = comb->slots;
-        a.comb_chunk = comb->chunk;
-        a.comb_stride = comb->stride;
-        a.comb_heads = comb->heads;
+        a.t.comb_part = comb->part;
+        a.t.comb_pos_dev = comb_pos_dev;
+        a.t.comb_pos = comb_pos;
+        a.t.comb_slots = comb->slots;
+        a.t.comb_chunk = comb->chunk;
+        a.t.comb_stride = comb->stride;
+        a.t.comb_heads = comb->heads;
         // (compiled for at most four waves -- K <= 4096, the 7B / 8B widths --: eight slots of partial states in flight beside the wave's weights need more registers than
         //  sixteen waves per CU leave)
         if (wk > 4) return TCE_ERR_UNSUPPORTED_SHAPE;
@@ -833,6 +972,17 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
         }
         return TCE_OK;
     }
+#ifdef TCE_LAB  // (the stamped instantiation: the lab build, build.py --lab)
+    if (g_i8_stamps && z8 && mb == 1 && gpu == 1 && rows == 1 && uw == 8) {
+        a.t.dbg = g_i8_stamps;
+        e = launch_i8<1, 1, 1, 8, true, 1024, false, false, 0, true>(a, blocks, m_blocks, wk, stream);
+        if (e != hipSuccess) {
+            if (hip_err) *hip_err = e;
+            return TCE_ERR_HIP;
+        }
+        return TCE_OK;
+    }
+#endif
 #define TCE_I8(MB_, GPU_, ROWS_, UW_, MAXT_)                                                                                        \
     if (mb == MB_ && gpu == GPU_ && rows == ROWS_ && uw == UW_) {                                                                   \
         e = z8 ? launch_i8<MB_, GPU_, ROWS_, UW_, true, MAXT_>(a, blocks, m_blocks, wk, stream)                                     \
@@ -855,7 +1005,7 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
     return TCE_OK;
 }
 
-// ---- the mixed launch: up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as ONE launch (the kernel with ARGS = I8MixArgs) ----
+// ---- the mixed launch: up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as ONE launch (w4a16_gemv_i8_mixed_kernel) ----
 static_assert(kI8MixMax == TCE_MAX_INDEPENDENT, "include/tce_matmul.h");
 
 bool gemv_i8_mixed_supports(const tce_w4a16_desc *descs, int count) {
@@ -986,7 +1136,7 @@ int launch_w4a16_gemv_i8_mixed(const tce_w4a16_desc *descs, int count, hipStream
         hipLaunchKernelGGL(kfn, dim3(blocks, 1, 1), dim3(64 * wl, 1, 1), lds, stream, a);
         return hipGetLastError();
     };
-    const hipError_t e = z8 ? launch(w4a16_gemv_i8_kernel<1, 1, 1, 8, true, 1024, false, false, 0, I8MixArgs>) : launch(w4a16_gemv_i8_kernel<1, 1, 1, 8, false, 1024, false, false, 0, I8MixArgs>);
+    const hipError_t e = z8 ? launch(w4a16_gemv_i8_mixed_kernel<true>) : launch(w4a16_gemv_i8_mixed_kernel<false>);
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;
         return TCE_ERR_HIP;

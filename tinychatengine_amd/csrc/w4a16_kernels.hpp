@@ -132,6 +132,7 @@ int i8_token_plan_status(I8TokenPlan *tp, unsigned *status, hipError_t *hip_err)
 int i8_token_plan_stages(const I8TokenPlan *tp);
 int i8_token_plan_blocks(const I8TokenPlan *tp);
 void i8_token_plan_destroy(I8TokenPlan *tp);
+void set_gemv_i8_stamps(void *buf);  // non-null (lab build): the plain decode launches record [workgroup][8] clock readings there (csrc/w4a16_gemv_i8.hip I8Stamps; scripts/decode_head_timeline.py)
 void set_i8_token_stamps(void *buf);  // non-null: plans built from now on record [workgroup][stage][8] wall-clock stamps there (scripts/token_timeline.py)
 void set_i8_token_max_units(int u);   // a stage with more units (16-row tile x 1024-k chunk) per workgroup ends the prefix the kernel takes (default 512)
 void set_i8_token_mode(int mode);     // 0: tagged plans take this kernel where the list allows (default), 1: never (round 2's token kernel on the fp16 body)
