@@ -334,6 +334,43 @@ TCE_API int tce_attention_prefill_paged_f16(const void *qkv, int ld_qkv, void *k
                                             unsigned short alpha_half_bits, void *stream);
 TCE_API const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int causal, const tce_prefill_segment *segments, int num_segments);
 
+/* FP8 pages: the paged cache with OCP e4m3 elements -- half the bytes held and half the bytes streamed per token -- for the paged step, the paged prefill and the copies.
+ *   k_pool, v_pool  uint8 [num_pages][kv_heads][page_keys][128] each.  Page sizes, block table, trust rule and "one page number addresses both pools" are
+ *                   tce_attention_decode_step_paged_f16's.  A row is 128 bytes; a group of four consecutive keys is 512 contiguous bytes and never crosses a page.
+ *   encoding        a byte is OCP e4m3fn: 1 sign, 4 exponent (bias 7), 3 mantissa bits; subnormals m * 2^-9; 0x7f / 0xff are NaN; no infinities; the largest finite
+ *                   value is 448.  (Not the fnuz encoding.)
+ *   scales          two per call and layer, k_scale_log2 and v_scale_log2, integers in [-8, 7] passed by value: a floating-point format needs a scale for range
+ *                   only, and a power of two keeps dequantisation exact.
+ *   dequant(b, e)   = e4m3(b) * 2^e as binary16, EXACT for every finite byte and every e in the range (448 * 2^7 = 57344 <= 65504; 2^-9 * 2^-8 = 2^-17 is a multiple
+ *                   of 2^-24); a NaN byte gives a NaN.
+ *   quant(x, e)     = e4m3_rne(clamp(float(x) * 2^-e, -448, 448)) for a binary16 x: the product is exact in fp32, rounding is to nearest with ties to the even
+ *                   mantissa, the clamp saturates (+-inf included), -0 stays -0 (0x80), NaN becomes a NaN byte.
+ * tce_attention_decode_step_paged_fp8 is tce_attention_decode_step_paged_f16 with the two exponents: workspace, grid, cut, pos_device, inactive rows and
+ * tce_attention_decode_describe_paged's text are that step's.  Rows are dequantised as they are read and every arithmetic instruction behind that is the fp16 paged
+ * step's: on pools whose fp16 image holds dequant(byte) the two steps' `out` rows are bit-identical.  The token's own key (rotated in binary16 as always) and value are
+ * quantised, stored as BYTES, and weighed DEQUANTISED: the step's result is a function of the pools' contents, and a token that arrived by prefill and one that arrived by
+ * a decode step are indistinguishable.
+ * tce_attention_prefill_paged_fp8 is tce_attention_prefill_paged_f16 with the two exponents: the same segment list, block forms, pairing rule, 1024-block limit and
+ * workspace function (tce_attention_prefill_describe_paged serves both).  Rotated keys and values are quantised into their pages; key / value tiles are dequantised into
+ * the fp16 images the fp16 launch stages, so `out` is bit-identical to that launch on pools holding dequant(byte) when the new rows are on the e4m3 grid.
+ * tce_kv_pages_scatter_fp8 / tce_kv_pages_gather_fp8: the f16 pair with an e4m3 pool side and a contiguous fp16 side; scatter quantises, gather dequantises; one
+ * exponent per pool.  tce_kv_pages_pool_bytes_fp8: the bytes of ONE pool (half of tce_kv_pages_pool_bytes), 0 for an unsupported shape.
+ * Every refusal happens before any HIP call and tce_last_error() names the argument; beyond the fp16 entry points' refusals: an exponent outside [-8, 7]
+ * (TCE_ERR_BAD_ARG) and a pointer that is not 16-byte aligned (TCE_ERR_UNSUPPORTED_SHAPE, named). */
+TCE_API size_t tce_kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int head_dim);
+TCE_API int tce_attention_decode_step_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
+                                                int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int k_scale_log2,
+                                                int v_scale_log2, void *stream);
+TCE_API int tce_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                            int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out, void *workspace,
+                                            int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments, int total_rows,
+                                            unsigned short alpha_half_bits, int k_scale_log2, int v_scale_log2, void *stream);
+TCE_API int tce_kv_pages_scatter_fp8(const void *k_src, const void *v_src, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
+                                     int num_pages, int kv_heads, int head_dim, int src_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream);
+TCE_API int tce_kv_pages_gather_fp8(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys,
+                                    int num_pages, int kv_heads, int head_dim, int dst_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream);
+
 /* Device-side sampling: what the reference does on the host between Int4LlamaForCausalLM::forward and the next token's Embedding (llm/src/Generate.cc driven by
  * LLaMA3Generate.cc:127-198), for `batch` rows of fp16 logits [batch][ld] (lm_head's output at M = batch; vocab <= ld) in TWO launches (csrc/sampling.hip), so that a
  * captured decode graph yields one token per replay for every sequence with no host round trip.  Per ACTIVE row (0 <= pos_device[b] <= pos_bound, the project's rule;

@@ -20,7 +20,7 @@ def resources(src, extra=()):
         raise SystemExit(r.returncode)
     rows, cur = [], None
     for ln in r.stderr.splitlines():
-        m = re.search(r"remark: (?:[^:]*:\d+:\d+: )?\s*([A-Za-z ]+(?:\[bytes/\w+\])?): (\S+)", ln)
+        m = re.search(r"remark: (?:[^:]*:\d+:\d+: )?\s*([A-Za-z ]+(?:\[[\w/]+\])?): (\S+)", ln)
         if "Function Name:" in ln:
             cur = {"name": ln.split("Function Name:")[1].split()[0]}
             rows.append(cur)
@@ -30,10 +30,14 @@ def resources(src, extra=()):
 
 
 def demangle(n):
-    try:
-        return subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt", n], capture_output=True, text=True).stdout.strip()
-    except OSError:
-        return n
+    for tool in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", "c++filt"):
+        try:
+            out = subprocess.run([tool, n], capture_output=True, text=True).stdout.strip()
+        except OSError:
+            continue
+        if out:
+            return out
+    return n
 
 
 if __name__ == "__main__":
@@ -49,4 +53,4 @@ if __name__ == "__main__":
         if flt and flt not in nm:
             continue
         print(f"{nm:90s} vgpr {r.get('VGPRs', '?'):>4} agpr {r.get('AGPRs', '?'):>4} spill {r.get('VGPRs Spill', '?'):>3} scratch {r.get('ScratchSize [bytes/lane]', '?'):>4} "
-              f"sgpr {r.get('SGPRs', '?'):>4} occ {r.get('Occupancy [waves/SIMD]', '?'):>2} lds {r.get('LDS Size [bytes/block]', '?')}")
+              f"sgpr {r.get('SGPRs', r.get('TotalSGPRs', '?')):>4} occ {r.get('Occupancy [waves/SIMD]', '?'):>2} lds {r.get('LDS Size [bytes/block]', '?')}")

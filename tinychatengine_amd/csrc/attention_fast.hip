@@ -26,6 +26,7 @@
 // device-scope loads: MI355X_MICROARCH.md, inter-workgroup visibility; no cache-wide fence).
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "fp8_kv.hpp"
 
 namespace tce {
 
@@ -54,6 +55,12 @@ struct FastAttnArgs {
 struct PagedAttnArgs : FastAttnArgs {
     const int *table;  // int32 [batch][table_stride]: logical key j of sequence b lives in page table[b][j >> page_shift], row j & (page_keys - 1)
     int table_stride, page_shift;  // page_keys = 1 << page_shift (16 .. 256)
+};
+
+// the e4m3 paged step's: kc / vc are pools of BYTES [num_pages][kv_heads][page_keys][hd] (include/tce_matmul.h, "FP8 pages"); the two powers of two and their inverses
+struct PagedFp8AttnArgs : PagedAttnArgs {
+    float k_scale, v_scale;  // 2^k_scale_log2, 2^v_scale_log2: a byte's value times this is the cache row's binary16 element, exactly
+    float k_inv, v_inv;      // 2^-k_scale_log2, 2^-v_scale_log2: what the token's own row is multiplied by before it is rounded to a byte
 };
 
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
@@ -114,9 +121,15 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 // 1 KiB contiguous.  Which table words a wave can need depends on the grid alone (its keys kw0 .. kw0 + per_wave - 1), so they are requested BEFORE the position
 // word is waited for -- one word per lane, plain ints inside the table -- and a cache request picks its page with v_readlane: no round trip is added to the
 // chain position word -> cache rows.  Only words 0 .. pos / page_keys of an active row become addresses (see page_of below); of an inactive row, none.
-template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false>
-__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs> a) {
+// FP8 (with PAGED): the pools hold OCP e4m3 bytes, a row is 128 bytes and a lane's cache load 8 of them: a wave instruction still covers four whole consecutive keys
+// (512 contiguous bytes).  The bytes stay as they are in the double buffer -- a conversion at the request would wait for the rows there -- and become the binary16
+// registers consume() has always read at its head: every instruction behind that, and its order, is the fp16 paged step's, so on pools whose fp16 image holds
+// dequant(byte) the two steps agree bit for bit.  The token's own row is rounded to bytes (fp8_kv.hpp: the format's rule), stored as bytes, and enters `newrow`
+// DEQUANTISED: the step weighs its own key and value as the cache will hold them.
+template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false>
+__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>> a) {
     static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
+    static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
     constexpr int NT = 64 * NW, NS = 4 * NW;
     __shared__ __attribute__((aligned(16))) float st[NS][R][2 + kHD];  // the (wave, slot) states per query head: m, l, o[hd]
     __shared__ __attribute__((aligned(16))) half_t newrow[2][kHD];  // the token's own (rotated) key and value
@@ -178,9 +191,10 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
     // exponentials are computed (the online-softmax state is the only loop-carried dependence; without the explicit double
     // buffer every step paid a full memory round trip: 20 us at 2048 keys, profiles/r2/attention_decode_step.jsonl)
     constexpr int BLK = 4;
-    half8_t kbuf[2][BLK], vbuf[2][BLK];
+    using row_t = std::conditional_t<FP8, uint2_t, half8_t>;  // what a lane holds of a cache row between request and use: 8 elements
+    row_t kbuf[2][BLK], vbuf[2][BLK];
     half_t mbuf[2][BLK];  // the keys' mask values travel with their rows (a load per step inside consume() drained the queue)
-    auto fetch = [&](half8_t (&kd)[BLK], half8_t (&vd)[BLK], half_t (&md)[BLK], int it0) {
+    auto fetch = [&](row_t (&kd)[BLK], row_t (&vd)[BLK], half_t (&md)[BLK], int it0) {
 #pragma unroll
         for (int u = 0; u < BLK; ++u) {
             const int key = kw0 + it0 + u * 4 + slot;
@@ -194,13 +208,20 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
                 const bool live = g < kw1;
                 const int page = __builtin_amdgcn_readlane(tabw, __builtin_amdgcn_readfirstlane(live ? (g >> a.page_shift) - tab_e0 : 63));
                 const size_t off = page_row(page, live ? (kk & ((1 << a.page_shift) - 1)) : slot) + piece * 8;
-                kd[u] = *reinterpret_cast<const half8_t *>(a.kc + off);
-                vd[u] = *reinterpret_cast<const half8_t *>(a.vc + off);
+                if constexpr (FP8) {  // (an element is a byte: the same offset counts bytes)
+                    kd[u] = *reinterpret_cast<const uint2_t *>(reinterpret_cast<const unsigned char *>(a.kc) + off);
+                    vd[u] = *reinterpret_cast<const uint2_t *>(reinterpret_cast<const unsigned char *>(a.vc) + off);
+                } else {
+                    kd[u] = *reinterpret_cast<const half8_t *>(a.kc + off);
+                    vd[u] = *reinterpret_cast<const half8_t *>(a.vc + off);
+                }
                 md[u] = (half_t)0;
                 continue;
             }
-            kd[u] = *reinterpret_cast<const half8_t *>(kbase + (size_t)kk * kHD + piece * 8);
-            vd[u] = *reinterpret_cast<const half8_t *>(vbase + (size_t)kk * kHD + piece * 8);
+            if constexpr (!FP8) {
+                kd[u] = *reinterpret_cast<const half8_t *>(kbase + (size_t)kk * kHD + piece * 8);
+                vd[u] = *reinterpret_cast<const half8_t *>(vbase + (size_t)kk * kHD + piece * 8);
+            }
             if constexpr (MASK) md[u] = a.mask[kk];
             else md[u] = (half_t)0;
         }
@@ -233,8 +254,15 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
     for (int r = 0; r < R; ++r) qh[r] = rope ? rope_apply(q_v[r], q_p[r], cc, ss, piece) : q_v[r];
     // ---- the new key / value of this head: into LDS for this workgroup's use, into the cache by the workgroup that owns index pos ----
     if (wave == 0) {
-        const half8_t kh = rope ? rope_apply(k_v, k_p, cc, ss, piece) : k_v;
-        const half8_t vh = v_v;
+        half8_t kh = rope ? rope_apply(k_v, k_p, cc, ss, piece) : k_v;
+        half8_t vh = v_v;
+        [[maybe_unused]] uint2_t kq, vq;  // FP8: the row's bytes, and the row as the cache will hold it
+        if constexpr (FP8) {
+            kq = fp8_quant8(kh, a.k_inv);
+            vq = fp8_quant8(vh, a.v_inv);
+            kh = fp8_dequant8(kq, a.k_scale);
+            vh = fp8_dequant8(vq, a.v_scale);
+        }
         if (slot == 0) {
             *reinterpret_cast<half8_t *>(&newrow[0][piece * 8]) = kh;
             *reinterpret_cast<half8_t *>(&newrow[1][piece * 8]) = vh;
@@ -244,8 +272,13 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
                     // the cos / sin pieces which do too: it delays this store, not the cache requests)
                     const int page = __builtin_amdgcn_readfirstlane(a.table[(size_t)seq * a.table_stride + (pos >> a.page_shift)]);
                     const size_t off = page_row(page, pos & ((1 << a.page_shift) - 1)) + piece * 8;
-                    *reinterpret_cast<half8_t *>(a.kc + off) = kh;
-                    *reinterpret_cast<half8_t *>(a.vc + off) = vh;
+                    if constexpr (FP8) {
+                        *reinterpret_cast<uint2_t *>(reinterpret_cast<unsigned char *>(a.kc) + off) = kq;
+                        *reinterpret_cast<uint2_t *>(reinterpret_cast<unsigned char *>(a.vc) + off) = vq;
+                    } else {
+                        *reinterpret_cast<half8_t *>(a.kc + off) = kh;
+                        *reinterpret_cast<half8_t *>(a.vc + off) = vh;
+                    }
                 } else {
                     *reinterpret_cast<half8_t *>(a.kc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = kh;
                     *reinterpret_cast<half8_t *>(a.vc + seq_cache + ((size_t)head * a.max_keys + pos) * kHD + piece * 8) = vh;
@@ -266,14 +299,19 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
     // of the accumulators, then the four weighted value rows as fused multiply-adds that take the binary16 value straight from its register (v_fma_mix_f32).  The
     // step-by-step form this replaces -- a rescale, two exponentials and 8 conversions per step -- was bound by exactly that arithmetic: 58 vector instructions per
     // step, one wave per SIMD, 0.62 us per block against a memory round trip of about the same length (profiles/r4/attention_block_softmax_ab.jsonl).
-    auto consume = [&](const half8_t (&kd)[BLK], const half8_t (&vd)[BLK], const half_t (&md)[BLK], int it0) {
+    auto consume = [&](const row_t (&kd)[BLK], const row_t (&vd)[BLK], const half_t (&md)[BLK], int it0) {
         half8_t kk[BLK], vv[BLK];
         float sco[R][BLK];
         bool valid[BLK];
 #pragma unroll
         for (int u = 0; u < BLK; ++u) {
-            kk[u] = kd[u];
-            vv[u] = vd[u];
+            if constexpr (FP8) {
+                kk[u] = fp8_dequant8(kd[u], a.k_scale);
+                vv[u] = fp8_dequant8(vd[u], a.v_scale);
+            } else {
+                kk[u] = kd[u];
+                vv[u] = vd[u];
+            }
             valid[u] = true;
         }
         // the rare blocks -- the one that runs past the wave's range, the one that holds the token's own row -- are told apart by a wave-uniform test, so the
@@ -682,6 +720,27 @@ __global__ __launch_bounds__(256) void kv_pages_copy_kernel(half_t *k_lin, half_
     else *reinterpret_cast<half8_t *>(pool + po) = *reinterpret_cast<const half8_t *>(lin + lo);
 }
 
+// The same pair of copies with an e4m3 pool side and a contiguous fp16 side: scatter quantises (fp8_kv.hpp: the format's rule), gather dequantises.  One thread per 8
+// elements -- 16 bytes of the contiguous row, 8 of the pool row; grid.y: K / V, each with its own power of two.
+template <bool GATHER>
+__global__ __launch_bounds__(256) void kv_pages_copy_fp8_kernel(half_t *k_lin, half_t *v_lin, unsigned char *k_pool, unsigned char *v_pool, const int *table_row, int page_shift,
+                                                                int num_pages, int kv_heads, int lin_max_keys, int key0, int nkeys, int k_log2, int v_log2) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int piece = (int)(i & 15);
+    const long long r = i >> 4;  // (head, key of the range)
+    if (r >= (long long)kv_heads * nkeys) return;
+    const int head = (int)(r / nkeys), key = key0 + (int)(r % nkeys);
+    const int page = table_row[key >> page_shift];
+    if (page < 0 || page >= num_pages) return;
+    const size_t po = ((((size_t)page * kv_heads + head) << page_shift) + (key & ((1 << page_shift) - 1))) * kHD + piece * 8;
+    const size_t lo = ((size_t)head * lin_max_keys + key) * kHD + piece * 8;
+    half_t *lin = blockIdx.y ? v_lin : k_lin;
+    unsigned char *pool = blockIdx.y ? v_pool : k_pool;
+    const int e = blockIdx.y ? v_log2 : k_log2;
+    if constexpr (GATHER) *reinterpret_cast<half8_t *>(lin + lo) = fp8_dequant8(*reinterpret_cast<const uint2_t *>(pool + po), fp8_pow2(e));
+    else *reinterpret_cast<uint2_t *>(pool + po) = fp8_quant8(*reinterpret_cast<const half8_t *>(lin + lo), fp8_pow2(-e));
+}
+
 // *violations = the number of table words an active row would follow that are not page numbers, plus the active rows whose position needs a word past the row
 // (one workgroup: the tables are a few thousand words)
 __global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *table, int table_stride, int page_shift, int num_pages, int batch, const int *pos_dev,
@@ -722,14 +781,29 @@ size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) {
     return (size_t)num_pages * kv_heads * page_keys * kHD * sizeof(half_t);
 }
 
-int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
-                                  void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
-                                  hipStream_t stream, hipError_t *hip_err) {
+size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd) {
+    if (num_pages <= 0 || kv_heads <= 0 || hd != kHD || page_shift_of(page_keys) < 0) return 0;
+    return (size_t)num_pages * kv_heads * page_keys * kHD;
+}
+
+static bool fp8_log2_ok(int e) { return e >= kFp8ScaleLog2Min && e <= kFp8ScaleLog2Max; }
+static float host_pow2(int e) {
+    const unsigned bits = (unsigned)(127 + e) << 23;
+    float f;
+    __builtin_memcpy(&f, &bits, 4);
+    return f;
+}
+
+// fp8 = true: the pools are e4m3 bytes and the two exponents apply (launch_attention_decode_paged_fp8); everything else is one text for both
+static int launch_paged_step(bool fp8, int k_log2, int v_log2, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                             const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound,
+                             unsigned short alpha_bits, hipStream_t stream, hipError_t *hip_err) {
     const int shift = page_shift_of(page_keys);
     if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !pos_dev || !table || shift < 0 || table_stride < 1 ||
         (long long)pos_bound >= ((long long)table_stride << shift))
         return TCE_ERR_UNSUPPORTED_SHAPE;
-    PagedAttnArgs a{};
+    if (fp8 && !(fp8_log2_ok(k_log2) && fp8_log2_ok(v_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedFp8AttnArgs a{};
     a.qkv = static_cast<const half_t *>(qkv);
     a.kc = static_cast<half_t *>(k_pool);
     a.vc = static_cast<half_t *>(v_pool);
@@ -756,13 +830,35 @@ int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, c
     half_t ah;
     __builtin_memcpy(&ah, &alpha_bits, 2);
     a.alpha = (float)ah;
-    hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
+    if (fp8) {
+        a.k_scale = host_pow2(k_log2);
+        a.v_scale = host_pow2(v_log2);
+        a.k_inv = host_pow2(-k_log2);
+        a.v_inv = host_pow2(-v_log2);
+        hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, static_cast<const PagedAttnArgs &>(a));
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;
         return TCE_ERR_HIP;
     }
     return TCE_OK;
+}
+
+int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
+                                  void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
+                                  hipStream_t stream, hipError_t *hip_err) {
+    return launch_paged_step(false, 0, 0, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev, pos_bound,
+                             alpha_bits, stream, hip_err);
+}
+
+int launch_attention_decode_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
+                                      void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
+                                      int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
+    return launch_paged_step(true, k_log2, v_log2, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev,
+                             pos_bound, alpha_bits, stream, hip_err);
 }
 
 int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
@@ -773,6 +869,23 @@ int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, vo
     auto h = [](void *p) { return static_cast<half_t *>(p); };
     if (gather) hipLaunchKernelGGL(kv_pages_copy_kernel<true>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), h(k_pool), h(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys);
     else hipLaunchKernelGGL(kv_pages_copy_kernel<false>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), h(k_pool), h(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_kv_pages_copy_fp8(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
+                             int lin_max_keys, int key0, int nkeys, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
+    const int shift = page_shift_of(page_keys);
+    if (shift < 0 || kv_heads <= 0 || nkeys <= 0 || key0 < 0 || (long long)key0 + nkeys > lin_max_keys || !fp8_log2_ok(k_log2) || !fp8_log2_ok(v_log2)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    const dim3 grid((unsigned)(((long long)kv_heads * nkeys * 16 + 255) / 256), 2);
+    auto h = [](void *p) { return static_cast<half_t *>(p); };
+    auto b = [](void *p) { return static_cast<unsigned char *>(p); };
+    if (gather) hipLaunchKernelGGL(kv_pages_copy_fp8_kernel<true>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), b(k_pool), b(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys, k_log2, v_log2);
+    else hipLaunchKernelGGL(kv_pages_copy_fp8_kernel<false>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), b(k_pool), b(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys, k_log2, v_log2);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;

@@ -40,6 +40,7 @@
 
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "fp8_kv.hpp"
 
 namespace tce {
 
@@ -80,11 +81,19 @@ struct PagedPrepareArgs {
     PrefillSegment seg[kMaxSegments];
 };
 
+// the e4m3 form's (tce_attention_prefill_paged_fp8): kc / vc are pools of bytes; what a rotated key / a value row is multiplied by before it is rounded to bytes
+struct PagedPrepareFp8Args : PagedPrepareArgs {
+    float k_inv, v_inv;  // 2^-k_scale_log2, 2^-v_scale_log2
+};
+
 // one thread per 16-byte piece of a (row, head slot): rotation as RotaryPosEmb_cuda_forward (hd = 128: the partner half is piece ^ 8)
 // PAGED: row r belongs to the segment whose row range holds it (a row in none is skipped), its position is that segment's pos + (r - row0), and the appended row goes
 // to the page the segment's table row names for that position.
-template <bool PAGED = false>
-__global__ __launch_bounds__(256) void attn_prefill_prepare_kernel(const std::conditional_t<PAGED, PagedPrepareArgs, PrepareArgs> a) {
+// FP8 (with PAGED): the rotation is the same binary16 statement; rows of query heads go to the fp16 workspace unchanged, rows of key and value heads are rounded to
+// e4m3 (fp8_kv.hpp) and stored as 8-byte pieces of their page's 128-byte row.
+template <bool PAGED = false, bool FP8 = false>
+__global__ __launch_bounds__(256) void attn_prefill_prepare_kernel(const std::conditional_t<FP8, PagedPrepareFp8Args, std::conditional_t<PAGED, PagedPrepareArgs, PrepareArgs>> a) {
+    static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
     const int slots = a.heads + 2 * a.kv_heads;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     int rows;
@@ -131,6 +140,12 @@ __global__ __launch_bounds__(256) void attn_prefill_prepare_kernel(const std::co
             const int page = a.table[(size_t)slot * a.table_stride + (key >> a.page_shift)];
             const int h = hs < a.heads + a.kv_heads ? hs - a.heads : hs - a.heads - a.kv_heads;
             const size_t off = ((((size_t)page * a.kv_heads + h) << a.page_shift) + (key & ((1 << a.page_shift) - 1))) * kHD;
+            if constexpr (FP8) {  // (an element is a byte: the same offset counts bytes)
+                const bool is_k = hs < a.heads + a.kv_heads;
+                unsigned char *row = reinterpret_cast<unsigned char *>(is_k ? a.kc : a.vc) + off;
+                *reinterpret_cast<uint2_t *>(row + piece * 8) = fp8_quant8(v, is_k ? a.k_inv : a.v_inv);
+                return;
+            }
             dst = (hs < a.heads + a.kv_heads ? a.kc : a.vc) + off;
         }
     } else {
@@ -228,6 +243,11 @@ struct PagedBlockArgs {
     float alpha;
 };
 
+// the e4m3 form's block arguments: the pools hold bytes, a tile's rows are dequantised on their way into LDS
+struct PagedBlockFp8Args : PagedBlockArgs {
+    float k_scale, v_scale;  // 2^k_scale_log2, 2^v_scale_log2
+};
+
 // what differs between the forms in the statements they share: the row count and first row of the segment inside qrot / out, and a key / value head's base
 __device__ __forceinline__ int qrows(const PrefillArgs &a) { return a.m; }
 __device__ __forceinline__ int qrows(const PagedBlockArgs &a) { return a.total_rows; }
@@ -258,9 +278,12 @@ struct TileWords<true> {
     }
 };
 
-template <bool MASK, int NW, int RT, bool PAGED = false>
-__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+// FP8 (with PAGED): a row of the pools is 128 e4m3 bytes; fetch_tile requests 8-byte pieces and the write into LDS dequantises them (exactly: fp8_kv.hpp), so the K
+// and V tiles in LDS are the same fp16 images at the same strides and everything behind them is shared text.
+template <bool MASK, int NW, int RT, bool PAGED = false, bool FP8 = false>
+__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8, PagedBlockFp8Args, std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs>> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
     static_assert(!PAGED || !MASK, "the paged form takes no additive mask");
+    static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
     constexpr int kBQ = 16 * RT * NW, NT = 64 * NW, KI = 1024 / NT;
     constexpr float kLog2e = 1.4426950408889634f;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -301,14 +324,20 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<PAGE
     // a tile's global loads, K and V alike: piece idx = tid + NT i -> key idx / 16, piece idx % 16 (coalesced rows).  The loads of tile kt + 1 are requested
     // before tile kt is multiplied (registers) and written to LDS once every wave is done with tile kt.  (A ring of 3-4 register sets, tiles requested that
     // far ahead, measured SLOWER -- 151 -> 202 us at 2048 rows: the registers cost occupancy and the rows were not what the waves waited for.)
-    half8_t kreg[KI], vreg[KI];
+    using piece_t = std::conditional_t<FP8, uint2_t, half8_t>;  // a lane's 8 elements of a row between request and LDS write
+    piece_t kreg[KI], vreg[KI];
     auto fetch_tile = [&](int kt) {
         const int key0 = kt * kBK;
 #pragma unroll
         for (int i = 0; i < KI; ++i) {
             const int idx = tid + NT * i, gk = key0 + (idx >> 4);
-            kreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
-            vreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+            if constexpr (FP8) {  // (byte 0 is +0)
+                kreg[i] = uint2_t{0u, 0u};
+                vreg[i] = uint2_t{0u, 0u};
+            } else {
+                kreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+                vreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+            }
             if (gk < kend) {
                 if constexpr (PAGED) {
                     // the piece's run of the tile: i with 4 waves (a pass of 256 pieces is 16 keys), 2 i + wave / 4 with 8 -- wave-uniform, so the page is a scalar
@@ -317,9 +346,14 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<PAGE
                     const size_t off = ((((size_t)page * a.kv_heads + kvh) << a.page_shift) + (run0 & ((1 << a.page_shift) - 1))) * kHD;
                     // (the lane's offset inside a 16-key run: row (tid / 16) % 16, its 16-byte piece -- the same for every tile)
                     const unsigned lane_off = (unsigned)(((tid >> 4) & 15) * kHD + (tid & 15) * 8);
-                    kreg[i] = *reinterpret_cast<const half8_t *>(kbase + off + lane_off);
-                    vreg[i] = *reinterpret_cast<const half8_t *>(vbase + off + lane_off);
-                } else {
+                    if constexpr (FP8) {  // (an element is a byte: the same offsets count bytes)
+                        kreg[i] = *reinterpret_cast<const uint2_t *>(reinterpret_cast<const unsigned char *>(a.kc) + off + lane_off);
+                        vreg[i] = *reinterpret_cast<const uint2_t *>(reinterpret_cast<const unsigned char *>(a.vc) + off + lane_off);
+                    } else {
+                        kreg[i] = *reinterpret_cast<const half8_t *>(kbase + off + lane_off);
+                        vreg[i] = *reinterpret_cast<const half8_t *>(vbase + off + lane_off);
+                    }
+                } else if constexpr (!FP8) {
                     kreg[i] = *reinterpret_cast<const half8_t *>(kbase + (size_t)gk * kHD + (idx & 15) * 8);
                     vreg[i] = *reinterpret_cast<const half8_t *>(vbase + (size_t)gk * kHD + (idx & 15) * 8);
                 }
@@ -341,8 +375,13 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<PAGE
 #pragma unroll
         for (int i = 0; i < KI; ++i) {
             const int idx = tid + NT * i;
-            *reinterpret_cast<half8_t *>(ks + (idx >> 4) * kKStride + (idx & 15) * 16) = kreg[i];
-            *reinterpret_cast<half8_t *>(vs + (idx >> 4) * kVStride + (idx & 15) * 16) = vreg[i];
+            if constexpr (FP8) {
+                *reinterpret_cast<half8_t *>(ks + (idx >> 4) * kKStride + (idx & 15) * 16) = fp8_dequant8(kreg[i], a.k_scale);
+                *reinterpret_cast<half8_t *>(vs + (idx >> 4) * kVStride + (idx & 15) * 16) = fp8_dequant8(vreg[i], a.v_scale);
+            } else {
+                *reinterpret_cast<half8_t *>(ks + (idx >> 4) * kKStride + (idx & 15) * 16) = kreg[i];
+                *reinterpret_cast<half8_t *>(vs + (idx >> 4) * kVStride + (idx & 15) * 16) = vreg[i];
+            }
         }
         if constexpr (PAGED) tw.latch();  // tile kt + 1's words arrived with tile kt's rows
         __syncthreads();
@@ -509,6 +548,40 @@ void attn_prefill_paged_kernel(const PagedPrefillArgs a) {
     }
 }
 
+// The e4m3 launch: the same workgroups, block list and pairs on pools of bytes.  (waves per SIMD: every form is pinned to what its fp16 counterpart has -- FP8_WAVES
+// below, from profiles/fp8_kv/kernel_resources.txt: a tile's pieces are 8 registers fewer per lane and pass, which by itself would let some forms fit one more wave and
+// take the schedule the compiler makes for it, the effect the note above describes.)
+struct PagedPrefillFp8Args : PagedPrefillArgs {
+    float k_scale, v_scale;
+};
+__device__ __forceinline__ PagedBlockFp8Args paged_block_args_fp8(const PagedPrefillFp8Args &a, const PrefillSegment sg) {
+    PagedBlockFp8Args b;
+    static_cast<PagedBlockArgs &>(b) = paged_block_args(a, sg);
+    b.k_scale = a.k_scale;
+    b.v_scale = a.v_scale;
+    return b;
+}
+// (the fp16 forms' registers -> waves per SIMD: 4 waves x 1 row tile 196 / 209 -> 2; 8 x 1 120 -> 4, paired 156 -> 3 (pinned); 8 x 2 221 / 232 -> 2; 4 x 2 301 / 314 -> 1)
+#define FP8_WAVES(NW, RT, PAIR) ((RT) == 2 ? ((NW) == 8 ? 2 : 1) : ((NW) == 8 ? ((PAIR) ? 3 : 4) : 2))
+template <int NW, int RT, bool PAIR>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FP8_WAVES(NW, RT, PAIR), FP8_WAVES(NW, RT, PAIR))))
+void attn_prefill_paged_fp8_kernel(const PagedPrefillFp8Args a) {
+    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile (fp16: dequantised on the way in)
+    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
+    const int i = (int)blockIdx.x;
+    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
+    attn_prefill_block<false, NW, RT, true, true>(paged_block_args_fp8(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
+    if constexpr (PAIR) {
+        const int j = a.nblocks - 1 - i;
+        if (i < j) {
+            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
+            attn_prefill_block<false, NW, RT, true, true>(paged_block_args_fp8(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
+        }
+    }
+}
+
+#undef FP8_WAVES
+
 thread_local int g_prefill_pair = 0;   // 0: by the rule; 1 / 2: pairing forced on / off
 thread_local int g_prefill_waves = 0;  // 0: by the rule in launch_attention_prefill; forced (tests, sweeps): 4 / 8 waves with one row tile per wave, 14 / 18: with two
 
@@ -665,18 +738,29 @@ int describe_attention_prefill_paged(int heads, int causal, const int *segments,
     return TCE_OK;
 }
 
-int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                   const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
-                                   int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err) {
+namespace {
+float host_pow2(int e) {
+    const unsigned bits = (unsigned)(127 + e) << 23;
+    float f;
+    __builtin_memcpy(&f, &bits, 4);
+    return f;
+}
+}  // namespace
+
+// fp8 = true: the pools are e4m3 bytes and the two exponents apply (launch_attention_prefill_paged_fp8); the plan and both launches' shapes are one text
+static int launch_paged_prefill(bool fp8, int k_log2, int v_log2, const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys,
+                                const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
+                                int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err) {
     const int shift = prefill_page_shift(page_keys);
     if (shift < 0 || nseg < 1 || nseg > kMaxSegments || !table || table_stride < 1 || kv_heads <= 0 || heads % kv_heads != 0 || total_rows < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
-    PagedPrefillArgs a{};
+    if (fp8 && (k_log2 < kFp8ScaleLog2Min || k_log2 > kFp8ScaleLog2Max || v_log2 < kFp8ScaleLog2Min || v_log2 > kFp8ScaleLog2Max)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedPrefillFp8Args a{};
     __builtin_memcpy(a.seg, segments, sizeof(PrefillSegment) * nseg);
     int form = 0;
     unsigned short order[kMaxListedBlocks] = {};
     if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order)) return TCE_ERR_UNSUPPORTED_SHAPE;
     for (int i = 0; i < a.nblocks; ++i) a.order[i >> 1] |= (unsigned)order[i] << ((i & 1) * 16);
-    PagedPrepareArgs p{};
+    PagedPrepareFp8Args p{};
     p.qkv = static_cast<const half_t *>(qkv);
     p.ld_qkv = ld_qkv;
     p.qrot = static_cast<half_t *>(workspace);
@@ -693,7 +777,15 @@ int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, vo
     p.nseg = nseg;
     __builtin_memcpy(p.seg, a.seg, sizeof(p.seg));
     const long long pieces = (long long)total_rows * (heads + 2 * kv_heads) * 16;
-    hipLaunchKernelGGL(attn_prefill_prepare_kernel<true>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, p);
+    if (fp8) {
+        p.k_inv = host_pow2(-k_log2);
+        p.v_inv = host_pow2(-v_log2);
+        a.k_scale = host_pow2(k_log2);
+        a.v_scale = host_pow2(v_log2);
+        hipLaunchKernelGGL((attn_prefill_prepare_kernel<true, true>), dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(attn_prefill_prepare_kernel<true>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, static_cast<const PagedPrepareArgs &>(p));
+    }
     a.qrot = p.qrot;
     a.kc = p.kc;
     a.vc = p.vc;
@@ -711,8 +803,13 @@ int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, vo
     auto go = [&](auto nw_c, auto rt_c) {
         constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
         const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
-        if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, a);
-        else hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
+        if (fp8) {
+            if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, a);
+            else hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
+        } else {
+            if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillArgs &>(a));
+            else hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillArgs &>(a));
+        }
     };
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
@@ -728,6 +825,20 @@ int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, vo
         return TCE_ERR_HIP;
     }
     return TCE_OK;
+}
+
+int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                   const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
+                                   int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err) {
+    return launch_paged_prefill(false, 0, 0, qkv, ld_qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, causal, out, ld_out, workspace, heads, kv_heads, segments,
+                                nseg, total_rows, alpha, stream, hip_err);
+}
+
+int launch_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                       const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
+                                       int total_rows, float alpha, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
+    return launch_paged_prefill(true, k_log2, v_log2, qkv, ld_qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, causal, out, ld_out, workspace, heads, kv_heads,
+                                segments, nseg, total_rows, alpha, stream, hip_err);
 }
 
 }  // namespace tce

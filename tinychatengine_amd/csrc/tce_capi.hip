@@ -1221,6 +1221,42 @@ int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int 
     return TCE_OK;
 }
 
+// the e4m3 pages' two exponents (include/tce_matmul.h, "FP8 pages")
+static int check_fp8_scales(const char *who, int k_scale_log2, int v_scale_log2) {
+    if (k_scale_log2 < -8 || k_scale_log2 > 7) return fail(TCE_ERR_BAD_ARG, "%s: k_scale_log2 %d outside [-8, 7]", who, k_scale_log2);
+    if (v_scale_log2 < -8 || v_scale_log2 > 7) return fail(TCE_ERR_BAD_ARG, "%s: v_scale_log2 %d outside [-8, 7]", who, v_scale_log2);
+    return TCE_OK;
+}
+
+size_t tce_kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes_fp8(num_pages, kv_heads, page_keys, hd); }
+
+int tce_attention_decode_step_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                        const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                        const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
+    static const char *who = "tce_attention_decode_step_paged_fp8";
+    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
+    if (table_stride < 1 || num_pages < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages >= 1", who);
+    if (batch <= 0 || heads <= 0 || pos_bound < 0 || (long long)pos_bound >= (long long)table_stride * page_keys)
+        return fail(TCE_ERR_BAD_ARG, "%s: need batch, heads > 0 and 0 <= pos_bound < table_stride * page_keys", who);
+    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
+    if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
+    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: batch %d (at most 65535: the grid's second dimension)", who, batch);
+    const void *ptrs[] = {qkv, k_pool, v_pool, cosv, sinv};
+    const char *names[] = {"qkv", "k_pool", "v_pool", "cos_table", "sin_table"};
+    for (int i = 0; i < 5; ++i)
+        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
+    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: pos_device must be int32-aligned", who);
+    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_attention_decode_paged_fp8(qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd,
+                                                          pos_device, pos_bound, alpha_bits, k_scale_log2, v_scale_log2, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "fp8 paged attention decode step launch") : rc;
+}
+
 int tce_attention_decode_step_paged_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                         const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
                                         const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
@@ -1272,6 +1308,39 @@ int tce_kv_pages_gather_f16(const void *k_pool, const void *v_pool, void *k_dst,
                             int kv_heads, int hd, int dst_max_keys, int key0, int nkeys, void *stream) {
     return kv_pages_copy("tce_kv_pages_gather_f16", true, k_dst, v_dst, const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, table_stride, page_keys, num_pages,
                          kv_heads, hd, dst_max_keys, key0, nkeys, stream);
+}
+
+static int kv_pages_copy_fp8(const char *who, bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
+                             int num_pages, int kv_heads, int hd, int lin_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream) {
+    if (!k_lin || !v_lin || !k_pool || !v_pool || !table_row) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
+    if (table_stride < 1 || num_pages < 1 || kv_heads < 1 || lin_max_keys < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages, kv_heads, max_keys >= 1", who);
+    if (key0 < 0 || nkeys < 1 || (long long)key0 + nkeys > lin_max_keys || (long long)key0 + nkeys > (long long)table_stride * page_keys)
+        return fail(TCE_ERR_BAD_ARG, "%s: rows [%d, %d + %d) must lie inside the contiguous cache (%d keys) and the table row (%d pages of %d)", who, key0, key0, nkeys,
+                    lin_max_keys, table_stride, page_keys);
+    if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
+    const void *ptrs[] = {k_lin, v_lin, k_pool, v_pool};
+    const char *names[] = {gather ? "k_dst" : "k_src", gather ? "v_dst" : "v_src", "k_pool", "v_pool"};
+    for (int i = 0; i < 4; ++i)
+        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
+    if (reinterpret_cast<uintptr_t>(table_row) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: the table row must be int32-aligned", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_kv_pages_copy_fp8(gather, k_lin, v_lin, k_pool, v_pool, table_row, page_keys, num_pages, kv_heads, lin_max_keys, key0, nkeys, k_scale_log2,
+                                                 v_scale_log2, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, who) : rc;
+}
+
+int tce_kv_pages_scatter_fp8(const void *k_src, const void *v_src, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
+                             int kv_heads, int hd, int src_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream) {
+    return kv_pages_copy_fp8("tce_kv_pages_scatter_fp8", false, const_cast<void *>(k_src), const_cast<void *>(v_src), k_pool, v_pool, table_row, table_stride, page_keys,
+                             num_pages, kv_heads, hd, src_max_keys, key0, nkeys, k_scale_log2, v_scale_log2, stream);
+}
+
+int tce_kv_pages_gather_fp8(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
+                            int kv_heads, int hd, int dst_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream) {
+    return kv_pages_copy_fp8("tce_kv_pages_gather_fp8", true, k_dst, v_dst, const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, table_stride, page_keys,
+                             num_pages, kv_heads, hd, dst_max_keys, key0, nkeys, k_scale_log2, v_scale_log2, stream);
 }
 
 int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
@@ -1449,6 +1518,46 @@ const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int ca
     std::snprintf(buf, sizeof(buf), "form=%d rows-per-block=%d pair=%s blocks=%d workgroups=%d segments=%d", form, form == 18 ? 256 : (form == 8 || form == 14 ? 128 : 64),
                   pair ? "yes" : "no", blocks, wgs, num_segments);
     return buf;
+}
+
+int tce_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride, int page_keys,
+                                    int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, int hd,
+                                    const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2,
+                                    void *stream) {
+    static const char *who = "tce_attention_prefill_paged_fp8";
+    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
+    if (table_stride < 1 || num_pages < 1 || table_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_rows, table_stride, num_pages >= 1", who);
+    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
+    if (heads <= 0 || total_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need heads, total_rows > 0", who);
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
+    if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
+    const int rcs = check_prefill_segments(who, segments, num_segments, table_rows, (long long)table_stride * page_keys, total_rows);
+    if (rcs != TCE_OK) return rcs;
+    const int width = (heads + 2 * kv_heads) * hd;
+    if (ld_qkv == 0) ld_qkv = width;
+    if (ld_out == 0) ld_out = heads * hd;
+    if (ld_qkv < width || ld_out < heads * hd) return fail(TCE_ERR_BAD_ARG, "%s: a leading dimension is shorter than its row", who);
+    if (ld_qkv % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_qkv must be a multiple of 8 (16-byte pieces)", who);
+    if (ld_out % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 7)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_out must be a multiple of 4 and out 8-byte aligned (8-byte stores)", who);
+    const void *ptrs[] = {qkv, k_pool, v_pool, cosv, sinv, workspace};
+    const char *names[] = {"qkv", "k_pool", "v_pool", "cos_table", "sin_table", "workspace"};
+    for (int i = 0; i < 6; ++i)
+        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
+    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
+    int form = 0, pair = 0, blocks = 0, wgs = 0;
+    if (tce::describe_attention_prefill_paged(heads, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, &form, &pair, &blocks, &wgs) != TCE_OK)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
+    tce::half_t ah;
+    __builtin_memcpy(&ah, &alpha_bits, 2);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_attention_prefill_paged_fp8(qkv, ld_qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, causal ? 1 : 0, out, ld_out, workspace,
+                                                           heads, kv_heads, reinterpret_cast<const int *>(segments), num_segments, total_rows, (float)ah, k_scale_log2,
+                                                           v_scale_log2, static_cast<hipStream_t>(stream), &he);
+    if (rc == TCE_ERR_HIP) return hip_fail(he, "fp8 paged attention prefill launch");
+    return rc == TCE_OK ? TCE_OK : fail(rc, "%s: unsupported shape", who);
 }
 
 int tce_attention_prefill_paged_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride, int page_keys,

@@ -286,6 +286,17 @@ int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, vo
                          int lin_max_keys, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err);
 int launch_kv_block_table_check(const int *table, int table_stride, int page_keys, int num_pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations,
                                 hipStream_t stream, hipError_t *hip_err);
+// the e4m3 forms of the paged step, the paged prefill and the copies (fp8_kv.hpp: the format): pools of bytes [num_pages][kv_heads][page_keys][hd], one power-of-two
+// exponent in [-8, 7] per pool; UNSUPPORTED_SHAPE for an exponent outside it.  The contiguous side of the copies stays fp16: scatter quantises, gather dequantises.
+size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd);
+int launch_attention_decode_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
+                                      void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
+                                      int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
+int launch_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                       const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
+                                       int total_rows, float alpha, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
+int launch_kv_pages_copy_fp8(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
+                             int lin_max_keys, int key0, int nkeys, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
 int launch_rope_half(void *q, void *k, const void *cosv, const void *sinv, int heads, int len, int hd, int start_idx, hipStream_t stream, hipError_t *hip_err);
 int launch_softmax_half(const void *x, void *out, long long rows, int n, hipStream_t stream, hipError_t *hip_err);
 int launch_prefetch(const void *ptr, long long bytes, int workgroups, hipStream_t stream, hipError_t *hip_err);

@@ -13,6 +13,10 @@ rows are bit-identical to tce_attention_decode_step_batch_f16 on contiguous cach
     PagedBatchedDecoder        BatchedDecoder's seven launches with the paged step as launch 3; prefill / prefill_many: BatchedDecoder.prefill's launches once for
                                the rows of all admitted sequences, the paged prefill in the middle (no staging cache, no gather, no scatter)
 
+kv_dtype="fp8_e4m3": the pools hold OCP e4m3 bytes (include/tce_matmul.h, "FP8 pages") -- half the bytes held and streamed per token -- with one power-of-two scale
+per pool, 2^k_scale_log2 and 2^v_scale_log2, exponents in [-8, 7].  dequant(byte) is exact in binary16 and the arithmetic behind it is the fp16 kernels'.
+fp8_quantize_reference / fp8_dequantize_reference restate the format on the host.
+
 Trust: the step follows only table words 0 .. pos // page_keys of an active row; everything else in the table may hold anything (a released slot's words stay as
 they were).  It does not validate page numbers: PageAllocator writes only numbers in [0, num_pages), and PagedBatchDecodeAttention.table_violations runs
 tce_kv_block_table_check for a caller who wants the table checked on the device before a launch.
@@ -29,6 +33,49 @@ from .attention_ops import DecodeAttention
 from .batch_decode import BatchedDecoder
 from .decoder_block import DecoderBlock
 from .linear import _stream
+
+
+FP8_SCALE_LOG2_MIN, FP8_SCALE_LOG2_MAX = -8, 7
+KV_DTYPES = ("fp16", "fp8_e4m3")
+
+
+def _check_scale_log2(e: int) -> int:
+    if int(e) != e or not FP8_SCALE_LOG2_MIN <= int(e) <= FP8_SCALE_LOG2_MAX:
+        raise ValueError(f"scale exponent {e}: an integer in [{FP8_SCALE_LOG2_MIN}, {FP8_SCALE_LOG2_MAX}]")
+    return int(e)
+
+
+def fp8_quantize_reference(x_f16, e: int) -> np.ndarray:
+    """quant(x, e) = e4m3_rne(clamp(float(x) * 2^-e, -448, 448)) of a binary16 array (numpy or torch), as uint8 of the same shape: the product is exact in fp32, nearest
+    with ties to the even mantissa, saturating (+-inf included), -0 stays 0x80, NaN becomes the NaN byte 0x7f.  tests/test_fp8_kv_host.py holds it to the format's
+    definition for every finite binary16 value and every exponent."""
+    e = _check_scale_log2(e)
+    x = x_f16.detach().cpu().numpy() if isinstance(x_f16, torch.Tensor) else np.asarray(x_f16)
+    if x.dtype != np.float16:
+        raise TypeError("fp8_quantize_reference takes binary16")
+    with np.errstate(invalid="ignore"):  # (NaN inputs pass through the product)
+        x32 = np.ascontiguousarray(x.astype(np.float32) * np.float32(2.0 ** -e))
+    out = torch.from_numpy(x32).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).numpy().copy()
+    out[np.isnan(x32)] = 0x7F
+    return out
+
+
+def fp8_dequantize_reference(b, e: int) -> np.ndarray:
+    """dequant(b, e) = e4m3(b) * 2^e of a uint8 array (numpy or torch) as binary16 of the same shape -- exact for every finite byte; the NaN bytes 0x7f / 0xff give the
+    NaN 0x7fff.  Built from sign / exponent / mantissa, not from a library conversion."""
+    e = _check_scale_log2(e)
+    b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
+    if b.dtype != np.uint8:
+        raise TypeError("fp8_dequantize_reference takes uint8")
+    i = b.astype(np.int32)
+    ex, m = (i >> 3) & 15, (i & 7).astype(np.float64)
+    v = np.where(ex == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * np.exp2((ex - 7).astype(np.float64)))
+    v = np.where(i & 0x80, -v, v) * 2.0 ** e
+    out = v.astype(np.float16)  # (exact: every value is representable)
+    assert np.array_equal(out.astype(np.float64), v)
+    out = out.view(np.uint16).copy()
+    out[(i & 0x7F) == 0x7F] = 0x7FFF
+    return out.view(np.float16)
 
 
 class PagePoolExhausted(MemoryError):
@@ -187,17 +234,25 @@ class PageAllocator:
 class PagedBatchDecodeAttention:
     """One layer's K and V pools and the step's workspace, over a PageAllocator's table."""
 
-    def __init__(self, allocator: PageAllocator, heads: int, kv_heads: int | None, device, cos: torch.Tensor | None = None, sin: torch.Tensor | None = None):
+    def __init__(self, allocator: PageAllocator, heads: int, kv_heads: int | None, device, cos: torch.Tensor | None = None, sin: torch.Tensor | None = None,
+                 kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
+        """kv_dtype "fp16" (the default: today's pools and entry points) or "fp8_e4m3": uint8 pools of the same shape, every call through the fp8 entry points with
+        the two scale exponents (integers in [-8, 7]; ignored for fp16)."""
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype {kv_dtype!r}: one of {KV_DTYPES}")
+        self.kv_dtype, self.fp8 = kv_dtype, kv_dtype == "fp8_e4m3"
+        self.k_scale_log2, self.v_scale_log2 = _check_scale_log2(k_scale_log2), _check_scale_log2(v_scale_log2)
         self.allocator, self.batch, self.heads, self.hd = allocator, allocator.batch, heads, 128
         self.kv_heads = heads if kv_heads is None else kv_heads
         self.page_keys, self.num_pages, self.max_keys = allocator.page_keys, allocator.num_pages, allocator.max_keys
         L = capi.lib()
-        if int(L.tce_kv_pages_pool_bytes(self.num_pages, self.kv_heads, self.page_keys, self.hd)) == 0:
+        pool_bytes = L.tce_kv_pages_pool_bytes_fp8 if self.fp8 else L.tce_kv_pages_pool_bytes
+        if int(pool_bytes(self.num_pages, self.kv_heads, self.page_keys, self.hd)) == 0:
             raise ValueError("unsupported page pool shape")
         need = int(L.tce_attention_decode_batch_workspace_bytes(self.batch, heads, self.max_keys, self.hd))
         if need == 0:
             raise ValueError("unsupported batched attention shape")
-        self.k_pool = torch.zeros((self.num_pages, self.kv_heads, self.page_keys, self.hd), dtype=torch.float16, device=device)
+        self.k_pool = torch.zeros((self.num_pages, self.kv_heads, self.page_keys, self.hd), dtype=torch.uint8 if self.fp8 else torch.float16, device=device)
         self.v_pool = torch.zeros_like(self.k_pool)
         self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)  # zeroed once: the per-(sequence, head) arrival counters
         self.slot_workspace_bytes = need // self.batch
@@ -206,6 +261,10 @@ class PagedBatchDecodeAttention:
         self._staging: DecodeAttention | None = None  # made on first use of staging(): nothing in this module asks for it
         self._prefill_ws: torch.Tensor | None = None
         self._violations = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _scales(self) -> tuple:
+        """The fp8 entry points' two extra arguments (in front of the stream); nothing for fp16."""
+        return (self.k_scale_log2, self.v_scale_log2) if self.fp8 else ()
 
     def _table_args(self):
         t = self.allocator.table
@@ -221,9 +280,10 @@ class PagedBatchDecodeAttention:
             out = torch.empty((self.batch, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
         assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == self.batch * self.heads * self.hd
         p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        capi.check(capi.lib().tce_attention_decode_step_paged_f16(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out),
-                                                                  p(self.workspace), self.batch, self.heads, self.kv_heads, self.hd, p(pos_device), int(pos_bound),
-                                                                  self.alpha_bits, C.c_void_p(_stream())))
+        L = capi.lib()
+        fn = L.tce_attention_decode_step_paged_fp8 if self.fp8 else L.tce_attention_decode_step_paged_f16
+        capi.check(fn(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out), p(self.workspace), self.batch, self.heads,
+                      self.kv_heads, self.hd, p(pos_device), int(pos_bound), self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
         return out
 
     def prefill(self, segments, qkv: torch.Tensor, out: torch.Tensor | None = None, causal: bool = True) -> torch.Tensor:
@@ -244,9 +304,10 @@ class PagedBatchDecodeAttention:
         t = self.allocator.table
         assert t.is_cuda and t.device == self.k_pool.device
         p = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
-        capi.check(L.tce_attention_prefill_paged_f16(p(qkv), 0, p(self.k_pool), p(self.v_pool), p(t), t.shape[0], t.shape[1], self.page_keys, self.num_pages, p(self.cos),
-                                                     p(self.sin), 1 if causal else 0, p(out), 0, p(self._prefill_ws), self.heads, self.kv_heads, self.hd,
-                                                     C.cast(segs, C.c_void_p), len(segments), total, self.alpha_bits, C.c_void_p(_stream())))
+        fn = L.tce_attention_prefill_paged_fp8 if self.fp8 else L.tce_attention_prefill_paged_f16
+        capi.check(fn(p(qkv), 0, p(self.k_pool), p(self.v_pool), p(t), t.shape[0], t.shape[1], self.page_keys, self.num_pages, p(self.cos), p(self.sin),
+                      1 if causal else 0, p(out), 0, p(self._prefill_ws), self.heads, self.kv_heads, self.hd, C.cast(segs, C.c_void_p), len(segments), total,
+                      self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
         return out
 
     def table_violations(self, pos_device: torch.Tensor, pos_bound: int) -> int:
@@ -269,8 +330,10 @@ class PagedBatchDecodeAttention:
         assert k.dtype == v.dtype == torch.float16 and k.is_contiguous() and v.is_contiguous() and tuple(k.shape) == tuple(v.shape) and k.shape[0] == self.kv_heads
         assert (key0 + nkeys - 1) // self.page_keys < len(self.allocator.pages[slot]), "reserve the slot's pages first"
         p = lambda t: C.c_void_p(t.data_ptr())
-        capi.check(capi.lib().tce_kv_pages_scatter_f16(p(k), p(v), p(self.k_pool), p(self.v_pool), self._row(slot), self.allocator.table.shape[1], self.page_keys,
-                                                       self.num_pages, self.kv_heads, self.hd, k.shape[1], int(key0), int(nkeys), C.c_void_p(_stream())))
+        L = capi.lib()
+        fn = L.tce_kv_pages_scatter_fp8 if self.fp8 else L.tce_kv_pages_scatter_f16  # (fp8: the contiguous side stays fp16, the rows are quantised on their way in)
+        capi.check(fn(p(k), p(v), p(self.k_pool), p(self.v_pool), self._row(slot), self.allocator.table.shape[1], self.page_keys, self.num_pages, self.kv_heads,
+                      self.hd, k.shape[1], int(key0), int(nkeys), *self._scales(), C.c_void_p(_stream())))
 
     def gather_into(self, slot: int, contiguous_attention, key0: int, nkeys: int) -> None:
         """The reverse of admit: the slot's rows [key0, key0 + nkeys) into a contiguous cache pair."""
@@ -278,11 +341,13 @@ class PagedBatchDecodeAttention:
         assert k.dtype == v.dtype == torch.float16 and k.is_contiguous() and v.is_contiguous() and tuple(k.shape) == tuple(v.shape) and k.shape[0] == self.kv_heads
         assert (key0 + nkeys - 1) // self.page_keys < len(self.allocator.pages[slot]), "the slot does not hold these keys"
         p = lambda t: C.c_void_p(t.data_ptr())
-        capi.check(capi.lib().tce_kv_pages_gather_f16(p(self.k_pool), p(self.v_pool), p(k), p(v), self._row(slot), self.allocator.table.shape[1], self.page_keys,
-                                                      self.num_pages, self.kv_heads, self.hd, k.shape[1], int(key0), int(nkeys), C.c_void_p(_stream())))
+        L = capi.lib()
+        fn = L.tce_kv_pages_gather_fp8 if self.fp8 else L.tce_kv_pages_gather_f16  # (fp8: dequantised -- exactly -- into the fp16 pair)
+        capi.check(fn(p(self.k_pool), p(self.v_pool), p(k), p(v), self._row(slot), self.allocator.table.shape[1], self.page_keys, self.num_pages, self.kv_heads,
+                      self.hd, k.shape[1], int(key0), int(nkeys), *self._scales(), C.c_void_p(_stream())))
 
     def read_back(self, slot: int, keys: int) -> tuple[torch.Tensor, torch.Tensor]:
-        """The slot's first `keys` keys as a fresh contiguous pair [kv_heads][keys][128]."""
+        """The slot's first `keys` keys as a fresh contiguous fp16 pair [kv_heads][keys][128] (fp8 pages: dequantised)."""
         class _Pair:
             pass
         pair = _Pair()
@@ -315,10 +380,12 @@ class PagedBatchedDecoder(BatchedDecoder):
     """BatchedDecoder on a paged cache: the same seven launches per layer (BatchedDecoder.step itself, with PagedBatchDecodeAttention.step as launch 3), the same
     prefill launches with the paged prefill in the middle.  One PageAllocator serves the decoders of all layers."""
 
-    def __init__(self, block: DecoderBlock, allocator: PageAllocator):  # (no BatchedDecoder.__init__: it would allocate the contiguous caches)
+    def __init__(self, block: DecoderBlock, allocator: PageAllocator, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
+        # (no BatchedDecoder.__init__: it would allocate the contiguous caches)
         self.block, self.batch, self.allocator = block, allocator.batch, allocator
         dev = block.gamma1.device
-        self.attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, dev, block.attention.cos, block.attention.sin)
+        self.attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, dev, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,
+                                                   k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
         e = lambda n: torch.empty((self.batch, n), dtype=torch.float16, device=dev)
         self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
         self.act = e(block.ffn)
