@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from deferred_pair import deferred as _deferred, plain as _plain
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,25 +41,6 @@ def _setup(dev, heads, kv_heads, max_keys, seed):
     qkv = torch.empty((heads + 2 * kv_heads) * 128, device=dev).normal_(0, 1, generator=g).to(torch.float16)
     res = torch.empty(1, hidden, device=dev).normal_(0, 1, generator=g).to(torch.float16)
     return atts, o, qkv, res
-
-
-def _plain(att, o, qkv, res, pos, pos_t=None):
-    from tinychatengine_amd import capi
-    x = torch.full((1, o.in_features), float("nan"), dtype=torch.float16, device=qkv.device)
-    y = res.clone()
-    att.step(qkv, pos, out=x.view(att.heads, 128), pos_device=pos_t)
-    capi.check(capi.w4a16_forward(o.desc(x, y, flags=capi.TCE_W4_ADD_TO_C), torch.cuda.current_stream().cuda_stream))
-    return x, y
-
-
-def _deferred(att, o, qkv, res, pos, pos_t=None):
-    from tinychatengine_amd import capi
-    x = torch.full((1, o.in_features), float("nan"), dtype=torch.float16, device=qkv.device)
-    y = res.clone()
-    att.step(qkv, pos, out=x.view(att.heads, 128), pos_device=pos_t, defer=True)
-    capi.check(capi.lib().tce_w4a16_forward_deferred_attention(C.byref(o.desc(x, y, flags=capi.TCE_W4_ADD_TO_C)), C.byref(att.deferred),
-                                                               C.c_void_p(pos_t.data_ptr() if pos_t is not None else 0), int(pos), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return x, y, att.deferred.slots
 
 
 @pytest.mark.parametrize("heads,kv_heads", [(32, 8), (32, 32), (8, 8)])
