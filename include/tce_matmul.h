@@ -371,6 +371,28 @@ TCE_API int tce_kv_pages_scatter_fp8(const void *k_src, const void *v_src, void 
 TCE_API int tce_kv_pages_gather_fp8(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys,
                                     int num_pages, int kv_heads, int head_dim, int dst_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream);
 
+/* The paged step with T = rows_per_seq QUERY ROWS PER SEQUENCE (1 .. TCE_SPEC_MAX_ROWS): the attention launch of speculative decoding, where a sequence's next token
+ * and up to T - 1 guessed continuations go through the layers together.  The arguments are tce_attention_decode_step_paged_f16 / _fp8's plus rows_per_seq:
+ *   qkv, out, pos_device   batch * T rows / words: virtual row y = b * T + t belongs to sequence b -- row b of block_table -- and sits at position pos_device[y]
+ *   workspace              tce_attention_decode_batch_workspace_bytes(batch * rows_per_seq, heads, table_stride * page_keys, head_dim) bytes, zeroed once: one slice
+ *                          per virtual row
+ * A row is active under the project's rule, 0 <= pos_device[y] <= pos_bound; an inactive row gets a zero `out` row and nothing else.  THE CALLER GUARANTEES that the
+ * active rows of a sequence are a prefix t < n_b and that their positions are p, p + 1, ..., p + n_b - 1.  The kernel TRUSTS this as it trusts page numbers: row t
+ * takes keys p .. p + t from the q/k/v rows y - t .. y of this call (rotated with the cos / sin row of each one's position; on e4m3 pools quantised and dequantised as
+ * the append does) and never from the pool, where other workgroups of the same launch are writing them; all it does on its own is never to reach below position 0.
+ * Each row appends only its own key / value row, at its own position: every pool row has one writer.
+ * CONTRACT (no tolerance): row (b, t)'s `out` and the pool rows one call appends are bit-identical to what t + 1 successive calls of
+ * tce_attention_decode_step_paged_f16 / _fp8 with the same pos_bound (hence the same cut) produce for sequence b; no other pool byte changes; rows_per_seq = 1 is
+ * that step.  batch <= 65535; refusals as for the steps, plus rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS (TCE_ERR_UNSUPPORTED_SHAPE). */
+#define TCE_SPEC_MAX_ROWS 8
+TCE_API int tce_attention_decode_step_paged_rows_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                     const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int rows_per_seq, int heads,
+                                                     int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, void *stream);
+TCE_API int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                     const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int rows_per_seq, int heads,
+                                                     int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int k_scale_log2,
+                                                     int v_scale_log2, void *stream);
+
 /* Device-side sampling: what the reference does on the host between Int4LlamaForCausalLM::forward and the next token's Embedding (llm/src/Generate.cc driven by
  * LLaMA3Generate.cc:127-198), for `batch` rows of fp16 logits [batch][ld] (lm_head's output at M = batch; vocab <= ld) in TWO launches (csrc/sampling.hip), so that a
  * captured decode graph yields one token per replay for every sequence with no host round trip.  Per ACTIVE row (0 <= pos_device[b] <= pos_bound, the project's rule;
@@ -435,6 +457,42 @@ typedef struct tce_sample_call {
 } tce_sample_call;
 TCE_API size_t tce_sample_workspace_bytes(int batch, int vocab);
 TCE_API int tce_sample_f16(const tce_sample_call *call, void *stream);
+/* Speculative decoding's two device-side pieces around the layers (csrc/sampling.hip): drafts from the sequence's own history, and the verifier.
+ * tce_draft_ngram (one launch).  history: DEVICE int32 [batch][hist_stride], history[b][i] = the token processed at position i (the prompt, then every emitted token;
+ * the token at index p is the one the next step feeds).  pos_device [batch]: the SEQUENCES' positions.  Written: row_token, row_pos [batch * rows_per_seq].
+ *   inactive sequence (p < 0, p > pos_bound or p >= hist_stride): every row (0, -1)
+ *   row 0: (history[b][p], p)
+ *   drafts, n = ngram (1 .. 4): i* = the largest i with n - 1 <= i < p and history[i - n + 1 .. i] == history[p - n + 1 .. p]; none, or p < n: no drafts.  Row t >= 1 is
+ *   (history[b][i* + t], p + t) while i* + t <= p and p + t <= pos_bound; every row behind that is inactive: (0, -1)
+ *   script (may be NULL; a test hook, int32 [batch][hist_stride]): replaces the lookup -- row t >= 1 is (script[b][p + t], p + t) while p + t <= pos_bound, p + t <
+ *   hist_stride and no script[b][p + 1 .. p + t] is negative.
+ * tce_sample_verify_f16 (three launches; the kernel boundary is the only ordering, no counters).  s: a tce_sample_call in which batch = B SEQUENCES -- rows, pos_device,
+ * next_token and out_log are per sequence --, logits is [B * T][ld] and uniform_override / debug are per VIRTUAL row y = b * T + t; workspace:
+ * tce_sample_verify_workspace_bytes(batch, rows_per_seq, vocab) bytes, zeroed once (its word 0 is tce_embed_rows_f16's counter, as tce_sample_f16's).  row_token /
+ * row_pos: what tce_draft_ngram wrote and the layers ran on.  Per ACTIVE sequence (0 <= pos_device[b] = p <= pos_bound) with n active rows and g = rows[b].generated,
+ * for t = 0, 1, ...:
+ *   1. y_t = the token tce_sample_f16 would choose from logits row (b, t) with the penalty window of the ring after y_0 .. y_{t-1} were pushed and the uniform keyed
+ *      (seed, g + t)
+ *   2. y_t is emitted with tce_sample_f16's tail: out_log[b][g + t], the ring push, generated += 1; and history[b][p + 1 + t] = y_t (where < hist_stride)
+ *   3. a stop id, or generated reaching max_new / log_stride: the sequence retires (pos_device[b] = -1) and the chain ends
+ *   4. t + 1 >= n or row_token[(b, t + 1)] != y_t: the chain ends with pos_device[b] = p + t + 1
+ *   and next_token[b] = the last y_t; emitted[b] = the tokens emitted (0 for an inactive sequence, whose state is not touched).
+ * LOSSLESS: the emitted tokens are those of tce_sample_f16 called once per token.  A row that is reached at all has had all its drafts accepted, so its window (the
+ * ring plus drafts 1 .. t) is known in advance: the select launch runs for all B * T rows at once, the draw per row into a candidate array, and a last small launch
+ * walks the chain and writes state.  Cache rows p + t + 1 .. of REJECTED drafts stay behind the position as garbage: the next step overwrites them or never weighs them.
+ * Refusals: tce_sample_f16's (tfs, typical, mirostat, k > 256 and whole-vocabulary top-k stay unbuilt), rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS, batch *
+ * rows_per_seq > 65535, ngram outside 1 .. 4, hist_stride <= pos_bound. */
+typedef struct tce_sample_verify_call {
+    tce_sample_call s;
+    int32_t rows_per_seq, hist_stride;
+    const int32_t *row_token, *row_pos; /* [batch * rows_per_seq] */
+    int32_t *history;                   /* [batch][hist_stride] */
+    int32_t *emitted;                   /* [batch] */
+} tce_sample_verify_call;
+TCE_API size_t tce_sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
+TCE_API int tce_sample_verify_f16(const tce_sample_verify_call *call, void *stream);
+TCE_API int tce_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos_device, int pos_bound, int batch, int rows_per_seq, int ngram,
+                            int32_t *row_token, int32_t *row_pos, void *stream);
 /* The next step's input rows, one launch: row token[b] of an fp16 table [vocab][hidden] into out[b] ([batch][hidden]) for every active row (pos_device / pos_bound as
  * above; inactive rows are left as they are).  The reference looks an fp32 table up and rounds with float2half (Int4llamaDecoder: Embedding + float2half); a table
  * rounded once to fp16 gives the same bits.  A token outside [0, vocab) is not followed: the row is written as zeros and word 0 of `workspace` (tce_sample_f16's, or

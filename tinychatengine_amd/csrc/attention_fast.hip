@@ -63,6 +63,12 @@ struct PagedFp8AttnArgs : PagedAttnArgs {
     float k_inv, v_inv;      // 2^-k_scale_log2, 2^-v_scale_log2: what the token's own row is multiplied by before it is rounded to a byte
 };
 
+// the multi-row paged step's (speculative decoding): the e4m3 step's arguments -- the two scales are unused on fp16 pools -- and T = rows per sequence.  The grid is
+// (heads x chunk slots, T, batch): virtual row y = b * T + t has q/k/v row, output row, workspace slice and position word y, and table row b
+struct PagedRowsAttnArgs : PagedFp8AttnArgs {
+    int rows_per_seq;  // 1 .. TCE_SPEC_MAX_ROWS
+};
+
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
     auto dpp = [](float x, auto ctrl) {
         return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, false));
@@ -126,16 +132,31 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 // registers consume() has always read at its head: every instruction behind that, and its order, is the fp16 paged step's, so on pools whose fp16 image holds
 // dequant(byte) the two steps agree bit for bit.  The token's own row is rounded to bytes (fp8_kv.hpp: the format's rule), stored as bytes, and enters `newrow`
 // DEQUANTISED: the step weighs its own key and value as the cache will hold them.
-template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false>
-__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>> a) {
+// ROWS (with PAGED): T = rows_per_seq rows per sequence in one launch (PagedRowsAttnArgs): row t of sequence b sits at position pos_device[b * T + t] = p + t and must
+// weigh keys p .. p + t - 1, which OTHER workgroups of this launch are appending -- so it never takes them from the pool.  The `newrow` idea, t + 1 times: the
+// workgroup loads the k / v pieces of q/k/v rows y - t .. y, rotates each with the cos / sin row of ITS position (the same binary16 rope_apply; e4m3: quantised and
+// dequantised as the appending wave does), keeps them in LDS and consume() takes every key in [pos - t, pos] from there.  Only the own row is appended: one writer per
+// pool row, nobody waits for anybody.  The caller guarantees that a sequence's active rows are a prefix with consecutive positions (include/tce_matmul.h); all the kernel
+// does about it is to clamp t to pos, so that no address is formed from a negative position.  The key loop is the paged step's: the wave-uniform rare-block test is a
+// range overlap instead of a membership, and the work it guards is the only per-key addition.
+template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false>
+__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
+    const std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>> a) {
     static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
     static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
+    static_assert(!ROWS || (PAGED && NW == 4), "several rows per sequence exist on pages only");
     constexpr int NT = 64 * NW, NS = 4 * NW;
+    constexpr int NEW = ROWS ? TCE_SPEC_MAX_ROWS : 1;  // rows kept in LDS: the token's own, and (ROWS) the up to 7 in front of it
+    static_assert(NEW <= NS, "one (wave, key slot) per new row");
     __shared__ __attribute__((aligned(16))) float st[NS][R][2 + kHD];  // the (wave, slot) states per query head: m, l, o[hd]
-    __shared__ __attribute__((aligned(16))) half_t newrow[2][kHD];  // the token's own (rotated) key and value
+    __shared__ __attribute__((aligned(16))) half_t newrow[NEW][2][kHD];  // the token's own (rotated) key and value (ROWS: row j is position pos - tprev + j)
     __shared__ unsigned last_flag;
     // the sequence's offsets into the batched arrays, in elements / words (BATCH == false: 0)
-    const unsigned seq = BATCH ? blockIdx.y : 0u;
+    const unsigned seq = [&]() -> unsigned {
+        if constexpr (ROWS) return blockIdx.z * (unsigned)a.rows_per_seq + blockIdx.y;  // the virtual row
+        else return BATCH ? blockIdx.y : 0u;
+    }();
+    const unsigned tseq = ROWS ? blockIdx.z : seq;  // the block table's row
     const size_t seq_qkv = (size_t)seq * (a.heads + 2 * a.kv_heads) * kHD, seq_cache = PAGED ? 0 : (size_t)seq * a.kv_heads * a.max_keys * kHD;
     const size_t seq_out = (size_t)seq * a.heads * kHD, seq_ws = BATCH ? seq * attn_workspace_words(a.heads, a.max_keys) : 0;
     // grp: this workgroup's group of R consecutive query heads (R == rep: all the query heads of a key / value head, its cache rows streamed
@@ -148,7 +169,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
         const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l_ = threadIdx.x & 63;
         tab_e0 = (c * a.chunk + w_ * (a.chunk / NW)) >> a.page_shift;
         const int e = l_ == 63 ? 0 : (tab_e0 + l_ < a.table_stride ? tab_e0 + l_ : a.table_stride - 1);
-        tabw = a.table[(size_t)seq * a.table_stride + e];
+        tabw = a.table[(size_t)tseq * a.table_stride + e];
     }
     // the position: by value, or from a device word (wave-uniform scalar load) -- then chunks past the context have nothing to do and the
     // head's combine expects only the chunks that exist
@@ -165,6 +186,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
         }
     }
     const int keys = pos + 1;
+    // ROWS: the rows of this sequence in front of this one, all in flight in this launch (keys pos - tprev .. pos - 1)
+    [[maybe_unused]] const int tprev = ROWS ? ((int)blockIdx.y < pos ? (int)blockIdx.y : pos) : 0;
     const int chunks = a.pos_dev ? (keys + a.chunk - 1) / a.chunk : a.chunks;  // active chunks (<= the grid's chunk slots)
     if (c >= chunks) return;
     const int head = (grp * R) / a.rep;  // the key / value head
@@ -240,7 +263,21 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
         q_p[r] = ld8(xq + r * kHD + (piece ^ 8) * 8);
     }
     const half8_t cc = ld8(cp + piece * 8), ss = ld8(sp + piece * 8);
+    // ROWS: (wave, slot) j <= tprev takes new row j -- q/k/v row y - tprev + j at position pos - tprev + j, with that position's cos / sin pieces (j > tprev: the own
+    // row's addresses again, not used)
+    [[maybe_unused]] const int nj = ROWS ? (wave * 4 + slot <= tprev ? wave * 4 + slot : tprev) : 0;
+    if constexpr (ROWS) {
+        const ptrdiff_t back = (ptrdiff_t)(tprev - nj);
+        xk -= back * (a.heads + 2 * a.kv_heads) * kHD;
+        xv -= back * (a.heads + 2 * a.kv_heads) * kHD;
+    }
+    [[maybe_unused]] const half_t *cpk = ROWS && rope ? cp - (ptrdiff_t)(tprev - nj) * kHD : cp, *spk = ROWS && rope ? sp - (ptrdiff_t)(tprev - nj) * kHD : sp;
     const half8_t k_v = ld8(xk + piece * 8), k_p = ld8(xk + (piece ^ 8) * 8), v_v = ld8(xv + piece * 8);
+    [[maybe_unused]] half8_t cck, ssk;
+    if constexpr (ROWS) {
+        cck = ld8(cpk + piece * 8);
+        ssk = ld8(spk + piece * 8);
+    }
     __builtin_amdgcn_sched_barrier(0);
     fetch(kbuf[0], vbuf[0], mbuf[0], 0);  // (the row at index pos may not be in the cache yet: consume() takes it from LDS)
     // (Round 4, tried: the SECOND block requested here too, so that a wave's first 32 keys cost one memory round trip instead of two.  Slower at every context, in
@@ -253,8 +290,10 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
 #pragma unroll
     for (int r = 0; r < R; ++r) qh[r] = rope ? rope_apply(q_v[r], q_p[r], cc, ss, piece) : q_v[r];
     // ---- the new key / value of this head: into LDS for this workgroup's use, into the cache by the workgroup that owns index pos ----
-    if (wave == 0) {
-        half8_t kh = rope ? rope_apply(k_v, k_p, cc, ss, piece) : k_v;
+    if (ROWS ? wave * 4 + slot <= tprev : wave == 0) {
+        half8_t kh;
+        if constexpr (ROWS) kh = rope ? rope_apply(k_v, k_p, cck, ssk, piece) : k_v;
+        else kh = rope ? rope_apply(k_v, k_p, cc, ss, piece) : k_v;
         half8_t vh = v_v;
         [[maybe_unused]] uint2_t kq, vq;  // FP8: the row's bytes, and the row as the cache will hold it
         if constexpr (FP8) {
@@ -263,14 +302,14 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
             kh = fp8_dequant8(kq, a.k_scale);
             vh = fp8_dequant8(vq, a.v_scale);
         }
-        if (slot == 0) {
-            *reinterpret_cast<half8_t *>(&newrow[0][piece * 8]) = kh;
-            *reinterpret_cast<half8_t *>(&newrow[1][piece * 8]) = vh;
-            if (appends && pos >= key0 && pos < key1) {
+        if (ROWS || slot == 0) {
+            *reinterpret_cast<half8_t *>(&newrow[nj][0][piece * 8]) = kh;
+            *reinterpret_cast<half8_t *>(&newrow[nj][1][piece * 8]) = vh;
+            if ((!ROWS || nj == tprev) && appends && pos >= key0 && pos < key1) {
                 if constexpr (PAGED) {
                     // the page that holds index pos: word pos / page_keys, the last one the row owns (a wave-uniform load that depends on the position word, beside
                     // the cos / sin pieces which do too: it delays this store, not the cache requests)
-                    const int page = __builtin_amdgcn_readfirstlane(a.table[(size_t)seq * a.table_stride + (pos >> a.page_shift)]);
+                    const int page = __builtin_amdgcn_readfirstlane(a.table[(size_t)tseq * a.table_stride + (pos >> a.page_shift)]);
                     const size_t off = page_row(page, pos & ((1 << a.page_shift) - 1)) + piece * 8;
                     if constexpr (FP8) {
                         *reinterpret_cast<uint2_t *>(reinterpret_cast<unsigned char *>(a.kc) + off) = kq;
@@ -317,14 +356,19 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(const std::co
         // the rare blocks -- the one that runs past the wave's range, the one that holds the token's own row -- are told apart by a wave-uniform test, so the
         // others carry no per-slot validity arithmetic at all
         const int b0 = kw0 + it0;
-        if (b0 + BLK * 4 > kw1 || (pos >= b0 && pos < b0 + BLK * 4)) {
+        if (b0 + BLK * 4 > kw1 || (pos >= b0 && pos - tprev < b0 + BLK * 4)) {  // (tprev: 0 unless ROWS)
 #pragma unroll
             for (int u = 0; u < BLK; ++u) {
                 const int key = b0 + u * 4 + slot;
                 valid[u] = key < kw1;
-                if (key == pos) {  // the token's own row: not necessarily visible in the cache yet
-                    kk[u] = *reinterpret_cast<const half8_t *>(&newrow[0][piece * 8]);
-                    vv[u] = *reinterpret_cast<const half8_t *>(&newrow[1][piece * 8]);
+                if constexpr (ROWS) {
+                    if (key >= pos - tprev && key <= pos) {  // this launch's rows of the sequence: in LDS, in the pool only once their workgroups have run
+                        kk[u] = *reinterpret_cast<const half8_t *>(&newrow[key - (pos - tprev)][0][piece * 8]);
+                        vv[u] = *reinterpret_cast<const half8_t *>(&newrow[key - (pos - tprev)][1][piece * 8]);
+                    }
+                } else if (key == pos) {  // the token's own row: not necessarily visible in the cache yet
+                    kk[u] = *reinterpret_cast<const half8_t *>(&newrow[0][0][piece * 8]);
+                    vv[u] = *reinterpret_cast<const half8_t *>(&newrow[0][1][piece * 8]);
                 }
                 // a slot past the range was loaded from a row that may hold anything (the row at `pos` before this launch wrote it, an
                 // uninitialised cache): its weight is 0, and 0 * inf would still be NaN -- the value row is zeroed, not just weighted
@@ -795,7 +839,8 @@ static float host_pow2(int e) {
 }
 
 // fp8 = true: the pools are e4m3 bytes and the two exponents apply (launch_attention_decode_paged_fp8); everything else is one text for both
-static int launch_paged_step(bool fp8, int k_log2, int v_log2, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+// rows = 0: the step; rows >= 1: the multi-row step with rows_per_seq = rows -- the same cut (pos_bound alone decides it), grid (heads x chunk slots, rows, batch)
+static int launch_paged_step(int rows, bool fp8, int k_log2, int v_log2, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
                              const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound,
                              unsigned short alpha_bits, hipStream_t stream, hipError_t *hip_err) {
     const int shift = page_shift_of(page_keys);
@@ -803,7 +848,9 @@ static int launch_paged_step(bool fp8, int k_log2, int v_log2, const void *qkv, 
         (long long)pos_bound >= ((long long)table_stride << shift))
         return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && !(fp8_log2_ok(k_log2) && fp8_log2_ok(v_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
-    PagedFp8AttnArgs a{};
+    if (rows < 0 || rows > TCE_SPEC_MAX_ROWS) return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedRowsAttnArgs a{};
+    a.rows_per_seq = rows;
     a.qkv = static_cast<const half_t *>(qkv);
     a.kc = static_cast<half_t *>(k_pool);
     a.vc = static_cast<half_t *>(v_pool);
@@ -835,7 +882,13 @@ static int launch_paged_step(bool fp8, int k_log2, int v_log2, const void *qkv, 
         a.v_scale = host_pow2(v_log2);
         a.k_inv = host_pow2(-k_log2);
         a.v_inv = host_pow2(-v_log2);
-        hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
+    }
+    if (rows) {
+        const dim3 grid(heads * a.chunks, rows, batch);
+        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, true>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, true>), grid, dim3(256), 0, stream, a);
+    } else if (fp8) {
+        hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, static_cast<const PagedFp8AttnArgs &>(a));
     } else {
         hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, static_cast<const PagedAttnArgs &>(a));
     }
@@ -850,15 +903,24 @@ static int launch_paged_step(bool fp8, int k_log2, int v_log2, const void *qkv, 
 int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
                                   void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
                                   hipStream_t stream, hipError_t *hip_err) {
-    return launch_paged_step(false, 0, 0, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev, pos_bound,
+    return launch_paged_step(0, false, 0, 0, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev, pos_bound,
                              alpha_bits, stream, hip_err);
 }
 
 int launch_attention_decode_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
                                       void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
                                       int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
-    return launch_paged_step(true, k_log2, v_log2, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev,
+    return launch_paged_step(0, true, k_log2, v_log2, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev,
                              pos_bound, alpha_bits, stream, hip_err);
+}
+
+// rows_per_seq query rows per sequence (1 .. TCE_SPEC_MAX_ROWS); fp8: the e4m3 pools with their two exponents (ignored otherwise)
+int launch_attention_decode_paged_rows(bool fp8, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                       const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd, const int *pos_dev,
+                                       int pos_bound, unsigned short alpha_bits, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
+    if (rows_per_seq < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
+    return launch_paged_step(rows_per_seq, fp8, k_log2, v_log2, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd,
+                             pos_dev, pos_bound, alpha_bits, stream, hip_err);
 }
 
 int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,

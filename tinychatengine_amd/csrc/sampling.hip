@@ -60,16 +60,21 @@ __device__ __forceinline__ int block_total(int wave_count, int (*cnt)[4], int ro
     return cnt[round & 1][0] + cnt[round & 1][1] + cnt[round & 1][2] + cnt[round & 1][3];
 }
 
+// SPEC (tce_sample_verify_f16): blockIdx.y is a VIRTUAL row y = seq * RT + t -- logits row, position word (row_pos) and survivors are y's, the sampling row is seq's.
+// Row t is only ever used when drafts 1 .. t were all accepted, so the window it must be sampled with is known now: the ring as it stands with row_token[(seq, 1)] ..
+// row_token[(seq, t)] pushed behind it.
+template <bool SPEC>
 __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *logits, int ld, int vocab, const tce_sample_row *rows, const int32_t *pos, int pos_bound,
-                                                                  int kbound, uint2_t *entries, int nchunks) {
+                                                                  int kbound, uint2_t *entries, int nchunks, int RT, const int32_t *row_token) {
     const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(pos, b, pos_bound)) return;
+    [[maybe_unused]] const int seq = SPEC ? b / RT : b, vt = SPEC ? b - seq * RT : 0;
     __shared__ int win_id[64], pen_id[64];
     __shared__ float pen_val[64];
     __shared__ unsigned mask[kThreads];
     __shared__ int cnt[2][4];
     __shared__ int nsel;
-    const tce_sample_row &r = rows[b];
+    const tce_sample_row &r = rows[SPEC ? seq : b];
     const int k = row_k(r, kbound);
     const half_t *row = logits + (size_t)b * ld;
     const int base = c * kChunk, i0 = base + tid * 16;
@@ -90,7 +95,8 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
     mask[tid] = 0;
     if (tid == 0) nsel = 0;
     if (tid < 64) {
-        win_id[tid] = tid < nwin ? r.ring[(r.ring_pushed - 1u - (unsigned)tid) & 63u] : -1;
+        if constexpr (SPEC) win_id[tid] = tid >= nwin ? -1 : tid < vt ? row_token[b - tid] : r.ring[(r.ring_pushed - 1u - (unsigned)(tid - vt)) & 63u];
+        else win_id[tid] = tid < nwin ? r.ring[(r.ring_pushed - 1u - (unsigned)tid) & 63u] : -1;
         pen_id[tid] = -1;
     }
     __syncthreads();
@@ -190,15 +196,27 @@ struct DrawArgs {
     int n_stop;
 };
 
-__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a) {
+// tce_sample_verify_f16's second and third launch: DrawArgs (pos = the SEQUENCES' position words) and the per-virtual-row arrays
+struct VerifyArgs {
+    DrawArgs d;
+    int T, hist_stride, batch;
+    const int32_t *row_token, *row_pos;
+    int32_t *cand;  // [batch * T]: the token virtual row y would emit
+    int32_t *history, *emitted;
+};
+
+// SPEC: blockIdx.x is a virtual row y = seq * RT + t (a.pos = row_pos): the draw of token generated + t of the sequence, into cand[y]; no state is written
+template <bool SPEC>
+__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(a.pos, b, a.pos_bound)) return;
+    [[maybe_unused]] const int seq = SPEC ? b / RT : b, vt = SPEC ? b - seq * RT : 0;
     __shared__ u64 sel[kMaxK];
     __shared__ float lg[kMaxK + 8], ex[kMaxK + 8], pr[kMaxK + 8], fp[kMaxK + 8];
     __shared__ int ids[kMaxK];
     __shared__ int cnt[2][4];
     __shared__ int nsel;
-    tce_sample_row &r = a.rows[b];
+    tce_sample_row &r = a.rows[SPEC ? seq : b];
     const int k = row_k(r, a.kbound);
     const int E = a.nchunks * k;  // <= 8192 (checked by the host)
 
@@ -247,7 +265,7 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a) {
     }
     __syncthreads();
 
-    const unsigned gen = r.generated;
+    const unsigned gen = SPEC ? r.generated + (unsigned)vt : r.generated;
     float u = 0.0f;
     int n = 1, choice = 0;
     if (r.temp > 0.0f) {
@@ -306,6 +324,10 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a) {
         }
     }
     // ---- the tail: the token, the log, the ring, the counters, the position ----
+    if constexpr (SPEC) {
+        if (tid == 0) cand[b] = ids[choice];
+        return;
+    }
     if (tid == 0) {
         const int tok = ids[choice];
         a.next_token[b] = tok;
@@ -316,6 +338,101 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a) {
         bool stop = (int)(gen + 1u) >= r.max_new || gen + 1u >= (unsigned)a.log_stride;
         for (int i = 0; i < a.n_stop; ++i) stop = stop || tok == a.stop_ids[i];
         a.pos[b] = stop ? -1 : a.pos[b] + 1;
+    }
+}
+
+// tce_sample_verify_f16's last launch: thread = sequence.  Walks the chain of candidates and writes state exactly as sample_draw_kernel's tail does, once per emitted token.
+__global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgs a) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.batch) return;
+    if (!row_active(a.d.pos, b, a.d.pos_bound)) {
+        a.emitted[b] = 0;
+        return;
+    }
+    tce_sample_row &r = a.d.rows[b];
+    const int p = a.d.pos[b], y0 = b * a.T;
+    int n = 0;  // the active rows: a prefix (the drafting launch wrote them so)
+    while (n < a.T && a.row_pos[y0 + n] >= 0 && a.row_pos[y0 + n] <= a.d.pos_bound) ++n;
+    const unsigned g = r.generated;
+    unsigned pushed = r.ring_pushed;
+    int t = 0, tok = 0, newpos = -1;
+    for (; t < n; ++t) {
+        tok = a.cand[y0 + t];
+        if (g + t < (unsigned)a.d.log_stride) a.d.out_log[(size_t)b * a.d.log_stride + g + t] = tok;
+        r.ring[pushed & 63u] = tok;
+        ++pushed;
+        if (p + 1 + t < a.hist_stride) a.history[(size_t)b * a.hist_stride + p + 1 + t] = tok;
+        bool stop = (int)(g + t + 1u) >= r.max_new || g + t + 1u >= (unsigned)a.d.log_stride;
+        for (int i = 0; i < a.d.n_stop; ++i) stop = stop || tok == a.d.stop_ids[i];
+        if (stop) {
+            ++t;
+            break;
+        }
+        if (t + 1 >= n || a.row_token[y0 + t + 1] != tok) {
+            newpos = p + t + 1;
+            ++t;
+            break;
+        }
+    }
+    // (n == 0 cannot happen for an active sequence -- row 0 is its own position --; it would emit nothing and leave the sequence where it is)
+    if (t > 0) {
+        a.d.next_token[b] = tok;
+        r.ring_pushed = pushed;
+        r.generated = g + (unsigned)t;
+        a.d.pos[b] = newpos;
+    }
+    a.emitted[b] = t;
+}
+
+// tce_draft_ngram: workgroup = sequence.  Row 0 is the sequence's certain next input; rows 1 .. are what followed the most recent earlier occurrence of its last
+// `ngram` tokens (prompt lookup), or -- script != null, a test hook -- script[b][p + t] up to the first -1.
+__global__ __launch_bounds__(kThreads) void draft_ngram_kernel(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int T,
+                                                                int ngram, int32_t *row_token, int32_t *row_pos) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    __shared__ int best;
+    const int p = pos[b];
+    if (p < 0 || p > pos_bound || p >= hist_stride) {
+        if (tid < T) {
+            row_token[b * T + tid] = 0;
+            row_pos[b * T + tid] = -1;
+        }
+        return;
+    }
+    const int32_t *h = history + (size_t)b * hist_stride;
+    if (tid == 0) best = -1;
+    __syncthreads();
+    if (!script && p >= ngram) {
+        int mine = -1;
+        for (int i = ngram - 1 + tid; i < p; i += kThreads) {
+            bool same = true;
+            for (int j = 0; j < ngram; ++j) same = same && h[i - j] == h[p - j];
+            if (same) mine = i;  // (ascending: the last one stays)
+        }
+        if (mine >= 0) atomicMax(&best, mine);
+    }
+    __syncthreads();
+    if (tid < T) {
+        const int t = tid;
+        int tok = 0, rp = -1;
+        if (t == 0) {
+            tok = h[p];
+            rp = p;
+        } else if (p + t <= pos_bound) {
+            if (script) {
+                const int32_t *sc = script + (size_t)b * hist_stride;
+                bool ok = p + t < hist_stride;
+                for (int j = 1; j <= t && ok; ++j) ok = sc[p + j] >= 0;  // the prefix ends at the first -1
+                if (ok) {
+                    tok = sc[p + t];
+                    rp = p + t;
+                }
+            } else if (best >= 0 && best + t <= p) {
+                tok = h[best + t];
+                rp = p + t;
+            }
+        }
+        row_token[b * T + t] = tok;
+        row_pos[b * T + t] = rp;
     }
 }
 
@@ -342,8 +459,8 @@ size_t sample_workspace_bytes(int batch, int vocab) {
 int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *hip_err) {
     const int nchunks = sample_chunks(c.vocab);
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
-    hipLaunchKernelGGL(sample_select_kernel, dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows, c.pos_device,
-                       c.pos_bound, c.top_k_bound, entries, nchunks);
+    hipLaunchKernelGGL(sample_select_kernel<false>, dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows, c.pos_device,
+                       c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         DrawArgs a;
@@ -360,9 +477,73 @@ int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *
         a.debug = c.debug;
         for (int i = 0; i < 4; ++i) a.stop_ids[i] = c.stop_ids[i];
         a.n_stop = c.n_stop;
-        hipLaunchKernelGGL(sample_draw_kernel, dim3(c.batch), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(sample_draw_kernel<false>, dim3(c.batch), dim3(kThreads), 0, stream, a, 1, static_cast<int32_t *>(nullptr));
         e = hipGetLastError();
     }
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+// the verifier's workspace: tce_sample_f16's layout for batch * rows_per_seq rows, then the candidates int32 [batch * rows_per_seq]
+static size_t verify_cand_offset(int batch, int rows_per_seq, int vocab) { return sample_workspace_bytes(batch * rows_per_seq, vocab); }
+
+size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
+    if (batch < 1 || rows_per_seq < 1 || vocab < 1) return 0;
+    return verify_cand_offset(batch, rows_per_seq, vocab) + (((size_t)batch * rows_per_seq * 4 + 255) & ~(size_t)255);
+}
+
+int launch_sample_verify_f16(const tce_sample_verify_call &v, hipStream_t stream, hipError_t *hip_err) {
+    const tce_sample_call &c = v.s;
+    const int nchunks = sample_chunks(c.vocab), T = v.rows_per_seq, vrows = c.batch * T;
+    uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
+    VerifyArgs a;
+    a.d.entries = entries;
+    a.d.nchunks = nchunks;
+    a.d.kbound = c.top_k_bound;
+    a.d.pos_bound = c.pos_bound;
+    a.d.log_stride = c.log_stride;
+    a.d.rows = c.rows;
+    a.d.pos = const_cast<int32_t *>(v.row_pos);  // (the draw launch reads the rows' positions; the chain launch gets the sequences' below)
+    a.d.next_token = c.next_token;
+    a.d.out_log = c.out_log;
+    a.d.uniform_override = c.uniform_override;
+    a.d.debug = c.debug;
+    for (int i = 0; i < 4; ++i) a.d.stop_ids[i] = c.stop_ids[i];
+    a.d.n_stop = c.n_stop;
+    a.T = T;
+    a.hist_stride = v.hist_stride;
+    a.batch = c.batch;
+    a.row_token = v.row_token;
+    a.row_pos = v.row_pos;
+    a.cand = reinterpret_cast<int32_t *>(static_cast<char *>(c.workspace) + verify_cand_offset(c.batch, T, c.vocab));
+    a.history = v.history;
+    a.emitted = v.emitted;
+    hipLaunchKernelGGL(sample_select_kernel<true>, dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows, v.row_pos,
+                       c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sample_draw_kernel<true>, dim3(vrows), dim3(kThreads), 0, stream, a.d, T, a.cand);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        a.d.pos = c.pos_device;
+        hipLaunchKernelGGL(sample_verify_chain_kernel, dim3((c.batch + 63) / 64), dim3(64), 0, stream, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
+                       int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err) {
+    hipLaunchKernelGGL(draft_ngram_kernel, dim3(batch), dim3(kThreads), 0, stream, history, script, hist_stride, pos, pos_bound, rows_per_seq, ngram, row_token, row_pos);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;
         return TCE_ERR_HIP;

@@ -23,6 +23,10 @@ size_t sample_workspace_bytes(int batch, int vocab);
 int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *hip_err);
 int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos, int pos_bound, void *workspace,
                           hipStream_t stream, hipError_t *hip_err);
+size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
+int launch_sample_verify_f16(const tce_sample_verify_call &v, hipStream_t stream, hipError_t *hip_err);
+int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
+                       int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err);
 }
 
 namespace {
@@ -1280,6 +1284,50 @@ int tce_attention_decode_step_paged_f16(const void *qkv, void *k_pool, void *v_p
     return rc == TCE_ERR_HIP ? hip_fail(he, "paged attention decode step launch") : rc;
 }
 
+// ---- the paged step with rows_per_seq query rows per sequence (speculative decoding): the steps' refusals, then the rows' ----
+static int paged_rows_step(const char *who, bool fp8, const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                           const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd,
+                           const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
+    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
+    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
+    if (table_stride < 1 || num_pages < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages >= 1", who);
+    if (batch <= 0 || heads <= 0 || pos_bound < 0 || (long long)pos_bound >= (long long)table_stride * page_keys)
+        return fail(TCE_ERR_BAD_ARG, "%s: need batch, heads > 0 and 0 <= pos_bound < table_stride * page_keys", who);
+    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
+    if (fp8)
+        if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
+    if (rows_per_seq < 1 || rows_per_seq > TCE_SPEC_MAX_ROWS)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, rows_per_seq, TCE_SPEC_MAX_ROWS);
+    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
+    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: batch %d (at most 65535: the grid's third dimension)", who, batch);
+    const void *ptrs[] = {qkv, k_pool, v_pool, cosv, sinv, out};
+    const char *names[] = {"qkv", "k_pool", "v_pool", "cos_table", "sin_table", "out"};
+    for (int i = 0; i < 6; ++i)
+        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
+    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: pos_device must be int32-aligned", who);
+    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_attention_decode_paged_rows(fp8, qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, out, workspace, batch, rows_per_seq, heads,
+                                                           kv_heads, hd, pos_device, pos_bound, alpha_bits, k_scale_log2, v_scale_log2, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "multi-row paged attention decode step launch") : rc;
+}
+
+int tce_attention_decode_step_paged_rows_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                             const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd,
+                                             const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
+    return paged_rows_step("tce_attention_decode_step_paged_rows_f16", false, qkv, k_pool, v_pool, block_table, table_stride, page_keys, num_pages, cosv, sinv, out, workspace,
+                           batch, rows_per_seq, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits, 0, 0, stream);
+}
+
+int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                             const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd,
+                                             const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
+    return paged_rows_step("tce_attention_decode_step_paged_rows_fp8", true, qkv, k_pool, v_pool, block_table, table_stride, page_keys, num_pages, cosv, sinv, out, workspace,
+                           batch, rows_per_seq, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits, k_scale_log2, v_scale_log2, stream);
+}
+
 static int kv_pages_copy(const char *who, bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
                          int num_pages, int kv_heads, int hd, int lin_max_keys, int key0, int nkeys, void *stream) {
     if (!k_lin || !v_lin || !k_pool || !v_pool || !table_row) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
@@ -1357,27 +1405,70 @@ int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int p
 
 size_t tce_sample_workspace_bytes(int batch, int vocab) { return batch < 1 || batch > 65535 || vocab < 1 || vocab > (1 << 20) ? 0 : tce::sample_workspace_bytes(batch, vocab); }
 
-int tce_sample_f16(const tce_sample_call *c, void *stream) {
-    if (!c) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: null call");
-    if (!c->logits || !c->rows || !c->pos_device || !c->next_token || !c->out_log || !c->workspace) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: null pointer");
-    if (c->batch < 1 || c->vocab < 1 || c->pos_bound < 0 || c->log_stride < 1) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: need batch, vocab, log_stride >= 1 and pos_bound >= 0");
-    if (c->vocab > c->ld) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: vocab %d > ld %d", c->vocab, c->ld);
-    if (c->n_stop < 0 || c->n_stop > 4) return fail(TCE_ERR_BAD_ARG, "tce_sample_f16: n_stop %d (0 .. 4)", c->n_stop);
+// tce_sample_f16's refusals, shared with the verifier (vrows: the logits rows of the call)
+static int check_sample_call(const char *who, const tce_sample_call *c, long long vrows) {
+    if (!c) return fail(TCE_ERR_BAD_ARG, "%s: null call", who);
+    if (!c->logits || !c->rows || !c->pos_device || !c->next_token || !c->out_log || !c->workspace) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (c->batch < 1 || c->vocab < 1 || c->pos_bound < 0 || c->log_stride < 1) return fail(TCE_ERR_BAD_ARG, "%s: need batch, vocab, log_stride >= 1 and pos_bound >= 0", who);
+    if (c->vocab > c->ld) return fail(TCE_ERR_BAD_ARG, "%s: vocab %d > ld %d", who, c->vocab, c->ld);
+    if (c->n_stop < 0 || c->n_stop > 4) return fail(TCE_ERR_BAD_ARG, "%s: n_stop %d (0 .. 4)", who, c->n_stop);
     if (c->tfs_z != 1.0f || c->typical_p != 1.0f || c->mirostat != 0)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: tail-free, typical and mirostat sampling are not built (tfs_z 1.0, typical_p 1.0, mirostat 0 only)");
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: tail-free, typical and mirostat sampling are not built (tfs_z 1.0, typical_p 1.0, mirostat 0 only)", who);
     if (c->top_k_bound < 1 || c->top_k_bound > 256)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: top_k_bound %d (1 .. 256; top_k <= 0 = the whole vocabulary is not built)", c->top_k_bound);
-    if (c->batch > 65535 || c->vocab > (1 << 20)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: batch <= 65535 and vocab <= 2^20");
-    if (c->ld % 8 != 0 || reinterpret_cast<uintptr_t>(c->logits) % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: logits 16-byte aligned with ld %% 8 == 0");
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: top_k_bound %d (1 .. 256; top_k <= 0 = the whole vocabulary is not built)", who, c->top_k_bound);
+    if (vrows > 65535 || c->vocab > (1 << 20)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: at most 65535 rows and vocab <= 2^20", who);
+    if (c->ld % 8 != 0 || reinterpret_cast<uintptr_t>(c->logits) % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: logits 16-byte aligned with ld %% 8 == 0", who);
     if ((reinterpret_cast<uintptr_t>(c->rows) | reinterpret_cast<uintptr_t>(c->workspace)) % 8 != 0 ||
         (reinterpret_cast<uintptr_t>(c->pos_device) | reinterpret_cast<uintptr_t>(c->next_token) | reinterpret_cast<uintptr_t>(c->out_log) | reinterpret_cast<uintptr_t>(c->uniform_override) |
          reinterpret_cast<uintptr_t>(c->debug)) % 4 != 0)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: rows / workspace 8-byte aligned, the int32 / fp32 arrays 4-byte aligned");
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows / workspace 8-byte aligned, the int32 / fp32 arrays 4-byte aligned", who);
     if ((long long)tce::sample_chunks(c->vocab) * c->top_k_bound > 8192)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_sample_f16: %d chunks of 4096 logits x top_k_bound %d > 8192 survivors", tce::sample_chunks(c->vocab), c->top_k_bound);
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d chunks of 4096 logits x top_k_bound %d > 8192 survivors", who, tce::sample_chunks(c->vocab), c->top_k_bound);
+    return TCE_OK;
+}
+
+int tce_sample_f16(const tce_sample_call *c, void *stream) {
+    if (const int rc = check_sample_call("tce_sample_f16", c, c ? c->batch : 0)) return rc;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_sample_f16(*c, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+size_t tce_sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
+    if (batch < 1 || rows_per_seq < 1 || rows_per_seq > TCE_SPEC_MAX_ROWS || (long long)batch * rows_per_seq > 65535 || vocab < 1 || vocab > (1 << 20)) return 0;
+    return tce::sample_verify_workspace_bytes(batch, rows_per_seq, vocab);
+}
+
+int tce_sample_verify_f16(const tce_sample_verify_call *v, void *stream) {
+    static const char *who = "tce_sample_verify_f16";
+    if (!v) return fail(TCE_ERR_BAD_ARG, "%s: null call", who);
+    if (v->rows_per_seq < 1 || v->rows_per_seq > TCE_SPEC_MAX_ROWS)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, v->rows_per_seq, TCE_SPEC_MAX_ROWS);
+    if (const int rc = check_sample_call(who, &v->s, (long long)v->s.batch * v->rows_per_seq)) return rc;
+    if (!v->row_token || !v->row_pos || !v->history || !v->emitted) return fail(TCE_ERR_BAD_ARG, "%s: null pointer (row_token, row_pos, history, emitted)", who);
+    if (v->hist_stride <= v->s.pos_bound) return fail(TCE_ERR_BAD_ARG, "%s: hist_stride %d <= pos_bound %d", who, v->hist_stride, v->s.pos_bound);
+    if ((reinterpret_cast<uintptr_t>(v->row_token) | reinterpret_cast<uintptr_t>(v->row_pos) | reinterpret_cast<uintptr_t>(v->history) | reinterpret_cast<uintptr_t>(v->emitted)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: int32-aligned row_token / row_pos / history / emitted", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_verify_f16(*v, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
+}
+
+int tce_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos_device, int pos_bound, int batch, int rows_per_seq, int ngram,
+                    int32_t *row_token, int32_t *row_pos, void *stream) {
+    static const char *who = "tce_draft_ngram";
+    if (!history || !pos_device || !row_token || !row_pos) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (batch < 1 || pos_bound < 0 || hist_stride <= pos_bound) return fail(TCE_ERR_BAD_ARG, "%s: need batch >= 1 and 0 <= pos_bound < hist_stride", who);
+    if (rows_per_seq < 1 || rows_per_seq > TCE_SPEC_MAX_ROWS)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, rows_per_seq, TCE_SPEC_MAX_ROWS);
+    if (ngram < 1 || ngram > 4) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ngram %d (1 .. 4)", who, ngram);
+    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: batch %d (at most 65535)", who, batch);
+    if ((reinterpret_cast<uintptr_t>(history) | reinterpret_cast<uintptr_t>(script) | reinterpret_cast<uintptr_t>(pos_device) | reinterpret_cast<uintptr_t>(row_token) |
+         reinterpret_cast<uintptr_t>(row_pos)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: int32-aligned arrays", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_draft_ngram(history, script, hist_stride, pos_device, pos_bound, batch, rows_per_seq, ngram, row_token, row_pos, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "draft launch") : rc;
 }
 
 int tce_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos_device, int pos_bound, void *workspace,

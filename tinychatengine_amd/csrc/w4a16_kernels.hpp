@@ -289,6 +289,9 @@ int launch_kv_block_table_check(const int *table, int table_stride, int page_key
 // the e4m3 forms of the paged step, the paged prefill and the copies (fp8_kv.hpp: the format): pools of bytes [num_pages][kv_heads][page_keys][hd], one power-of-two
 // exponent in [-8, 7] per pool; UNSUPPORTED_SHAPE for an exponent outside it.  The contiguous side of the copies stays fp16: scatter quantises, gather dequantises.
 size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd);
+int launch_attention_decode_paged_rows(bool fp8, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
+                                       const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd, const int *pos_dev,
+                                       int pos_bound, unsigned short alpha_bits, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
 int launch_attention_decode_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
                                       void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
                                       int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);

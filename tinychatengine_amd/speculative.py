@@ -1,0 +1,475 @@
+"""Speculative decoding on the paged generator: T rows per sequence and step -- the certain next token plus up to T - 1 guessed continuations -- through the layers
+at once, and a verifier that emits every token the plain loop (generate.py) would have emitted.
+
+A decode token is a chain of dependent launches (7 L + 5) and memory round trips that no kernel can shorten from inside.  Here the chain is
+spread over up to T tokens of the SAME sequence: the linears run at M = B T and still stream their weights once, the launch count does not change.
+
+    1        tce_draft_ngram              rows (token, position) per sequence: row 0 = the next input, rows 1 .. = what followed the last occurrence of the
+                                          sequence's most recent n-gram in its own history (prompt lookup; no second model)
+    1        tce_embed_rows_f16           B T rows (inactive rows skipped)
+    7 x L    the layers                   SpeculativeDecoder.step: BatchedDecoder's seven launches at B T rows, tce_attention_decode_step_paged_rows_* as launch 3
+    1        tce_rmsnorm_half             the final norm
+    1        tce_w4a16_forward            lm_head at M = B T
+    3        tce_sample_verify_f16        select for all rows, draw per row, walk the chain: 1 .. T tokens per sequence
+
+LOSSLESS by construction: row t is sampled with the window and the Philox counter (seed, index of the token in its sequence) the plain loop would use, and a draft is
+kept only if it EQUALS the token sampled in front of it.  There is no draft distribution and no rejection sampling; draft models and tree drafts are not built.
+
+    ngram_draft_reference, verify_reference   the two device pieces restated in numpy (verify_reference from sample_reference, ring_window and uniform only)
+    SpecSlotBook                              which pages run(n) must reserve: positions up to p + n T - 1, whatever the budget (rejected rows are written too)
+    SpeculativeDecoder                        PagedBatchedDecoder at B T rows
+    SpeculativeGenerator                      BatchedGenerator's surface (admit / run / tokens / release) + rows_per_seq, ngram, emitted_per_step()
+    HostDrivenSpeculativeLoop                 the same decoders and launches run eagerly, logits to the host, drafts / sampling / acceptance in numpy: the yardstick
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import capi
+from .linear import _stream, rmsnorm_half
+from .paged_kv import PagedBatchDecodeAttention, PagedBatchedDecoder
+from .generate import RING, Sampler, SamplingParams, SlotBook, embed_rows, ring_window, sample_reference, uniform
+
+MAX_ROWS = capi.TCE_SPEC_MAX_ROWS
+
+
+def _check_rows(rows_per_seq: int, ngram: int = 1) -> None:
+    if not 1 <= int(rows_per_seq) <= MAX_ROWS:
+        raise ValueError(f"rows_per_seq {rows_per_seq}: 1 .. {MAX_ROWS} (tree drafts and longer chains are not built)")
+    if not 1 <= int(ngram) <= 4:
+        raise ValueError(f"ngram {ngram}: 1 .. 4")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the two device pieces in numpy
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+def ngram_draft_reference(history, p: int, ngram: int, rows_per_seq: int, pos_bound: int, script=None) -> tuple[np.ndarray, np.ndarray]:
+    """tce_draft_ngram for one sequence: history[i] = the token processed at position i (valid up to index p), p its position.  Returns (row_token, row_pos), int32
+    [rows_per_seq]; an inactive row is (0, -1).  script (a test hook): row t >= 1 takes script[p + t]; the first negative value ends the prefix."""
+    _check_rows(rows_per_seq, ngram)
+    T = int(rows_per_seq)
+    tok, pos = np.zeros(T, np.int32), np.full(T, -1, np.int32)
+    h = np.asarray(history, dtype=np.int64).reshape(-1)
+    if p < 0 or p > pos_bound or p >= h.size:
+        return tok, pos
+    tok[0], pos[0] = h[p], p
+    if script is not None:
+        sc = np.asarray(script, dtype=np.int64).reshape(-1)
+        for t in range(1, T):
+            if p + t > pos_bound or p + t >= sc.size or sc[p + t] < 0:
+                break
+            tok[t], pos[t] = sc[p + t], p + t
+        return tok, pos
+    n = int(ngram)
+    if p < n:
+        return tok, pos
+    best = -1
+    for i in range(n - 1, p):
+        if np.array_equal(h[i - n + 1:i + 1], h[p - n + 1:p + 1]):
+            best = i  # (ascending: the most recent match stays)
+    if best < 0:
+        return tok, pos
+    for t in range(1, T):
+        if best + t > p or p + t > pos_bound:
+            break
+        tok[t], pos[t] = h[best + t], p + t
+    return tok, pos
+
+
+def verify_reference(logit_rows, drafts, ring, pushed: int, generated: int, params: SamplingParams, seed: int, stop_ids, max_new: int, uniforms=None,
+                     log_stride: int | None = None) -> dict:
+    """tce_sample_verify_f16 for one sequence: logit_rows fp16 [n][vocab] are its n active rows, drafts[t] the token row t + 1 was fed (n - 1 of them).  Row t is
+    sampled as the plain loop samples token `generated + t`: the window of the ring with y_0 .. y_{t-1} pushed, the uniform keyed (seed, generated + t) -- or
+    uniforms[t], a test hook.  Returns tokens (1 .. n of them), ring / pushed / generated after them, retired (a stop id or the budget) and accepted (the drafts kept)."""
+    ring = np.array(ring, dtype=np.int32).copy()
+    assert ring.shape == (RING,)
+    n = len(logit_rows)
+    drafts = [int(d) for d in drafts]
+    assert n >= 1 and len(drafts) >= n - 1
+    stop = {int(s) for s in stop_ids}
+    pushed, generated = int(pushed), int(generated)
+    tokens, retired = [], False
+    for t in range(n):
+        u = uniforms[t] if uniforms is not None else uniform(seed, generated)
+        y = int(sample_reference(logit_rows[t], ring_window(ring, pushed, params.repeat_last_n), params, u)["token"])
+        tokens.append(y)
+        ring[pushed % RING] = y
+        pushed += 1
+        generated += 1
+        if y in stop or generated >= max_new or (log_stride is not None and generated >= log_stride):
+            retired = True
+            break
+        if t + 1 >= n or drafts[t] != y:
+            break
+    return {"tokens": tokens, "ring": ring, "pushed": pushed, "generated": generated, "retired": retired, "accepted": len(tokens) - 1}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# host bookkeeping
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+class SpecSlotBook(SlotBook):
+    """SlotBook for steps of rows_per_seq rows: a replay appends rows p .. p + T - 1 of a live slot whatever it then accepts -- rejected rows are written too and stay
+    behind the position --, and moves p by 1 .. T.  So n replays can touch every key up to p + n T - 1, and the reservation does not depend on the budget."""
+
+    def __init__(self, batch: int, max_keys: int, rows_per_seq: int):
+        _check_rows(rows_per_seq)
+        super().__init__(batch, max_keys)
+        self.rows_per_seq = int(rows_per_seq)
+
+    def wanted(self, n: int) -> list[tuple[int, int]]:
+        return [(s, min(self.pos[s] + n * self.rows_per_seq - 1, self.max_keys - 1)) for s in self.live()]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the layers at B T rows
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
+    """PagedBatchDecodeAttention whose step takes rows_per_seq rows per sequence (tce_attention_decode_step_paged_rows_f16 / _fp8): a workspace slice per virtual
+    row; prefill and the copies are the parent's."""
+
+    def __init__(self, allocator, heads, kv_heads, device, cos=None, sin=None, rows_per_seq: int = 1, **kw):
+        _check_rows(rows_per_seq)
+        super().__init__(allocator, heads, kv_heads, device, cos, sin, **kw)
+        self.rows_per_seq = int(rows_per_seq)
+        need = int(capi.lib().tce_attention_decode_batch_workspace_bytes(self.batch * self.rows_per_seq, heads, self.max_keys, self.hd))
+        if need == 0:
+            raise ValueError("unsupported batched attention shape")
+        self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)  # zeroed once
+        self.slot_workspace_bytes = need // (self.batch * self.rows_per_seq)
+
+    def step(self, qkv, pos_device, pos_bound: int, out=None):
+        """qkv fp16 [batch * T][(heads + 2 kv_heads) * 128], pos_device int32 [batch * T]: the ROWS' positions (a prefix p, p + 1, ... per sequence, -1 behind
+        it).  One launch."""
+        n = self.batch * self.rows_per_seq
+        rw = (self.heads + 2 * self.kv_heads) * self.hd
+        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == n * rw
+        assert pos_device.dtype == torch.int32 and pos_device.is_cuda and pos_device.is_contiguous() and pos_device.numel() == n
+        if out is None:
+            out = torch.empty((n, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == n * self.heads * self.hd
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        L = capi.lib()
+        fn = L.tce_attention_decode_step_paged_rows_fp8 if self.fp8 else L.tce_attention_decode_step_paged_rows_f16
+        capi.check(fn(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out), p(self.workspace), self.batch, self.rows_per_seq,
+                      self.heads, self.kv_heads, self.hd, p(pos_device), int(pos_bound), self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
+        return out
+
+class SpeculativeDecoder(PagedBatchedDecoder):
+    """PagedBatchedDecoder whose step runs batch * rows_per_seq rows: the same seven launches, the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill /
+    prefill_many are the parent's."""
+
+    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
+        _check_rows(rows_per_seq)
+        self.block, self.batch, self.allocator, self.rows_per_seq = block, allocator.batch, allocator, int(rows_per_seq)
+        dev = block.gamma1.device
+        self.attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, dev, block.attention.cos, block.attention.sin, rows_per_seq=rows_per_seq,
+                                                  kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
+        self.rows = self.batch * self.rows_per_seq
+        e = lambda n: torch.empty((self.rows, n), dtype=torch.float16, device=dev)
+        self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
+        self.act = e(block.ffn)
+        self._up = None
+
+    def step(self, hidden, row_pos, pos_bound: int) -> None:
+        """hidden fp16 [batch * T][hidden], updated in place; row_pos int32 [batch * T] (tce_draft_ngram's)."""
+        blk = self.block
+        assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.rows, blk.hidden)
+        st = _stream()
+        rmsnorm_half(hidden, blk.gamma1, blk.eps, out=self.xn)
+        capi.check(capi.w4a16_forward(blk.qkv.desc(self.xn, self.qkv_out), st))
+        self.attention.step(self.qkv_out, row_pos, pos_bound, out=self.attn_out)
+        capi.check(capi.w4a16_forward(blk.o.desc(self.attn_out, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+        rmsnorm_half(hidden, blk.gamma2, blk.eps, out=self.xn)
+        self._gate_up(self.xn, st)
+        capi.check(capi.w4a16_forward(blk.down.desc(self.act, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+
+
+def draft_ngram(history, script, pos_device, pos_bound: int, rows_per_seq: int, ngram: int, row_token, row_pos) -> None:
+    """tce_draft_ngram (one launch on the current stream): history / script int32 [batch][hist_stride] (script may be None), pos_device int32 [batch]."""
+    for t in (history, pos_device, row_token, row_pos) + ((script,) if script is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    batch = pos_device.numel()
+    assert history.dim() == 2 and history.shape[0] == batch and row_token.numel() == row_pos.numel() == batch * rows_per_seq
+    assert script is None or tuple(script.shape) == tuple(history.shape)
+    capi.check(capi.lib().tce_draft_ngram(history.data_ptr(), script.data_ptr() if script is not None else None, history.shape[1], pos_device.data_ptr(), int(pos_bound),
+                                          batch, int(rows_per_seq), int(ngram), row_token.data_ptr(), row_pos.data_ptr(), _stream()))
+
+
+class Verifier:
+    """tce_sample_verify_f16 over a Sampler's per-sequence state: the workspace for batch * rows_per_seq rows and `emitted`."""
+
+    def __init__(self, sampler: Sampler, rows_per_seq: int, debug: bool = False):
+        _check_rows(rows_per_seq)
+        self.sampler, self.rows_per_seq = sampler, int(rows_per_seq)
+        dev = sampler.rows.device
+        need = int(capi.lib().tce_sample_verify_workspace_bytes(sampler.batch, self.rows_per_seq, sampler.vocab))
+        if need == 0:
+            raise ValueError("unsupported verify shape (batch * rows_per_seq <= 65535, vocab <= 2^20)")
+        self.workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
+        self.emitted = torch.zeros(sampler.batch, dtype=torch.int32, device=dev)
+        self.uniform_override = None  # fp32 [batch * rows_per_seq] on the device (tests)
+        self.debug = torch.zeros((sampler.batch * self.rows_per_seq, C.sizeof(capi.SampleDebug) // 4), dtype=torch.int32, device=dev) if debug else None
+
+    def step(self, logits, row_token, row_pos, history, pos_device, pos_bound: int) -> None:
+        """logits fp16 [batch * T][ld]; pos_device int32 [batch] (the sequences' positions) is read and written; three launches on the current stream."""
+        s = self.sampler
+        n = s.batch * self.rows_per_seq
+        assert logits.dtype == torch.float16 and logits.is_contiguous() and logits.dim() == 2 and logits.shape[0] == n and logits.shape[1] >= s.vocab and logits.is_cuda
+        for t, m in ((row_token, n), (row_pos, n), (pos_device, s.batch)):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda and t.numel() == m
+        assert history.dtype == torch.int32 and history.is_contiguous() and history.is_cuda and history.dim() == 2 and history.shape[0] == s.batch
+        c = s.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound)
+        c.workspace = self.workspace.data_ptr()
+        c.uniform_override = self.uniform_override.data_ptr() if self.uniform_override is not None else None
+        c.debug = self.debug.data_ptr() if self.debug is not None else None
+        v = capi.SampleVerifyCall(s=c, rows_per_seq=self.rows_per_seq, hist_stride=history.shape[1], row_token=row_token.data_ptr(), row_pos=row_pos.data_ptr(),
+                                  history=history.data_ptr(), emitted=self.emitted.data_ptr())
+        capi.check(capi.sample_verify_f16(v, _stream()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the front
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+class SpeculativeGenerator:
+    """decoders: one SpeculativeDecoder per layer over ONE PageAllocator, all with the same rows_per_seq.  The token step is captured once in one torch.cuda.graph;
+    one replay is 1 .. rows_per_seq tokens per live sequence.  script=True (a test hook) allocates `script` int32 [batch][hist_stride], -1 everywhere, which then
+    REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t]."""
+
+    def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
+                 graph: bool = True, script: bool = False, record_steps: int = 4096):
+        self.decoders = list(decoders)
+        d0 = self.decoders[0]
+        self.batch, self.hidden_size, self.rows_per_seq, self.ngram = d0.batch, d0.block.hidden, d0.rows_per_seq, int(ngram)
+        _check_rows(self.rows_per_seq, self.ngram)
+        self.allocator = d0.allocator
+        assert all(d.allocator is self.allocator and d.batch == self.batch and d.rows_per_seq == self.rows_per_seq for d in self.decoders), "one allocator, one batch size, one T"
+        self.max_keys = d0.attention.max_keys
+        self.pos_bound = self.max_keys - 1
+        self.final_gamma, self.lm_head, self.embed_table = final_gamma, lm_head, embed_table
+        self.eps = d0.block.eps if eps is None else eps
+        self.vocab = embed_table.shape[0]
+        assert embed_table.dtype == torch.float16 and embed_table.shape[1] == self.hidden_size and lm_head.in_features == self.hidden_size and lm_head.out_features >= self.vocab
+        dev = embed_table.device
+        self.device = dev
+        B, T = self.batch, self.rows_per_seq
+        self.sampler = Sampler(B, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids)
+        self.verifier = Verifier(self.sampler, T)
+        self.book = SpecSlotBook(B, self.max_keys, T)
+        self.hist_stride = self.max_keys + 8  # (the verifier writes index p + 1 + t <= max_keys)
+        z = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=dev)
+        self.pos, self.row_token, self.row_pos = z(B, fill=-1), z(B * T), z(B * T, fill=-1)
+        self.history = z(B, self.hist_stride)
+        self.script = z(B, self.hist_stride, fill=-1) if script else None
+        self.hidden = torch.zeros((B * T, self.hidden_size), dtype=torch.float16, device=dev)
+        self.xn = torch.zeros_like(self.hidden)
+        self.logits = torch.zeros((B * T, lm_head.out_features), dtype=torch.float16, device=dev)
+        self._adm_pos = z(B, fill=-1)
+        self._adm_hidden = torch.zeros((B, self.hidden_size), dtype=torch.float16, device=dev)
+        self._adm_xn = torch.zeros_like(self._adm_hidden)
+        self._adm_logits = torch.zeros((B, lm_head.out_features), dtype=torch.float16, device=dev)
+        self._emit_log = z(int(record_steps), B)
+        self._steps = 0
+        self.launches_per_token = 1 + 1 + d0.LAUNCHES * len(self.decoders) + 1 + 1 + 3
+        self._graph = None
+        if graph:
+            self.token_step()  # the warm-up: every sequence inactive
+            torch.cuda.synchronize()
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                self.token_step()
+
+    # ---- one step: 1 .. T tokens for every live sequence ----
+    def token_step(self) -> None:
+        draft_ngram(self.history, self.script, self.pos, self.pos_bound, self.rows_per_seq, self.ngram, self.row_token, self.row_pos)
+        embed_rows(self.embed_table, self.row_token, self.hidden, self.row_pos, self.pos_bound, self.sampler.workspace)
+        for d in self.decoders:
+            d.step(self.hidden, self.row_pos, self.pos_bound)
+        rmsnorm_half(self.hidden, self.final_gamma, self.eps, out=self.xn)
+        capi.check(capi.w4a16_forward(self.lm_head.desc(self.xn, self.logits), _stream()))
+        self.verifier.step(self.logits, self.row_token, self.row_pos, self.history, self.pos, self.pos_bound)
+
+    # ---- admission: BatchedGenerator.admit's launches (prefill, the first token through tce_sample_f16), then the history row ----
+    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None) -> list[int]:
+        """admit(slot, prompt_ids, params, seed, max_new), or admit([(slot, prompt_ids, params, seed, max_new), ...]): several sequences through ONE prefill_many.
+        Synchronises.  Returns the slots that retired on their first token."""
+        adm = slot if prompt_ids is None else [(slot, prompt_ids, params, seed, max_new)]
+        adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(self.sampler.log_stride if mn is None else mn)) for s, ids, p, sd, mn in adm]
+        if len({s for s, *_ in adm}) != len(adm):
+            raise ValueError("admit: a slot is named twice")
+        for s, ids, p, sd, mn in adm:
+            if not 0 <= s < self.batch:
+                raise IndexError(f"slot {s} of {self.batch}")
+            if self.book.pos[s] >= 0:
+                raise ValueError(f"slot {s} is live")
+            if any(not 0 <= t < self.vocab for t in ids):
+                raise ValueError("a prompt token lies outside the vocabulary")
+            p.check(self.sampler.top_k_bound)
+            if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
+                raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new 1 .. {self.sampler.log_stride}")
+        if any(self.allocator.pages[s] for s, *_ in adm):
+            raise ValueError("admit: a slot still holds pages (release it first)")
+        self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])  # all or nothing, before anything changes
+        rows = []
+        for s, ids, p, sd, mn in adm:
+            tok = torch.tensor(ids, dtype=torch.int32).to(self.device)
+            r = torch.empty((len(ids), self.hidden_size), dtype=torch.float16, device=self.device)
+            embed_rows(self.embed_table, tok, r, torch.zeros(len(ids), dtype=torch.int32, device=self.device), 0, self.sampler.workspace)
+            rows.append(r)
+        for d in self.decoders:
+            d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
+        self._adm_pos.fill_(-1)
+        for (s, ids, p, sd, mn), r in zip(adm, rows):
+            self.sampler.set_row(s, p, sd, mn, ids)
+            self.sampler.out_log[s].fill_(-1)
+            self._adm_hidden[s].copy_(r[-1])
+            self._adm_pos[s] = len(ids) - 1
+        rmsnorm_half(self._adm_hidden, self.final_gamma, self.eps, out=self._adm_xn)
+        capi.check(capi.w4a16_forward(self.lm_head.desc(self._adm_xn, self._adm_logits), _stream()))
+        self.sampler.step(self._adm_logits, self._adm_pos, self.pos_bound)  # the first token: leaves len(ids) -- or -1 -- in the admitted slots' words
+        slots = torch.tensor([s for s, *_ in adm], dtype=torch.int64, device=self.device)
+        self.pos.index_copy_(0, slots, self._adm_pos.index_select(0, slots))
+        first = self.sampler.next_token.cpu().numpy()  # (synchronises)
+        for s, ids, p, sd, mn in adm:
+            row = torch.tensor(ids + [int(first[s])], dtype=torch.int32)
+            self.history[s, :row.numel()].copy_(row)
+            self.book.admit(s, len(ids), mn)
+        return self._sync()
+
+    def set_script(self, slot: int, tokens) -> None:
+        """The test hook's row for `slot`: tokens[i] is fed as the draft for position i (-1: no draft from there on); the rest of the row is -1."""
+        if self.script is None:
+            raise ValueError("set_script: the generator was built without script=True")
+        row = np.full(self.hist_stride, -1, np.int32)
+        tokens = np.asarray(tokens, np.int32)[:self.hist_stride]
+        row[:tokens.size] = tokens
+        self.script[slot].copy_(torch.from_numpy(row))
+
+    # ---- running ----
+    def run(self, n: int, record: bool = True) -> list[int]:
+        """n steps -- n .. n T tokens -- for every live slot: pages for positions up to p + n T - 1 are reserved first (all or nothing: PagePoolExhausted and nothing
+        changed), then the step is replayed n times with no host synchronisation, then ONE synchronise.  record: a stream-ordered device copy of `emitted` behind every
+        replay, for emitted_per_step() (no synchronisation).  Returns the slots that retired."""
+        if n < 1:
+            raise ValueError("run: n >= 1")
+        self.book.reserve(self.allocator, n)
+        for _ in range(n):
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self.token_step()
+            if record and self._steps < self._emit_log.shape[0]:
+                self._emit_log[self._steps].copy_(self.verifier.emitted)
+                self._steps += 1
+        return self._sync()
+
+    def _sync(self) -> list[int]:
+        return self.book.update(self.pos.cpu().numpy(), self.sampler.generated())
+
+    def emitted_per_step(self) -> np.ndarray:
+        """int32 [recorded steps][batch]: the tokens every slot emitted in each recorded replay (0: inactive)."""
+        return self._emit_log[:self._steps].cpu().numpy()
+
+    def tokens(self, slot: int) -> list[int]:
+        n = int(self.sampler.generated()[slot])
+        return self.sampler.out_log[slot, :n].cpu().numpy().tolist()
+
+    def release(self, slot: int) -> list[int]:
+        self.pos[slot] = -1
+        self.book.clear(slot)
+        return self.allocator.release(slot)
+
+    def embed_violations(self) -> int:
+        return int(self.sampler.workspace[:4].cpu().numpy().view(np.uint32)[0])
+
+
+class HostDrivenSpeculativeLoop:
+    """The same decoders and the same M = B T launches run eagerly, driven from the host: drafts (ngram_draft_reference), sampling and acceptance (verify_reference)
+    in numpy on logits copied back every step.  The yardstick of tests/test_gpu_speculative.py and scripts/speculative_time.py."""
+
+    def __init__(self, decoders, final_gamma, lm_head, embed_table, ngram: int = 2, eps: float | None = None, stop_ids=()):
+        self.decoders = list(decoders)
+        d0 = self.decoders[0]
+        self.batch, self.allocator, self.rows_per_seq, self.ngram = d0.batch, d0.allocator, d0.rows_per_seq, int(ngram)
+        _check_rows(self.rows_per_seq, self.ngram)
+        self.max_keys = d0.attention.max_keys
+        self.pos_bound = self.max_keys - 1
+        self.final_gamma, self.lm_head = final_gamma, lm_head
+        self.eps = d0.block.eps if eps is None else eps
+        self.table_host = embed_table.cpu()
+        self.vocab = embed_table.shape[0]
+        dev = embed_table.device
+        self.device = dev
+        n = self.batch * self.rows_per_seq
+        self.hidden = torch.zeros((n, d0.block.hidden), dtype=torch.float16, device=dev)
+        self.xn = torch.zeros_like(self.hidden)
+        self.logits = torch.zeros((n, lm_head.out_features), dtype=torch.float16, device=dev)
+        self.row_pos = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.pos_host = np.full(self.batch, -1, np.int64)
+        self.stop_ids = [int(s) for s in stop_ids]
+        self.state: list[dict | None] = [None] * self.batch
+        self.script: list | None = None  # [batch] rows (or None per slot): replaces the lookup, as SpeculativeGenerator's
+        self.emitted: list[list[int]] = []
+
+    def _logits(self, hidden, xn, out) -> np.ndarray:
+        rmsnorm_half(hidden, self.final_gamma, self.eps, out=xn)
+        capi.check(capi.w4a16_forward(self.lm_head.desc(xn, out), _stream()))
+        return out.cpu().numpy()[:, :self.vocab]  # (synchronises)
+
+    def admit(self, admissions) -> None:
+        """[(slot, prompt_ids, params, seed, max_new)]: the prefill launches SpeculativeGenerator.admit makes for the same call, the first token sampled on the host."""
+        adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(mn)) for s, ids, p, sd, mn in admissions]
+        rows = [self.table_host[torch.tensor(ids, dtype=torch.int64)].to(self.device).contiguous() for _, ids, *_ in adm]
+        for d in self.decoders:
+            d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
+        last = torch.zeros((self.batch, self.hidden.shape[1]), dtype=torch.float16, device=self.device)
+        for (s, *_), r in zip(adm, rows):
+            last[s].copy_(r[-1])
+        lg = self._logits(last, torch.empty_like(last), torch.empty((self.batch, self.logits.shape[1]), dtype=torch.float16, device=self.device))
+        for s, ids, p, sd, mn in adm:
+            ring = np.zeros(RING, np.int32)
+            for i, t in enumerate(ids):
+                ring[i % RING] = t
+            st = {"params": p, "seed": sd, "max_new": mn, "ring": ring, "pushed": len(ids), "generated": 0, "out": [], "history": list(ids)}
+            v = verify_reference(lg[s:s + 1], [], st["ring"], st["pushed"], 0, p, sd, self.stop_ids, mn)
+            self._take(s, st, v, len(ids) - 1)
+            self.state[s] = st
+
+    def _take(self, slot: int, st: dict, v: dict, p: int) -> None:
+        st["ring"], st["pushed"], st["generated"] = v["ring"], v["pushed"], v["generated"]
+        st["out"] += v["tokens"]
+        st["history"] = st["history"][:p + 1] + v["tokens"]
+        self.pos_host[slot] = -1 if v["retired"] else p + len(v["tokens"])
+
+    def step(self) -> None:
+        T = self.rows_per_seq
+        live = [s for s in range(self.batch) if 0 <= self.pos_host[s] <= self.pos_bound]
+        if live:
+            self.allocator.reserve_many([(s, min(int(self.pos_host[s]) + T - 1, self.max_keys - 1)) for s in live])
+        tok, pos = np.zeros(self.batch * T, np.int64), np.full(self.batch * T, -1, np.int32)
+        for s in live:
+            sc = self.script[s] if self.script is not None else None
+            tok[s * T:(s + 1) * T], pos[s * T:(s + 1) * T] = ngram_draft_reference(self.state[s]["history"], int(self.pos_host[s]), self.ngram, T, self.pos_bound, script=sc)
+        self.row_pos.copy_(torch.from_numpy(pos))
+        self.hidden.copy_(self.table_host[torch.from_numpy(tok)])  # host -> device
+        for d in self.decoders:
+            d.step(self.hidden, self.row_pos, self.pos_bound)
+        lg = self._logits(self.hidden, self.xn, self.logits)
+        emitted = [0] * self.batch
+        for s in live:
+            st, p = self.state[s], int(self.pos_host[s])
+            n = int((pos[s * T:(s + 1) * T] >= 0).sum())
+            v = verify_reference(lg[s * T:s * T + n], tok[s * T + 1:s * T + n], st["ring"], st["pushed"], st["generated"], st["params"], st["seed"], self.stop_ids,
+                                 st["max_new"])
+            self._take(s, st, v, p)
+            emitted[s] = len(v["tokens"])
+        self.emitted.append(emitted)
+
+    def tokens(self, slot: int) -> list[int]:
+        return list(self.state[slot]["out"])
+
+    def release(self, slot: int) -> None:
+        self.pos_host[slot] = -1
+        self.allocator.release(slot)
