@@ -47,7 +47,7 @@ extern "C" {
 
 #define TCE_API __attribute__((visibility("default")))
 
-#define TCE_VERSION 113 /* additive, unversioned: tce_sample_workspace_bytes, tce_sample_f16, tce_embed_rows_f16 (device-side sampling and the embedding lookup: one graph replay is one token); tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
+#define TCE_VERSION 113 /* additive, unversioned: tce_w4a16_prepack_group_bytes, tce_w4a16_prepack_group (one packed copy for linears that are always launched together; a member's descriptor names the copy, its first tile and the copy's rows in `prepacked`, `reserved`, `reserved2` -- fields that were zero before, and zero still means an individual copy.  BEHAVIOUR CHANGE under the unchanged number: the two reserved fields are now READ, so a caller that left them uninitialised -- non-zero, with no packed copy or not describing N rows of one -- gets TCE_ERR_BAD_ARG from every W4A16 entry point where it ran before; zero them); tce_sample_workspace_bytes, tce_sample_f16, tce_embed_rows_f16 (device-side sampling and the embedding lookup: one graph replay is one token); tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
 
 /* error codes (return values) */
 #define TCE_OK 0
@@ -84,11 +84,11 @@ typedef struct tce_w4a16_desc {
     int32_t lda, ldc;                     /* elements; 0 = dense */
     int32_t scales_stride, zeros_stride;  /* elements / words; 0 = reference default */
     int32_t flags;                        /* TCE_W4_* */
-    int32_t reserved;
+    int32_t reserved;                     /* 0, or -- a member of a group copy (tce_w4a16_prepack_group) -- its first 16-row tile inside the copy */
     const void *rmsnorm_gamma;            /* NULL = none.  fp32 [K]: A is the UN-normalised hidden state and the kernel stages
                                              RMSNorm(A) * gamma (generalT5LayerNorm arithmetic, see tce_rmsnorm_half); M = 1 */
     float rmsnorm_eps;
-    int32_t reserved2;
+    int32_t reserved2;                    /* 0 = `prepacked` is this linear's own copy; > 0: `prepacked` is a group copy of this many rows */
     const void *prepacked;                /* NULL = none.  The q4_mfma copy of this linear's weights built by tce_w4a16_prepack
                                              (same N, K, group size): the prefill GEMM for large M AND the decode kernel for M <= 4
                                              (round 4: csrc/w4a16_gemv_i8.hip) read it instead of qweight / scales / zeros (which must
@@ -540,6 +540,18 @@ TCE_API size_t tce_w4a16_gemm_scratch_bytes(void); /* size of tce_w4a16_desc.scr
  * 4096 bytes are zeroed again.  A host that keeps a scratch area for a long time calls this where it synchronises anyway (the adapter: at teardown and on request). */
 TCE_API int tce_w4a16_gemm_scratch_faults(const void *scratch, void *stream, uint32_t *faults);
 TCE_API int tce_w4a16_prepack(const tce_w4a16_desc *d, void *packed, void *stream);
+
+/* ONE packed copy for `count` (<= TCE_MAX_GROUP) linears that are always launched together (q/k/v; gate, up).  The copy is, byte for byte, what
+ * tce_w4a16_prepack writes for the row-concatenated linear (rows of descs[0], then descs[1], ...): words, then scales, then zero points.  Valid when every member
+ * shares K and the group size and every member's N is a multiple of 16 (so that no 16-row tile holds rows of two members); otherwise _bytes returns 0 and
+ * tce_w4a16_prepack_group TCE_ERR_UNSUPPORTED_SHAPE, and the caller keeps individual copies.  `packed`: tce_w4a16_prepack_group_bytes(descs, count) bytes, 256-byte aligned.
+ * A member's descriptor then carries `prepacked` = the copy's base, `reserved` = its first 16-row tile inside the copy (the rows in front of it / 16) and `reserved2` =
+ * the copy's rows (the sum of the members' N).  Every entry point that reads `prepacked` takes such a descriptor: it addresses the member's slice, which holds the
+ * bytes of the member's own copy -- same results, bit for bit.  tce_w4a16_forward_group / _group_rmsnorm (and plans) given the members of ONE copy in the copy's order,
+ * without a gap, launch them as one linear on it: no per-linear addressing in front of the weight requests (csrc/w4a16_gemv_i8.hip).  Any other member list runs as
+ * a group of individual linears. */
+TCE_API size_t tce_w4a16_prepack_group_bytes(const tce_w4a16_desc *descs, int count);
+TCE_API int tce_w4a16_prepack_group(const tce_w4a16_desc *descs, int count, void *packed, void *stream);
 
 /* count (<= TCE_MAX_GROUP) linears with identical M, K, group_size and A/lda, one launch (GEMV path only). */
 #define TCE_MAX_GROUP 4

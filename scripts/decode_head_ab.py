@@ -6,7 +6,8 @@ stream-ordered launches (the decode kernels' flat / preloaded arguments, profile
 
   1. parent / new / parent / new ... (`TCE_LIB_PATH=<parent>` against the in-tree build, as scripts/probes/ab_libs.sh alternates builds): every bench line -> DIR/bench_ab.jsonl,
      closed by a verdict row: the gain of the medians against three times the parent's own max - min over its repeats;
-  2. `bench.py --dump-outputs` under both builds: the .npy files compared byte for byte (a row of bench_ab.jsonl);
+  2. `bench.py --dump-outputs` under both builds: the .npy files compared byte for byte (a row of bench_ab.jsonl); `bench.py --shapes-only` under both builds, untraced:
+     the token's launch shapes on their own (a row per build);
   3. `rocprofv3 --kernel-trace --stats` around `bench.py --shapes-only` under both builds (kernel trace only: counters never share a run with tracing): the durations per
      (kernel, grid, workgroup) -> DIR/kernel_stats_{parent,new}.txt.
 
@@ -118,6 +119,12 @@ def main():
         differing = [n for n in names if n not in names_new or not filecmp.cmp(os.path.join(tmp, "parent", n), os.path.join(tmp, "new", n), shallow=False)]
         rows.append({"dump_outputs": "byte-identical" if names and names == names_new and not differing else "DIFFERENT", "files": len(names), "differing": differing})
         print(json.dumps(rows[-1]), flush=True)
+        # the token's launch shapes on their own (`roofline.shapes` of the full bench line: graph-replayed, weights rotating over the layers), untraced
+        for build in ("parent", "new"):
+            out = gpu_step(f"launch shapes {build}", [sys.executable, "bench.py", "--shapes-only"], 600, envs[build])
+            shapes = bench_line(out)["decode_launch_shapes"]["linears"]
+            rows.append({"build": build, "launch_shapes": [{"name": r.get("name"), "launch": r.get("launch"), "us": r.get("us"), "frac_of_8TBs": r.get("frac_of_8TBs")} for r in shapes]})
+            print(json.dumps(rows[-1]), flush=True)
         with open(os.path.join(a.out, "bench_ab.jsonl"), "w") as f:
             f.write("".join(json.dumps(r) + "\n" for r in rows))
         if differing or not names or names != names_new:

@@ -13,6 +13,7 @@
 
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "w4a16_mfma_layout.hpp"
 
 namespace tce {
 int launch_w8a8(const tce_w8a8_desc &d, hipStream_t stream, hipError_t *hip_err, void *scratch = nullptr, char *describe = nullptr, int describe_len = 0);
@@ -68,6 +69,9 @@ int check_w4a16(const tce_w4a16_desc *d) {
     }
     // the RMSNorm prologue lives in the GEMV kernels only: a forced GEMM would silently contract the un-normalised A
     if (d->rmsnorm_gamma && (d->flags & TCE_W4_FORCE_GEMM)) return fail(TCE_ERR_BAD_ARG, "rmsnorm_gamma cannot be combined with TCE_W4_FORCE_GEMM");
+    // a member of a group copy (tce_w4a16_prepack_group): `reserved` = its first 16-row tile inside the copy, `reserved2` = the copy's rows; 0 / 0: an individual copy
+    if ((d->reserved || d->reserved2) && (!d->prepacked || !tce::pk::group_member_ok(d->N, d->reserved, d->reserved2)))
+        return fail(TCE_ERR_BAD_ARG, "group-copy fields (first tile %d, rows of the copy %d) do not describe N=%d rows of a packed copy", d->reserved, d->reserved2, d->N);
     return TCE_OK;
 }
 
@@ -732,6 +736,9 @@ int tce_w4a16_describe_dispatch(const tce_w4a16_desc *d, char *buf, int buf_len)
         return TCE_OK;
     }
     if (g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_supports(d, 1)) {
+        if (d->reserved2 > 0)  // a member of a group copy: launched with its neighbours (in order) the group is ONE linear on the shared copy
+            std::snprintf(buf, (size_t)buf_len, "gemv-i8 rows-per-pass=%d group=%d group-copy first-tile=%d rows=%d", tce::gemv_i8_rows_per_pass(d->M, d->K, d->group_size), d->group_size, d->reserved, d->reserved2);
+        else
         std::snprintf(buf, (size_t)buf_len, "gemv-i8 rows-per-pass=%d group=%d", tce::gemv_i8_rows_per_pass(d->M, d->K, d->group_size), d->group_size);
         return TCE_OK;
     }
@@ -779,6 +786,28 @@ int tce_w4a16_prepack(const tce_w4a16_desc *d, void *packed, void *stream) {
     const int rc = tce::launch_w4a16_prepack(*d, packed, static_cast<hipStream_t>(stream), &he);
     if (rc == TCE_ERR_HIP) return hip_fail(he, "prepack launch");
     if (rc != TCE_OK) return fail(rc, "tce_w4a16_prepack: unsupported shape");
+    return TCE_OK;
+}
+
+size_t tce_w4a16_prepack_group_bytes(const tce_w4a16_desc *descs, int count) {
+    if (!descs || count < 1 || count > TCE_MAX_GROUP) return 0;
+    return tce::prepack_group_bytes(descs, count);
+}
+
+int tce_w4a16_prepack_group(const tce_w4a16_desc *descs, int count, void *packed, void *stream) {
+    if (!descs || !packed || count < 1 || count > TCE_MAX_GROUP) return fail(TCE_ERR_BAD_ARG, "tce_w4a16_prepack_group: null argument / count not in 1..%d", TCE_MAX_GROUP);
+    for (int i = 0; i < count; ++i) {
+        const tce_w4a16_desc &d = descs[i];
+        if (!d.qweight || !d.scales || !d.zeros || d.N <= 0 || d.K <= 0) return fail(TCE_ERR_BAD_ARG, "tce_w4a16_prepack_group: null weights / non-positive N, K");
+        if (d.group_size != 128 && d.group_size != 64 && d.group_size != 32) return fail(TCE_ERR_UNSUPPORTED_GROUP, "Unsupported group size: %d", d.group_size);
+    }
+    if (tce::prepack_group_bytes(descs, count) == 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_w4a16_prepack_group: the members must share K (a multiple of 128) and the group size, every N a multiple of 16: keep individual copies");
+    if (reinterpret_cast<uintptr_t>(packed) % 256 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_w4a16_prepack_group: the packed buffer must be 256-byte aligned");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_w4a16_prepack_group(descs, count, packed, static_cast<hipStream_t>(stream), &he);
+    if (rc == TCE_ERR_HIP) return hip_fail(he, "prepack launch");
+    if (rc != TCE_OK) return fail(rc, "tce_w4a16_prepack_group: unsupported shape");
     return TCE_OK;
 }
 

@@ -1213,19 +1213,20 @@ size_t prepack_bytes(int N, int K, int G) {
     return pk::total_bytes(N, K, G);
 }
 
-int launch_w4a16_prepack(const tce_w4a16_desc &d, void *out, hipStream_t stream, hipError_t *hip_err) {
-    if (d.K % 128 != 0) return TCE_ERR_UNSUPPORTED_SHAPE;
+int launch_w4a16_prepack(const tce_w4a16_desc &d, void *out, hipStream_t stream, hipError_t *hip_err, int tile0, int rows_total) {
+    if (d.K % 128 != 0 || !pk::group_member_ok(d.N, tile0, rows_total)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    const pk::PackedView pv = pk::packed_view(d.N, d.K, d.group_size, tile0, rows_total);  // (rows_total > 0: the member's slice of a group copy)
     const int zw = zeros_width(d.K, d.group_size);
     PrepackArgs a{};
     a.qweight = static_cast<const unsigned *>(d.qweight);
     a.scales = static_cast<const half_t *>(d.scales);
     a.zeros = static_cast<const unsigned *>(d.zeros);
     unsigned char *base = static_cast<unsigned char *>(out);
-    a.words = reinterpret_cast<unsigned *>(base);
-    a.consts = reinterpret_cast<uint2_t *>(base + pk::consts_offset(d.N, d.K));
-    a.last = reinterpret_cast<float *>(base + pk::last_offset(d.N, d.K, d.group_size));
-    a.dscales = reinterpret_cast<half_t *>(base + pk::dscales_offset(d.N, d.K, d.group_size));
-    a.dzeros = reinterpret_cast<unsigned *>(base + pk::dzeros_offset(d.N, d.K, d.group_size));
+    a.words = reinterpret_cast<unsigned *>(base + pv.words);
+    a.consts = reinterpret_cast<uint2_t *>(base + pv.consts);
+    a.last = reinterpret_cast<float *>(base + pv.last);
+    a.dscales = reinterpret_cast<half_t *>(base + pv.dscales);
+    a.dzeros = reinterpret_cast<unsigned *>(base + pv.dzeros);
     a.N = d.N;
     a.K = d.K;
     a.log2g = d.group_size == 128 ? 7 : (d.group_size == 64 ? 6 : 5);
@@ -1239,6 +1240,31 @@ int launch_w4a16_prepack(const tce_w4a16_desc &d, void *out, hipStream_t stream,
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;
         return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+size_t prepack_group_bytes(const tce_w4a16_desc *descs, int count) {
+    if (!descs || count < 1) return 0;
+    long long rows = 0;
+    for (int i = 0; i < count; ++i) {
+        if (descs[i].N <= 0 || descs[i].N % 16 != 0 || descs[i].K != descs[0].K || descs[i].group_size != descs[0].group_size) return 0;
+        rows += descs[i].N;
+    }
+    if (rows >= (1LL << 31)) return 0;
+    return prepack_bytes((int)rows, descs[0].K, descs[0].group_size);
+}
+
+// the group copy: every member packed into its slice of the copy of the row-concatenated linear (whole 16-row tiles: the same bytes as packing the concatenation)
+int launch_w4a16_prepack_group(const tce_w4a16_desc *descs, int count, void *out, hipStream_t stream, hipError_t *hip_err) {
+    if (prepack_group_bytes(descs, count) == 0) return TCE_ERR_UNSUPPORTED_SHAPE;
+    int rows = 0;
+    for (int i = 0; i < count; ++i) rows += descs[i].N;
+    int tile0 = 0;
+    for (int i = 0; i < count; ++i) {
+        const int rc = launch_w4a16_prepack(descs[i], out, stream, hip_err, tile0, rows);
+        if (rc != TCE_OK) return rc;
+        tile0 += descs[i].N / 16;
     }
     return TCE_OK;
 }
@@ -1419,8 +1445,10 @@ int launch_w4a16_gemm_pk(const tce_w4a16_desc &d, const void *packed, hipStream_
     PkGemmArgs g{};
     const unsigned char *base = static_cast<const unsigned char *>(packed);
     g.A = static_cast<const half_t *>(d.A);
-    g.words = reinterpret_cast<const uint4_t *>(base);
-    g.consts = reinterpret_cast<const uint2_t *>(base + pk::consts_offset(d.N, d.K));
+    if (!pk::group_member_ok(d.N, d.reserved, d.reserved2)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    const pk::PackedView pv = pk::packed_view(d.N, d.K, d.group_size, d.reserved, d.reserved2);  // (a member of a group copy: its slice of every part)
+    g.words = reinterpret_cast<const uint4_t *>(base + pv.words);
+    g.consts = reinterpret_cast<const uint2_t *>(base + pv.consts);
     g.C = static_cast<half_t *>(d.C);
     g.M = d.M;
     g.N = d.N;

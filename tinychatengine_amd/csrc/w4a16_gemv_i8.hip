@@ -42,7 +42,7 @@ namespace {
 //            3     U          K / 128                          11     N          linear 0's rows
 //            4- 5  A          activations                      12     M
 //            6     lda                                         13     geom       waves that split K (the workgroup's width / 64; not read from the hidden
-//            7     K                                                             arguments any more) | linears of the launch << 8
+//            7     K                                                             arguments any more) | linears of the launch << 8 | members of a group copy << 16
 // Everything else -- what is used BEHIND the weight requests (C, ldc, epilogue flags, zero points), linears 1.. of a grouped launch, gamma, the RNORM / COMB fields -- is the
 // tail struct: ordinary scalar loads, issued with the wave's first instructions and waited for where first used (a grouped launch: ONE batch holding every further
 // linear's addressing fields, chosen by scalar selects -- at most one wait in front of the weight requests; nothing behind the K reduction's barrier).
@@ -60,6 +60,10 @@ struct I8SegRest {  // what the epilogue (and the general-zero-point forms) need
 struct I8Tail {
     I8SegRest rest[TCE_MAX_GROUP];
     I8SegHead head[TCE_MAX_GROUP - 1];
+    // a launch on a GROUP COPY (tce_w4a16_prepack_group: q/k/v, gate+up packed as one row-concatenated linear; geom: one linear, members << 16): the leading parameters
+    // address the whole copy exactly like a single linear's, rest[0] carries its zero points; what differs per member -- rest[i].C / ldc / epilogue -- is chosen by the
+    // member's first 16-row tile, behind the weight requests
+    int mtile[TCE_MAX_GROUP];
     const float *gamma;  // non-null: the activation is the UN-normalised hidden state; the conversion stages RMSNorm(A) * gamma (generalT5LayerNorm arithmetic; M = 1)
     float eps;
     // RNORM (tce_w4a16_forward_residual_rmsnorm): the residual epilogue also produces the NEXT RMSNorm of the updated row -- out_gamma fp32 [N], xn_out fp16 [N],
@@ -164,7 +168,7 @@ __device__ __forceinline__ void keep_scalar(T &v) {
 // `args` is the launch's tail (I8Tail) or the mixed launch's struct, for the prologue / epilogue fields.
 template <int MB, int GPU, int ROWS, int UW, bool Z8, bool NORM, bool RNORM, int COMB, bool MIX, typename ARGS, bool STAMPS = false>
 __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned char *smem, int tid, const int WK, const int U, const int K_, const int lda_, int M_, const half_t *A_,
-                                                   I8Seg seg, const int tile0, const bool gathers, const unsigned g_epoch, I8Stamps *st = nullptr) {
+                                                   I8Seg seg, const int tile0, const bool gathers, const unsigned g_epoch, I8Stamps *st = nullptr, const int nmem = 0) {
     static_assert(!MIX || (MB == 1 && GPU == 1 && ROWS == 1 && UW == 8 && !NORM && !RNORM && !COMB), "the mixed launch: one decode row, groups of 128, one tile per wave group");
     static_assert(!COMB || (MB == 1 && ROWS == 1 && GPU == 1 && UW == 8 && !NORM && !RNORM), "the deferred-attention prologue: one decode row, groups of 128, K a multiple of 1024");
     static_assert(MB * GPU <= 4, "sixteen output columns: rows x groups-per-unit x 4 planes");
@@ -414,15 +418,47 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
     __builtin_amdgcn_wave_barrier();
     if constexpr (STAMPS) st->t[2] = __builtin_amdgcn_s_memrealtime();
 
+    // a launch on a group copy (nmem > 0): the member each of the wave's tiles belongs to -- where its rows are stored and how.  Up to here the launch was one linear of
+    // the members' rows together (seg.N: all of them); member rows are whole tiles, so a tile that exists lies inside exactly one member
+    half_t *mC[ROWS];
+    int mldc[ROWS], mepi[ROWS], mrow0[ROWS];  // mrow0: the member's first row in the copy
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        mC[r] = seg.C;
+        mldc[r] = seg.ldc;
+        mepi[r] = seg.epilogue;
+        mrow0[r] = 0;
+    }
+    if constexpr (!MIX) {
+        if (nmem > 0) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                int mi = 0;
+#pragma unroll
+                for (int i = 1; i < TCE_MAX_GROUP; ++i) mi = (i < nmem && tile0 + r >= args.mtile[i]) ? i : mi;
+                mC[r] = args.rest[mi].C;
+                mldc[r] = args.rest[mi].ldc;
+                mepi[r] = args.rest[mi].epilogue;
+                mrow0[r] = args.mtile[mi] * 16;
+            }
+        }
+    }
+    // (the thread's own tile r: wave-uniform for one tile per wave)
+    auto of_tile = [&](auto *v, int r) {
+        auto x = v[0];
+#pragma unroll
+        for (int r2 = 1; r2 < ROWS; ++r2) x = r == r2 ? v[r2] : x;
+        return x;
+    };
     // the residual epilogue's old values (TCE_W4_ADD_TO_C): requested by the lanes that will add to them, BEHIND the weight requests and the conversion (the flags, C and
     // ldc are tail arguments: asking here, not in front of the weights, keeps every scalar wait out of the head; loads return in order, and the value is needed behind
     // the K reduction's barrier only -- where a load issued there was a memory round trip at the very end of every o_proj / down_proj launch)
     half_t c_old = (half_t)0.0f;
     if constexpr (!RNORM) {
-        if (wk == 0 && (seg.epilogue & TCE_W4_ADD_TO_C) && tid < ROWS * MB * 16) {
+        if (wk == 0 && tid < ROWS * MB * 16) {
             const int i16 = tid & 15, m = (tid >> 4) % MB, r = tid / (16 * MB);
             const int row = (tile0 + r) * 16 + i16;
-            if (m0 + m < M_ && row < seg.N) c_old = seg.C[(size_t)(m0 + m) * seg.ldc + row];
+            if ((of_tile(mepi, r) & TCE_W4_ADD_TO_C) && m0 + m < M_ && row < seg.N) c_old = of_tile(mC, r)[(size_t)(m0 + m) * of_tile(mldc, r) + (row - of_tile(mrow0, r))];
         }
     }
 
@@ -540,9 +576,13 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
             if (p_l == 0 && (j >> 2) < MB) red[((wk * ROWS + r) * MB + m_l) * 16 + kq * 4 + q] = v;
         }
     // nothing behind the barrier waits on scalar memory: what the store needs is in registers by now
-    keep_scalar(seg.C);
-    keep_scalar(seg.ldc);
-    keep_scalar(seg.epilogue);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        keep_scalar(mC[r]);
+        keep_scalar(mldc[r]);
+        keep_scalar(mepi[r]);
+        keep_scalar(mrow0[r]);
+    }
     keep_scalar(seg.N);
     keep_scalar(M_);
     float *ws_ = nullptr, *out_gamma_ = nullptr;
@@ -576,19 +616,20 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
         half_t hnew = (half_t)0.0f;
         (void)hnew;
         if (m0 + m < M_ && row < seg.N) {
-            half_t *crow = seg.C + (size_t)(m0 + m) * seg.ldc;
-            if (seg.epilogue & TCE_W4_SILU_MUL_PAIRS) {
-                if ((i16 & 1) == 0) crow[row >> 1] = silu_mul_half(y, y_other);
-            } else if (seg.epilogue & TCE_W4_ADD_TO_C) {
-                if constexpr (RNORM) hnew = crow[row] + y;  // (stored below, write-through)
-                else crow[row] = c_old + y;
+            const int epi = of_tile(mepi, r), mrow = row - of_tile(mrow0, r);  // the row inside its member (a group copy; otherwise the row itself)
+            half_t *crow = of_tile(mC, r) + (size_t)(m0 + m) * of_tile(mldc, r);
+            if (epi & TCE_W4_SILU_MUL_PAIRS) {
+                if ((i16 & 1) == 0) crow[mrow >> 1] = silu_mul_half(y, y_other);
+            } else if (epi & TCE_W4_ADD_TO_C) {
+                if constexpr (RNORM) hnew = crow[mrow] + y;  // (stored below, write-through)
+                else crow[mrow] = c_old + y;
             } else {
-                crow[row] = y;
+                crow[mrow] = y;
             }
             if constexpr (MIX) {
                 if (gathers) {
                     // (a) the tile's 16 values into EVERY rank's window -- buffer (slot, parity of the epoch), this rank's slice -- past every cache (comm.hip's protocol)
-                    const half_t outv = (seg.epilogue & TCE_W4_ADD_TO_C) ? (half_t)(c_old + y) : y;
+                    const half_t outv = (epi & TCE_W4_ADD_TO_C) ? (half_t)(c_old + y) : y;
                     const size_t off = ((size_t)args.g.slot * 2 + (g_epoch & 1u)) * args.g.vec_bytes + ((size_t)args.g.rank * args.g.slice_elems + (size_t)row) * 2;
 #pragma unroll
                     for (int p = 0; p < kCommMaxRanks; ++p)
@@ -731,7 +772,7 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const void *words, 
         st.t[5] = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_sched_barrier(0);
     }
-    const int WK = geom & 0xFF, nseg = geom >> 8;
+    const int WK = geom & 0xFF, nseg = (geom >> 8) & 0xFF, nmem = geom >> 16;
     int si = 0, block_begin = 0;
     if (nseg > 1) {
         // a grouped launch (q/k/v, gate+up): every further linear's addressing fields in ONE batch of scalar loads, the workgroup's own by scalar selects
@@ -755,7 +796,7 @@ __global__ __launch_bounds__(MAXT) void w4a16_gemv_i8_kernel(const void *words, 
     }
     const I8SegRest &r = t.rest[si];
     const I8Seg seg{words, dscales, r.dzeros, r.C, N, r.ldc, r.epilogue, bytes_w, bytes_s, r.bytes_z, block_begin};
-    w4a16_gemv_i8_body<MB, GPU, ROWS, UW, Z8, NORM, RNORM, COMB, false, I8Tail, STAMPS>(t, smem_wg, (int)threadIdx.x, WK, U, K, lda, M, A, seg, ((int)blockIdx.x - block_begin) * ROWS, false, 0u, &st);
+    w4a16_gemv_i8_body<MB, GPU, ROWS, UW, Z8, NORM, RNORM, COMB, false, I8Tail, STAMPS>(t, smem_wg, (int)threadIdx.x, WK, U, K, lda, M, A, seg, ((int)blockIdx.x - block_begin) * ROWS, false, 0u, &st, nmem);
 }
 
 // The mixed launch (I8MixArgs, above): the linear, its activation and k range per WORKGROUP, the tile per wave group.  Its arguments stay one struct by value (P > 1
@@ -799,7 +840,7 @@ thread_local unsigned long long *g_i8_stamps = nullptr;  // lab build: the plain
 struct I8Launch {
     const void *words;
     const half_t *dscales, *A;
-    int bytes_w, bytes_s, U, lda, K, N, M, nseg;
+    int bytes_w, bytes_s, U, lda, K, N, M, nseg, nmem;
     I8Tail t;
 };
 
@@ -811,7 +852,7 @@ hipError_t launch_i8(const I8Launch &a, int blocks, int m_blocks, int wk, hipStr
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kfn, dim3(blocks, m_blocks, 1), dim3(64 * wk, 1, 1), lds, stream, a.words, a.bytes_w, a.U, static_cast<const void *>(a.A), a.lda, a.K, static_cast<const void *>(a.dscales), a.bytes_s, a.N, a.M, wk | (a.nseg << 8), a.t);
+    hipLaunchKernelGGL(kfn, dim3(blocks, m_blocks, 1), dim3(64 * wk, 1, 1), lds, stream, a.words, a.bytes_w, a.U, static_cast<const void *>(a.A), a.lda, a.K, static_cast<const void *>(a.dscales), a.bytes_s, a.N, a.M, wk | (a.nseg << 8) | (a.nmem << 16), a.t);
     return hipGetLastError();
 }
 
@@ -847,11 +888,26 @@ bool gemv_i8_supports(const tce_w4a16_desc *descs, int count, bool with_norm) {
     if (uw == 0 || (uw == 16 && (d0.M > 1 || d0.group_size != 128))) return false;  // (very long K: single rows only -- the registers hold 16 KiB of weights per wave)
     for (int i = 0; i < count; ++i) {
         const tce_w4a16_desc &d = descs[i];
-        if (!d.prepacked || (reinterpret_cast<uintptr_t>(d.prepacked) & 255)) return false;
+        if (!d.prepacked || (reinterpret_cast<uintptr_t>(d.prepacked) & 255) || !pk::group_member_ok(d.N, d.reserved, d.reserved2)) return false;
         if ((long long)pk::nt16(d.N) * (d.K / 2) * 16 >= (1LL << 31)) return false;  // buffer descriptors address 32-bit byte offsets
         if (d.flags & TCE_W4_FORCE_GEMM) return false;
     }
     return true;
+}
+
+// > 0: the `count` (> 1) linears are members of ONE group copy (tce_w4a16_prepack_group), named in the copy's order with consecutive tile ranges -- the launch addresses
+// them as one linear (the count is returned); 0: today's grouped launch, every linear through its own addressing fields (individual copies, or members out of order / with a gap)
+int gemv_i8_group_copy_members(const tce_w4a16_desc *descs, int count) {
+    if (count < 2 || count > TCE_MAX_GROUP || descs[0].reserved2 <= 0) return 0;
+    long long tiles = 0;
+    for (int i = 0; i < count; ++i) {
+        const tce_w4a16_desc &d = descs[i];
+        if (d.prepacked != descs[0].prepacked || d.reserved2 != descs[0].reserved2 || !pk::group_member_ok(d.N, d.reserved, d.reserved2)) return 0;
+        if (i > 0 && d.reserved != descs[i - 1].reserved + descs[i - 1].N / 16) return 0;
+        tiles += d.N / 16;
+    }
+    if (tiles * (descs[0].K / 2) * 16 >= (1LL << 31)) return 0;  // (the whole range behind one buffer descriptor)
+    return count;
 }
 
 int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t stream, hipError_t *hip_err, const float *gamma, float eps, const I8ResidualNorm *rn,
@@ -893,13 +949,16 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
     const long long resident = 256LL * (20 / wk);
     if (gamma && two_ok && total_tiles > resident && total_tiles * 5 <= resident * 6) rows = 2;
     if (g_i8_rows && two_ok) rows = g_i8_rows;
+    // members of ONE group copy, in the copy's order and without a gap: the launch is one linear of their rows together (gemv_i8_group_copy_members)
+    const bool shared = gemv_i8_group_copy_members(descs, count) > 0;
     int blocks = 0;
     for (int i = 0; i < count; ++i) {
         const tce_w4a16_desc &d = descs[i];
         const unsigned char *base = static_cast<const unsigned char *>(d.prepacked);
+        const pk::PackedView pv = pk::packed_view(d.N, d.K, d.group_size, d.reserved, d.reserved2);  // (a member of a group copy: its slice of every part)
         I8SegHead h{};
-        h.words = base;
-        h.dscales = reinterpret_cast<const half_t *>(base + pk::dscales_offset(d.N, d.K, d.group_size));
+        h.words = base + pv.words;
+        h.dscales = reinterpret_cast<const half_t *>(base + pv.dscales);
         h.bytes_w = (int)pk::words_bytes(d.N, d.K);
         h.bytes_s = (int)pk::dscales_bytes(d.N, d.K, d.group_size);
         h.N = d.N;
@@ -915,7 +974,7 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
         }
         I8SegRest &r = a.t.rest[i];
         r.C = static_cast<half_t *>(d.C);
-        r.dzeros = reinterpret_cast<const unsigned *>(base + pk::dzeros_offset(d.N, d.K, d.group_size));
+        r.dzeros = reinterpret_cast<const unsigned *>(base + pv.dzeros);
         r.epilogue = d.flags & (TCE_W4_SILU_MUL_PAIRS | TCE_W4_ADD_TO_C);
         r.ldc = d.ldc ? d.ldc : ((r.epilogue & TCE_W4_SILU_MUL_PAIRS) ? d.N / 2 : d.N);
         r.bytes_z = (int)pk::dzeros_bytes(d.N, d.K, d.group_size);
@@ -924,6 +983,18 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
     for (int i = count; i < TCE_MAX_GROUP; ++i) {  // (never chosen: the kernel's selects stop at the launch's count)
         a.t.rest[i] = a.t.rest[0];
         a.t.head[i - 1] = I8SegHead{a.words, a.dscales, a.bytes_w, a.bytes_s, a.N, 0};
+    }
+    if (shared) {
+        // member 0's slices are where the launch's rows begin; the sizes become those of all members' rows, the workgroups walk their tiles as one range
+        const int rows_all = (int)total_tiles * 16;
+        a.nseg = 1;
+        a.nmem = count;
+        a.N = rows_all;
+        a.bytes_w = (int)pk::words_bytes(rows_all, d0.K);
+        a.bytes_s = (int)pk::dscales_bytes(rows_all, d0.K, d0.group_size);
+        a.t.rest[0].bytes_z = (int)pk::dzeros_bytes(rows_all, d0.K, d0.group_size);
+        for (int i = 0; i < TCE_MAX_GROUP; ++i) a.t.mtile[i] = i < count ? descs[i].reserved - d0.reserved : 0;
+        blocks = (int)((total_tiles + rows - 1) / rows);
     }
     hipError_t e = hipErrorInvalidConfiguration;
     if (rn) {  // residual add + the next RMSNorm: one decode row, one linear, groups of 128, N <= 16384 (the 2048 slots of the order)
@@ -1014,7 +1085,7 @@ bool gemv_i8_mixed_supports(const tce_w4a16_desc *descs, int count) {
         const tce_w4a16_desc &d = descs[i];
         // one decode row, groups of 128, eight units per wave (K <= 16384), no prologue: the <1, 1, 1, 8> body
         if (d.M != 1 || d.group_size != 128 || d.K % 128 != 0 || d.K > 16384 || d.rmsnorm_gamma) return false;
-        if (!d.prepacked || (reinterpret_cast<uintptr_t>(d.prepacked) & 255)) return false;
+        if (!d.prepacked || (reinterpret_cast<uintptr_t>(d.prepacked) & 255) || !pk::group_member_ok(d.N, d.reserved, d.reserved2)) return false;
         if ((long long)pk::nt16(d.N) * (d.K / 2) * 16 >= (1LL << 31)) return false;
         if (d.flags & TCE_W4_FORCE_GEMM) return false;
     }
@@ -1112,9 +1183,10 @@ int launch_w4a16_gemv_i8_mixed(const tce_w4a16_desc *descs, int count, hipStream
         m.K = d.K;
         I8Seg &s = m.seg;
         const unsigned char *base = static_cast<const unsigned char *>(d.prepacked);
-        s.words = base;
-        s.dscales = reinterpret_cast<const half_t *>(base + pk::dscales_offset(d.N, d.K, d.group_size));
-        s.dzeros = reinterpret_cast<const unsigned *>(base + pk::dzeros_offset(d.N, d.K, d.group_size));
+        const pk::PackedView pv = pk::packed_view(d.N, d.K, d.group_size, d.reserved, d.reserved2);  // (a member of a group copy: its slice of every part)
+        s.words = base + pv.words;
+        s.dscales = reinterpret_cast<const half_t *>(base + pv.dscales);
+        s.dzeros = reinterpret_cast<const unsigned *>(base + pv.dzeros);
         s.C = static_cast<half_t *>(d.C);
         s.N = d.N;
         s.epilogue = d.flags & (TCE_W4_SILU_MUL_PAIRS | TCE_W4_ADD_TO_C);

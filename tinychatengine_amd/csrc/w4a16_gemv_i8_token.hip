@@ -508,13 +508,15 @@ int i8_token_plan_create(const tce_w4a16_desc *descs, const int32_t *groups, int
         for (int i = 0; i < groups[l] && ok; ++i) {
             const tce_w4a16_desc &d = descs[off + i];
             ok = d.M == 1 && d.K == d0.K && d.group_size == 128 && d.A == d0.A && d.prepacked && !(reinterpret_cast<uintptr_t>(d.prepacked) & 255) && (d.flags & TCE_W4_ZERO_POINT_IS_8) &&
-                 !(d.flags & TCE_W4_FORCE_GEMM) && !d.rmsnorm_gamma && (long long)pk::nt16(d.N) * (d.K / 2) * 16 < (1LL << 31) && !(d.flags & ~(TCE_W4_ZERO_POINT_IS_8 | TCE_W4_SILU_MUL_PAIRS | TCE_W4_ADD_TO_C));
+                 !(d.flags & TCE_W4_FORCE_GEMM) && !d.rmsnorm_gamma && (long long)pk::nt16(d.N) * (d.K / 2) * 16 < (1LL << 31) && !(d.flags & ~(TCE_W4_ZERO_POINT_IS_8 | TCE_W4_SILU_MUL_PAIRS | TCE_W4_ADD_TO_C)) &&
+                 pk::group_member_ok(d.N, d.reserved, d.reserved2);
             if ((d.flags & TCE_W4_SILU_MUL_PAIRS) && (d.N % 2 != 0 || (d.flags & TCE_W4_ADD_TO_C))) ok = false;
             if (!ok) break;
             TokSeg &sg = st.seg[i];
             const unsigned char *base = static_cast<const unsigned char *>(d.prepacked);
-            sg.words = base;
-            sg.dscales = reinterpret_cast<const half_t *>(base + pk::dscales_offset(d.N, d.K, d.group_size));
+            const pk::PackedView pv = pk::packed_view(d.N, d.K, d.group_size, d.reserved, d.reserved2);  // (a member of a group copy: its slice of every part)
+            sg.words = base + pv.words;
+            sg.dscales = reinterpret_cast<const half_t *>(base + pv.dscales);
             sg.C = static_cast<half_t *>(d.C);
             sg.C_tag = nullptr;
             sg.N = d.N;

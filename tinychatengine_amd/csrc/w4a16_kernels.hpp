@@ -106,6 +106,7 @@ int launch_w4a16_gemv(const tce_w4a16_desc *descs, int count, int forced_rows, i
 
 // w4a16_gemv_i8.hip: the decode GEMV (M <= 4) as an int8 contraction on the pre-packed copy
 bool gemv_i8_supports(const tce_w4a16_desc *descs, int count, bool with_norm = false);
+int gemv_i8_group_copy_members(const tce_w4a16_desc *descs, int count);  // > 0: the group is launched as ONE linear on its shared copy
 int gemv_i8_rows_per_pass(int M, int K, int group_size);
 void set_gemv_i8_mode(int mode, int rows);  // mode 0 automatic (taken wherever a packed copy comes with the descriptors), 1 off; rows 0 the rule, 1 / 2 tiles per wave
 struct I8ResidualNorm {  // tce_w4a16_forward_residual_rmsnorm: the RMSNorm that follows the residual add, produced by the same launch
@@ -160,7 +161,10 @@ int launch_w4a16_gemm(const tce_w4a16_desc &d, int forced_mt, int forced_nt, hip
 
 // w4a16_gemm_pk.hip: the 128-row GEMM on pre-packed weights (q4_mfma, w4a16_mfma_layout.hpp)
 size_t prepack_bytes(int N, int K, int G);
-int launch_w4a16_prepack(const tce_w4a16_desc &d, void *out, hipStream_t stream, hipError_t *hip_err);
+int launch_w4a16_prepack(const tce_w4a16_desc &d, void *out, hipStream_t stream, hipError_t *hip_err, int tile0 = 0, int rows_total = 0);
+// group copies (w4a16_mfma_layout.hpp): 0 bytes = the members cannot share a copy (N % 16, differing K / group size)
+size_t prepack_group_bytes(const tce_w4a16_desc *descs, int count);
+int launch_w4a16_prepack_group(const tce_w4a16_desc *descs, int count, void *out, hipStream_t stream, hipError_t *hip_err);
 int launch_w4a16_gemm_pk(const tce_w4a16_desc &d, const void *packed, hipStream_t stream, hipError_t *hip_err);
 void set_gemm_pk256_auto(int on);  // 0: the dispatcher never picks the 256-row forms by itself
 void set_gemm_pk_wide_auto(int on);

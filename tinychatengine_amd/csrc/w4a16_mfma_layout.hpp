@@ -62,6 +62,29 @@ TCE_HD size_t dscales_offset(int N, int K, int G) { return last_offset(N, K, G) 
 TCE_HD size_t dzeros_offset(int N, int K, int G) { return dscales_offset(N, K, G) + align256(dscales_bytes(N, K, G)); }
 TCE_HD size_t total_bytes(int N, int K, int G) { return dzeros_offset(N, K, G) + align256(dzeros_bytes(N, K, G)); }
 
+// ---- group copies (tce_w4a16_prepack_group): linears that are always launched together (q/k/v; gate, up) packed as ONE row-concatenated linear ----
+// Every part of the layout is tile-major along N and a tile's bytes depend on its own 16 rows, K and G only, so with every member's N a multiple of 16 the copy of
+// the concatenation is the members' tiles one behind the other in each part.  A member is then rows [16 * tile0, 16 * tile0 + N) of a copy of `rows_total` rows: its
+// slice of every part starts at the byte offsets below and is, byte for byte, the part of the member's own copy.  rows_total == 0: an individual copy (tile0 ignored).
+struct PackedView {
+    size_t words, consts, last, dscales, dzeros;  // byte offsets from the copy's base
+};
+TCE_HD bool group_member_ok(int N, int tile0, int rows_total) {
+    if (rows_total == 0) return tile0 == 0;
+    return N > 0 && N % 16 == 0 && rows_total % 16 == 0 && tile0 >= 0 && (long long)tile0 * 16 + N <= rows_total;
+}
+TCE_HD PackedView packed_view(int N, int K, int G, int tile0, int rows_total) {
+    const int NT = rows_total > 0 ? rows_total : N;
+    const size_t t = rows_total > 0 ? (size_t)tile0 : 0;
+    PackedView v;
+    v.words = t * (K / 128) * 1024;
+    v.consts = consts_offset(NT, K) + t * (K / G) * 128;
+    v.last = last_offset(NT, K, G) + t * 64;
+    v.dscales = dscales_offset(NT, K, G) + t * (K / G) * 32;
+    v.dzeros = dzeros_offset(NT, K, G) + t * (K / G) * 8;
+    return v;
+}
+
 // ---- packed words ----
 // position of code (n, k): index of the u32 word in `words`, and the nibble (0..7) inside it
 TCE_HD size_t word_index(int n, int k, int K) {

@@ -99,6 +99,11 @@ class DecodeLinears:
         self.lm_head = mk(shape.vocab, h, 999_983)
         self.prepacked = bool(prepack)
         if prepack:  # load-time re-layout (tce_w4a16_prepack): the descriptors then carry the packed copy and the decode launches run on it (csrc/w4a16_gemv_i8.hip)
+            # q/k/v and gate+up are always launched together: ONE copy per group (tce_w4a16_prepack_group), addressed by the grouped launch like a single linear;
+            # members that cannot share one (a width that is no multiple of 16) keep copies of their own
+            for b in self.blocks:
+                Linear_half_int4.prepack_group(b["qkv"])
+                Linear_half_int4.prepack_group([b["gate"], b["up"]])
             for l in self.all_linears():
                 l.prepack()
         # activations (fp16).  x ~ N(0,1); every buffer a linear READS is full width (replicated input).

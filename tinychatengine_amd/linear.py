@@ -36,6 +36,7 @@ class Linear_half_int4:
         # the reference quantizer writes zero point 8 everywhere; verified once here so the GEMV can skip the zeros stream
         self.zeros_are_8 = bool((zeros == -2004318072).all().item())
         self.packed = None  # q4_mfma copy for the prefill GEMM (prepack())
+        self.group_tile0, self.group_rows = 0, 0  # a member of a group copy (prepack_group): its first 16-row tile inside the copy, the copy's rows; 0 / 0: a copy of its own
         self._op = MatmulOperator()
 
     def prepack(self) -> "Linear_half_int4":
@@ -53,6 +54,35 @@ class Linear_half_int4:
                                    scales=_ptr(self.scale), zeros=_ptr(self.zero_point))
                 capi.check(capi.lib().tce_w4a16_prepack(d, self.packed.data_ptr(), _stream()))
         return self
+
+    @staticmethod
+    def prepack_group(linears: list["Linear_half_int4"]) -> bool:
+        """ONE packed copy for linears that are always launched together (q/k/v; gate, up): tce_w4a16_prepack_group -- byte for byte the copy of the row-concatenated
+        linear.  Every member's descriptor then names the copy's base, its first tile and the copy's rows; a grouped launch of the members in this order runs as one
+        linear on it (no per-linear addressing in front of the weight requests), any other use addresses the member's slice: same bits.  Members do not keep a copy of
+        their own.  Returns False -- and packs every member on its own -- when the members cannot share a copy (differing K / group size, an N that is no multiple of 16,
+        more than TCE_MAX_GROUP members, a member that is packed already)."""
+        import ctypes as C
+        descs = [capi.W4A16Desc(M=1, N=l.out_features, K=l.in_features, group_size=l.group_size, qweight=_ptr(l.weight), scales=_ptr(l.scale), zeros=_ptr(l.zero_point))
+                 for l in linears]
+        arr = (capi.W4A16Desc * len(descs))(*descs)
+        need = 0
+        L = capi.lib()
+        if capi.HAS_GROUP_COPIES and len(linears) > 1 and all(l.packed is None for l in linears):  # (a library from before the group copies, loaded for an A/B run: individual copies)
+            need = int(L.tce_w4a16_prepack_group_bytes(arr, len(descs)))  # 0: the library refuses this group (shapes, count)
+        if not need:
+            for l in linears:
+                l.prepack()
+            return False
+        buf = torch.empty(need + 256, dtype=torch.uint8, device=linears[0].weight.device)
+        off = (-buf.data_ptr()) % 256
+        packed = buf[off:off + need]
+        capi.check(capi.lib().tce_w4a16_prepack_group(arr, len(descs), packed.data_ptr(), _stream()))
+        rows, tile0 = sum(l.out_features for l in linears), 0
+        for l in linears:
+            l._packed_storage, l.packed, l.group_tile0, l.group_rows = buf, packed, tile0, rows
+            tile0 += l.out_features // 16
+        return True
 
     @classmethod
     def from_float(cls, w: torch.Tensor, group_size: int = quantize.QK4_6):
@@ -89,6 +119,7 @@ class Linear_half_int4:
         return capi.W4A16Desc(M=m, N=self.out_features, K=self.in_features, group_size=self.group_size, A=x.data_ptr(),
                               qweight=self.weight.data_ptr(), scales=self.scale.data_ptr(), zeros=self.zero_point.data_ptr(),
                               C=out.data_ptr(), ldc=ldc, flags=flags | (capi.TCE_W4_ZERO_POINT_IS_8 if self.zeros_are_8 else 0),
+                              reserved=self.group_tile0 if self.packed is not None else 0, reserved2=self.group_rows if self.packed is not None else 0,
                               rmsnorm_gamma=gamma.data_ptr() if gamma is not None else None, rmsnorm_eps=float(eps),
                               prepacked=self.packed.data_ptr() if self.packed is not None else None,
                               scratch=gemm_scratch(self.weight.device).data_ptr() if self.packed is not None and m > 128 else None)
