@@ -493,6 +493,32 @@ TCE_API size_t tce_sample_verify_workspace_bytes(int batch, int rows_per_seq, in
 TCE_API int tce_sample_verify_f16(const tce_sample_verify_call *call, void *stream);
 TCE_API int tce_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos_device, int pos_bound, int batch, int rows_per_seq, int ngram,
                             int32_t *row_token, int32_t *row_pos, void *stream);
+/* Log-probabilities on the device (csrc/sampling.hip; additive within ABI 113, no existing struct or entry point changes): of the token just sampled, and of given
+ * target tokens (scoring, perplexity).  ONE definition serves both:
+ *   logprob(row, t) = x_t - LSE(x),  LSE(x) = M + logf(sum_i expf(x_i - M)),  M = max_i x_i,  i < vocab,
+ * x = the row's RAW fp16 logits as lm_head wrote them, widened exactly to fp32; fp32 arithmetic.  It is the model's distribution: it does NOT depend on penalties,
+ * top-k, top-p, temperature, seed or slot -- a sampled token's value and a scored prompt token's value are comparable.  The sums are taken in one fixed order in
+ * every entry point (per 4096-logit chunk: 16 per thread in index order, a wave butterfly, waves 0 .. 3 in order; then the <= 256 chunk pairs (m_c, s_c) through a
+ * fixed tree), so a value does not depend on batch size, slot, or eager versus captured launches either.  For rows with every |x_i| <= 64 the result lies within
+ * 2^-16 of the float64 value.  Degenerate rows are defined: a NaN or +inf logit, or a row of -inf only, gives NaN; a chunk of -inf beside finite chunks takes no part.
+ * tce_logprob_out: out_logprob fp32 [batch][log_stride], indexed as out_log (value g of sequence b beside token g, written under the same bound); last_lse fp32
+ *   [batch], may be NULL: the LSE of the row the sequence's last token was drawn from; partials: tce_logprobs_workspace_bytes(rows, vocab) bytes, 8-byte aligned, need
+ *   not be zeroed (every word read in a call was written by that call's first launch), rows = batch, for the verifier batch * rows_per_seq.
+ * tce_sample_logprobs_f16: tce_sample_f16 -- token, log, ring, counters, position and debug record bit for bit -- plus the value; still two launches.
+ * tce_sample_verify_logprobs_f16: tce_sample_verify_f16 plus out_logprob[b][g + t] for every EMITTED y_t (rejected rows write nothing); still three launches.
+ * tce_logprobs_f16 (two launches; the kernel boundary is the only ordering): logits fp16 [rows][ld], target DEVICE int32 [rows]; out_logprob fp32 [rows]; out_lse fp32
+ *   [rows], may be NULL.  target -1 = "no target": out_logprob 0.0, the LSE still written; any other target outside [0, vocab): NaN.  rows <= 65535.
+ * Refusals, before any launch: tce_sample_f16's / tce_sample_verify_f16's own (alignment, ld % 8, vocab <= ld, vocab <= 2^20, ...), a NULL tce_logprob_out, out_logprob
+ * or partials (TCE_ERR_BAD_ARG), partials not 8-byte or a float array not 4-byte aligned (TCE_ERR_UNSUPPORTED_SHAPE). */
+typedef struct tce_logprob_out {
+    float *out_logprob;
+    float *last_lse;
+    void *partials;
+} tce_logprob_out;
+TCE_API size_t tce_logprobs_workspace_bytes(int rows, int vocab);
+TCE_API int tce_sample_logprobs_f16(const tce_sample_call *call, const tce_logprob_out *lp, void *stream);
+TCE_API int tce_sample_verify_logprobs_f16(const tce_sample_verify_call *call, const tce_logprob_out *lp, void *stream);
+TCE_API int tce_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, void *stream);
 /* The next step's input rows, one launch: row token[b] of an fp16 table [vocab][hidden] into out[b] ([batch][hidden]) for every active row (pos_device / pos_bound as
  * above; inactive rows are left as they are).  The reference looks an fp32 table up and rounds with float2half (Int4llamaDecoder: Embedding + float2half); a table
  * rounded once to fp16 gives the same bits.  A token outside [0, vocab) is not followed: the row is written as zeros and word 0 of `workspace` (tce_sample_f16's, or

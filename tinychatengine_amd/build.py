@@ -38,7 +38,8 @@ EXTRA_FLAGS: dict[str, list[str]] = {"w4a16_gemv_i8.hip": ["-mllvm", "-amdgpu-ke
 NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_kernel"],
                                         "w4a16_gemv_stream.hip": ["w4a16_gemv_token_kernel"],
                                         # the sampler's two kernels keep 16 / 32 64-bit numbers per thread in registers through ~50 counting rounds: in scratch every round would re-read them
-                                        "sampling.hip": ["sample_select_kernel", "sample_draw_kernel"],
+                                        # (every instantiation, the logprob forms included; the two scoring kernels hold the same 16 logits per thread)
+                                        "sampling.hip": ["sample_select_kernel", "sample_draw_kernel", "logprobs_partials_kernel", "logprobs_merge_kernel"],
                                         # the e4m3 forms of the paged step, the paged prefill (every block form) and the copies: a spilled piece of a tile or of the double
                                         # buffer would turn requests that are meant to be in flight together into load -> wait -> scratch store
                                         # (the e4m3 name is a prefix of its multi-row form's; the second name is the fp16 multi-row form: both keep the paged step's double buffer)

@@ -16,7 +16,15 @@
 //
 // The kernel boundary is the only ordering between the two: no counters, no flags, nothing to reset -- launch 200 of a workspace is launch 1.
 // A row whose position word is < 0 or > pos_bound is skipped by both kernels before it reads anything of the row.
+//
+// LOG-PROBABILITIES (tce_sample_logprobs_f16, tce_sample_verify_logprobs_f16, tce_logprobs_f16): logprob = x_t - LSE(x) on the RAW fp16 logits widened to fp32 -- the
+// model's distribution, whatever the penalties, top-k, top-p, temperature, seed or slot.  The LSE = true forms of the two kernels carry it along: the select launch
+// already holds the chunk's 16 logits per thread and stores the chunk's pair (m_c, s_c = sum expf(x_i - m_c)) before it patches the penalties in; the draw launch
+// merges the row's <= 256 pairs and subtracts.  The summation order is FIXED (chunk_lse_pair, merge_lse below), so a value does not depend on the batch, the slot or
+// the entry point: scoring (logprobs_partials_kernel -> logprobs_merge_kernel) calls the same two device functions.  The LSE = false forms are the code they were.
 #include "tce_common.hpp"
+
+#include <type_traits>
 
 namespace tce {
 
@@ -28,6 +36,7 @@ constexpr int kMaxK = 256;
 constexpr int kMergePerThread = 32;  // the draw launch holds chunks x k <= 256 x 32 survivors in registers
 
 typedef unsigned long long u64;
+typedef float float2_t __attribute__((ext_vector_type(2)));  // a chunk's (m_c, s_c): one 8-byte store / load
 
 // fp32 -> 32-bit integer with the same order (-0 and +0 are one value for the reference's comparisons: both map to +0's key).  0 is kept for "no element".
 __device__ __forceinline__ unsigned order_key(float x) {
@@ -60,12 +69,71 @@ __device__ __forceinline__ int block_total(int wave_count, int (*cnt)[4], int ro
     return cnt[round & 1][0] + cnt[round & 1][1] + cnt[round & 1][2] + cnt[round & 1][3];
 }
 
+// ---- log-sum-exp in two levels; every sum in one written-down order ----
+// The chunk's pair for x[16] = the thread's logits (index i0 + e) BEFORE any penalty: m_c = the maximum of the chunk's in-vocabulary values, s_c = sum expf(x_i - m_c).
+//   per thread   e = 0 .. 15 in index order, sequentially
+//   per wave     a butterfly: s += s of lane ^ 1, ^ 2, ^ 4, ^ 8, ^ 16, ^ 32 (fp32 addition commutes, so all 64 lanes hold the same bits)
+//   across waves ((w0 + w1) + w2) + w3
+// An entry past `vocab` and a -inf logit contribute exactly 0 and do not move the maximum, so a chunk of -inf only gives (-inf, 0).  A NaN logit is not a maximum
+// (fmaxf drops it) but its term is NaN; a +inf logit gives expf(inf - inf) = NaN: both make s_c, and with it the row's LSE, NaN.  Returned to every thread.
+__device__ __forceinline__ float2_t chunk_lse_pair(const float (&x)[16], int i0, int vocab, int wave, int lane) {
+    __shared__ float wave_max[4], wave_sum[4];
+    const float ninf = -__builtin_inff();
+    float m = ninf;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) m = fmaxf(m, i0 + e < vocab ? x[e] : ninf);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) m = fmaxf(m, __shfl_xor(m, off));
+    if (lane == 0) wave_max[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
+    float s = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s += (i0 + e < vocab && x[e] != ninf) ? expf(x[e] - m) : 0.0f;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
+    if (lane == 0) wave_sum[wave] = s;
+    __syncthreads();
+    float2_t pair;
+    pair.x = m;
+    pair.y = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+    return pair;
+}
+
+// The row's LSE from its nchunks (<= 256 = kThreads) pairs: thread c < nchunks holds pair c; M = the workgroup's maximum of m_c; the term of pair c is
+// s_c * expf(m_c - M), exactly 0 where s_c == 0 (a chunk of -inf; also where the whole row is -inf and m_c - M would be inf - inf); S = the terms through a FIXED tree --
+// the wave butterfly above (6 levels), then (w0 + w1) + (w2 + w3) --, never a sequential sum over the chunks; lse = M + logf(S).  A row of -inf only: -inf + logf(0) =
+// -inf, and x_t - lse = NaN.  Returned to every thread.
+__device__ __forceinline__ float merge_lse(const float2_t *pairs, int nchunks, int tid, int wave, int lane) {
+    __shared__ float merge_max[4], merge_sum[4];
+    const float ninf = -__builtin_inff();
+    float2_t p;
+    p.x = ninf;
+    p.y = 0.0f;
+    if (tid < nchunks) p = pairs[tid];
+    float M = p.x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
+    if (lane == 0) merge_max[wave] = M;
+    __syncthreads();
+    M = fmaxf(fmaxf(merge_max[0], merge_max[1]), fmaxf(merge_max[2], merge_max[3]));
+    float S = p.y == 0.0f ? 0.0f : p.y * expf(p.x - M);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) S += __shfl_xor(S, off);
+    if (lane == 0) merge_sum[wave] = S;
+    __syncthreads();
+    S = (merge_sum[0] + merge_sum[1]) + (merge_sum[2] + merge_sum[3]);
+    return M + logf(S);
+}
+
 // SPEC (tce_sample_verify_f16): blockIdx.y is a VIRTUAL row y = seq * RT + t -- logits row, position word (row_pos) and survivors are y's, the sampling row is seq's.
 // Row t is only ever used when drafts 1 .. t were all accepted, so the window it must be sampled with is known now: the ring as it stands with row_token[(seq, 1)] ..
 // row_token[(seq, t)] pushed behind it.
-template <bool SPEC>
+// LSE: the chunk's pair of the RAW logits goes to partials[row][chunk] (one 8-byte store) before the penalties are patched in.
+template <bool SPEC, bool LSE>
 __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *logits, int ld, int vocab, const tce_sample_row *rows, const int32_t *pos, int pos_bound,
-                                                                  int kbound, uint2_t *entries, int nchunks, int RT, const int32_t *row_token) {
+                                                                  int kbound, uint2_t *entries, int nchunks, int RT, const int32_t *row_token,
+                                                                  [[maybe_unused]] float2_t *partials) {
     const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(pos, b, pos_bound)) return;
     [[maybe_unused]] const int seq = SPEC ? b / RT : b, vt = SPEC ? b - seq * RT : 0;
@@ -86,6 +154,10 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
         if (i0 + 8 * h < vocab) v = *reinterpret_cast<const half8_t *>(row + i0 + 8 * h);  // (a piece across `vocab` stays inside the row: vocab <= ld, ld % 8 == 0)
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[8 * h + j] = (float)v[j];
+    }
+    if constexpr (LSE) {
+        const float2_t pair = chunk_lse_pair(x, i0, vocab, wave, lane);
+        if (tid == 0) partials[(size_t)b * nchunks + c] = pair;
     }
 
     // ---- penalties: window slot t < nwin is the t-th most recent token of the ring; the first occurrence of an id that lies in this chunk patches its logit ----
@@ -196,6 +268,16 @@ struct DrawArgs {
     int n_stop;
 };
 
+// the LSE = true forms' arguments: a struct of their own (DrawArgs first), so the LSE = false instantiations keep their argument layout
+struct DrawLseArgs : DrawArgs {
+    const half_t *logits;     // the rows the select launch read: [rows][ld]
+    int ld, vocab;
+    const float2_t *partials; // [rows][nchunks]
+    float *out_logprob;       // [batch][log_stride] (the plain form; the chain launch writes it in the SPEC form)
+    float *last_lse;          // [batch] or null (as out_logprob)
+    float *cand_logprob, *cand_lse;  // SPEC: [batch * T] beside cand
+};
+
 // tce_sample_verify_f16's second and third launch: DrawArgs (pos = the SEQUENCES' position words) and the per-virtual-row arrays
 struct VerifyArgs {
     DrawArgs d;
@@ -206,10 +288,13 @@ struct VerifyArgs {
 };
 
 // SPEC: blockIdx.x is a virtual row y = seq * RT + t (a.pos = row_pos): the draw of token generated + t of the sequence, into cand[y]; no state is written
-template <bool SPEC>
-__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
+// LSE: the row's log-sum-exp from the select launch's pairs (merge_lse); logprob = the RAW logit of the token drawn - lse, written beside the token.
+template <bool SPEC, bool LSE>
+__global__ __launch_bounds__(kThreads) void sample_draw_kernel(std::conditional_t<LSE, DrawLseArgs, DrawArgs> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(a.pos, b, a.pos_bound)) return;
+    [[maybe_unused]] float lse = 0.0f;
+    if constexpr (LSE) lse = merge_lse(a.partials + (size_t)b * a.nchunks, a.nchunks, tid, wave, lane);
     [[maybe_unused]] const int seq = SPEC ? b / RT : b, vt = SPEC ? b - seq * RT : 0;
     __shared__ u64 sel[kMaxK];
     __shared__ float lg[kMaxK + 8], ex[kMaxK + 8], pr[kMaxK + 8], fp[kMaxK + 8];
@@ -324,14 +409,31 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a, [[may
         }
     }
     // ---- the tail: the token, the log, the ring, the counters, the position ----
+    [[maybe_unused]] float lp = 0.0f;
+    if constexpr (LSE) {  // (ids[] holds vocabulary indices only; the test keeps the read inside the row whatever happens)
+        if (tid == 0) {
+            const int tok = ids[choice];
+            lp = tok >= 0 && tok < a.vocab ? (float)a.logits[(size_t)b * a.ld + tok] - lse : __builtin_nanf("");
+        }
+    }
     if constexpr (SPEC) {
-        if (tid == 0) cand[b] = ids[choice];
+        if (tid == 0) {
+            cand[b] = ids[choice];
+            if constexpr (LSE) {
+                a.cand_logprob[b] = lp;
+                a.cand_lse[b] = lse;
+            }
+        }
         return;
     }
     if (tid == 0) {
         const int tok = ids[choice];
         a.next_token[b] = tok;
         if (gen < (unsigned)a.log_stride) a.out_log[(size_t)b * a.log_stride + gen] = tok;
+        if constexpr (LSE) {
+            if (gen < (unsigned)a.log_stride) a.out_logprob[(size_t)b * a.log_stride + gen] = lp;
+            if (a.last_lse) a.last_lse[b] = lse;
+        }
         r.ring[r.ring_pushed & 63u] = tok;
         r.ring_pushed = r.ring_pushed + 1u;
         r.generated = gen + 1u;
@@ -342,7 +444,14 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgs a, [[may
 }
 
 // tce_sample_verify_f16's last launch: thread = sequence.  Walks the chain of candidates and writes state exactly as sample_draw_kernel's tail does, once per emitted token.
-__global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgs a) {
+// LSE: where y_t is emitted, out_logprob[b][g + t] = cand_logprob[y] (under out_log's bound); last_lse[b] = the last emitted row's; rejected rows write nothing.
+struct VerifyLseArgs : VerifyArgs {
+    const float *cand_logprob, *cand_lse;
+    float *out_logprob, *last_lse;
+};
+
+template <bool LSE>
+__global__ __launch_bounds__(64) void sample_verify_chain_kernel(std::conditional_t<LSE, VerifyLseArgs, VerifyArgs> a) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.batch) return;
     if (!row_active(a.d.pos, b, a.d.pos_bound)) {
@@ -359,6 +468,9 @@ __global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgs a) {
     for (; t < n; ++t) {
         tok = a.cand[y0 + t];
         if (g + t < (unsigned)a.d.log_stride) a.d.out_log[(size_t)b * a.d.log_stride + g + t] = tok;
+        if constexpr (LSE) {
+            if (g + t < (unsigned)a.d.log_stride) a.out_logprob[(size_t)b * a.d.log_stride + g + t] = a.cand_logprob[y0 + t];
+        }
         r.ring[pushed & 63u] = tok;
         ++pushed;
         if (p + 1 + t < a.hist_stride) a.history[(size_t)b * a.hist_stride + p + 1 + t] = tok;
@@ -380,6 +492,9 @@ __global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgs a) {
         r.ring_pushed = pushed;
         r.generated = g + (unsigned)t;
         a.d.pos[b] = newpos;
+        if constexpr (LSE) {
+            if (a.last_lse) a.last_lse[b] = a.cand_lse[y0 + t - 1];
+        }
     }
     a.emitted[b] = t;
 }
@@ -436,6 +551,35 @@ __global__ __launch_bounds__(kThreads) void draft_ngram_kernel(const int32_t *hi
     }
 }
 
+// tce_logprobs_f16 (scoring), first launch: grid (chunks, rows); sample_select_kernel's loads, the same chunk_lse_pair
+__global__ __launch_bounds__(kThreads) void logprobs_partials_kernel(const half_t *logits, int ld, int vocab, int nchunks, float2_t *partials) {
+    const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const half_t *row = logits + (size_t)b * ld;
+    const int i0 = c * kChunk + tid * 16;
+    float x[16];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        half8_t v = {};
+        if (i0 + 8 * h < vocab) v = *reinterpret_cast<const half8_t *>(row + i0 + 8 * h);  // (a piece across `vocab` stays inside the row: vocab <= ld, ld % 8 == 0)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[8 * h + j] = (float)v[j];
+    }
+    const float2_t pair = chunk_lse_pair(x, i0, vocab, wave, lane);
+    if (tid == 0) partials[(size_t)b * nchunks + c] = pair;
+}
+
+// second launch: grid (rows); sample_draw_kernel<., true>'s merge, then the target's raw logit.  target -1: "no target" (0.0); any other id outside the vocabulary: NaN
+__global__ __launch_bounds__(kThreads) void logprobs_merge_kernel(const half_t *logits, int ld, int vocab, int nchunks, const float2_t *partials, const int32_t *target,
+                                                                   float *out_logprob, float *out_lse) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float lse = merge_lse(partials + (size_t)b * nchunks, nchunks, tid, wave, lane);
+    if (tid == 0) {
+        const int t = target[b];
+        out_logprob[b] = t == -1 ? 0.0f : (t >= 0 && t < vocab ? (float)logits[(size_t)b * ld + t] - lse : __builtin_nanf(""));
+        if (out_lse) out_lse[b] = lse;
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void embed_rows_kernel(const uint4_t *table, int vocab, int pieces, const int32_t *token, uint4_t *out, const int32_t *pos, int pos_bound,
                                                                unsigned *violations) {
     const int b = blockIdx.x;
@@ -456,11 +600,24 @@ size_t sample_workspace_bytes(int batch, int vocab) {
     return 256 + (size_t)batch * sample_chunks(vocab) * kMaxK * sizeof(uint2_t);  // 256 bytes of counters (word 0: tce_embed_rows_f16's refused ids), then the survivors
 }
 
-int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *hip_err) {
+// the logprob workspace: the pairs [rows][chunks], then the verifier's cand_logprob and cand_lse [rows] each
+static size_t logprobs_cand_offset(int rows, int vocab) { return (size_t)rows * sample_chunks(vocab) * sizeof(float2_t); }
+
+size_t logprobs_workspace_bytes(int rows, int vocab) {
+    if (rows < 1 || vocab < 1) return 0;
+    return (logprobs_cand_offset(rows, vocab) + (size_t)rows * 2 * sizeof(float) + 255) & ~(size_t)255;
+}
+
+// lp == null: tce_sample_f16, the launches they were
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err) {
     const int nchunks = sample_chunks(c.vocab);
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
-    hipLaunchKernelGGL(sample_select_kernel<false>, dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows, c.pos_device,
-                       c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr));
+    if (lp)
+        hipLaunchKernelGGL((sample_select_kernel<false, true>), dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
+                           c.pos_device, c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr), static_cast<float2_t *>(lp->partials));
+    else
+        hipLaunchKernelGGL((sample_select_kernel<false, false>), dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
+                           c.pos_device, c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr), static_cast<float2_t *>(nullptr));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         DrawArgs a;
@@ -477,7 +634,20 @@ int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *
         a.debug = c.debug;
         for (int i = 0; i < 4; ++i) a.stop_ids[i] = c.stop_ids[i];
         a.n_stop = c.n_stop;
-        hipLaunchKernelGGL(sample_draw_kernel<false>, dim3(c.batch), dim3(kThreads), 0, stream, a, 1, static_cast<int32_t *>(nullptr));
+        if (lp) {
+            DrawLseArgs la;
+            static_cast<DrawArgs &>(la) = a;
+            la.logits = static_cast<const half_t *>(c.logits);
+            la.ld = c.ld;
+            la.vocab = c.vocab;
+            la.partials = static_cast<const float2_t *>(lp->partials);
+            la.out_logprob = lp->out_logprob;
+            la.last_lse = lp->last_lse;
+            la.cand_logprob = la.cand_lse = nullptr;
+            hipLaunchKernelGGL((sample_draw_kernel<false, true>), dim3(c.batch), dim3(kThreads), 0, stream, la, 1, static_cast<int32_t *>(nullptr));
+        } else {
+            hipLaunchKernelGGL((sample_draw_kernel<false, false>), dim3(c.batch), dim3(kThreads), 0, stream, a, 1, static_cast<int32_t *>(nullptr));
+        }
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
@@ -495,7 +665,7 @@ size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
     return verify_cand_offset(batch, rows_per_seq, vocab) + (((size_t)batch * rows_per_seq * 4 + 255) & ~(size_t)255);
 }
 
-int launch_sample_verify_f16(const tce_sample_verify_call &v, hipStream_t stream, hipError_t *hip_err) {
+int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err) {
     const tce_sample_call &c = v.s;
     const int nchunks = sample_chunks(c.vocab), T = v.rows_per_seq, vrows = c.batch * T;
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
@@ -521,16 +691,64 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, hipStream_t stream
     a.cand = reinterpret_cast<int32_t *>(static_cast<char *>(c.workspace) + verify_cand_offset(c.batch, T, c.vocab));
     a.history = v.history;
     a.emitted = v.emitted;
-    hipLaunchKernelGGL(sample_select_kernel<true>, dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows, v.row_pos,
-                       c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token);
+    VerifyLseArgs la;
+    DrawLseArgs ld;
+    if (lp) {
+        float *cl = reinterpret_cast<float *>(static_cast<char *>(lp->partials) + logprobs_cand_offset(vrows, c.vocab));
+        ld.logits = static_cast<const half_t *>(c.logits);
+        ld.ld = c.ld;
+        ld.vocab = c.vocab;
+        ld.partials = static_cast<const float2_t *>(lp->partials);
+        ld.out_logprob = nullptr;  // (the chain launch writes them)
+        ld.last_lse = nullptr;
+        ld.cand_logprob = cl;
+        ld.cand_lse = cl + vrows;
+        la.cand_logprob = cl;
+        la.cand_lse = cl + vrows;
+        la.out_logprob = lp->out_logprob;
+        la.last_lse = lp->last_lse;
+        hipLaunchKernelGGL((sample_select_kernel<true, true>), dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
+                           v.row_pos, c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token, static_cast<float2_t *>(lp->partials));
+    } else {
+        hipLaunchKernelGGL((sample_select_kernel<true, false>), dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
+                           v.row_pos, c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token, static_cast<float2_t *>(nullptr));
+    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(sample_draw_kernel<true>, dim3(vrows), dim3(kThreads), 0, stream, a.d, T, a.cand);
+        if (lp) {
+            static_cast<DrawArgs &>(ld) = a.d;
+            hipLaunchKernelGGL((sample_draw_kernel<true, true>), dim3(vrows), dim3(kThreads), 0, stream, ld, T, a.cand);
+        } else {
+            hipLaunchKernelGGL((sample_draw_kernel<true, false>), dim3(vrows), dim3(kThreads), 0, stream, a.d, T, a.cand);
+        }
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
         a.d.pos = c.pos_device;
-        hipLaunchKernelGGL(sample_verify_chain_kernel, dim3((c.batch + 63) / 64), dim3(64), 0, stream, a);
+        if (lp) {
+            static_cast<VerifyArgs &>(la) = a;
+            hipLaunchKernelGGL(sample_verify_chain_kernel<true>, dim3((c.batch + 63) / 64), dim3(64), 0, stream, la);
+        } else {
+            hipLaunchKernelGGL(sample_verify_chain_kernel<false>, dim3((c.batch + 63) / 64), dim3(64), 0, stream, a);
+        }
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, hipStream_t stream,
+                        hipError_t *hip_err) {
+    const int nchunks = sample_chunks(vocab);
+    hipLaunchKernelGGL(logprobs_partials_kernel, dim3(nchunks, rows), dim3(kThreads), 0, stream, static_cast<const half_t *>(logits), ld, vocab, nchunks,
+                       static_cast<float2_t *>(partials));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(logprobs_merge_kernel, dim3(rows), dim3(kThreads), 0, stream, static_cast<const half_t *>(logits), ld, vocab, nchunks,
+                           static_cast<const float2_t *>(partials), target, out_logprob, out_lse);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {

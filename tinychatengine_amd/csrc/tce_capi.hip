@@ -21,11 +21,14 @@ size_t w8a8_scratch_bytes();
 void set_w8a8_xsplit(int xs);
 int sample_chunks(int vocab);
 size_t sample_workspace_bytes(int batch, int vocab);
-int launch_sample_f16(const tce_sample_call &c, hipStream_t stream, hipError_t *hip_err);
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err);
+size_t logprobs_workspace_bytes(int rows, int vocab);
+int launch_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, hipStream_t stream,
+                        hipError_t *hip_err);
 int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos, int pos_bound, void *workspace,
                           hipStream_t stream, hipError_t *hip_err);
 size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
-int launch_sample_verify_f16(const tce_sample_verify_call &v, hipStream_t stream, hipError_t *hip_err);
+int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err);
 int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
                        int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err);
 }
@@ -1459,8 +1462,43 @@ static int check_sample_call(const char *who, const tce_sample_call *c, long lon
 int tce_sample_f16(const tce_sample_call *c, void *stream) {
     if (const int rc = check_sample_call("tce_sample_f16", c, c ? c->batch : 0)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_sample_f16(*c, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_sample_f16(*c, nullptr, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+size_t tce_logprobs_workspace_bytes(int rows, int vocab) { return rows < 1 || rows > 65535 || vocab < 1 || vocab > (1 << 20) ? 0 : tce::logprobs_workspace_bytes(rows, vocab); }
+
+// the logprob forms' own refusals (after the sampling call's)
+static int check_logprob_out(const char *who, const tce_logprob_out *lp) {
+    if (!lp) return fail(TCE_ERR_BAD_ARG, "%s: null tce_logprob_out", who);
+    if (!lp->out_logprob || !lp->partials) return fail(TCE_ERR_BAD_ARG, "%s: null pointer (out_logprob, partials)", who);
+    if (reinterpret_cast<uintptr_t>(lp->partials) % 8 != 0 || (reinterpret_cast<uintptr_t>(lp->out_logprob) | reinterpret_cast<uintptr_t>(lp->last_lse)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: partials 8-byte aligned, out_logprob / last_lse 4-byte aligned", who);
+    return TCE_OK;
+}
+
+int tce_sample_logprobs_f16(const tce_sample_call *c, const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_logprobs_f16";
+    if (const int rc = check_sample_call(who, c, c ? c->batch : 0)) return rc;
+    if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_f16(*c, lp, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+int tce_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, void *stream) {
+    static const char *who = "tce_logprobs_f16";
+    if (!logits || !target || !out_logprob || !partials) return fail(TCE_ERR_BAD_ARG, "%s: null pointer (logits, target, out_logprob, partials)", who);
+    if (rows < 1 || vocab < 1) return fail(TCE_ERR_BAD_ARG, "%s: need rows, vocab >= 1", who);
+    if (vocab > ld) return fail(TCE_ERR_BAD_ARG, "%s: vocab %d > ld %d", who, vocab, ld);
+    if (rows > 65535 || vocab > (1 << 20)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: at most 65535 rows and vocab <= 2^20", who);
+    if (ld % 8 != 0 || reinterpret_cast<uintptr_t>(logits) % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: logits 16-byte aligned with ld %% 8 == 0", who);
+    if (reinterpret_cast<uintptr_t>(partials) % 8 != 0 ||
+        (reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(out_logprob) | reinterpret_cast<uintptr_t>(out_lse)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: partials 8-byte aligned, target / out_logprob / out_lse 4-byte aligned", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_logprobs_f16(logits, ld, vocab, rows, target, out_logprob, out_lse, partials, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "logprobs launch") : rc;
 }
 
 size_t tce_sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
@@ -1468,8 +1506,7 @@ size_t tce_sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab)
     return tce::sample_verify_workspace_bytes(batch, rows_per_seq, vocab);
 }
 
-int tce_sample_verify_f16(const tce_sample_verify_call *v, void *stream) {
-    static const char *who = "tce_sample_verify_f16";
+static int check_verify_call(const char *who, const tce_sample_verify_call *v) {
     if (!v) return fail(TCE_ERR_BAD_ARG, "%s: null call", who);
     if (v->rows_per_seq < 1 || v->rows_per_seq > TCE_SPEC_MAX_ROWS)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, v->rows_per_seq, TCE_SPEC_MAX_ROWS);
@@ -1478,8 +1515,22 @@ int tce_sample_verify_f16(const tce_sample_verify_call *v, void *stream) {
     if (v->hist_stride <= v->s.pos_bound) return fail(TCE_ERR_BAD_ARG, "%s: hist_stride %d <= pos_bound %d", who, v->hist_stride, v->s.pos_bound);
     if ((reinterpret_cast<uintptr_t>(v->row_token) | reinterpret_cast<uintptr_t>(v->row_pos) | reinterpret_cast<uintptr_t>(v->history) | reinterpret_cast<uintptr_t>(v->emitted)) % 4 != 0)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: int32-aligned row_token / row_pos / history / emitted", who);
+    return TCE_OK;
+}
+
+int tce_sample_verify_f16(const tce_sample_verify_call *v, void *stream) {
+    if (const int rc = check_verify_call("tce_sample_verify_f16", v)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_sample_verify_f16(*v, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_sample_verify_f16(*v, nullptr, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
+}
+
+int tce_sample_verify_logprobs_f16(const tce_sample_verify_call *v, const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_verify_logprobs_f16";
+    if (const int rc = check_verify_call(who, v)) return rc;
+    if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_verify_f16(*v, lp, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
 }
 

@@ -7,15 +7,19 @@ The batched / paged decoders (batch_decode.py, paged_kv.py) run a "step" = the l
     1        tce_rmsnorm_half        the final norm, B rows
     1        tce_w4a16_forward       lm_head at M = B -> logits fp16 [B][vocab]
     2        tce_sample_f16          penalties, top-k, softmax, top-p, temperature, draw; token -> next_token, log, ring; pos += 1 or -1 (retired)
+                                     (logprobs=True: tce_sample_logprobs_f16, the same two launches, which also write the token's log-probability)
 
 7 L + 5 launches, captured once in one torch.cuda.graph: ONE REPLAY IS ONE TOKEN for all B sequences, with no host round trip.  Everything a replay needs lives
 on the device (positions, sampling parameters, recent-token rings, generator counters, output logs), so a slot changes hands without recapture.
 
     sample_reference      the sampling chain restated in numpy (fp32 throughout, sequential sums, the ordering rule): the CPU-side yardstick of tce_sample_f16
     philox4x32_10, uniform   the counter-based generator restated in numpy; the device matches it bit for bit
+    logprob_reference     logprob = x_t - LSE(x) on the raw fp16 logits, in float64: the yardstick of the device's log-probabilities
     Sampler               the per-row device state + workspace; step(logits, pos_device, pos_bound)
+    score_plan            score()'s host bookkeeping: slots, reservations, packed tokens and targets, row chunks.  No device, no launch.
     SlotBook              host bookkeeping of live slots (positions, budgets): which pages run(n) must reserve.  No device, no launch.
-    BatchedGenerator      admit / run / tokens / release over a list of PagedBatchedDecoder (one PageAllocator) or BatchedDecoder
+    BatchedGenerator      admit / run / tokens / logprobs / release over a list of PagedBatchedDecoder (one PageAllocator) or BatchedDecoder; score(prompts): the
+                          log-probability of every prompt token given the tokens before it (perplexity), with no logits leaving the device
     HostDrivenLoop        the same decoders driven from the host -- logits copied back, numpy argmax, the row looked up and copied over: what a caller had to do
                           before this module, kept as the yardstick for tests and scripts/generate_time.py
 
@@ -157,6 +161,28 @@ def sample_reference(logits_f16_row: np.ndarray, recent, params: SamplingParams,
     return {"ids": ids, "logits": l, "p": p, "n": n, "final_p": fp, "choice": choice, "token": int(ids[choice])}
 
 
+def logprob_reference(logits_f16_row: np.ndarray, target: int) -> float:
+    """logprob = x_t - LSE(x) over the row's RAW fp16 logits (no penalties, no truncation, no temperature: the model's distribution), LSE(x) = M + log sum exp(x_i - M),
+    in float64.  The device's degenerate rows: a NaN or +inf logit, or a row of -inf only, gives NaN.  target -1 ("no target"): 0.0; any other id outside the row: NaN."""
+    assert logits_f16_row.dtype == np.float16 and logits_f16_row.ndim == 1 and logits_f16_row.size >= 1
+    target = int(target)
+    if target == -1:
+        return 0.0
+    if not 0 <= target < logits_f16_row.size:
+        return float("nan")
+    x = logits_f16_row.astype(np.float64)
+    m = x.max() if not np.isnan(x).any() else np.nan
+    if not np.isfinite(m):  # NaN, +inf, or every entry -inf
+        return float("nan")
+    return float(x[target] - (m + np.log(np.exp(x - m).sum())))
+
+
+def perplexity(values) -> float:
+    """exp(-mean logprob) over the values of one or several score() results."""
+    v = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in values]) if isinstance(values, (list, tuple)) else np.asarray(values, np.float64).reshape(-1)
+    return float(np.exp(-v.mean()))
+
+
 def ring_window(ring: np.ndarray, pushed: int, repeat_last_n: int) -> np.ndarray:
     """The penalty window of a ring [64] after `pushed` pushes: its last repeat_last_n entries (zeros where fewer tokens have been pushed)."""
     n = min(max(int(repeat_last_n), 0), RING)
@@ -184,10 +210,12 @@ def make_row(params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> 
 
 class Sampler:
     """The per-row device state of tce_sample_f16 for `batch` rows: rows (parameters, ring, counters), next_token, the output log [batch][log_stride], the workspace
-    (zeroed once).  debug=True keeps the sorted candidates of the last call (tests)."""
+    (zeroed once).  debug=True keeps the sorted candidates of the last call (tests).  logprobs=True: step() calls tce_sample_logprobs_f16 -- the same two launches --
+    and out_logprob fp32 [batch][log_stride] holds, beside every token of out_log, its log-probability under the raw logits (NaN where nothing was written yet); last_lse
+    [batch] the log-sum-exp of the row each slot's last token was drawn from.  logprobs=False: the call, the launches and a captured graph are what they were."""
 
     def __init__(self, batch: int, vocab: int, log_stride: int, device, top_k_bound: int = 40, stop_ids=(), debug: bool = False, tfs_z: float = 1.0,
-                 typical_p: float = 1.0, mirostat: int = 0):
+                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False):
         import torch
         if len(stop_ids) > 4:
             raise ValueError("at most 4 stop ids")
@@ -202,6 +230,16 @@ class Sampler:
         self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)
         self.uniform_override = None  # fp32 [batch] on the device: replaces the generator (tests)
         self.debug = torch.zeros((batch, _DEBUG_WORDS), dtype=torch.int32, device=device) if debug else None
+        self.logprobs = bool(logprobs)
+        self.out_logprob = self.last_lse = self.partials = None
+        if self.logprobs:
+            self.out_logprob = torch.full((batch, self.log_stride), float("nan"), dtype=torch.float32, device=device)
+            self.last_lse = torch.full((batch,), float("nan"), dtype=torch.float32, device=device)
+            self.partials = torch.empty(int(capi.lib().tce_logprobs_workspace_bytes(batch, vocab)), dtype=torch.uint8, device=device)  # (need not be zeroed)
+
+    def logprob_out(self, partials=None) -> capi.LogprobOut:
+        """struct tce_logprob_out over this sampler's arrays (partials: another workspace -- the verifier's, for batch * rows_per_seq rows)."""
+        return capi.LogprobOut(out_logprob=self.out_logprob.data_ptr(), last_lse=self.last_lse.data_ptr(), partials=(self.partials if partials is None else partials).data_ptr())
 
     def set_row(self, slot: int, params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> None:
         """The slot changes hands: one stream-ordered copy of its row (parameters, a fresh ring with the prompt pushed, counters at zero)."""
@@ -220,7 +258,11 @@ class Sampler:
         assert logits.dtype == torch.float16 and logits.is_contiguous() and logits.dim() == 2 and logits.shape[0] == self.batch and logits.shape[1] >= self.vocab
         assert pos_device.dtype == torch.int32 and pos_device.is_contiguous() and pos_device.numel() == self.batch
         assert logits.is_cuda and pos_device.is_cuda
-        capi.check(capi.sample_f16(self.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound), _stream()))
+        c = self.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound)
+        if self.logprobs:
+            capi.check(capi.sample_logprobs_f16(c, self.logprob_out(), _stream()))
+        else:
+            capi.check(capi.sample_f16(c, _stream()))
 
     def call(self, logits_ptr: int, ld: int, pos_ptr: int, pos_bound: int) -> capi.SampleCall:
         c = capi.SampleCall(logits=logits_ptr, ld=ld, vocab=self.vocab, batch=self.batch, top_k_bound=self.top_k_bound, rows=self.rows.data_ptr(), pos_device=pos_ptr,
@@ -310,6 +352,39 @@ class SlotBook:
         self.pos[slot], self.generated[slot], self.max_new[slot] = -1, 0, 0
 
 
+def score_plan(prompts, free_slots, max_keys: int, vocab: int, chunk_rows: int = 256) -> dict:
+    """BatchedGenerator.score's bookkeeping (host only): which prompts need rows ("work": those of >= 2 tokens), the free slot each takes, the pages to reserve
+    [(slot, last key index)], the packed token row and its targets (the next token; -1 for a prompt's last row), the row chunks [(row0, rows)] of at most
+    chunk_rows rows, and split(values [total rows]) -> one fp32 array of n - 1 values per prompt (empty for a 1-token prompt)."""
+    if int(chunk_rows) < 1:
+        raise ValueError("score: chunk_rows >= 1")
+    prompts = [[int(t) for t in ids] for ids in prompts]
+    for ids in prompts:
+        if not 1 <= len(ids) <= max_keys:
+            raise ValueError(f"a prompt of 1 .. {max_keys} tokens")
+        if any(not 0 <= t < vocab for t in ids):
+            raise ValueError("a prompt token lies outside the vocabulary")
+    work = [i for i, ids in enumerate(prompts) if len(ids) >= 2]
+    free_slots = list(free_slots)
+    if len(work) > min(len(free_slots), capi.TCE_PREFILL_MAX_SEGMENTS):
+        raise ValueError(f"score: {len(work)} prompts, {len(free_slots)} free slots (at most {capi.TCE_PREFILL_MAX_SEGMENTS} per call)")
+    slots = free_slots[:len(work)]
+    total = sum(len(prompts[i]) for i in work)
+    chunk = max(1, min(int(chunk_rows), total))
+
+    def split(values) -> list:
+        out, r0 = [np.zeros(0, np.float32) for _ in prompts], 0
+        for i in work:
+            n = len(prompts[i])
+            out[i] = np.asarray(values[r0:r0 + n - 1], np.float32).copy()
+            r0 += n
+        return out
+
+    return {"prompts": prompts, "work": work, "slots": slots, "reserve": [(s, len(prompts[i]) - 1) for s, i in zip(slots, work)],
+            "tokens": [t for i in work for t in prompts[i]], "targets": [t for i in work for t in prompts[i][1:] + [-1]], "chunk": chunk,
+            "chunks": [(r0, min(chunk, total - r0)) for r0 in range(0, total, chunk)], "split": split}
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the front
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -319,7 +394,7 @@ class BatchedGenerator:
     inactive) and run() replays it."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
-                 debug: bool = False):
+                 debug: bool = False, logprobs: bool = False):
         import torch
         self.decoders = list(decoders)
         d0 = self.decoders[0]
@@ -334,7 +409,9 @@ class BatchedGenerator:
         assert embed_table.dtype == torch.float16 and embed_table.shape[1] == self.hidden_size and lm_head.in_features == self.hidden_size and lm_head.out_features >= self.vocab
         dev = embed_table.device
         self.device = dev
-        self.sampler = Sampler(self.batch, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, debug=debug)
+        self.sampler = Sampler(self.batch, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, debug=debug, logprobs=logprobs)
+        self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
+        self.score_logits: list = []
         self.book = SlotBook(self.batch, self.max_keys)
         self.pos = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
         self.hidden = torch.zeros((self.batch, self.hidden_size), dtype=torch.float16, device=dev)
@@ -405,6 +482,8 @@ class BatchedGenerator:
         for (s, ids, p, sd, mn), r in zip(adm, rows):
             self.sampler.set_row(s, p, sd, mn, ids)
             self.sampler.out_log[s].fill_(-1)
+            if self.sampler.logprobs:
+                self.sampler.out_logprob[s].fill_(float("nan"))
             self._adm_hidden[s].copy_(r[-1])
             self._adm_pos[s] = len(ids) - 1
         self._head(self._adm_hidden, self._adm_pos)  # the first token: the sampler leaves len(ids) -- or -1 -- in the admitted slots' words
@@ -437,11 +516,69 @@ class BatchedGenerator:
         n = int(self.sampler.generated()[slot])
         return self.sampler.out_log[slot, :n].cpu().numpy().tolist()
 
+    def logprobs(self, slot: int) -> np.ndarray:
+        """fp32, one value per token of tokens(slot): the token's log-probability under the raw logits it was drawn from (logprob_reference's definition; the token
+        sampled at admission included).  Needs logprobs=True."""
+        if not self.sampler.logprobs:
+            raise ValueError("logprobs: the generator was built without logprobs=True")
+        n = int(self.sampler.generated()[slot])
+        return self.sampler.out_logprob[slot, :n].cpu().numpy()
+
     def release(self, slot: int) -> list[int]:
         """The slot is free again: its position word is -1 and (paged) its pages go back to the pool; returns them."""
         self.pos[slot] = -1
         self.book.clear(slot)
         return self.allocator.release(slot) if self.allocator is not None else []
+
+    # ---- scoring ----
+    def free_slots(self) -> list[int]:
+        """Slots that are neither live nor still holding pages."""
+        return [s for s in range(self.batch) if self.book.pos[s] < 0 and not (self.allocator is not None and self.allocator.pages[s])]
+
+    def score(self, prompts, chunk_rows: int = 256) -> list[np.ndarray]:
+        """For each prompt of n tokens the n - 1 values logprob(token[i + 1] | token[.. i]) (fp32; empty for a 1-token prompt), logprob_reference's definition on the
+        logits this call produces.  The prompts take free slots and pages, all or nothing (PagePoolExhausted, or ValueError when there are fewer free slots than
+        prompts: nothing changed), are embedded and run through every layer by ONE prefill_many; then, in chunks of at most chunk_rows rows: final norm -> lm_head at
+        M = chunk -> tce_logprobs_f16 with the next tokens as targets (-1 for a prompt's last row), so at most chunk_rows * ld * 2 bytes of logits exist and none leave
+        the device.  Slots and pages are released afterwards; ONE synchronise.  Live sequences are not disturbed.  Paged decoders only (fp16 or fp8_e4m3 pages)."""
+        import torch
+        from .linear import _stream, rmsnorm_half
+        if self.allocator is None:
+            raise ValueError("score: paged decoders only")
+        plan = score_plan(prompts, self.free_slots(), self.max_keys, self.vocab, chunk_rows)
+        prompts, work, slots = plan["prompts"], plan["work"], plan["slots"]
+        if not work:
+            return plan["split"](np.zeros(0, np.float32))
+        self.allocator.reserve_many(plan["reserve"])  # all or nothing, before anything changes
+        try:
+            tok = torch.tensor(plan["tokens"], dtype=torch.int32).to(self.device)
+            target = torch.tensor(plan["targets"], dtype=torch.int32).to(self.device)
+            total = tok.numel()
+            hidden = torch.empty((total, self.hidden_size), dtype=torch.float16, device=self.device)
+            embed_rows(self.embed_table, tok, hidden, torch.zeros(total, dtype=torch.int32, device=self.device), 0, self.sampler.workspace)
+            rows, r0 = [], 0
+            for i in work:
+                rows.append(hidden[r0:r0 + len(prompts[i])])
+                r0 += len(prompts[i])
+            for d in self.decoders:
+                d.prefill_many([(s, r, 0) for s, r in zip(slots, rows)])
+            chunk = plan["chunk"]
+            ld = self.lm_head.out_features
+            xn = torch.empty((chunk, self.hidden_size), dtype=torch.float16, device=self.device)
+            logits = torch.empty((chunk, ld), dtype=torch.float16, device=self.device)
+            partials = torch.empty(int(capi.lib().tce_logprobs_workspace_bytes(chunk, self.vocab)), dtype=torch.uint8, device=self.device)
+            values = torch.empty(total, dtype=torch.float32, device=self.device)
+            self.score_logits = []
+            for r0, m in plan["chunks"]:
+                rmsnorm_half(hidden[r0:r0 + m], self.final_gamma, self.eps, out=xn[:m])
+                capi.check(capi.w4a16_forward(self.lm_head.desc(xn[:m], logits[:m]), _stream()))
+                capi.check(capi.logprobs_f16(logits.data_ptr(), ld, self.vocab, m, target[r0:].data_ptr(), values[r0:].data_ptr(), None, partials.data_ptr(), _stream()))
+                if self.score_keep_logits:
+                    self.score_logits.append(logits[:m].clone())
+        finally:
+            for s in slots:
+                self.allocator.release(s)
+        return plan["split"](values.cpu().numpy())  # (synchronises)
 
     def embed_violations(self) -> int:
         """Token ids tce_embed_rows_f16 refused since the workspace was made (0 unless something wrote next_token from outside)."""

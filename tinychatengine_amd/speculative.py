@@ -18,7 +18,7 @@ kept only if it EQUALS the token sampled in front of it.  There is no draft dist
     ngram_draft_reference, verify_reference   the two device pieces restated in numpy (verify_reference from sample_reference, ring_window and uniform only)
     SpecSlotBook                              which pages run(n) must reserve: positions up to p + n T - 1, whatever the budget (rejected rows are written too)
     SpeculativeDecoder                        PagedBatchedDecoder at B T rows
-    SpeculativeGenerator                      BatchedGenerator's surface (admit / run / tokens / release) + rows_per_seq, ngram, emitted_per_step()
+    SpeculativeGenerator                      BatchedGenerator's surface (admit / run / tokens / logprobs / release) + rows_per_seq, ngram, emitted_per_step()
     HostDrivenSpeculativeLoop                 the same decoders and launches run eagerly, logits to the host, drafts / sampling / acceptance in numpy: the yardstick
 """
 from __future__ import annotations
@@ -199,7 +199,9 @@ def draft_ngram(history, script, pos_device, pos_bound: int, rows_per_seq: int, 
 
 
 class Verifier:
-    """tce_sample_verify_f16 over a Sampler's per-sequence state: the workspace for batch * rows_per_seq rows and `emitted`."""
+    """tce_sample_verify_f16 over a Sampler's per-sequence state: the workspace for batch * rows_per_seq rows and `emitted`.  A Sampler built with logprobs=True:
+    tce_sample_verify_logprobs_f16 -- the same three launches --, which writes the sampler's out_logprob beside every emitted token (partials for batch * rows_per_seq
+    rows live here)."""
 
     def __init__(self, sampler: Sampler, rows_per_seq: int, debug: bool = False):
         _check_rows(rows_per_seq)
@@ -212,6 +214,9 @@ class Verifier:
         self.emitted = torch.zeros(sampler.batch, dtype=torch.int32, device=dev)
         self.uniform_override = None  # fp32 [batch * rows_per_seq] on the device (tests)
         self.debug = torch.zeros((sampler.batch * self.rows_per_seq, C.sizeof(capi.SampleDebug) // 4), dtype=torch.int32, device=dev) if debug else None
+        self.partials = None
+        if sampler.logprobs:
+            self.partials = torch.empty(int(capi.lib().tce_logprobs_workspace_bytes(sampler.batch * self.rows_per_seq, sampler.vocab)), dtype=torch.uint8, device=dev)
 
     def step(self, logits, row_token, row_pos, history, pos_device, pos_bound: int) -> None:
         """logits fp16 [batch * T][ld]; pos_device int32 [batch] (the sequences' positions) is read and written; three launches on the current stream."""
@@ -227,7 +232,10 @@ class Verifier:
         c.debug = self.debug.data_ptr() if self.debug is not None else None
         v = capi.SampleVerifyCall(s=c, rows_per_seq=self.rows_per_seq, hist_stride=history.shape[1], row_token=row_token.data_ptr(), row_pos=row_pos.data_ptr(),
                                   history=history.data_ptr(), emitted=self.emitted.data_ptr())
-        capi.check(capi.sample_verify_f16(v, _stream()))
+        if s.logprobs:
+            capi.check(capi.sample_verify_logprobs_f16(v, s.logprob_out(self.partials), _stream()))
+        else:
+            capi.check(capi.sample_verify_f16(v, _stream()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -239,7 +247,7 @@ class SpeculativeGenerator:
     REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t]."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
-                 graph: bool = True, script: bool = False, record_steps: int = 4096):
+                 graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False):
         self.decoders = list(decoders)
         d0 = self.decoders[0]
         self.batch, self.hidden_size, self.rows_per_seq, self.ngram = d0.batch, d0.block.hidden, d0.rows_per_seq, int(ngram)
@@ -255,7 +263,7 @@ class SpeculativeGenerator:
         dev = embed_table.device
         self.device = dev
         B, T = self.batch, self.rows_per_seq
-        self.sampler = Sampler(B, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids)
+        self.sampler = Sampler(B, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, logprobs=logprobs)
         self.verifier = Verifier(self.sampler, T)
         self.book = SpecSlotBook(B, self.max_keys, T)
         self.hist_stride = self.max_keys + 8  # (the verifier writes index p + 1 + t <= max_keys)
@@ -324,6 +332,8 @@ class SpeculativeGenerator:
         for (s, ids, p, sd, mn), r in zip(adm, rows):
             self.sampler.set_row(s, p, sd, mn, ids)
             self.sampler.out_log[s].fill_(-1)
+            if self.sampler.logprobs:
+                self.sampler.out_logprob[s].fill_(float("nan"))
             self._adm_hidden[s].copy_(r[-1])
             self._adm_pos[s] = len(ids) - 1
         rmsnorm_half(self._adm_hidden, self.final_gamma, self.eps, out=self._adm_xn)
@@ -375,6 +385,13 @@ class SpeculativeGenerator:
     def tokens(self, slot: int) -> list[int]:
         n = int(self.sampler.generated()[slot])
         return self.sampler.out_log[slot, :n].cpu().numpy().tolist()
+
+    def logprobs(self, slot: int) -> np.ndarray:
+        """fp32, one value per token of tokens(slot): BatchedGenerator.logprobs' values for the same tokens.  Needs logprobs=True."""
+        if not self.sampler.logprobs:
+            raise ValueError("logprobs: the generator was built without logprobs=True")
+        n = int(self.sampler.generated()[slot])
+        return self.sampler.out_logprob[slot, :n].cpu().numpy()
 
     def release(self, slot: int) -> list[int]:
         self.pos[slot] = -1
