@@ -43,6 +43,12 @@ def _host():
     return buf, (C.addressof(buf) + 15) & ~15
 
 
+def _shared_faults(p):
+    """The faults the contiguous batched step knows too, as changes to a valid call on the host buffer p."""
+    return [dict(batch=0), dict(batch=-1), dict(kv=3), dict(kv=0), dict(bound=-1), dict(bound=64), dict(cos=p), dict(sin=p), dict(hd=64), dict(batch=65536),
+            dict(qkv=p + 8), dict(kp=p + 8), dict(vpool=p + 8), dict(cos=p + 2, sin=p), dict(cos=p, sin=p + 4), dict(pos=p + 2), dict(heads=0)]
+
+
 def test_paged_step_argument_validation_needs_no_gpu(capi):
     """Every refusal happens before a HIP call: host buffers stand in for the device pointers and are never dereferenced.  The shared faults return the batched
     step's codes."""
@@ -65,9 +71,7 @@ def test_paged_step_argument_validation_needs_no_gpu(capi):
         assert step(**{name: None}) == capi.TCE_ERR_BAD_ARG, name
     assert "null pointer" in capi.last_error()
     # the faults the batched step knows: the same codes
-    shared = [dict(batch=0), dict(batch=-1), dict(kv=3), dict(kv=0), dict(bound=-1), dict(bound=64), dict(cos=p), dict(sin=p), dict(hd=64), dict(batch=65536),
-              dict(qkv=p + 8), dict(kp=p + 8), dict(vpool=p + 8), dict(cos=p + 2, sin=p), dict(cos=p, sin=p + 4), dict(pos=p + 2), dict(heads=0)]
-    for kw in shared:
+    for kw in _shared_faults(p):
         assert step(**kw) == batch(**kw), kw
         assert step(**kw) in (capi.TCE_ERR_BAD_ARG, capi.TCE_ERR_UNSUPPORTED_SHAPE), kw
     assert step(kv=3) == capi.TCE_ERR_BAD_ARG and "do not divide" in capi.last_error()
@@ -83,6 +87,47 @@ def test_paged_step_argument_validation_needs_no_gpu(capi):
     assert step(bound=64) == capi.TCE_ERR_BAD_ARG and "table_stride * page_keys" in capi.last_error()  # 4 pages of 16 keys hold indices 0 .. 63
     assert step(stride=1, pk=16, bound=16) == capi.TCE_ERR_BAD_ARG
     assert step(tab=p + 2) == capi.TCE_ERR_UNSUPPORTED_SHAPE and "block_table" in capi.last_error()
+
+
+def test_paged_rows_step_argument_validation_needs_no_gpu(capi):
+    """The multi-row step's two entry points refuse before any HIP call (host buffers, never dereferenced): the single-row step's code for every shared fault, then
+    the rows' own -- the row count, `out` in 16-byte pieces -- and the e4m3 exponents."""
+    L = capi.lib()
+    keep, p = _host()
+    vp = C.c_void_p
+    BAD, SHAPE = capi.TCE_ERR_BAD_ARG, capi.TCE_ERR_UNSUPPORTED_SHAPE
+
+    def args(kw, rows):
+        g = lambda k, d: kw[k] if k in kw else d
+        return [vp(g("qkv", p)), vp(g("kp", p)), vp(g("vpool", p)), vp(g("tab", p)), g("stride", 4), g("pk", 16), g("np", 8), vp(g("cos", None)), vp(g("sin", None)),
+                vp(g("out", p)), vp(g("ws", p)), g("batch", 2)] + ([g("rows", 3)] if rows else []) + [g("heads", 4), g("kv", 2), g("hd", 128), vp(g("pos", p)), g("bound", 10), 0x2DA8]
+
+    step = lambda **kw: L.tce_attention_decode_step_paged_f16(*args(kw, False), None)
+    forms = {"tce_attention_decode_step_paged_rows_f16": lambda **kw: L.tce_attention_decode_step_paged_rows_f16(*args(kw, True), None),
+             "tce_attention_decode_step_paged_rows_fp8": lambda **kw: L.tce_attention_decode_step_paged_rows_fp8(*args(kw, True), kw.get("k_e", 0), kw.get("v_e", 0), None)}
+    for name, rows in forms.items():
+        for ptr in ("qkv", "kp", "vpool", "tab", "out", "ws", "pos"):
+            assert rows(**{ptr: None}) == BAD and name in capi.last_error() and "null pointer" in capi.last_error(), (name, ptr)
+        for kw in _shared_faults(p):
+            want = step(**kw)
+            assert want in (BAD, SHAPE), kw
+            assert rows(**kw) == want, (name, kw)
+        for pk in (0, 8, 15, 24, 48, 512, -16):
+            assert rows(pk=pk) == BAD and "page_keys" in capi.last_error(), (name, pk)
+        for kw in (dict(stride=0), dict(stride=-4), dict(np=0), dict(bound=64), dict(stride=1, pk=16, bound=16)):
+            assert rows(**kw) == BAD == step(**kw), (name, kw)
+        assert rows(tab=p + 2) == SHAPE and "block_table" in capi.last_error()
+        # the rows' own
+        for n in (0, 9):
+            assert rows(rows=n) == SHAPE and "rows_per_seq" in capi.last_error(), (name, n)
+        assert rows(out=p + 8) == SHAPE and "out" in capi.last_error() and "16-byte" in capi.last_error(), name
+        assert rows(rows=0, batch=0) == BAD and rows(out=p + 8, kv=3) == BAD, name  # an argument fault wins over a shape fault
+    fp8 = forms["tce_attention_decode_step_paged_rows_fp8"]
+    for e in (-9, 8):
+        assert fp8(k_e=e) == BAD and "k_scale_log2" in capi.last_error() and str(e) in capi.last_error(), e
+        assert fp8(v_e=e) == BAD and "v_scale_log2" in capi.last_error() and str(e) in capi.last_error(), e
+        assert fp8(k_e=e, hd=64) == BAD, e
+    del keep
 
 
 def test_scatter_gather_and_check_validation_needs_no_gpu(capi):

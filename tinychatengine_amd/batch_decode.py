@@ -84,21 +84,24 @@ class BatchedDecoder:
 
     LAUNCHES = 7  # per layer and step, with the SiLU*mul pairs accepted (9 otherwise)
 
-    def __init__(self, block: DecoderBlock, batch: int):
-        self.block, self.batch = block, batch
+    def __init__(self, block: DecoderBlock, batch: int, attention=None, rows: int | None = None):
+        """attention: the step's attention object (default: a BatchDecodeAttention with contiguous caches of its own); rows: the rows one step carries, where that is
+        not `batch` (the speculative step's batch * rows_per_seq)."""
+        self.block, self.batch, self.rows = block, batch, batch if rows is None else rows
         dev = block.gamma1.device
-        self.attention = BatchDecodeAttention(batch, block.heads, block.attention.max_keys, dev, block.attention.cos, block.attention.sin, kv_heads=block.kv_heads)
-        e = lambda n: torch.empty((batch, n), dtype=torch.float16, device=dev)
+        self.attention = attention if attention is not None else BatchDecodeAttention(batch, block.heads, block.attention.max_keys, dev, block.attention.cos,
+                                                                                      block.attention.sin, kv_heads=block.kv_heads)
+        e = lambda n: torch.empty((self.rows, n), dtype=torch.float16, device=dev)
         self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
         self.act = e(block.ffn)
-        self._up = None  # gate / up / SiLU*mul as three launches: up's output rows (only where the dispatcher refuses the pairs at M = batch)
+        self._up = None  # gate / up / SiLU*mul as three launches: up's output rows (only where the dispatcher refuses the pairs at M = rows)
 
     def step(self, hidden: torch.Tensor, pos_device: torch.Tensor, pos_bound: int) -> None:
-        """hidden fp16 [batch][hidden], updated in place (each row is its sequence's residual stream); pos_device int32 [batch], -1 for an inactive slot: its
+        """hidden fp16 [rows][hidden], updated in place (each row is its sequence's residual stream); pos_device int32 [rows], -1 for an inactive slot: its
         attention row is zero and its caches are untouched (its hidden row still passes through the MLP and means nothing).  Capturable in one
         torch.cuda.graph and replayable token after token with pos_device advanced on the device."""
         blk = self.block
-        assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.batch, blk.hidden)
+        assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.rows, blk.hidden)
         st = _stream()
         rmsnorm_half(hidden, blk.gamma1, blk.eps, out=self.xn)
         capi.check(capi.w4a16_forward(blk.qkv.desc(self.xn, self.qkv_out), st))

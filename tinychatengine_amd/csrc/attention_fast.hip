@@ -705,20 +705,19 @@ size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys
     return (size_t)batch * attention_decode_workspace_bytes(heads, max_keys, hd);
 }
 
-int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
-                                  int kv_heads, int hd, int max_keys, const int *pos_dev, int pos_bound, unsigned short alpha_bits, hipStream_t stream,
-                                  hipError_t *hip_err) {
-    if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !pos_dev) return TCE_ERR_UNSUPPORTED_SHAPE;
+int launch_attention_decode_batch(const AttnStepArgs &s, void *kc, void *vc, int max_keys, hipStream_t stream, hipError_t *hip_err) {
+    const int batch = s.batch, heads = s.heads, kv_heads = s.kv_heads, hd = s.hd, pos_bound = s.pos_bound;
+    if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !s.pos_device) return TCE_ERR_UNSUPPORTED_SHAPE;
     FastAttnArgs a{};
-    a.qkv = static_cast<const half_t *>(qkv);
+    a.qkv = static_cast<const half_t *>(s.qkv);
     a.kc = static_cast<half_t *>(kc);
     a.vc = static_cast<half_t *>(vc);
-    a.cosv = static_cast<const half_t *>(cosv);
-    a.sinv = static_cast<const half_t *>(sinv);
-    a.out = static_cast<half_t *>(out);
+    a.cosv = static_cast<const half_t *>(s.cosv);
+    a.sinv = static_cast<const half_t *>(s.sinv);
+    a.out = static_cast<half_t *>(s.out);
     const size_t cnt_bytes = ((size_t)heads * 4 + 255) & ~(size_t)255;  // (one sequence's slice: the single step's layout)
-    a.cnt = static_cast<unsigned *>(workspace);
-    a.part = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + cnt_bytes);
+    a.cnt = static_cast<unsigned *>(s.workspace);
+    a.part = reinterpret_cast<float *>(static_cast<unsigned char *>(s.workspace) + cnt_bytes);
     a.heads = heads;
     a.kv_heads = kv_heads;
     a.rep = heads / kv_heads;
@@ -726,12 +725,12 @@ int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const voi
     a.max_keys = max_keys;
     a.pos = pos_bound;
     a.keys = pos_bound + 1;
-    a.pos_dev = pos_dev;
+    a.pos_dev = s.pos_device;
     int nw = 4;
     describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
     if (a.chunks > 1024 || nw != 4) return TCE_ERR_UNSUPPORTED_SHAPE;
     half_t ah;
-    __builtin_memcpy(&ah, &alpha_bits, 2);
+    __builtin_memcpy(&ah, &s.alpha_bits, 2);
     a.alpha = (float)ah;
     hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
     const hipError_t e = hipGetLastError();
@@ -838,28 +837,28 @@ static float host_pow2(int e) {
     return f;
 }
 
-// fp8 = true: the pools are e4m3 bytes and the two exponents apply (launch_attention_decode_paged_fp8); everything else is one text for both
+// pages.fp8: the pools are e4m3 bytes and the two exponents apply; everything else is one text for both
 // rows = 0: the step; rows >= 1: the multi-row step with rows_per_seq = rows -- the same cut (pos_bound alone decides it), grid (heads x chunk slots, rows, batch)
-static int launch_paged_step(int rows, bool fp8, int k_log2, int v_log2, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                             const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound,
-                             unsigned short alpha_bits, hipStream_t stream, hipError_t *hip_err) {
-    const int shift = page_shift_of(page_keys);
-    if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !pos_dev || !table || shift < 0 || table_stride < 1 ||
+int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int rows, hipStream_t stream, hipError_t *hip_err) {
+    const int batch = s.batch, heads = s.heads, kv_heads = s.kv_heads, hd = s.hd, pos_bound = s.pos_bound, table_stride = pg.table_stride;
+    const bool fp8 = pg.fp8;
+    const int shift = page_shift_of(pg.page_keys);
+    if (hd != kHD || kv_heads <= 0 || heads % kv_heads != 0 || batch <= 0 || batch > 65535 || !s.pos_device || !pg.table || shift < 0 || table_stride < 1 ||
         (long long)pos_bound >= ((long long)table_stride << shift))
         return TCE_ERR_UNSUPPORTED_SHAPE;
-    if (fp8 && !(fp8_log2_ok(k_log2) && fp8_log2_ok(v_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (fp8 && !(fp8_log2_ok(pg.k_scale_log2) && fp8_log2_ok(pg.v_scale_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
     if (rows < 0 || rows > TCE_SPEC_MAX_ROWS) return TCE_ERR_UNSUPPORTED_SHAPE;
     PagedRowsAttnArgs a{};
     a.rows_per_seq = rows;
-    a.qkv = static_cast<const half_t *>(qkv);
-    a.kc = static_cast<half_t *>(k_pool);
-    a.vc = static_cast<half_t *>(v_pool);
-    a.cosv = static_cast<const half_t *>(cosv);
-    a.sinv = static_cast<const half_t *>(sinv);
-    a.out = static_cast<half_t *>(out);
+    a.qkv = static_cast<const half_t *>(s.qkv);
+    a.kc = static_cast<half_t *>(pg.k_pool);
+    a.vc = static_cast<half_t *>(pg.v_pool);
+    a.cosv = static_cast<const half_t *>(s.cosv);
+    a.sinv = static_cast<const half_t *>(s.sinv);
+    a.out = static_cast<half_t *>(s.out);
     const size_t cnt_bytes = ((size_t)heads * 4 + 255) & ~(size_t)255;
-    a.cnt = static_cast<unsigned *>(workspace);
-    a.part = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + cnt_bytes);
+    a.cnt = static_cast<unsigned *>(s.workspace);
+    a.part = reinterpret_cast<float *>(static_cast<unsigned char *>(s.workspace) + cnt_bytes);
     a.heads = heads;
     a.kv_heads = kv_heads;
     a.rep = heads / kv_heads;
@@ -867,21 +866,21 @@ static int launch_paged_step(int rows, bool fp8, int k_log2, int v_log2, const v
     a.max_keys = table_stride << shift;  // (the workspace slices' size; no cache address is formed from it)
     a.pos = pos_bound;
     a.keys = pos_bound + 1;
-    a.pos_dev = pos_dev;
-    a.table = table;
+    a.pos_dev = s.pos_device;
+    a.table = pg.table;
     a.table_stride = table_stride;
     a.page_shift = shift;
     int nw = 4;
     describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
     if (a.chunks > 1024 || nw != 4) return TCE_ERR_UNSUPPORTED_SHAPE;
     half_t ah;
-    __builtin_memcpy(&ah, &alpha_bits, 2);
+    __builtin_memcpy(&ah, &s.alpha_bits, 2);
     a.alpha = (float)ah;
     if (fp8) {
-        a.k_scale = host_pow2(k_log2);
-        a.v_scale = host_pow2(v_log2);
-        a.k_inv = host_pow2(-k_log2);
-        a.v_inv = host_pow2(-v_log2);
+        a.k_scale = host_pow2(pg.k_scale_log2);
+        a.v_scale = host_pow2(pg.v_scale_log2);
+        a.k_inv = host_pow2(-pg.k_scale_log2);
+        a.v_inv = host_pow2(-pg.v_scale_log2);
     }
     if (rows) {
         const dim3 grid(heads * a.chunks, rows, batch);
@@ -900,54 +899,20 @@ static int launch_paged_step(int rows, bool fp8, int k_log2, int v_log2, const v
     return TCE_OK;
 }
 
-int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
-                                  void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
-                                  hipStream_t stream, hipError_t *hip_err) {
-    return launch_paged_step(0, false, 0, 0, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev, pos_bound,
-                             alpha_bits, stream, hip_err);
-}
-
-int launch_attention_decode_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
-                                      void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
-                                      int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
-    return launch_paged_step(0, true, k_log2, v_log2, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_dev,
-                             pos_bound, alpha_bits, stream, hip_err);
-}
-
-// rows_per_seq query rows per sequence (1 .. TCE_SPEC_MAX_ROWS); fp8: the e4m3 pools with their two exponents (ignored otherwise)
-int launch_attention_decode_paged_rows(bool fp8, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                       const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd, const int *pos_dev,
-                                       int pos_bound, unsigned short alpha_bits, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
-    if (rows_per_seq < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
-    return launch_paged_step(rows_per_seq, fp8, k_log2, v_log2, qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd,
-                             pos_dev, pos_bound, alpha_bits, stream, hip_err);
-}
-
-int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
-                         int lin_max_keys, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err) {
-    const int shift = page_shift_of(page_keys);
-    if (shift < 0 || kv_heads <= 0 || nkeys <= 0 || key0 < 0 || (long long)key0 + nkeys > lin_max_keys) return TCE_ERR_UNSUPPORTED_SHAPE;
-    const dim3 grid((unsigned)(((long long)kv_heads * nkeys * 16 + 255) / 256), 2);
-    auto h = [](void *p) { return static_cast<half_t *>(p); };
-    if (gather) hipLaunchKernelGGL(kv_pages_copy_kernel<true>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), h(k_pool), h(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys);
-    else hipLaunchKernelGGL(kv_pages_copy_kernel<false>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), h(k_pool), h(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
-}
-
-int launch_kv_pages_copy_fp8(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
-                             int lin_max_keys, int key0, int nkeys, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
-    const int shift = page_shift_of(page_keys);
-    if (shift < 0 || kv_heads <= 0 || nkeys <= 0 || key0 < 0 || (long long)key0 + nkeys > lin_max_keys || !fp8_log2_ok(k_log2) || !fp8_log2_ok(v_log2)) return TCE_ERR_UNSUPPORTED_SHAPE;
+// rows [key0, key0 + nkeys) between the contiguous pair and the pages of the table row pages.table; pages.fp8: scatter quantises, gather dequantises
+int launch_kv_pages_copy(const KvPages &pg, const KvLinear &lin, bool gather, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err) {
+    const int shift = page_shift_of(pg.page_keys), kv_heads = lin.kv_heads, k_log2 = pg.k_scale_log2, v_log2 = pg.v_scale_log2;
+    if (shift < 0 || kv_heads <= 0 || nkeys <= 0 || key0 < 0 || (long long)key0 + nkeys > lin.max_keys) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (pg.fp8 && !(fp8_log2_ok(k_log2) && fp8_log2_ok(v_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
     const dim3 grid((unsigned)(((long long)kv_heads * nkeys * 16 + 255) / 256), 2);
     auto h = [](void *p) { return static_cast<half_t *>(p); };
     auto b = [](void *p) { return static_cast<unsigned char *>(p); };
-    if (gather) hipLaunchKernelGGL(kv_pages_copy_fp8_kernel<true>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), b(k_pool), b(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys, k_log2, v_log2);
-    else hipLaunchKernelGGL(kv_pages_copy_fp8_kernel<false>, grid, dim3(256), 0, stream, h(k_lin), h(v_lin), b(k_pool), b(v_pool), table_row, shift, num_pages, kv_heads, lin_max_keys, key0, nkeys, k_log2, v_log2);
+    auto go = [&](auto kernel, auto pool, auto... exponents) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, h(lin.k), h(lin.v), pool(pg.k_pool), pool(pg.v_pool), pg.table, shift, pg.num_pages, kv_heads, lin.max_keys, key0, nkeys,
+                           exponents...);
+    };
+    if (!pg.fp8) gather ? go(kv_pages_copy_kernel<true>, h) : go(kv_pages_copy_kernel<false>, h);
+    else gather ? go(kv_pages_copy_fp8_kernel<true>, b, k_log2, v_log2) : go(kv_pages_copy_fp8_kernel<false>, b, k_log2, v_log2);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;
@@ -956,11 +921,10 @@ int launch_kv_pages_copy_fp8(bool gather, void *k_lin, void *v_lin, void *k_pool
     return TCE_OK;
 }
 
-int launch_kv_block_table_check(const int *table, int table_stride, int page_keys, int num_pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations,
-                                hipStream_t stream, hipError_t *hip_err) {
-    const int shift = page_shift_of(page_keys);
-    if (shift < 0 || table_stride < 1 || batch < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
-    hipLaunchKernelGGL(kv_block_table_check_kernel, dim3(1), dim3(1024), 0, stream, table, table_stride, shift, num_pages, batch, pos_dev, pos_bound, violations);
+int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err) {
+    const int shift = page_shift_of(pg.page_keys);
+    if (shift < 0 || pg.table_stride < 1 || batch < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
+    hipLaunchKernelGGL(kv_block_table_check_kernel, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;

@@ -747,27 +747,29 @@ float host_pow2(int e) {
 }
 }  // namespace
 
-// fp8 = true: the pools are e4m3 bytes and the two exponents apply (launch_attention_prefill_paged_fp8); the plan and both launches' shapes are one text
-static int launch_paged_prefill(bool fp8, int k_log2, int v_log2, const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys,
-                                const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
-                                int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err) {
-    const int shift = prefill_page_shift(page_keys);
+// pages.fp8: the pools are e4m3 bytes and the two exponents apply; the plan and both launches' shapes are one text
+int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, const PrefillRows &r, hipStream_t stream, hipError_t *hip_err) {
+    const int heads = s.heads, kv_heads = s.kv_heads, nseg = r.nseg, total_rows = r.total_rows, causal = r.causal, table_stride = pg.table_stride;
+    const int k_log2 = pg.k_scale_log2, v_log2 = pg.v_scale_log2;
+    const bool fp8 = pg.fp8;
+    const int *const table = pg.table;
+    const int shift = prefill_page_shift(pg.page_keys);
     if (shift < 0 || nseg < 1 || nseg > kMaxSegments || !table || table_stride < 1 || kv_heads <= 0 || heads % kv_heads != 0 || total_rows < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && (k_log2 < kFp8ScaleLog2Min || k_log2 > kFp8ScaleLog2Max || v_log2 < kFp8ScaleLog2Min || v_log2 > kFp8ScaleLog2Max)) return TCE_ERR_UNSUPPORTED_SHAPE;
     PagedPrefillFp8Args a{};
-    __builtin_memcpy(a.seg, segments, sizeof(PrefillSegment) * nseg);
+    __builtin_memcpy(a.seg, r.segments, sizeof(PrefillSegment) * nseg);
     int form = 0;
     unsigned short order[kMaxListedBlocks] = {};
     if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order)) return TCE_ERR_UNSUPPORTED_SHAPE;
     for (int i = 0; i < a.nblocks; ++i) a.order[i >> 1] |= (unsigned)order[i] << ((i & 1) * 16);
     PagedPrepareFp8Args p{};
-    p.qkv = static_cast<const half_t *>(qkv);
-    p.ld_qkv = ld_qkv;
-    p.qrot = static_cast<half_t *>(workspace);
-    p.kc = static_cast<half_t *>(k_pool);
-    p.vc = static_cast<half_t *>(v_pool);
-    p.cosv = static_cast<const half_t *>(cosv);
-    p.sinv = static_cast<const half_t *>(sinv);
+    p.qkv = static_cast<const half_t *>(s.qkv);
+    p.ld_qkv = r.ld_qkv;
+    p.qrot = static_cast<half_t *>(s.workspace);
+    p.kc = static_cast<half_t *>(pg.k_pool);
+    p.vc = static_cast<half_t *>(pg.v_pool);
+    p.cosv = static_cast<const half_t *>(s.cosv);
+    p.sinv = static_cast<const half_t *>(s.sinv);
     p.table = table;
     p.table_stride = table_stride;
     p.page_shift = shift;
@@ -789,9 +791,9 @@ static int launch_paged_prefill(bool fp8, int k_log2, int v_log2, const void *qk
     a.qrot = p.qrot;
     a.kc = p.kc;
     a.vc = p.vc;
-    a.out = static_cast<half_t *>(out);
+    a.out = static_cast<half_t *>(s.out);
     a.table = table;
-    a.ld_out = ld_out;
+    a.ld_out = r.ld_out;
     a.heads = heads;
     a.rep = heads / kv_heads;
     a.kv_heads = kv_heads;
@@ -799,7 +801,9 @@ static int launch_paged_prefill(bool fp8, int k_log2, int v_log2, const void *qk
     a.causal = causal;
     a.table_stride = table_stride;
     a.page_shift = shift;
-    a.alpha = alpha;
+    half_t ah;
+    __builtin_memcpy(&ah, &s.alpha_bits, 2);
+    a.alpha = (float)ah;
     auto go = [&](auto nw_c, auto rt_c) {
         constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
         const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
@@ -825,20 +829,6 @@ static int launch_paged_prefill(bool fp8, int k_log2, int v_log2, const void *qk
         return TCE_ERR_HIP;
     }
     return TCE_OK;
-}
-
-int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                   const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
-                                   int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err) {
-    return launch_paged_prefill(false, 0, 0, qkv, ld_qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, causal, out, ld_out, workspace, heads, kv_heads, segments,
-                                nseg, total_rows, alpha, stream, hip_err);
-}
-
-int launch_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                       const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
-                                       int total_rows, float alpha, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err) {
-    return launch_paged_prefill(true, k_log2, v_log2, qkv, ld_qkv, k_pool, v_pool, table, table_stride, page_keys, cosv, sinv, causal, out, ld_out, workspace, heads, kv_heads,
-                                segments, nseg, total_rows, alpha, stream, hip_err);
 }
 
 }  // namespace tce

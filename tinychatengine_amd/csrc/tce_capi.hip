@@ -1224,28 +1224,76 @@ int tce_attention_decode_describe_batch(int batch, int heads, int kv_heads, int 
     return TCE_OK;
 }
 
+// ---- the refusal rules of the batched step and the paged family (the paged step and its multi-row form, the paged prefill, the page copies, the table check), once.
+// Each helper reports through fail() and returns its code, or TCE_OK.  An entry point runs every TCE_ERR_BAD_ARG rule before its first TCE_ERR_UNSUPPORTED_SHAPE rule (the
+// prefill's segment and leading-dimension rules, which follow head_dim, are the one exception the ABI has had from the start), and every rule before any HIP call. ----
+static bool page_keys_ok(int page_keys) { return page_keys >= 16 && page_keys <= 256 && (page_keys & (page_keys - 1)) == 0; }
+
+static int check_rope_pair(const char *who, const void *cosv, const void *sinv) {
+    return (cosv == nullptr) != (sinv == nullptr) ? fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who) : TCE_OK;
+}
+
+static int check_head_dim(const char *who, int hd) { return hd != 128 ? fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd) : TCE_OK; }
+
+static int check_heads(const char *who, int heads, int kv_heads, int hd) {
+    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
+    return check_head_dim(who, hd);
+}
+
+struct NamedPtr {
+    const char *name;
+    const void *ptr;
+};
+// bytes: 16 (the pieces the kernels load and store) or 4 (an int32 array); a null pointer passes
+static int check_aligned(const char *who, int bytes, std::initializer_list<NamedPtr> ptrs) {
+    for (const NamedPtr &p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p.ptr) & (uintptr_t)(bytes - 1)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be %s", who, p.name, bytes == 4 ? "int32-aligned" : "16-byte aligned");
+    return TCE_OK;
+}
+
+// the pages' own rules, all TCE_ERR_BAD_ARG: pointers, page size, counts, the e4m3 pools' two exponents (include/tce_matmul.h, "FP8 pages").  pools = false: the table alone
+static int check_pages(const char *who, const tce::KvPages &pg, bool pools = true) {
+    if (!pg.table || (pools && (!pg.k_pool || !pg.v_pool))) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (!page_keys_ok(pg.page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, pg.page_keys);
+    if (pg.table_stride < 1 || pg.num_pages < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages >= 1", who);
+    if (pg.fp8 && (pg.k_scale_log2 < -8 || pg.k_scale_log2 > 7)) return fail(TCE_ERR_BAD_ARG, "%s: k_scale_log2 %d outside [-8, 7]", who, pg.k_scale_log2);
+    if (pg.fp8 && (pg.v_scale_log2 < -8 || pg.v_scale_log2 > 7)) return fail(TCE_ERR_BAD_ARG, "%s: v_scale_log2 %d outside [-8, 7]", who, pg.v_scale_log2);
+    return TCE_OK;
+}
+
+// keys one table row addresses; the step and the prefill hand the kernels this product as an int (the copies and the table check never form it)
+static long long row_keys(const tce::KvPages &pg) { return (long long)pg.table_stride * pg.page_keys; }
+static int check_row_keys(const char *who, const tce::KvPages &pg) {
+    return row_keys(pg) > 0x7fffffffLL ? fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who) : TCE_OK;
+}
+
+// what the batched steps share besides the cache: pointers, counts and pos_bound < max_keys (`bound`: its name in the message), heads, head_dim, the grid's limit
+static int check_step(const char *who, const tce::AttnStepArgs &s, long long max_keys, const char *bound) {
+    if (!s.qkv || !s.out || !s.workspace || !s.pos_device) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = check_rope_pair(who, s.cosv, s.sinv)) return rc;
+    if (s.batch <= 0 || s.heads <= 0 || max_keys <= 0 || s.pos_bound < 0 || s.pos_bound >= max_keys)
+        return fail(TCE_ERR_BAD_ARG, "%s: need batch, heads > 0 and 0 <= pos_bound < %s", who, bound);
+    if (const int rc = check_heads(who, s.heads, s.kv_heads, s.hd)) return rc;
+    if (s.batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: batch %d (at most 65535: a grid dimension)", who, s.batch);
+    return TCE_OK;
+}
+
 int tce_attention_decode_step_batch_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
                                         int kv_heads, int hd, int max_keys, const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
-    if (!qkv || !kc || !vc || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: null pointer");
-    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: cos and sin tables come together");
-    if (batch <= 0 || heads <= 0 || max_keys <= 0 || pos_bound < 0 || pos_bound >= max_keys)
-        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: need batch, heads > 0 and 0 <= pos_bound < max_keys");
-    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_batch_f16: %d query heads do not divide over %d key / value heads", heads, kv_heads);
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: head_dim %d (128 only: Llama's)", hd);
-    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: batch %d (at most 65535: the grid's second dimension)", batch);
-    for (const void *p : {qkv, (const void *)kc, (const void *)vc, cosv, sinv})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: 16-byte aligned pointers");
-    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_batch_f16: pos_device must be int32-aligned");
+    static const char *who = "tce_attention_decode_step_batch_f16";
+    const tce::AttnStepArgs s{qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits};
+    if (!kc || !vc) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = check_step(who, s, max_keys, "max_keys")) return rc;
+    if (const int rc = check_aligned(who, 16, {{"qkv", qkv}, {"k_cache", kc}, {"v_cache", vc}, {"cos_table", cosv}, {"sin_table", sinv}})) return rc;
+    if (const int rc = check_aligned(who, 4, {{"pos_device", pos_device}})) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_decode_batch(qkv, kc, vc, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, max_keys, pos_device, pos_bound, alpha_bits,
-                                                      static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_attention_decode_batch(s, kc, vc, max_keys, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "batched attention decode step launch") : rc;
 }
 
-// ---- the paged step and its companions (csrc/attention_fast.hip): every refusal below happens before any HIP call ----
+// ---- the paged step and its companions (csrc/attention_fast.hip) ----
 size_t tce_kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes(num_pages, kv_heads, page_keys, hd); }
-
-static bool page_keys_ok(int page_keys) { return page_keys >= 16 && page_keys <= 256 && (page_keys & (page_keys - 1)) == 0; }
+size_t tce_kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes_fp8(num_pages, kv_heads, page_keys, hd); }
 
 int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int pos_bound, int page_keys, char *buf, int buf_len) {
     if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys))
@@ -1257,181 +1305,102 @@ int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int 
     return TCE_OK;
 }
 
-// the e4m3 pages' two exponents (include/tce_matmul.h, "FP8 pages")
-static int check_fp8_scales(const char *who, int k_scale_log2, int v_scale_log2) {
-    if (k_scale_log2 < -8 || k_scale_log2 > 7) return fail(TCE_ERR_BAD_ARG, "%s: k_scale_log2 %d outside [-8, 7]", who, k_scale_log2);
-    if (v_scale_log2 < -8 || v_scale_log2 > 7) return fail(TCE_ERR_BAD_ARG, "%s: v_scale_log2 %d outside [-8, 7]", who, v_scale_log2);
-    return TCE_OK;
-}
-
-size_t tce_kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes_fp8(num_pages, kv_heads, page_keys, hd); }
-
-int tce_attention_decode_step_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
-                                        const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
-                                        const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
-    static const char *who = "tce_attention_decode_step_paged_fp8";
-    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
-    if (table_stride < 1 || num_pages < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages >= 1", who);
-    if (batch <= 0 || heads <= 0 || pos_bound < 0 || (long long)pos_bound >= (long long)table_stride * page_keys)
-        return fail(TCE_ERR_BAD_ARG, "%s: need batch, heads > 0 and 0 <= pos_bound < table_stride * page_keys", who);
-    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
-    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
-    if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
-    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: batch %d (at most 65535: the grid's second dimension)", who, batch);
-    const void *ptrs[] = {qkv, k_pool, v_pool, cosv, sinv};
-    const char *names[] = {"qkv", "k_pool", "v_pool", "cos_table", "sin_table"};
-    for (int i = 0; i < 5; ++i)
-        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
-    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: pos_device must be int32-aligned", who);
-    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
+// rows_per_seq null: the step.  Else the multi-row form (speculative decoding), which has two rules of its own: the row count, and `out` 16-byte aligned (it stores
+// `out` in 16-byte pieces; the step never required it, and callers rely on that)
+static int paged_step(const char *who, const tce::KvPages &pg, const tce::AttnStepArgs &s, const int *rows_per_seq, void *stream) {
+    if (const int rc = check_pages(who, pg)) return rc;
+    if (const int rc = check_row_keys(who, pg)) return rc;
+    if (const int rc = check_step(who, s, row_keys(pg), "table_stride * page_keys")) return rc;
+    if (rows_per_seq && (*rows_per_seq < 1 || *rows_per_seq > TCE_SPEC_MAX_ROWS))
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, *rows_per_seq, TCE_SPEC_MAX_ROWS);
+    if (const int rc = check_aligned(who, 16, {{"qkv", s.qkv}, {"k_pool", pg.k_pool}, {"v_pool", pg.v_pool}, {"cos_table", s.cosv}, {"sin_table", s.sinv},
+                                               {"out", rows_per_seq ? s.out : nullptr}}))
+        return rc;
+    if (const int rc = check_aligned(who, 4, {{"pos_device", s.pos_device}, {"block_table", pg.table}})) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_decode_paged_fp8(qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd,
-                                                          pos_device, pos_bound, alpha_bits, k_scale_log2, v_scale_log2, static_cast<hipStream_t>(stream), &he);
-    return rc == TCE_ERR_HIP ? hip_fail(he, "fp8 paged attention decode step launch") : rc;
+    const int rc = tce::launch_attention_decode_paged(pg, s, rows_per_seq ? *rows_per_seq : 0, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "paged attention decode step launch") : rc;
 }
 
 int tce_attention_decode_step_paged_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                         const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
                                         const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
-    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: null pointer");
-    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: cos and sin tables come together");
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: page_keys %d (a power of two from 16 to 256)", page_keys);
-    if (table_stride < 1 || num_pages < 1) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: need table_stride, num_pages >= 1");
-    if (batch <= 0 || heads <= 0 || pos_bound < 0 || (long long)pos_bound >= (long long)table_stride * page_keys)
-        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: need batch, heads > 0 and 0 <= pos_bound < table_stride * page_keys");
-    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: table_stride * page_keys overflows int");
-    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_step_paged_f16: %d query heads do not divide over %d key / value heads", heads, kv_heads);
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: head_dim %d (128 only: Llama's)", hd);
-    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: batch %d (at most 65535: the grid's second dimension)", batch);
-    for (const void *p : {qkv, (const void *)k_pool, (const void *)v_pool, cosv, sinv})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: 16-byte aligned pointers");
-    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: pos_device must be int32-aligned");
-    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_attention_decode_step_paged_f16: block_table must be int32-aligned");
-    hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_decode_paged(qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, out, workspace, batch, heads, kv_heads, hd,
-                                                      pos_device, pos_bound, alpha_bits, static_cast<hipStream_t>(stream), &he);
-    return rc == TCE_ERR_HIP ? hip_fail(he, "paged attention decode step launch") : rc;
+    return paged_step("tce_attention_decode_step_paged_f16", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream);
 }
 
-// ---- the paged step with rows_per_seq query rows per sequence (speculative decoding): the steps' refusals, then the rows' ----
-static int paged_rows_step(const char *who, bool fp8, const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
-                           const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd,
-                           const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
-    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !pos_device) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
-    if (table_stride < 1 || num_pages < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages >= 1", who);
-    if (batch <= 0 || heads <= 0 || pos_bound < 0 || (long long)pos_bound >= (long long)table_stride * page_keys)
-        return fail(TCE_ERR_BAD_ARG, "%s: need batch, heads > 0 and 0 <= pos_bound < table_stride * page_keys", who);
-    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
-    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
-    if (fp8)
-        if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
-    if (rows_per_seq < 1 || rows_per_seq > TCE_SPEC_MAX_ROWS)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, rows_per_seq, TCE_SPEC_MAX_ROWS);
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
-    if (batch > 65535) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: batch %d (at most 65535: the grid's third dimension)", who, batch);
-    const void *ptrs[] = {qkv, k_pool, v_pool, cosv, sinv, out};
-    const char *names[] = {"qkv", "k_pool", "v_pool", "cos_table", "sin_table", "out"};
-    for (int i = 0; i < 6; ++i)
-        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
-    if (reinterpret_cast<uintptr_t>(pos_device) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: pos_device must be int32-aligned", who);
-    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
-    hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_decode_paged_rows(fp8, qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, out, workspace, batch, rows_per_seq, heads,
-                                                           kv_heads, hd, pos_device, pos_bound, alpha_bits, k_scale_log2, v_scale_log2, static_cast<hipStream_t>(stream), &he);
-    return rc == TCE_ERR_HIP ? hip_fail(he, "multi-row paged attention decode step launch") : rc;
+int tce_attention_decode_step_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                        const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                        const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream);
 }
 
 int tce_attention_decode_step_paged_rows_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                              const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd,
                                              const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, void *stream) {
-    return paged_rows_step("tce_attention_decode_step_paged_rows_f16", false, qkv, k_pool, v_pool, block_table, table_stride, page_keys, num_pages, cosv, sinv, out, workspace,
-                           batch, rows_per_seq, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits, 0, 0, stream);
+    return paged_step("tce_attention_decode_step_paged_rows_f16", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream);
 }
 
 int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                              const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd,
                                              const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
-    return paged_rows_step("tce_attention_decode_step_paged_rows_fp8", true, qkv, k_pool, v_pool, block_table, table_stride, page_keys, num_pages, cosv, sinv, out, workspace,
-                           batch, rows_per_seq, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits, k_scale_log2, v_scale_log2, stream);
+    return paged_step("tce_attention_decode_step_paged_rows_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream);
 }
 
-static int kv_pages_copy(const char *who, bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
-                         int num_pages, int kv_heads, int hd, int lin_max_keys, int key0, int nkeys, void *stream) {
-    if (!k_lin || !v_lin || !k_pool || !v_pool || !table_row) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
-    if (table_stride < 1 || num_pages < 1 || kv_heads < 1 || lin_max_keys < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages, kv_heads, max_keys >= 1", who);
-    if (key0 < 0 || nkeys < 1 || (long long)key0 + nkeys > lin_max_keys || (long long)key0 + nkeys > (long long)table_stride * page_keys)
+// rows [key0, key0 + nkeys) between a contiguous pair and the pages of one table row (pg.table: that row)
+static int kv_pages_copy(const char *who, bool gather, const tce::KvPages &pg, const tce::KvLinear &lin, int hd, int key0, int nkeys, void *stream) {
+    if (!lin.k || !lin.v) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = check_pages(who, pg)) return rc;
+    if (lin.kv_heads < 1 || lin.max_keys < 1) return fail(TCE_ERR_BAD_ARG, "%s: need kv_heads, max_keys >= 1", who);
+    if (key0 < 0 || nkeys < 1 || (long long)key0 + nkeys > lin.max_keys || (long long)key0 + nkeys > row_keys(pg))
         return fail(TCE_ERR_BAD_ARG, "%s: rows [%d, %d + %d) must lie inside the contiguous cache (%d keys) and the table row (%d pages of %d)", who, key0, key0, nkeys,
-                    lin_max_keys, table_stride, page_keys);
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
-    for (const void *p : {(const void *)k_lin, (const void *)v_lin, (const void *)k_pool, (const void *)v_pool})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned pointers", who);
-    if (reinterpret_cast<uintptr_t>(table_row) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: the table row must be int32-aligned", who);
+                    lin.max_keys, pg.table_stride, pg.page_keys);
+    if (const int rc = check_head_dim(who, hd)) return rc;
+    if (const int rc = check_aligned(who, 16, {{gather ? "k_dst" : "k_src", lin.k}, {gather ? "v_dst" : "v_src", lin.v}, {"k_pool", pg.k_pool}, {"v_pool", pg.v_pool}})) return rc;
+    if (const int rc = check_aligned(who, 4, {{"table_row", pg.table}})) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_kv_pages_copy(gather, k_lin, v_lin, k_pool, v_pool, table_row, page_keys, num_pages, kv_heads, lin_max_keys, key0, nkeys,
-                                             static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_kv_pages_copy(pg, lin, gather, key0, nkeys, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, who) : rc;
 }
 
 int tce_kv_pages_scatter_f16(const void *k_src, const void *v_src, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
                              int kv_heads, int hd, int src_max_keys, int key0, int nkeys, void *stream) {
-    return kv_pages_copy("tce_kv_pages_scatter_f16", false, const_cast<void *>(k_src), const_cast<void *>(v_src), k_pool, v_pool, table_row, table_stride, page_keys, num_pages,
-                         kv_heads, hd, src_max_keys, key0, nkeys, stream);
+    return kv_pages_copy("tce_kv_pages_scatter_f16", false, {k_pool, v_pool, table_row, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                         {const_cast<void *>(k_src), const_cast<void *>(v_src), kv_heads, src_max_keys}, hd, key0, nkeys, stream);
 }
 
 int tce_kv_pages_gather_f16(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
                             int kv_heads, int hd, int dst_max_keys, int key0, int nkeys, void *stream) {
-    return kv_pages_copy("tce_kv_pages_gather_f16", true, k_dst, v_dst, const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, table_stride, page_keys, num_pages,
-                         kv_heads, hd, dst_max_keys, key0, nkeys, stream);
-}
-
-static int kv_pages_copy_fp8(const char *who, bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys,
-                             int num_pages, int kv_heads, int hd, int lin_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream) {
-    if (!k_lin || !v_lin || !k_pool || !v_pool || !table_row) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
-    if (table_stride < 1 || num_pages < 1 || kv_heads < 1 || lin_max_keys < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_stride, num_pages, kv_heads, max_keys >= 1", who);
-    if (key0 < 0 || nkeys < 1 || (long long)key0 + nkeys > lin_max_keys || (long long)key0 + nkeys > (long long)table_stride * page_keys)
-        return fail(TCE_ERR_BAD_ARG, "%s: rows [%d, %d + %d) must lie inside the contiguous cache (%d keys) and the table row (%d pages of %d)", who, key0, key0, nkeys,
-                    lin_max_keys, table_stride, page_keys);
-    if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
-    const void *ptrs[] = {k_lin, v_lin, k_pool, v_pool};
-    const char *names[] = {gather ? "k_dst" : "k_src", gather ? "v_dst" : "v_src", "k_pool", "v_pool"};
-    for (int i = 0; i < 4; ++i)
-        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
-    if (reinterpret_cast<uintptr_t>(table_row) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: the table row must be int32-aligned", who);
-    hipError_t he = hipSuccess;
-    const int rc = tce::launch_kv_pages_copy_fp8(gather, k_lin, v_lin, k_pool, v_pool, table_row, page_keys, num_pages, kv_heads, lin_max_keys, key0, nkeys, k_scale_log2,
-                                                 v_scale_log2, static_cast<hipStream_t>(stream), &he);
-    return rc == TCE_ERR_HIP ? hip_fail(he, who) : rc;
+    return kv_pages_copy("tce_kv_pages_gather_f16", true, {const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                         {k_dst, v_dst, kv_heads, dst_max_keys}, hd, key0, nkeys, stream);
 }
 
 int tce_kv_pages_scatter_fp8(const void *k_src, const void *v_src, void *k_pool, void *v_pool, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
                              int kv_heads, int hd, int src_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream) {
-    return kv_pages_copy_fp8("tce_kv_pages_scatter_fp8", false, const_cast<void *>(k_src), const_cast<void *>(v_src), k_pool, v_pool, table_row, table_stride, page_keys,
-                             num_pages, kv_heads, hd, src_max_keys, key0, nkeys, k_scale_log2, v_scale_log2, stream);
+    return kv_pages_copy("tce_kv_pages_scatter_fp8", false, {k_pool, v_pool, table_row, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                         {const_cast<void *>(k_src), const_cast<void *>(v_src), kv_heads, src_max_keys}, hd, key0, nkeys, stream);
 }
 
 int tce_kv_pages_gather_fp8(const void *k_pool, const void *v_pool, void *k_dst, void *v_dst, const int32_t *table_row, int table_stride, int page_keys, int num_pages,
                             int kv_heads, int hd, int dst_max_keys, int key0, int nkeys, int k_scale_log2, int v_scale_log2, void *stream) {
-    return kv_pages_copy_fp8("tce_kv_pages_gather_fp8", true, k_dst, v_dst, const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, table_stride, page_keys,
-                             num_pages, kv_heads, hd, dst_max_keys, key0, nkeys, k_scale_log2, v_scale_log2, stream);
+    return kv_pages_copy("tce_kv_pages_gather_fp8", true,
+                         {const_cast<void *>(k_pool), const_cast<void *>(v_pool), table_row, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                         {k_dst, v_dst, kv_heads, dst_max_keys}, hd, key0, nkeys, stream);
 }
 
 int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
                              uint32_t *violations, void *stream) {
-    if (!block_table || !pos_device || !violations) return fail(TCE_ERR_BAD_ARG, "tce_kv_block_table_check: null pointer");
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "tce_kv_block_table_check: page_keys %d (a power of two from 16 to 256)", page_keys);
-    if (table_stride < 1 || num_pages < 1 || batch < 1 || pos_bound < 0) return fail(TCE_ERR_BAD_ARG, "tce_kv_block_table_check: need table_stride, num_pages, batch >= 1 and pos_bound >= 0");
-    if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(pos_device) | reinterpret_cast<uintptr_t>(violations)) & 3)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_kv_block_table_check: int32-aligned pointers");
+    static const char *who = "tce_kv_block_table_check";
+    const tce::KvPages pg{nullptr, nullptr, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0};
+    if (!pos_device || !violations) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = check_pages(who, pg, false)) return rc;
+    if (batch < 1 || pos_bound < 0) return fail(TCE_ERR_BAD_ARG, "%s: need batch >= 1 and pos_bound >= 0", who);
+    if (const int rc = check_aligned(who, 4, {{"block_table", block_table}, {"pos_device", pos_device}, {"violations", violations}})) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_kv_block_table_check(block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_kv_block_table_check(pg, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "block table check launch") : rc;
 }
 
@@ -1691,79 +1660,50 @@ const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int ca
     return buf;
 }
 
-int tce_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride, int page_keys,
-                                    int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, int hd,
-                                    const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2,
-                                    void *stream) {
-    static const char *who = "tce_attention_prefill_paged_fp8";
-    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
-    if (table_stride < 1 || num_pages < 1 || table_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_rows, table_stride, num_pages >= 1", who);
-    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
-    if (heads <= 0 || total_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need heads, total_rows > 0", who);
-    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
-    if (const int rc = check_fp8_scales(who, k_scale_log2, v_scale_log2)) return rc;
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
-    const int rcs = check_prefill_segments(who, segments, num_segments, table_rows, (long long)table_stride * page_keys, total_rows);
-    if (rcs != TCE_OK) return rcs;
-    const int width = (heads + 2 * kv_heads) * hd;
-    if (ld_qkv == 0) ld_qkv = width;
-    if (ld_out == 0) ld_out = heads * hd;
-    if (ld_qkv < width || ld_out < heads * hd) return fail(TCE_ERR_BAD_ARG, "%s: a leading dimension is shorter than its row", who);
-    if (ld_qkv % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_qkv must be a multiple of 8 (16-byte pieces)", who);
-    if (ld_out % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 7)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_out must be a multiple of 4 and out 8-byte aligned (8-byte stores)", who);
-    const void *ptrs[] = {qkv, k_pool, v_pool, cosv, sinv, workspace};
-    const char *names[] = {"qkv", "k_pool", "v_pool", "cos_table", "sin_table", "workspace"};
-    for (int i = 0; i < 6; ++i)
-        if (reinterpret_cast<uintptr_t>(ptrs[i]) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %s must be 16-byte aligned", who, names[i]);
-    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
+// r: ld_qkv / ld_out 0 = dense.  The only entry point that knows the table's row count: a segment names its slot.
+static int paged_prefill(const char *who, const tce::KvPages &pg, const tce::AttnStepArgs &s, tce::PrefillRows r, void *stream) {
+    const tce_prefill_segment *segments = reinterpret_cast<const tce_prefill_segment *>(r.segments);
+    if (!s.qkv || !s.out || !s.workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = check_pages(who, pg)) return rc;
+    if (const int rc = check_rope_pair(who, s.cosv, s.sinv)) return rc;
+    if (pg.table_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_rows >= 1", who);
+    if (const int rc = check_row_keys(who, pg)) return rc;
+    if (s.heads <= 0 || r.total_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need heads, total_rows > 0", who);
+    if (const int rc = check_heads(who, s.heads, s.kv_heads, s.hd)) return rc;
+    if (const int rc = check_prefill_segments(who, segments, r.nseg, pg.table_rows, row_keys(pg), r.total_rows)) return rc;
+    const int width = (s.heads + 2 * s.kv_heads) * s.hd;
+    if (r.ld_qkv == 0) r.ld_qkv = width;
+    if (r.ld_out == 0) r.ld_out = s.heads * s.hd;
+    if (r.ld_qkv < width || r.ld_out < s.heads * s.hd) return fail(TCE_ERR_BAD_ARG, "%s: a leading dimension is shorter than its row", who);
+    if (r.ld_qkv % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_qkv must be a multiple of 8 (16-byte pieces)", who);
+    if (r.ld_out % 4 != 0 || (reinterpret_cast<uintptr_t>(s.out) & 7)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_out must be a multiple of 4 and out 8-byte aligned (8-byte stores)", who);
+    if (const int rc = check_aligned(who, 16, {{"qkv", s.qkv}, {"k_pool", pg.k_pool}, {"v_pool", pg.v_pool}, {"cos_table", s.cosv}, {"sin_table", s.sinv}, {"workspace", s.workspace}}))
+        return rc;
+    if (const int rc = check_aligned(who, 4, {{"block_table", pg.table}})) return rc;
     int form = 0, pair = 0, blocks = 0, wgs = 0;
-    if (tce::describe_attention_prefill_paged(heads, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, &form, &pair, &blocks, &wgs) != TCE_OK)
+    if (tce::describe_attention_prefill_paged(s.heads, r.causal, r.segments, r.nseg, &form, &pair, &blocks, &wgs) != TCE_OK)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
-    tce::half_t ah;
-    __builtin_memcpy(&ah, &alpha_bits, 2);
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_prefill_paged_fp8(qkv, ld_qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, causal ? 1 : 0, out, ld_out, workspace,
-                                                           heads, kv_heads, reinterpret_cast<const int *>(segments), num_segments, total_rows, (float)ah, k_scale_log2,
-                                                           v_scale_log2, static_cast<hipStream_t>(stream), &he);
-    if (rc == TCE_ERR_HIP) return hip_fail(he, "fp8 paged attention prefill launch");
+    const int rc = tce::launch_attention_prefill_paged(pg, s, r, static_cast<hipStream_t>(stream), &he);
+    if (rc == TCE_ERR_HIP) return hip_fail(he, "paged attention prefill launch");
     return rc == TCE_OK ? TCE_OK : fail(rc, "%s: unsupported shape", who);
 }
 
 int tce_attention_prefill_paged_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride, int page_keys,
                                     int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, int hd,
                                     const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, void *stream) {
-    static const char *who = "tce_attention_prefill_paged_f16";
-    if (!qkv || !k_pool || !v_pool || !block_table || !out || !workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if ((cosv == nullptr) != (sinv == nullptr)) return fail(TCE_ERR_BAD_ARG, "%s: cos and sin tables come together", who);
-    if (!page_keys_ok(page_keys)) return fail(TCE_ERR_BAD_ARG, "%s: page_keys %d (a power of two from 16 to 256)", who, page_keys);
-    if (table_stride < 1 || num_pages < 1 || table_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_rows, table_stride, num_pages >= 1", who);
-    if ((long long)table_stride * page_keys > 0x7fffffffLL) return fail(TCE_ERR_BAD_ARG, "%s: table_stride * page_keys overflows int", who);
-    if (heads <= 0 || total_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need heads, total_rows > 0", who);
-    if (kv_heads <= 0 || heads % kv_heads != 0) return fail(TCE_ERR_BAD_ARG, "%s: %d query heads do not divide over %d key / value heads", who, heads, kv_heads);
-    if (hd != 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (128 only: Llama's)", who, hd);
-    const int rcs = check_prefill_segments(who, segments, num_segments, table_rows, (long long)table_stride * page_keys, total_rows);
-    if (rcs != TCE_OK) return rcs;
-    const int width = (heads + 2 * kv_heads) * hd;
-    if (ld_qkv == 0) ld_qkv = width;
-    if (ld_out == 0) ld_out = heads * hd;
-    if (ld_qkv < width || ld_out < heads * hd) return fail(TCE_ERR_BAD_ARG, "%s: a leading dimension is shorter than its row", who);
-    if (ld_qkv % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_qkv must be a multiple of 8 (16-byte pieces)", who);
-    if (ld_out % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 7)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ld_out must be a multiple of 4 and out 8-byte aligned (8-byte stores)", who);
-    for (const void *p : {qkv, (const void *)k_pool, (const void *)v_pool, cosv, sinv, (const void *)workspace})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned pointers", who);
-    if (reinterpret_cast<uintptr_t>(block_table) & 3) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: block_table must be int32-aligned", who);
-    int form = 0, pair = 0, blocks = 0, wgs = 0;
-    if (tce::describe_attention_prefill_paged(heads, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, &form, &pair, &blocks, &wgs) != TCE_OK)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
-    tce::half_t ah;
-    __builtin_memcpy(&ah, &alpha_bits, 2);
-    hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_prefill_paged(qkv, ld_qkv, k_pool, v_pool, block_table, table_stride, page_keys, cosv, sinv, causal ? 1 : 0, out, ld_out, workspace, heads,
-                                                       kv_heads, reinterpret_cast<const int *>(segments), num_segments, total_rows, (float)ah, static_cast<hipStream_t>(stream), &he);
-    if (rc == TCE_ERR_HIP) return hip_fail(he, "paged attention prefill launch");
-    return rc == TCE_OK ? TCE_OK : fail(rc, "%s: unsupported shape", who);
+    return paged_prefill("tce_attention_prefill_paged_f16", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, false, 0, 0},
+                         {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
+                         {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream);
+}
+
+int tce_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride, int page_keys,
+                                    int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, int hd,
+                                    const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2,
+                                    void *stream) {
+    return paged_prefill("tce_attention_prefill_paged_fp8", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                         {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
+                         {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream);
 }
 
 int tce_layernorm_q_w8a8_group(const float *x, const float *ln_weight, const float *ln_bias, int m, int k, const tce_w8a8_desc *lin, int count,

@@ -255,13 +255,37 @@ void set_attention_prefill_waves(int w);  // 0 automatic, 4 / 8 forced
 int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, int ld_mask, int causal,
                              void *out, int ld_out, void *workspace, int heads, int kv_heads, int max_keys, int pos, int m, float alpha, hipStream_t stream,
                              hipError_t *hip_err);
-// the paged prefill: both launches on the paged step's pools and block table, up to 16 segments {slot, pos, m, row0} (int32 x 4 each: tce_prefill_segment) per
-// launch; UNSUPPORTED_SHAPE: more query blocks than one launch lists (1024).  describe: the form (4 / 8 / 14 / 18), pairing, query blocks and workgroups; no HIP call.
+// ---- the paged family's arguments, from the C ABI (tce_capi.hip: the refusal rules) to the launchers ----
+struct KvPages {  // the pools [num_pages][kv_heads][page_keys][hd] and the block table int32 [table_rows][table_stride] that names their pages
+    void *k_pool, *v_pool;
+    const int *table;
+    int table_rows;  // the prefill's segments name their row (slot); 0: not checked -- the steps use rows 0 .. batch - 1, the copies see one row
+    int table_stride, page_keys, num_pages;
+    bool fp8;  // e4m3 bytes with one power-of-two exponent in [-8, 7] per pool (fp8_kv.hpp), else fp16
+    int k_scale_log2, v_scale_log2;
+};
+struct AttnStepArgs {  // what every batched step (contiguous, paged, multi-row) and the paged prefill take besides the cache
+    const void *qkv, *cosv, *sinv;
+    void *out, *workspace;
+    int batch, heads, kv_heads, hd;
+    const int *pos_device;
+    int pos_bound;
+    unsigned short alpha_bits;
+};
+struct PrefillRows {  // the paged prefill's rows: up to 16 segments {slot, pos, m, row0} (int32 x 4 each: tce_prefill_segment) of total_rows rows
+    int ld_qkv, ld_out, causal;
+    const int *segments;
+    int nseg, total_rows;
+};
+struct KvLinear {  // a contiguous single-sequence cache pair fp16 [kv_heads][max_keys][hd]: the other side of the page copies
+    void *k, *v;
+    int kv_heads, max_keys;
+};
+// the paged prefill: both launches on the pools and block table; UNSUPPORTED_SHAPE: more query blocks than one launch lists (1024), or an exponent outside [-8, 7].
+// describe: the form (4 / 8 / 14 / 18), pairing, query blocks and workgroups; no HIP call.
 size_t attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd);
 int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups);
-int launch_attention_prefill_paged(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                   const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
-                                   int total_rows, float alpha, hipStream_t stream, hipError_t *hip_err);
+int launch_attention_prefill_paged(const KvPages &pages, const AttnStepArgs &step, const PrefillRows &rows, hipStream_t stream, hipError_t *hip_err);
 // what a deferred attention step leaves for its consumer (tce_attention_deferred of the C ABI, field for field)
 struct AttnDeferred {
     int slots;   // chunk slots of the launch's grid: 1 = nothing deferred (`out` is final); 2 .. kAttnDeferMaxSlots = partial states per (query head, slot)
@@ -277,33 +301,15 @@ int launch_attention_decode_fast(const void *qkv, void *kc, void *vc, const void
 // the batched step: `batch` sequences in one launch, each with its own position word, cache slot, q/k/v and output rows and workspace slice
 void describe_attention_decode_batch(int heads, int kv_heads, int pos_bound, int *chunk, int *chunks, int *waves);
 size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int hd);
-int launch_attention_decode_batch(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads,
-                                  int kv_heads, int hd, int max_keys, const int *pos_dev, int pos_bound, unsigned short alpha_bits, hipStream_t stream,
-                                  hipError_t *hip_err);
-// the paged step: the batched step with the caches in pools of pages [num_pages][kv_heads][page_keys][hd] behind a block table int32 [batch][table_stride]; its
-// companions: rows of a contiguous single-sequence pair <-> the pages of one table row (gather: pages -> contiguous), and the table check (*violations = count)
+int launch_attention_decode_batch(const AttnStepArgs &step, void *kc, void *vc, int max_keys, hipStream_t stream, hipError_t *hip_err);
+// the paged step: the batched step with the caches in pools of pages behind a block table int32 [batch][table_stride].  rows_per_seq 0: the step; 1 ..
+// TCE_SPEC_MAX_ROWS: that many query rows per sequence.  Its companions: rows [key0, key0 + nkeys) of a contiguous pair <-> the pages of one table row (gather:
+// pages -> contiguous; e4m3 pools: scatter quantises, gather dequantises), and the table check (*violations = count)
 size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd);
-int launch_attention_decode_paged(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
-                                  void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
-                                  hipStream_t stream, hipError_t *hip_err);
-int launch_kv_pages_copy(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
-                         int lin_max_keys, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err);
-int launch_kv_block_table_check(const int *table, int table_stride, int page_keys, int num_pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations,
-                                hipStream_t stream, hipError_t *hip_err);
-// the e4m3 forms of the paged step, the paged prefill and the copies (fp8_kv.hpp: the format): pools of bytes [num_pages][kv_heads][page_keys][hd], one power-of-two
-// exponent in [-8, 7] per pool; UNSUPPORTED_SHAPE for an exponent outside it.  The contiguous side of the copies stays fp16: scatter quantises, gather dequantises.
 size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd);
-int launch_attention_decode_paged_rows(bool fp8, const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                       const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads, int hd, const int *pos_dev,
-                                       int pos_bound, unsigned short alpha_bits, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
-int launch_attention_decode_paged_fp8(const void *qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv, const void *sinv,
-                                      void *out, void *workspace, int batch, int heads, int kv_heads, int hd, const int *pos_dev, int pos_bound, unsigned short alpha_bits,
-                                      int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
-int launch_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int *table, int table_stride, int page_keys, const void *cosv,
-                                       const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads, int kv_heads, const int *segments, int nseg,
-                                       int total_rows, float alpha, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
-int launch_kv_pages_copy_fp8(bool gather, void *k_lin, void *v_lin, void *k_pool, void *v_pool, const int *table_row, int page_keys, int num_pages, int kv_heads,
-                             int lin_max_keys, int key0, int nkeys, int k_log2, int v_log2, hipStream_t stream, hipError_t *hip_err);
+int launch_attention_decode_paged(const KvPages &pages, const AttnStepArgs &step, int rows_per_seq, hipStream_t stream, hipError_t *hip_err);
+int launch_kv_pages_copy(const KvPages &pages, const KvLinear &lin, bool gather, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err);
+int launch_kv_block_table_check(const KvPages &pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err);
 int launch_rope_half(void *q, void *k, const void *cosv, const void *sinv, int heads, int len, int hd, int start_idx, hipStream_t stream, hipError_t *hip_err);
 int launch_softmax_half(const void *x, void *out, long long rows, int n, hipStream_t stream, hipError_t *hip_err);
 int launch_prefetch(const void *ptr, long long bytes, int workgroups, hipStream_t stream, hipError_t *hip_err);

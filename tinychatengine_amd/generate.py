@@ -388,13 +388,14 @@ def score_plan(prompts, free_slots, max_keys: int, vocab: int, chunk_rows: int =
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the front
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
-class BatchedGenerator:
-    """decoders: one PagedBatchedDecoder per layer over ONE PageAllocator, or one BatchedDecoder per layer.  final_gamma fp32 [hidden], lm_head a Linear_half_int4
-    [vocab][hidden], embed_table fp16 [vocab][hidden] (the reference's fp32 table rounded once).  graph=True captures the token step once (at construction, every row
-    inactive) and run() replays it."""
+class _GeneratorBase:
+    """What BatchedGenerator and speculative.SpeculativeGenerator share: the construction, the graph, admission, the replay loop and the read-outs.  A subclass gives
+    token_step() (what one replay runs) and launches_per_token, and calls _capture() once its own buffers exist."""
 
-    def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
-                 debug: bool = False, logprobs: bool = False):
+    def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None, top_k_bound: int, stop_ids, rows_per_seq: int | None = None,
+                 **sampler_kw):
+        """rows_per_seq None: the token step carries one row per slot, and admission runs its head on the step's xn / logits.  An integer: hidden / xn / logits are
+        batch * rows_per_seq rows and admission has batch rows of its own (_adm_xn / _adm_logits)."""
         import torch
         self.decoders = list(decoders)
         d0 = self.decoders[0]
@@ -409,38 +410,33 @@ class BatchedGenerator:
         assert embed_table.dtype == torch.float16 and embed_table.shape[1] == self.hidden_size and lm_head.in_features == self.hidden_size and lm_head.out_features >= self.vocab
         dev = embed_table.device
         self.device = dev
-        self.sampler = Sampler(self.batch, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, debug=debug, logprobs=logprobs)
-        self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
-        self.score_logits: list = []
+        self.sampler = Sampler(self.batch, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, **sampler_kw)
         self.book = SlotBook(self.batch, self.max_keys)
+        rows = self.batch * (rows_per_seq or 1)
+        h = lambda n, width: torch.zeros((n, width), dtype=torch.float16, device=dev)
         self.pos = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
-        self.hidden = torch.zeros((self.batch, self.hidden_size), dtype=torch.float16, device=dev)
-        self.xn = torch.zeros_like(self.hidden)
-        self.logits = torch.zeros((self.batch, lm_head.out_features), dtype=torch.float16, device=dev)
+        self.hidden, self.xn, self.logits = h(rows, self.hidden_size), h(rows, self.hidden_size), h(rows, lm_head.out_features)
         self._adm_pos = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
-        self._adm_hidden = torch.zeros_like(self.hidden)
-        self.launches_per_token = 1 + d0.LAUNCHES * len(self.decoders) + 1 + 1 + 2
+        self._adm_hidden = h(self.batch, self.hidden_size)
+        self._adm_xn, self._adm_logits = (self.xn, self.logits) if rows_per_seq is None else (h(self.batch, self.hidden_size), h(self.batch, lm_head.out_features))
         self._graph = None
-        if graph:
-            self.token_step()  # the warm-up: every row inactive -- nothing is embedded, appended or sampled; the gate/up form is settled
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self.token_step()
 
-    # ---- one token for every live row ----
-    def token_step(self) -> None:
-        embed_rows(self.embed_table, self.sampler.next_token, self.hidden, self.pos, self.pos_bound, self.sampler.workspace)
-        for d in self.decoders:
-            d.step(self.hidden, self.pos, self.pos_bound)
-        self._head(self.hidden, self.pos)
+    def _capture(self) -> None:
+        """token_step once eagerly -- the warm-up: every row inactive, so nothing is embedded, appended or sampled; the gate/up form is settled --, then once into the
+        graph run() replays."""
+        import torch
+        self.token_step()
+        torch.cuda.synchronize()
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.token_step()
 
-    def _head(self, hidden, pos) -> None:
-        """final norm -> lm_head at M = batch -> sampling (which advances or retires `pos`)"""
+    def _head(self, hidden, pos, xn, logits) -> None:
+        """final norm -> lm_head -> sampling (which advances or retires `pos`), at M = batch"""
         from .linear import _stream, rmsnorm_half
-        rmsnorm_half(hidden, self.final_gamma, self.eps, out=self.xn)
-        capi.check(capi.w4a16_forward(self.lm_head.desc(self.xn, self.logits), _stream()))
-        self.sampler.step(self.logits, pos, self.pos_bound)
+        rmsnorm_half(hidden, self.final_gamma, self.eps, out=xn)
+        capi.check(capi.w4a16_forward(self.lm_head.desc(xn, logits), _stream()))
+        self.sampler.step(logits, pos, self.pos_bound)
 
     # ---- admission ----
     def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None) -> list[int]:
@@ -486,17 +482,21 @@ class BatchedGenerator:
                 self.sampler.out_logprob[s].fill_(float("nan"))
             self._adm_hidden[s].copy_(r[-1])
             self._adm_pos[s] = len(ids) - 1
-        self._head(self._adm_hidden, self._adm_pos)  # the first token: the sampler leaves len(ids) -- or -1 -- in the admitted slots' words
+        self._head(self._adm_hidden, self._adm_pos, self._adm_xn, self._adm_logits)  # the first token: the sampler leaves len(ids) -- or -1 -- in the admitted slots' words
         slots = torch.tensor([s for s, *_ in adm], dtype=torch.int64, device=self.device)
         self.pos.index_copy_(0, slots, self._adm_pos.index_select(0, slots))
+        self._admitted([(s, ids) for s, ids, *_ in adm])
         for s, ids, p, sd, mn in adm:
             self.book.admit(s, len(ids), mn)
         return self._sync()
 
+    def _admitted(self, admitted) -> None:
+        """A subclass's own record of [(slot, prompt ids)], the first tokens sampled (sampler.next_token)."""
+
     # ---- running ----
     def run(self, n: int) -> list[int]:
-        """n tokens for every live slot: pages for the next n positions are reserved first (all or nothing), then the step is replayed n times with no host
-        synchronisation and no host-to-device copy in between, then ONE synchronise.  Returns the slots that retired (a stop id, or their budget)."""
+        """n replays of the token step for every live slot: pages for the positions they can touch are reserved first (all or nothing), then the step is replayed n
+        times with no host synchronisation and no host-to-device copy in between, then ONE synchronise.  Returns the slots that retired (a stop id, or their budget)."""
         if n < 1:
             raise ValueError("run: n >= 1")
         if self.allocator is not None:
@@ -506,7 +506,11 @@ class BatchedGenerator:
                 self._graph.replay()
             else:
                 self.token_step()
+            self._replayed()
         return self._sync()
+
+    def _replayed(self) -> None:
+        """Behind every replay of run(): a subclass's stream-ordered device work (no synchronisation)."""
 
     def _sync(self) -> list[int]:
         return self.book.update(self.pos.cpu().numpy(), self.sampler.generated())
@@ -529,6 +533,32 @@ class BatchedGenerator:
         self.pos[slot] = -1
         self.book.clear(slot)
         return self.allocator.release(slot) if self.allocator is not None else []
+
+    def embed_violations(self) -> int:
+        """Token ids tce_embed_rows_f16 refused since the workspace was made (0 unless something wrote next_token from outside)."""
+        return int(self.sampler.workspace[:4].cpu().numpy().view(np.uint32)[0])
+
+
+class BatchedGenerator(_GeneratorBase):
+    """decoders: one PagedBatchedDecoder per layer over ONE PageAllocator, or one BatchedDecoder per layer.  final_gamma fp32 [hidden], lm_head a Linear_half_int4
+    [vocab][hidden], embed_table fp16 [vocab][hidden] (the reference's fp32 table rounded once).  graph=True captures the token step once (at construction, every row
+    inactive) and run() replays it: one replay is one token for every live slot."""
+
+    def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
+                 debug: bool = False, logprobs: bool = False):
+        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs)
+        self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
+        self.score_logits: list = []
+        self.launches_per_token = 1 + self.decoders[0].LAUNCHES * len(self.decoders) + 1 + 1 + 2
+        if graph:
+            self._capture()
+
+    # ---- one token for every live row ----
+    def token_step(self) -> None:
+        embed_rows(self.embed_table, self.sampler.next_token, self.hidden, self.pos, self.pos_bound, self.sampler.workspace)
+        for d in self.decoders:
+            d.step(self.hidden, self.pos, self.pos_bound)
+        self._head(self.hidden, self.pos, self.xn, self.logits)
 
     # ---- scoring ----
     def free_slots(self) -> list[int]:
@@ -579,10 +609,6 @@ class BatchedGenerator:
             for s in slots:
                 self.allocator.release(s)
         return plan["split"](values.cpu().numpy())  # (synchronises)
-
-    def embed_violations(self) -> int:
-        """Token ids tce_embed_rows_f16 refused since the workspace was made (0 unless something wrote next_token from outside)."""
-        return int(self.sampler.workspace[:4].view(self.sampler.workspace.dtype).cpu().numpy().view(np.uint32)[0])
 
 
 class HostDrivenLoop:

@@ -273,16 +273,21 @@ class PagedBatchDecodeAttention:
 
     def step(self, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """BatchDecodeAttention.step on the pages: one launch; the table is read when the kernel runs."""
+        return self._step("tce_attention_decode_step_paged", None, qkv, pos_device, pos_bound, out)
+
+    def _step(self, entry: str, rows_per_seq: int | None, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None) -> torch.Tensor:
+        """The step's assertions and call, `entry`_f16 or _fp8, for batch * rows_per_seq rows (None: one row per sequence, and an entry point without that argument)."""
+        n = self.batch * (rows_per_seq or 1)
         rw = (self.heads + 2 * self.kv_heads) * self.hd
-        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == self.batch * rw
-        assert pos_device.dtype == torch.int32 and pos_device.is_cuda and pos_device.is_contiguous() and pos_device.numel() == self.batch
+        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == n * rw
+        assert pos_device.dtype == torch.int32 and pos_device.is_cuda and pos_device.is_contiguous() and pos_device.numel() == n
         if out is None:
-            out = torch.empty((self.batch, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
-        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == self.batch * self.heads * self.hd
+            out = torch.empty((n, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == n * self.heads * self.hd
         p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        L = capi.lib()
-        fn = L.tce_attention_decode_step_paged_fp8 if self.fp8 else L.tce_attention_decode_step_paged_f16
-        capi.check(fn(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out), p(self.workspace), self.batch, self.heads,
+        fn = getattr(capi.lib(), entry + ("_fp8" if self.fp8 else "_f16"))
+        rows = () if rows_per_seq is None else (rows_per_seq,)
+        capi.check(fn(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out), p(self.workspace), self.batch, *rows, self.heads,
                       self.kv_heads, self.hd, p(pos_device), int(pos_bound), self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
         return out
 
@@ -380,16 +385,14 @@ class PagedBatchedDecoder(BatchedDecoder):
     """BatchedDecoder on a paged cache: the same seven launches per layer (BatchedDecoder.step itself, with PagedBatchDecodeAttention.step as launch 3), the same
     prefill launches with the paged prefill in the middle.  One PageAllocator serves the decoders of all layers."""
 
-    def __init__(self, block: DecoderBlock, allocator: PageAllocator, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
-        # (no BatchedDecoder.__init__: it would allocate the contiguous caches)
-        self.block, self.batch, self.allocator = block, allocator.batch, allocator
-        dev = block.gamma1.device
-        self.attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, dev, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,
-                                                   k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
-        e = lambda n: torch.empty((self.batch, n), dtype=torch.float16, device=dev)
-        self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
-        self.act = e(block.ffn)
-        self._up = None
+    def __init__(self, block: DecoderBlock, allocator: PageAllocator, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, attention=None,
+                 rows: int | None = None):
+        """attention, rows: BatchedDecoder's (a subclass with an attention object of its own over the same allocator; the default is built here)."""
+        self.allocator = allocator
+        if attention is None:
+            attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,
+                                                  k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
+        super().__init__(block, allocator.batch, attention=attention, rows=rows)
 
     def prefill_many(self, admissions) -> None:
         """Admit several sequences at once: admissions [(slot, rows, pos)], at most 16, distinct slots; rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated

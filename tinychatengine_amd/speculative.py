@@ -7,7 +7,7 @@ spread over up to T tokens of the SAME sequence: the linears run at M = B T and 
     1        tce_draft_ngram              rows (token, position) per sequence: row 0 = the next input, rows 1 .. = what followed the last occurrence of the
                                           sequence's most recent n-gram in its own history (prompt lookup; no second model)
     1        tce_embed_rows_f16           B T rows (inactive rows skipped)
-    7 x L    the layers                   SpeculativeDecoder.step: BatchedDecoder's seven launches at B T rows, tce_attention_decode_step_paged_rows_* as launch 3
+    7 x L    the layers                   SpeculativeDecoder: BatchedDecoder.step's seven launches at B T rows, tce_attention_decode_step_paged_rows_* as launch 3
     1        tce_rmsnorm_half             the final norm
     1        tce_w4a16_forward            lm_head at M = B T
     3        tce_sample_verify_f16        select for all rows, draw per row, walk the chain: 1 .. T tokens per sequence
@@ -18,7 +18,7 @@ kept only if it EQUALS the token sampled in front of it.  There is no draft dist
     ngram_draft_reference, verify_reference   the two device pieces restated in numpy (verify_reference from sample_reference, ring_window and uniform only)
     SpecSlotBook                              which pages run(n) must reserve: positions up to p + n T - 1, whatever the budget (rejected rows are written too)
     SpeculativeDecoder                        PagedBatchedDecoder at B T rows
-    SpeculativeGenerator                      BatchedGenerator's surface (admit / run / tokens / logprobs / release) + rows_per_seq, ngram, emitted_per_step()
+    SpeculativeGenerator                      BatchedGenerator's surface (admit / run / tokens / logprobs / release: one base class) + rows_per_seq, ngram, emitted_per_step()
     HostDrivenSpeculativeLoop                 the same decoders and launches run eagerly, logits to the host, drafts / sampling / acceptance in numpy: the yardstick
 """
 from __future__ import annotations
@@ -31,7 +31,7 @@ import torch
 from . import capi
 from .linear import _stream, rmsnorm_half
 from .paged_kv import PagedBatchDecodeAttention, PagedBatchedDecoder
-from .generate import RING, Sampler, SamplingParams, SlotBook, embed_rows, ring_window, sample_reference, uniform
+from .generate import RING, Sampler, SamplingParams, SlotBook, _GeneratorBase, embed_rows, ring_window, sample_reference, uniform
 
 MAX_ROWS = capi.TCE_SPEC_MAX_ROWS
 
@@ -143,48 +143,19 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
     def step(self, qkv, pos_device, pos_bound: int, out=None):
         """qkv fp16 [batch * T][(heads + 2 kv_heads) * 128], pos_device int32 [batch * T]: the ROWS' positions (a prefix p, p + 1, ... per sequence, -1 behind
         it).  One launch."""
-        n = self.batch * self.rows_per_seq
-        rw = (self.heads + 2 * self.kv_heads) * self.hd
-        assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == n * rw
-        assert pos_device.dtype == torch.int32 and pos_device.is_cuda and pos_device.is_contiguous() and pos_device.numel() == n
-        if out is None:
-            out = torch.empty((n, self.heads * self.hd), dtype=torch.float16, device=qkv.device)
-        assert out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda and out.numel() == n * self.heads * self.hd
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        L = capi.lib()
-        fn = L.tce_attention_decode_step_paged_rows_fp8 if self.fp8 else L.tce_attention_decode_step_paged_rows_f16
-        capi.check(fn(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out), p(self.workspace), self.batch, self.rows_per_seq,
-                      self.heads, self.kv_heads, self.hd, p(pos_device), int(pos_bound), self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
-        return out
+        return self._step("tce_attention_decode_step_paged_rows", self.rows_per_seq, qkv, pos_device, pos_bound, out)
+
 
 class SpeculativeDecoder(PagedBatchedDecoder):
-    """PagedBatchedDecoder whose step runs batch * rows_per_seq rows: the same seven launches, the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill /
-    prefill_many are the parent's."""
+    """PagedBatchedDecoder whose step runs batch * rows_per_seq rows: the same seven launches (BatchedDecoder.step: hidden fp16 [batch * T][hidden], the position
+    words tce_draft_ngram's row_pos int32 [batch * T]), the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill / prefill_many are the parent's."""
 
     def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
         _check_rows(rows_per_seq)
-        self.block, self.batch, self.allocator, self.rows_per_seq = block, allocator.batch, allocator, int(rows_per_seq)
-        dev = block.gamma1.device
-        self.attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, dev, block.attention.cos, block.attention.sin, rows_per_seq=rows_per_seq,
-                                                  kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
-        self.rows = self.batch * self.rows_per_seq
-        e = lambda n: torch.empty((self.rows, n), dtype=torch.float16, device=dev)
-        self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
-        self.act = e(block.ffn)
-        self._up = None
-
-    def step(self, hidden, row_pos, pos_bound: int) -> None:
-        """hidden fp16 [batch * T][hidden], updated in place; row_pos int32 [batch * T] (tce_draft_ngram's)."""
-        blk = self.block
-        assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.rows, blk.hidden)
-        st = _stream()
-        rmsnorm_half(hidden, blk.gamma1, blk.eps, out=self.xn)
-        capi.check(capi.w4a16_forward(blk.qkv.desc(self.xn, self.qkv_out), st))
-        self.attention.step(self.qkv_out, row_pos, pos_bound, out=self.attn_out)
-        capi.check(capi.w4a16_forward(blk.o.desc(self.attn_out, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
-        rmsnorm_half(hidden, blk.gamma2, blk.eps, out=self.xn)
-        self._gate_up(self.xn, st)
-        capi.check(capi.w4a16_forward(blk.down.desc(self.act, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+        self.rows_per_seq = int(rows_per_seq)
+        attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin,
+                                             rows_per_seq=rows_per_seq, kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
+        super().__init__(block, allocator, attention=attention, rows=allocator.batch * self.rows_per_seq)
 
 
 def draft_ngram(history, script, pos_device, pos_bound: int, rows_per_seq: int, ngram: int, row_token, row_pos) -> None:
@@ -241,53 +212,31 @@ class Verifier:
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the front
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
-class SpeculativeGenerator:
+class SpeculativeGenerator(_GeneratorBase):
     """decoders: one SpeculativeDecoder per layer over ONE PageAllocator, all with the same rows_per_seq.  The token step is captured once in one torch.cuda.graph;
     one replay is 1 .. rows_per_seq tokens per live sequence.  script=True (a test hook) allocates `script` int32 [batch][hist_stride], -1 everywhere, which then
-    REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t]."""
+    REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t].  admit / tokens / logprobs / release are BatchedGenerator's."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False):
-        self.decoders = list(decoders)
-        d0 = self.decoders[0]
-        self.batch, self.hidden_size, self.rows_per_seq, self.ngram = d0.batch, d0.block.hidden, d0.rows_per_seq, int(ngram)
+        decoders = list(decoders)
+        self.rows_per_seq, self.ngram = decoders[0].rows_per_seq, int(ngram)
         _check_rows(self.rows_per_seq, self.ngram)
-        self.allocator = d0.allocator
-        assert all(d.allocator is self.allocator and d.batch == self.batch and d.rows_per_seq == self.rows_per_seq for d in self.decoders), "one allocator, one batch size, one T"
-        self.max_keys = d0.attention.max_keys
-        self.pos_bound = self.max_keys - 1
-        self.final_gamma, self.lm_head, self.embed_table = final_gamma, lm_head, embed_table
-        self.eps = d0.block.eps if eps is None else eps
-        self.vocab = embed_table.shape[0]
-        assert embed_table.dtype == torch.float16 and embed_table.shape[1] == self.hidden_size and lm_head.in_features == self.hidden_size and lm_head.out_features >= self.vocab
-        dev = embed_table.device
-        self.device = dev
-        B, T = self.batch, self.rows_per_seq
-        self.sampler = Sampler(B, self.vocab, max_new, dev, top_k_bound=top_k_bound, stop_ids=stop_ids, logprobs=logprobs)
+        assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
+        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, rows_per_seq=self.rows_per_seq, logprobs=logprobs)
+        B, T, dev = self.batch, self.rows_per_seq, self.device
         self.verifier = Verifier(self.sampler, T)
         self.book = SpecSlotBook(B, self.max_keys, T)
         self.hist_stride = self.max_keys + 8  # (the verifier writes index p + 1 + t <= max_keys)
         z = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=dev)
-        self.pos, self.row_token, self.row_pos = z(B, fill=-1), z(B * T), z(B * T, fill=-1)
+        self.row_token, self.row_pos = z(B * T), z(B * T, fill=-1)
         self.history = z(B, self.hist_stride)
         self.script = z(B, self.hist_stride, fill=-1) if script else None
-        self.hidden = torch.zeros((B * T, self.hidden_size), dtype=torch.float16, device=dev)
-        self.xn = torch.zeros_like(self.hidden)
-        self.logits = torch.zeros((B * T, lm_head.out_features), dtype=torch.float16, device=dev)
-        self._adm_pos = z(B, fill=-1)
-        self._adm_hidden = torch.zeros((B, self.hidden_size), dtype=torch.float16, device=dev)
-        self._adm_xn = torch.zeros_like(self._adm_hidden)
-        self._adm_logits = torch.zeros((B, lm_head.out_features), dtype=torch.float16, device=dev)
         self._emit_log = z(int(record_steps), B)
-        self._steps = 0
-        self.launches_per_token = 1 + 1 + d0.LAUNCHES * len(self.decoders) + 1 + 1 + 3
-        self._graph = None
+        self._steps, self._record = 0, True
+        self.launches_per_token = 1 + 1 + decoders[0].LAUNCHES * len(decoders) + 1 + 1 + 3
         if graph:
-            self.token_step()  # the warm-up: every sequence inactive
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self.token_step()
+            self._capture()
 
     # ---- one step: 1 .. T tokens for every live sequence ----
     def token_step(self) -> None:
@@ -299,54 +248,12 @@ class SpeculativeGenerator:
         capi.check(capi.w4a16_forward(self.lm_head.desc(self.xn, self.logits), _stream()))
         self.verifier.step(self.logits, self.row_token, self.row_pos, self.history, self.pos, self.pos_bound)
 
-    # ---- admission: BatchedGenerator.admit's launches (prefill, the first token through tce_sample_f16), then the history row ----
-    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None) -> list[int]:
-        """admit(slot, prompt_ids, params, seed, max_new), or admit([(slot, prompt_ids, params, seed, max_new), ...]): several sequences through ONE prefill_many.
-        Synchronises.  Returns the slots that retired on their first token."""
-        adm = slot if prompt_ids is None else [(slot, prompt_ids, params, seed, max_new)]
-        adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(self.sampler.log_stride if mn is None else mn)) for s, ids, p, sd, mn in adm]
-        if len({s for s, *_ in adm}) != len(adm):
-            raise ValueError("admit: a slot is named twice")
-        for s, ids, p, sd, mn in adm:
-            if not 0 <= s < self.batch:
-                raise IndexError(f"slot {s} of {self.batch}")
-            if self.book.pos[s] >= 0:
-                raise ValueError(f"slot {s} is live")
-            if any(not 0 <= t < self.vocab for t in ids):
-                raise ValueError("a prompt token lies outside the vocabulary")
-            p.check(self.sampler.top_k_bound)
-            if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
-                raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new 1 .. {self.sampler.log_stride}")
-        if any(self.allocator.pages[s] for s, *_ in adm):
-            raise ValueError("admit: a slot still holds pages (release it first)")
-        self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])  # all or nothing, before anything changes
-        rows = []
-        for s, ids, p, sd, mn in adm:
-            tok = torch.tensor(ids, dtype=torch.int32).to(self.device)
-            r = torch.empty((len(ids), self.hidden_size), dtype=torch.float16, device=self.device)
-            embed_rows(self.embed_table, tok, r, torch.zeros(len(ids), dtype=torch.int32, device=self.device), 0, self.sampler.workspace)
-            rows.append(r)
-        for d in self.decoders:
-            d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
-        self._adm_pos.fill_(-1)
-        for (s, ids, p, sd, mn), r in zip(adm, rows):
-            self.sampler.set_row(s, p, sd, mn, ids)
-            self.sampler.out_log[s].fill_(-1)
-            if self.sampler.logprobs:
-                self.sampler.out_logprob[s].fill_(float("nan"))
-            self._adm_hidden[s].copy_(r[-1])
-            self._adm_pos[s] = len(ids) - 1
-        rmsnorm_half(self._adm_hidden, self.final_gamma, self.eps, out=self._adm_xn)
-        capi.check(capi.w4a16_forward(self.lm_head.desc(self._adm_xn, self._adm_logits), _stream()))
-        self.sampler.step(self._adm_logits, self._adm_pos, self.pos_bound)  # the first token: leaves len(ids) -- or -1 -- in the admitted slots' words
-        slots = torch.tensor([s for s, *_ in adm], dtype=torch.int64, device=self.device)
-        self.pos.index_copy_(0, slots, self._adm_pos.index_select(0, slots))
+    def _admitted(self, admitted) -> None:
+        """The history rows the drafts are looked up in: the prompt, then the first token."""
         first = self.sampler.next_token.cpu().numpy()  # (synchronises)
-        for s, ids, p, sd, mn in adm:
+        for s, ids in admitted:
             row = torch.tensor(ids + [int(first[s])], dtype=torch.int32)
             self.history[s, :row.numel()].copy_(row)
-            self.book.admit(s, len(ids), mn)
-        return self._sync()
 
     def set_script(self, slot: int, tokens) -> None:
         """The test hook's row for `slot`: tokens[i] is fed as the draft for position i (-1: no draft from there on); the rest of the row is -1."""
@@ -362,44 +269,17 @@ class SpeculativeGenerator:
         """n steps -- n .. n T tokens -- for every live slot: pages for positions up to p + n T - 1 are reserved first (all or nothing: PagePoolExhausted and nothing
         changed), then the step is replayed n times with no host synchronisation, then ONE synchronise.  record: a stream-ordered device copy of `emitted` behind every
         replay, for emitted_per_step() (no synchronisation).  Returns the slots that retired."""
-        if n < 1:
-            raise ValueError("run: n >= 1")
-        self.book.reserve(self.allocator, n)
-        for _ in range(n):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self.token_step()
-            if record and self._steps < self._emit_log.shape[0]:
-                self._emit_log[self._steps].copy_(self.verifier.emitted)
-                self._steps += 1
-        return self._sync()
+        self._record = record
+        return super().run(n)
 
-    def _sync(self) -> list[int]:
-        return self.book.update(self.pos.cpu().numpy(), self.sampler.generated())
+    def _replayed(self) -> None:
+        if self._record and self._steps < self._emit_log.shape[0]:
+            self._emit_log[self._steps].copy_(self.verifier.emitted)
+            self._steps += 1
 
     def emitted_per_step(self) -> np.ndarray:
         """int32 [recorded steps][batch]: the tokens every slot emitted in each recorded replay (0: inactive)."""
         return self._emit_log[:self._steps].cpu().numpy()
-
-    def tokens(self, slot: int) -> list[int]:
-        n = int(self.sampler.generated()[slot])
-        return self.sampler.out_log[slot, :n].cpu().numpy().tolist()
-
-    def logprobs(self, slot: int) -> np.ndarray:
-        """fp32, one value per token of tokens(slot): BatchedGenerator.logprobs' values for the same tokens.  Needs logprobs=True."""
-        if not self.sampler.logprobs:
-            raise ValueError("logprobs: the generator was built without logprobs=True")
-        n = int(self.sampler.generated()[slot])
-        return self.sampler.out_logprob[slot, :n].cpu().numpy()
-
-    def release(self, slot: int) -> list[int]:
-        self.pos[slot] = -1
-        self.book.clear(slot)
-        return self.allocator.release(slot)
-
-    def embed_violations(self) -> int:
-        return int(self.sampler.workspace[:4].cpu().numpy().view(np.uint32)[0])
 
 
 class HostDrivenSpeculativeLoop:
