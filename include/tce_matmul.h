@@ -393,6 +393,45 @@ TCE_API int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_po
                                                      int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int k_scale_log2,
                                                      int v_scale_log2, void *stream);
 
+/* SLIDING-WINDOW attention on the paged cache (Mistral-7B v0.1, the local layers of Gemma-2/3, Phi-3): window = W >= 1, a query at position p weighs keys lo(p) .. p,
+ * lo(p) = max(0, p - W + 1) -- the last W keys, its own included.  A per-layer property: each entry point below is its unwindowed namesake with `int window` in front
+ * of `stream`, and everything not said here (arguments, workspace, inactive rows, appended rows, e4m3 rules, refusals) is the namesake's.
+ *   key range   the step's workgroups cover keys from base = lo & ~3 on, not from 0: the keys base .. lo - 1 of the first group of four are loaded -- they lie in the
+ *               page of key lo -- and weigh NOTHING (excluded from the maximum and the sum, like keys beyond the position).  The prefill's query blocks walk key tiles
+ *               from the tile of lo(their first row) on; tiles wholly below are neither requested nor computed.
+ *   cut         the batched step's fitted rule for min(pos_bound + 1, W + 3) keys: the grid follows the window, not pos_bound
+ *               (tce_attention_decode_describe_paged_window; text as tce_attention_decode_describe_paged).  The workspace and its per-sequence slices are the unwindowed
+ *               step's, so one workspace serves both.
+ *   trust       of an active row only table words lo / page_keys .. pos / page_keys become addresses (prefill: from lo(first row of the block) / page_keys); the words
+ *               below may hold anything -- the pages they named can be handed to another sequence (PageAllocator.release_behind).  Page numbers are NOT validated:
+ *               tce_kv_block_table_check_window is tce_kv_block_table_check restricted to the words a windowed row follows.
+ *   identities  (no tolerance) 1. NEVER BINDING: with W >= pos_bound + 1 (prefill: W >= pos + m of every segment) `out` and every pool byte equal the unwindowed entry
+ *               point's.  2. RE-BASED: where lo is a multiple of page_keys, the windowed step at pos = lo + W - 1 equals the unwindowed step at position W - 1 with
+ *               pos_bound W + 2, a table row that starts at word lo / page_keys and cos / sin tables advanced by lo rows -- both launches use the same cut.
+ *               Elsewhere: a float64 evaluation over keys lo .. p within the steps' stated bound.
+ *   refusals    window < 1: TCE_ERR_BAD_ARG; the prefill with causal == 0: TCE_ERR_BAD_ARG (a row's window ends at its own key).  Before any HIP call, BAD_ARG rules
+ *               before UNSUPPORTED_SHAPE rules, as everywhere in the paged family.
+ * NOT BUILT: the multi-row (speculative) step with a window; windows on contiguous caches and on the single-sequence step; attention sinks (first keys kept beside the
+ * window: the pools hold ROTATED keys, so positions inside the cache would have to be re-rotated). */
+TCE_API int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len);
+TCE_API int tce_attention_decode_step_paged_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                       const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
+                                                       int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int window, void *stream);
+TCE_API int tce_attention_decode_step_paged_window_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                       const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
+                                                       int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int k_scale_log2,
+                                                       int v_scale_log2, int window, void *stream);
+TCE_API int tce_attention_prefill_paged_window_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                                   int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out,
+                                                   void *workspace, int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments,
+                                                   int total_rows, unsigned short alpha_half_bits, int window, void *stream);
+TCE_API int tce_attention_prefill_paged_window_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                                   int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out,
+                                                   void *workspace, int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments,
+                                                   int total_rows, unsigned short alpha_half_bits, int k_scale_log2, int v_scale_log2, int window, void *stream);
+TCE_API int tce_kv_block_table_check_window(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                                            uint32_t *violations, int window, void *stream);
+
 /* Device-side sampling: what the reference does on the host between Int4LlamaForCausalLM::forward and the next token's Embedding (llm/src/Generate.cc driven by
  * LLaMA3Generate.cc:127-198), for `batch` rows of fp16 logits [batch][ld] (lm_head's output at M = batch; vocab <= ld) in TWO launches (csrc/sampling.hip), so that a
  * captured decode graph yields one token per replay for every sequence with no host round trip.  Per ACTIVE row (0 <= pos_device[b] <= pos_bound, the project's rule;

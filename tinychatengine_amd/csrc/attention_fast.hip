@@ -69,6 +69,12 @@ struct PagedRowsAttnArgs : PagedFp8AttnArgs {
     int rows_per_seq;  // 1 .. TCE_SPEC_MAX_ROWS
 };
 
+// the windowed paged step's (sliding-window attention): the e4m3 step's arguments -- the two scales are unused on fp16 pools -- and W = window: a row at position p
+// weighs keys max(0, p - W + 1) .. p.  chunk / chunks were cut for min(pos_bound + 1, W + 3) keys
+struct PagedWindowAttnArgs : PagedFp8AttnArgs {
+    int window;  // >= 1
+};
+
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
     auto dpp = [](float x, auto ctrl) {
         return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, false));
@@ -139,9 +145,20 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 // pool row, nobody waits for anybody.  The caller guarantees that a sequence's active rows are a prefix with consecutive positions (include/tce_matmul.h); all the kernel
 // does about it is to clamp t to pos, so that no address is formed from a negative position.  The key loop is the paged step's: the wave-uniform rare-block test is a
 // range overlap instead of a membership, and the work it guards is the only per-key addition.
-template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false>
+// WINDOW (with PAGED, not with ROWS): the row weighs keys lo .. pos only, lo = max(0, pos - W + 1) (PagedWindowAttnArgs).  The workgroup's key range starts at
+// base = lo & ~3 instead of 0 -- chunk slot c covers keys base + c * chunk .. --, so the span pos - base + 1 <= W + 3 is what the grid was cut for, whatever pos is.
+// Keys base .. lo - 1 of the first group of four are loaded -- they lie in the page of key lo, a group of four never crosses a page -- and weigh nothing, exactly as
+// keys at and beyond kw1 do: excluded from the maximum and the sum by the same rare-block text.  TABLE WORDS: kw0 now depends on the position, so a wave's words
+// cannot be requested in front of the position word's wait: the request follows it, ONE MORE DEPENDENT ROUND TRIP in the chain position word -> table word -> cache
+// rows (DESIGN.md 3.4 says why the alternatives were not taken).  Lane i asks for word kw0 / page_keys + i clamped into [lo / page_keys, pos / page_keys] -- the only
+// words of the row that become addresses; everything below may name a page that was given back --, lane 63 for word pos / page_keys: the page wholly invalid groups
+// are read from (word 0's page may be gone).  The appending wave, newrow, RoPE, the e4m3 round trip of the own row, both merges, the counters and the inactive rows
+// are the paged step's text.
+template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false, bool WINDOW = false>
 __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
-    const std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>> a) {
+    const std::conditional_t<WINDOW, PagedWindowAttnArgs,
+                             std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>>> a) {
+    static_assert(!WINDOW || (PAGED && !ROWS && NW == 4), "a window exists on the paged step only (one row per sequence)");
     static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
     static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
     static_assert(!ROWS || (PAGED && NW == 4), "several rows per sequence exist on pages only");
@@ -161,11 +178,28 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
     const size_t seq_out = (size_t)seq * a.heads * kHD, seq_ws = BATCH ? seq * attn_workspace_words(a.heads, a.max_keys) : 0;
     // grp: this workgroup's group of R consecutive query heads (R == rep: all the query heads of a key / value head, its cache rows streamed
     // once for all of them; R < rep: rep / R workgroups read the same cache rows -- from HBM once, the others from the memory-side cache)
-    const int grp = blockIdx.x / a.chunks, c = blockIdx.x - grp * a.chunks;
+    // WINDOW: the same (query head, chunk slot) pairs in another order.  The cut for W + 3 keys is rarely a power of two of slots (W = 4096: nine), and with
+    // blockIdx.x = grp * 9 + c the rep query heads that stream the SAME cache rows land on rep different XCDs -- workgroups are dealt round-robin over the eight of
+    // them, each with an L2 of its own (MI355X_MICROARCH.md; observed, not promised: only the speed depends on it) -- so every row came from beyond the L2 rep times:
+    // 1.9 x the time of the unwindowed step over as many keys (profiles/window/).  Here pair p = key / value head * chunks + c takes the blockIdx.x that are
+    // congruent to p modulo 8, its rep query heads 8 apart; the grid is padded to whole groups of 8 pairs and the padding returns at once.
+    const unsigned bx = [&]() -> unsigned {
+        if constexpr (WINDOW) {
+            const int p = (int)(blockIdx.x / (8u * a.rep)) * 8 + (int)(blockIdx.x & 7u);
+            if (p >= a.kv_heads * a.chunks) return ~0u;
+            return (unsigned)(((p / a.chunks) * a.rep + (int)((blockIdx.x >> 3) % (unsigned)a.rep)) * a.chunks + p % a.chunks);  // query head * chunks + c, as below
+        } else {
+            return blockIdx.x;
+        }
+    }();
+    if constexpr (WINDOW) {
+        if (bx == ~0u) return;
+    }
+    const int grp = bx / a.chunks, c = bx - grp * a.chunks;
     // PAGED: lane i's table word kw0 / page_keys + i of this sequence's row (clamped into the row; lane 63: word 0, which every active row owns -- the page that
     // wholly invalid groups of four are read from).  Requested here, in front of the position word's wait: a load of an int inside the table, whatever it holds.
     int tabw = 0, tab_e0 = 0;
-    if constexpr (PAGED) {
+    if constexpr (PAGED && !WINDOW) {
         const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l_ = threadIdx.x & 63;
         tab_e0 = (c * a.chunk + w_ * (a.chunk / NW)) >> a.page_shift;
         const int e = l_ == 63 ? 0 : (tab_e0 + l_ < a.table_stride ? tab_e0 + l_ : a.table_stride - 1);
@@ -186,15 +220,30 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         }
     }
     const int keys = pos + 1;
+    // WINDOW: the first key that weighs, and the first key of the workgroups' range (a multiple of four: the groups of four stay aligned); else 0
+    [[maybe_unused]] const int lo = [&]() -> int {
+        if constexpr (WINDOW) return pos - a.window + 1 > 0 ? pos - a.window + 1 : 0;
+        else return 0;
+    }();
+    const int base = WINDOW ? lo & ~3 : 0;
     // ROWS: the rows of this sequence in front of this one, all in flight in this launch (keys pos - tprev .. pos - 1)
     [[maybe_unused]] const int tprev = ROWS ? ((int)blockIdx.y < pos ? (int)blockIdx.y : pos) : 0;
-    const int chunks = a.pos_dev ? (keys + a.chunk - 1) / a.chunk : a.chunks;  // active chunks (<= the grid's chunk slots)
+    const int chunks = a.pos_dev ? (keys - base + a.chunk - 1) / a.chunk : a.chunks;  // active chunks (<= the grid's chunk slots)
     if (c >= chunks) return;
+    if constexpr (WINDOW) {
+        // the table words, behind the position (see above): of an active row, words lo / page_keys .. pos / page_keys and no other
+        const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l_ = threadIdx.x & 63;
+        const int e_lo = lo >> a.page_shift, e_hi = pos >> a.page_shift;
+        tab_e0 = (base + c * a.chunk + w_ * (a.chunk / NW)) >> a.page_shift;
+        int e = l_ == 63 ? e_hi : tab_e0 + l_;
+        e = e < e_lo ? e_lo : (e > e_hi ? e_hi : e);
+        tabw = a.table[(size_t)tseq * a.table_stride + e];
+    }
     const int head = (grp * R) / a.rep;  // the key / value head
     const bool appends = (grp * R) % a.rep == 0;  // one workgroup group per key / value head writes the token's row into the caches
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int slot = lane >> 4, piece = lane & 15;
-    const int key0 = c * a.chunk, key1 = key0 + a.chunk < keys ? key0 + a.chunk : keys;
+    const int key0 = base + c * a.chunk, key1 = key0 + a.chunk < keys ? key0 + a.chunk : keys;
     const half_t *cosr = a.cosv ? a.cosv + (size_t)pos * kHD : nullptr, *sinr = a.sinv ? a.sinv + (size_t)pos * kHD : nullptr;
     const size_t hoff = (size_t)head * kHD;
     // ---- this wave's keys: chunk / 4 consecutive ones, 4 per step.  Their addresses depend on nothing but the arguments, so the
@@ -227,6 +276,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
                 // g / page_keys <= pos / page_keys is one the row owns and one of this wave's (lane g / page_keys - tab_e0 < 63 holds it); a slot past the range
                 // is clamped to keys - 1, which then lies in the same group (kw1 is a multiple of 4 or keys itself) and so in the same page.  g >= kw1: nothing of
                 // the group is weighted; it is read from rows 0 .. 3 of word 0's page (lane 63) -- never from a word past pos / page_keys.
+                // WINDOW: g >= base, so g / page_keys >= lo / page_keys too (base and lo share a group of four, hence a page); lane 63 holds word pos / page_keys.
                 const int g = kw0 + it0 + u * 4;
                 const bool live = g < kw1;
                 const int page = __builtin_amdgcn_readlane(tabw, __builtin_amdgcn_readfirstlane(live ? (g >> a.page_shift) - tab_e0 : 63));
@@ -356,11 +406,12 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         // the rare blocks -- the one that runs past the wave's range, the one that holds the token's own row -- are told apart by a wave-uniform test, so the
         // others carry no per-slot validity arithmetic at all
         const int b0 = kw0 + it0;
-        if (b0 + BLK * 4 > kw1 || (pos >= b0 && pos - tprev < b0 + BLK * 4)) {  // (tprev: 0 unless ROWS)
+        if (b0 + BLK * 4 > kw1 || (pos >= b0 && pos - tprev < b0 + BLK * 4) || (WINDOW && b0 < lo)) {  // (tprev: 0 unless ROWS; WINDOW: the block of keys base .. lo - 1)
 #pragma unroll
             for (int u = 0; u < BLK; ++u) {
                 const int key = b0 + u * 4 + slot;
                 valid[u] = key < kw1;
+                if constexpr (WINDOW) valid[u] = valid[u] && key >= lo;
                 if constexpr (ROWS) {
                     if (key >= pos - tprev && key <= pos) {  // this launch's rows of the sequence: in LDS, in the pool only once their workgroups have run
                         kk[u] = *reinterpret_cast<const half8_t *>(&newrow[key - (pos - tprev)][0][piece * 8]);
@@ -700,6 +751,13 @@ void describe_attention_decode_batch(int heads, int kv_heads, int pos_bound, int
     *chunks = (pos_bound + 1 + *chunk - 1) / *chunk;
 }
 
+// the windowed paged step's cut: the same rule for the keys a workgroup group can span, min(pos_bound + 1, window + 3) -- base = lo & ~3 puts up to three keys in front
+// of the window's first (no HIP call)
+int attention_window_cut_keys(int pos_bound, int window) { return (long long)window + 3 < (long long)pos_bound + 1 ? window + 3 : pos_bound + 1; }
+void describe_attention_decode_window(int heads, int kv_heads, int pos_bound, int window, int *chunk, int *chunks, int *waves) {
+    describe_attention_decode_batch(heads, kv_heads, attention_window_cut_keys(pos_bound, window) - 1, chunk, chunks, waves);
+}
+
 size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int hd) {
     if (batch <= 0) return 0;
     return (size_t)batch * attention_decode_workspace_bytes(heads, max_keys, hd);
@@ -786,8 +844,10 @@ __global__ __launch_bounds__(256) void kv_pages_copy_fp8_kernel(half_t *k_lin, h
 
 // *violations = the number of table words an active row would follow that are not page numbers, plus the active rows whose position needs a word past the row
 // (one workgroup: the tables are a few thousand words)
+// WINDOW: of the words a WINDOWED row would follow, lo / page_keys .. pos / page_keys (lo = max(0, pos - window + 1)); else from word 0 (`window` unused)
+template <bool WINDOW>
 __global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *table, int table_stride, int page_shift, int num_pages, int batch, const int *pos_dev,
-                                                                    int pos_bound, unsigned *violations) {
+                                                                    int pos_bound, unsigned *violations, int window) {
     __shared__ unsigned bad;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
@@ -800,7 +860,8 @@ __global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *t
             if (threadIdx.x == 0) ++mine;
             last = table_stride - 1;
         }
-        for (int e = threadIdx.x; e <= last; e += 1024) {
+        const int first = WINDOW && pos - window + 1 > 0 ? (pos - window + 1) >> page_shift : 0;
+        for (int e = first + threadIdx.x; e <= last; e += 1024) {
             const int page = table[(size_t)b * table_stride + e];
             if (page < 0 || page >= num_pages) ++mine;
         }
@@ -839,6 +900,8 @@ static float host_pow2(int e) {
 
 // pages.fp8: the pools are e4m3 bytes and the two exponents apply; everything else is one text for both
 // rows = 0: the step; rows >= 1: the multi-row step with rows_per_seq = rows -- the same cut (pos_bound alone decides it), grid (heads x chunk slots, rows, batch)
+// s.window >= 1 (rows = 0 only): the windowed step -- the cut and the grid are made for min(pos_bound + 1, window + 3) keys.  The workspace slices stay where every
+// other launch on the same workspace has them (one per table row's keys): the arrival counters at their heads are zero between launches only there
 int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int rows, hipStream_t stream, hipError_t *hip_err) {
     const int batch = s.batch, heads = s.heads, kv_heads = s.kv_heads, hd = s.hd, pos_bound = s.pos_bound, table_stride = pg.table_stride;
     const bool fp8 = pg.fp8;
@@ -847,7 +910,7 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         (long long)pos_bound >= ((long long)table_stride << shift))
         return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && !(fp8_log2_ok(pg.k_scale_log2) && fp8_log2_ok(pg.v_scale_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
-    if (rows < 0 || rows > TCE_SPEC_MAX_ROWS) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (rows < 0 || rows > TCE_SPEC_MAX_ROWS || s.window < 0 || (s.window && rows)) return TCE_ERR_UNSUPPORTED_SHAPE;
     PagedRowsAttnArgs a{};
     a.rows_per_seq = rows;
     a.qkv = static_cast<const half_t *>(s.qkv);
@@ -871,7 +934,8 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
     a.table_stride = table_stride;
     a.page_shift = shift;
     int nw = 4;
-    describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
+    if (s.window) describe_attention_decode_window(heads, kv_heads, pos_bound, s.window, &a.chunk, &a.chunks, &nw);
+    else describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
     if (a.chunks > 1024 || nw != 4) return TCE_ERR_UNSUPPORTED_SHAPE;
     half_t ah;
     __builtin_memcpy(&ah, &s.alpha_bits, 2);
@@ -882,7 +946,14 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         a.k_inv = host_pow2(-pg.k_scale_log2);
         a.v_inv = host_pow2(-pg.v_scale_log2);
     }
-    if (rows) {
+    if (s.window) {
+        PagedWindowAttnArgs w{};
+        static_cast<PagedFp8AttnArgs &>(w) = a;
+        w.window = s.window;
+        const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, batch);  // (whole groups of 8 (key / value head, chunk slot) pairs x rep query heads: see the kernel)
+        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, false, true>), grid, dim3(256), 0, stream, w);
+        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, false, true>), grid, dim3(256), 0, stream, w);
+    } else if (rows) {
         const dim3 grid(heads * a.chunks, rows, batch);
         if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, true>), grid, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, true>), grid, dim3(256), 0, stream, a);
@@ -921,10 +992,11 @@ int launch_kv_pages_copy(const KvPages &pg, const KvLinear &lin, bool gather, in
     return TCE_OK;
 }
 
-int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err) {
+int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err, int window) {
     const int shift = page_shift_of(pg.page_keys);
     if (shift < 0 || pg.table_stride < 1 || batch < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
-    hipLaunchKernelGGL(kv_block_table_check_kernel, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations);
+    if (window > 0) hipLaunchKernelGGL(kv_block_table_check_kernel<true>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, window);
+    else hipLaunchKernelGGL(kv_block_table_check_kernel<false>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, 0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;

@@ -248,6 +248,11 @@ struct PagedBlockFp8Args : PagedBlockArgs {
     float k_scale, v_scale;  // 2^k_scale_log2, 2^v_scale_log2
 };
 
+// the windowed form's (causal only; the two scales are unused on fp16 pools): row i of the segment sits at p = pos + i and weighs keys max(0, p - window + 1) .. p
+struct PagedBlockWindowArgs : PagedBlockFp8Args {
+    int window;  // >= 1
+};
+
 // what differs between the forms in the statements they share: the row count and first row of the segment inside qrot / out, and a key / value head's base
 __device__ __forceinline__ int qrows(const PrefillArgs &a) { return a.m; }
 __device__ __forceinline__ int qrows(const PagedBlockArgs &a) { return a.total_rows; }
@@ -272,6 +277,12 @@ struct TileWords<true> {
         const int e = (kt * kBK + 16 * (lane & 3)) >> a.page_shift;
         v = a.trow[e < lastw ? e : lastw];
     }
+    // WINDOW: additionally clamped from below to the word of the block's first visible key, `firstw`: words under it may name pages that were given back
+    __device__ __forceinline__ void request_from(const PagedBlockArgs &a, int kt, int kend, int lane, int firstw) {
+        const int lastw = (kend - 1) >> a.page_shift;
+        const int e = (kt * kBK + 16 * (lane & 3)) >> a.page_shift;
+        v = a.trow[e < firstw ? firstw : (e < lastw ? e : lastw)];
+    }
     __device__ __forceinline__ void latch() {
 #pragma unroll
         for (int r = 0; r < 4; ++r) w[r] = __builtin_amdgcn_readlane(v, r);
@@ -280,9 +291,13 @@ struct TileWords<true> {
 
 // FP8 (with PAGED): a row of the pools is 128 e4m3 bytes; fetch_tile requests 8-byte pieces and the write into LDS dequantises them (exactly: fp8_kv.hpp), so the K
 // and V tiles in LDS are the same fp16 images at the same strides and everything behind them is shared text.
-template <bool MASK, int NW, int RT, bool PAGED = false, bool FP8 = false>
-__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8, PagedBlockFp8Args, std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs>> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+// WINDOW (with PAGED, causal launches only): sliding-window attention (PagedBlockWindowArgs).  The block walks key tiles from the tile of klo = lo(its first row) to the
+// tile of its last row's position; tiles wholly below are neither requested nor computed, and keys below klo -- which may lie in pages that were given back -- are staged
+// as zeros like the keys at and beyond kend.  The lower bound is tested on the tiles that hold a key below the lo of one of the wave's rows: the causal diagonal's `edge`.
+template <bool MASK, int NW, int RT, bool PAGED = false, bool FP8 = false, bool WINDOW = false>
+__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WINDOW, PagedBlockWindowArgs, std::conditional_t<FP8, PagedBlockFp8Args, std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs>>> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
     static_assert(!PAGED || !MASK, "the paged form takes no additive mask");
+    static_assert(!WINDOW || PAGED, "a window exists on pages only");
     static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
     constexpr int kBQ = 16 * RT * NW, NT = 64 * NW, KI = 1024 / NT;
     constexpr float kLog2e = 1.4426950408889634f;
@@ -296,6 +311,12 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8,
     const int last_row = (qb * kBQ + kBQ < a.m ? qb * kBQ + kBQ : a.m) - 1;
     const int kend = a.causal ? a.pos + last_row + 1 : tgz;
     const int ntiles = (kend + kBK - 1) / kBK;
+    // WINDOW: the first key the block's first row weighs -- no row of the block weighs an earlier one -- and its tile; else 0
+    [[maybe_unused]] const int klo = [&]() -> int {
+        if constexpr (WINDOW) return a.pos + qb * kBQ - a.window + 1 > 0 ? a.pos + qb * kBQ - a.window + 1 : 0;
+        else return 0;
+    }();
+    const int kt0 = WINDOW ? klo / kBK : 0;
     const float scale2 = a.alpha * kLog2e;  // scores in units of log2: exp(x) = exp2(x * log2 e), one v_exp_f32 per probability
 
     // Q fragments of row tile t: row r0 + 16 t + n16 (clamped), head dimensions 32 s + 8 quad ..; that row is also the lane's softmax row
@@ -338,7 +359,7 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8,
                 kreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
                 vreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
             }
-            if (gk < kend) {
+            if (gk < kend && (!WINDOW || gk >= klo)) {
                 if constexpr (PAGED) {
                     // the piece's run of the tile: i with 4 waves (a pass of 256 pieces is 16 keys), 2 i + wave / 4 with 8 -- wave-uniform, so the page is a scalar
                     const int page = NT == 256 ? tw.w[i] : (wave >= 4 ? tw.w[(2 * i + 1) & 3] : tw.w[(2 * i) & 3]);
@@ -360,15 +381,19 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8,
             }
         }
     };
+    [[maybe_unused]] auto request_words = [&](int kt) {
+        if constexpr (WINDOW) tw.request_from(a, kt, kend, lane, klo >> a.page_shift);
+        else if constexpr (PAGED) tw.request(a, kt, kend, lane);
+    };
     if constexpr (PAGED) {
-        tw.request(a, 0, kend, lane);  // (the one table round trip a block waits for)
+        request_words(kt0);  // (the one table round trip a block waits for)
         tw.latch();
     }
-    fetch_tile(0);
-    if constexpr (PAGED) tw.request(a, 1, kend, lane);
+    fetch_tile(kt0);
+    if constexpr (PAGED) request_words(kt0 + 1);
     // this lane's piece of a [4 keys][16 head dimensions] block for the transpose read: key 4 quad + n16 / 4, head dimensions 4 (n16 % 4) ..
     const unsigned char *vfrag = vs + (4 * quad + (n16 >> 2)) * kVStride + (n16 & 3) * 8;
-    for (int kt = 0; kt < ntiles; ++kt) {
+    for (int kt = kt0; kt < ntiles; ++kt) {
         const int key0 = kt * kBK;
         __syncthreads();  // everybody has read the previous tiles
         // ---- both tiles as they lie ----
@@ -386,7 +411,7 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8,
         if constexpr (PAGED) tw.latch();  // tile kt + 1's words arrived with tile kt's rows
         __syncthreads();
         if (kt + 1 < ntiles) fetch_tile(kt + 1);
-        if constexpr (PAGED) tw.request(a, kt + 2, kend, lane);  // behind tile kt + 1's row requests, for the fetch a tile from now
+        if constexpr (PAGED) request_words(kt + 2);  // behind tile kt + 1's row requests, for the fetch a tile from now
         // ---- S^T = K Q^T (64 keys x this wave's 16 RT rows): a K fragment feeds the RT row tiles ----
         float4_t sacc[RT][4];
 #pragma unroll
@@ -401,7 +426,11 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8,
             }
         }
         // does this tile hold keys some row of the wave must not see?  (wave-uniform; the last tile, and the tiles on the wave's causal diagonal)
-        const bool edge = key0 + kBK > tgz || (a.causal && key0 + kBK - 1 > a.pos + r0);
+        const bool edge = [&]() -> bool {
+            const bool e = key0 + kBK > tgz || (a.causal && key0 + kBK - 1 > a.pos + r0);
+            if constexpr (WINDOW) return e || key0 < a.pos + r0 + 16 * RT - 1 - a.window + 1;  // (the lo of the wave's last row)
+            else return e;
+        }();
         // ---- scale, mask, cut; online softmax: the lane's row is rowc[t], its keys key0 + 16 j + 4 quad + r ----
         half4_t pb[RT][4];
 #pragma unroll
@@ -431,6 +460,7 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<FP8,
                     if (MASK || edge) {
                         const int key = key0 + 16 * j + 4 * quad + r;
                         cut = edge && !(key < tgz && !(a.causal && key > a.pos + rowc[t]));
+                        if constexpr (WINDOW) cut = cut || key < a.pos + rowc[t] - a.window + 1;
                     }
                     s = cut ? kNegBig : (in_range ? s : -65504.0f * kLog2e);
                     sacc[t][j][r] = s;
@@ -580,6 +610,37 @@ void attn_prefill_paged_fp8_kernel(const PagedPrefillFp8Args a) {
     }
 }
 
+
+// The windowed launch, fp16 and e4m3 pools: the same workgroups, block list and pairs.  (waves per SIMD: every form is pinned to its unwindowed counterpart's, as above.)
+struct PagedPrefillWindowArgs : PagedPrefillFp8Args {
+    int window;
+};
+template <bool FP8>
+__device__ __forceinline__ PagedBlockWindowArgs paged_block_args_window(const PagedPrefillWindowArgs &a, const PrefillSegment sg) {
+    PagedBlockWindowArgs b;
+    static_cast<PagedBlockArgs &>(b) = paged_block_args(a, sg);
+    b.k_scale = FP8 ? a.k_scale : 0.f;
+    b.v_scale = FP8 ? a.v_scale : 0.f;
+    b.window = a.window;
+    return b;
+}
+template <int NW, int RT, bool PAIR, bool FP8>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FP8_WAVES(NW, RT, PAIR), FP8_WAVES(NW, RT, PAIR))))
+void attn_prefill_paged_window_kernel(const PagedPrefillWindowArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile
+    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
+    const int i = (int)blockIdx.x;
+    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
+    attn_prefill_block<false, NW, RT, true, FP8, true>(paged_block_args_window<FP8>(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
+    if constexpr (PAIR) {
+        const int j = a.nblocks - 1 - i;
+        if (i < j) {
+            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
+            attn_prefill_block<false, NW, RT, true, FP8, true>(paged_block_args_window<FP8>(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
+        }
+    }
+}
+
 #undef FP8_WAVES
 
 thread_local int g_prefill_pair = 0;   // 0: by the rule; 1 / 2: pairing forced on / off
@@ -690,7 +751,8 @@ int prefill_page_shift(int page_keys) {  // log2 of a power of two in [16, 256],
 }
 
 // form, pairing and the block list (heaviest first; ties: in segment order, a segment's later blocks first) of a paged launch; false: more blocks than the list holds
-bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int nseg, int *form_out, int *pair_out, int *nblocks_out, unsigned short *order) {
+// window >= 1 (causal): a block walks the tiles from the one of its first row's first visible key on -- those are what it is weighed by
+bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int nseg, int *form_out, int *pair_out, int *nblocks_out, unsigned short *order, int window = 0) {
     auto blocks = [&](int rows) {
         long long n = 0;
         for (int s = 0; s < nseg; ++s) n += (seg[s].m + rows - 1) / rows;
@@ -713,6 +775,10 @@ bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int ns
             const int last_row = (qb * rows + rows < seg[s].m ? qb * rows + rows : seg[s].m) - 1;
             const int kend = causal ? seg[s].pos + last_row + 1 : seg[s].pos + seg[s].m;
             tiles[n] = (kend + kBK - 1) / kBK;
+            if (window > 0) {
+                const long long klo = (long long)seg[s].pos + (long long)qb * rows - window + 1;
+                tiles[n] -= klo > 0 ? (int)(klo / kBK) : 0;
+            }
             order[n++] = (unsigned short)(s << 12 | qb);
         }
     }
@@ -729,11 +795,11 @@ bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int ns
 
 size_t attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd) { return attention_prefill_workspace_bytes(heads, total_rows, hd); }
 
-int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups) {
+int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups, int window) {
     PrefillSegment seg[kMaxSegments];
     if (nseg < 1 || nseg > kMaxSegments || heads < 1) return TCE_ERR_BAD_ARG;
     __builtin_memcpy(seg, segments, sizeof(PrefillSegment) * nseg);
-    if (!plan_paged_prefill(heads, causal, seg, nseg, form, pair, nblocks, nullptr)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (!plan_paged_prefill(heads, causal, seg, nseg, form, pair, nblocks, nullptr, window)) return TCE_ERR_UNSUPPORTED_SHAPE;
     *workgroups = (*pair ? (*nblocks + 1) / 2 : *nblocks) * heads;
     return TCE_OK;
 }
@@ -756,11 +822,14 @@ int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, con
     const int shift = prefill_page_shift(pg.page_keys);
     if (shift < 0 || nseg < 1 || nseg > kMaxSegments || !table || table_stride < 1 || kv_heads <= 0 || heads % kv_heads != 0 || total_rows < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && (k_log2 < kFp8ScaleLog2Min || k_log2 > kFp8ScaleLog2Max || v_log2 < kFp8ScaleLog2Min || v_log2 > kFp8ScaleLog2Max)) return TCE_ERR_UNSUPPORTED_SHAPE;
-    PagedPrefillFp8Args a{};
+    const int window = s.window;
+    if (window < 0 || (window && !causal)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedPrefillWindowArgs a{};
+    a.window = window;
     __builtin_memcpy(a.seg, r.segments, sizeof(PrefillSegment) * nseg);
     int form = 0;
     unsigned short order[kMaxListedBlocks] = {};
-    if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order, window)) return TCE_ERR_UNSUPPORTED_SHAPE;
     for (int i = 0; i < a.nblocks; ++i) a.order[i >> 1] |= (unsigned)order[i] << ((i & 1) * 16);
     PagedPrepareFp8Args p{};
     p.qkv = static_cast<const half_t *>(s.qkv);
@@ -807,9 +876,17 @@ int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, con
     auto go = [&](auto nw_c, auto rt_c) {
         constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
         const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
-        if (fp8) {
-            if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, a);
-            else hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
+        if (window) {
+            if (fp8) {
+                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, true>), grid, dim3(64 * NW), 0, stream, a);
+                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, true>), grid, dim3(64 * NW), 0, stream, a);
+            } else {
+                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, false>), grid, dim3(64 * NW), 0, stream, a);
+                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, false>), grid, dim3(64 * NW), 0, stream, a);
+            }
+        } else if (fp8) {
+            if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillFp8Args &>(a));
+            else hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillFp8Args &>(a));
         } else {
             if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillArgs &>(a));
             else hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillArgs &>(a));

@@ -1307,10 +1307,17 @@ int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int 
 
 // rows_per_seq null: the step.  Else the multi-row form (speculative decoding), which has two rules of its own: the row count, and `out` 16-byte aligned (it stores
 // `out` in 16-byte pieces; the step never required it, and callers rely on that)
-static int paged_step(const char *who, const tce::KvPages &pg, const tce::AttnStepArgs &s, const int *rows_per_seq, void *stream) {
+// window null: every key.  Else the windowed step (sliding-window attention; never together with rows_per_seq), whose one rule of its own is window >= 1
+static int check_window(const char *who, const int *window) {
+    return window && *window < 1 ? fail(TCE_ERR_BAD_ARG, "%s: window %d (>= 1: the last `window` keys, the row's own included)", who, *window) : TCE_OK;
+}
+
+static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, const int *rows_per_seq, void *stream, const int *window = nullptr) {
     if (const int rc = check_pages(who, pg)) return rc;
     if (const int rc = check_row_keys(who, pg)) return rc;
+    if (const int rc = check_window(who, window)) return rc;
     if (const int rc = check_step(who, s, row_keys(pg), "table_stride * page_keys")) return rc;
+    s.window = window ? *window : 0;
     if (rows_per_seq && (*rows_per_seq < 1 || *rows_per_seq > TCE_SPEC_MAX_ROWS))
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, *rows_per_seq, TCE_SPEC_MAX_ROWS);
     if (const int rc = check_aligned(who, 16, {{"qkv", s.qkv}, {"k_pool", pg.k_pool}, {"v_pool", pg.v_pool}, {"cos_table", s.cosv}, {"sin_table", s.sinv},
@@ -1334,6 +1341,31 @@ int tce_attention_decode_step_paged_fp8(const void *qkv, void *k_pool, void *v_p
                                         const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
     return paged_step("tce_attention_decode_step_paged_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                       {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream);
+}
+
+int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len) {
+    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys) || window < 1)
+        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_paged_window: bad argument");
+    int chunk = 0, chunks = 0, waves = 0;
+    tce::describe_attention_decode_window(heads, kv_heads, pos_bound, window, &chunk, &chunks, &waves);
+    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
+                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
+    return TCE_OK;
+}
+
+int tce_attention_decode_step_paged_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                               const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                               const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int window, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_window_f16", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream, &window);
+}
+
+int tce_attention_decode_step_paged_window_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                               const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                               const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, int window,
+                                               void *stream) {
+    return paged_step("tce_attention_decode_step_paged_window_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream, &window);
 }
 
 int tce_attention_decode_step_paged_rows_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
@@ -1391,17 +1423,27 @@ int tce_kv_pages_gather_fp8(const void *k_pool, const void *v_pool, void *k_dst,
                          {k_dst, v_dst, kv_heads, dst_max_keys}, hd, key0, nkeys, stream);
 }
 
-int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
-                             uint32_t *violations, void *stream) {
-    static const char *who = "tce_kv_block_table_check";
+static int table_check(const char *who, const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                       uint32_t *violations, const int *window, void *stream) {
     const tce::KvPages pg{nullptr, nullptr, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0};
     if (!pos_device || !violations) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
     if (const int rc = check_pages(who, pg, false)) return rc;
+    if (const int rc = check_window(who, window)) return rc;
     if (batch < 1 || pos_bound < 0) return fail(TCE_ERR_BAD_ARG, "%s: need batch >= 1 and pos_bound >= 0", who);
     if (const int rc = check_aligned(who, 4, {{"block_table", block_table}, {"pos_device", pos_device}, {"violations", violations}})) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_kv_block_table_check(pg, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_kv_block_table_check(pg, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he, window ? *window : 0);
     return rc == TCE_ERR_HIP ? hip_fail(he, "block table check launch") : rc;
+}
+
+int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                             uint32_t *violations, void *stream) {
+    return table_check("tce_kv_block_table_check", block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, nullptr, stream);
+}
+
+int tce_kv_block_table_check_window(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                                    uint32_t *violations, int window, void *stream) {
+    return table_check("tce_kv_block_table_check_window", block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, &window, stream);
 }
 
 size_t tce_sample_workspace_bytes(int batch, int vocab) { return batch < 1 || batch > 65535 || vocab < 1 || vocab > (1 << 20) ? 0 : tce::sample_workspace_bytes(batch, vocab); }
@@ -1661,10 +1703,14 @@ const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int ca
 }
 
 // r: ld_qkv / ld_out 0 = dense.  The only entry point that knows the table's row count: a segment names its slot.
-static int paged_prefill(const char *who, const tce::KvPages &pg, const tce::AttnStepArgs &s, tce::PrefillRows r, void *stream) {
+// window null: every key a row may see.  Else the windowed prefill: window >= 1, causal launches only
+static int paged_prefill(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, tce::PrefillRows r, void *stream, const int *window = nullptr) {
     const tce_prefill_segment *segments = reinterpret_cast<const tce_prefill_segment *>(r.segments);
     if (!s.qkv || !s.out || !s.workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
     if (const int rc = check_pages(who, pg)) return rc;
+    if (const int rc = check_window(who, window)) return rc;
+    if (window && !r.causal) return fail(TCE_ERR_BAD_ARG, "%s: a window needs causal != 0 (the window of a row ends at the row's own key)", who);
+    s.window = window ? *window : 0;
     if (const int rc = check_rope_pair(who, s.cosv, s.sinv)) return rc;
     if (pg.table_rows < 1) return fail(TCE_ERR_BAD_ARG, "%s: need table_rows >= 1", who);
     if (const int rc = check_row_keys(who, pg)) return rc;
@@ -1681,7 +1727,7 @@ static int paged_prefill(const char *who, const tce::KvPages &pg, const tce::Att
         return rc;
     if (const int rc = check_aligned(who, 4, {{"block_table", pg.table}})) return rc;
     int form = 0, pair = 0, blocks = 0, wgs = 0;
-    if (tce::describe_attention_prefill_paged(s.heads, r.causal, r.segments, r.nseg, &form, &pair, &blocks, &wgs) != TCE_OK)
+    if (tce::describe_attention_prefill_paged(s.heads, r.causal, r.segments, r.nseg, &form, &pair, &blocks, &wgs, s.window) != TCE_OK)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
     hipError_t he = hipSuccess;
     const int rc = tce::launch_attention_prefill_paged(pg, s, r, static_cast<hipStream_t>(stream), &he);
@@ -1704,6 +1750,24 @@ int tce_attention_prefill_paged_fp8(const void *qkv, int ld_qkv, void *k_pool, v
     return paged_prefill("tce_attention_prefill_paged_fp8", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                          {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
                          {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream);
+}
+
+int tce_attention_prefill_paged_window_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                           int page_keys, int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads,
+                                           int kv_heads, int hd, const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, int window,
+                                           void *stream) {
+    return paged_prefill("tce_attention_prefill_paged_window_f16", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, false, 0, 0},
+                         {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
+                         {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream, &window);
+}
+
+int tce_attention_prefill_paged_window_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                           int page_keys, int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads,
+                                           int kv_heads, int hd, const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits,
+                                           int k_scale_log2, int v_scale_log2, int window, void *stream) {
+    return paged_prefill("tce_attention_prefill_paged_window_fp8", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                         {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
+                         {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream, &window);
 }
 
 int tce_layernorm_q_w8a8_group(const float *x, const float *ln_weight, const float *ln_bias, int m, int k, const tce_w8a8_desc *lin, int count,

@@ -459,7 +459,7 @@ class _GeneratorBase:
             if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
                 raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new 1 .. {self.sampler.log_stride}")
         if self.allocator is not None:  # all or nothing, before anything changes
-            if any(self.allocator.pages[s] for s, *_ in adm):
+            if any(self.allocator.pages[s] or self.allocator.gone[s] for s, *_ in adm):
                 raise ValueError("admit: a slot still holds pages (release it first)")
             self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])
         rows = []
@@ -500,6 +500,7 @@ class _GeneratorBase:
         if n < 1:
             raise ValueError("run: n >= 1")
         if self.allocator is not None:
+            self._release_behind()
             self.book.reserve(self.allocator, n)
         for _ in range(n):
             if self._graph is not None:
@@ -507,7 +508,20 @@ class _GeneratorBase:
             else:
                 self.token_step()
             self._replayed()
-        return self._sync()
+        retired = self._sync()
+        if self.allocator is not None:
+            self._release_behind()
+        return retired
+
+    def _release_behind(self) -> None:
+        """Sliding windows: when EVERY layer has one, no layer weighs a key below pos - max(windows) + 1 of a live slot at position pos again -- the pages wholly below
+        go back to the pool (PageAllocator.release_behind; host bookkeeping only: the table words stay, so the captured graph stays valid).  Between bursts a slot then
+        holds at most ceil((max W + n) / page_keys) + 1 pages.  One unwindowed layer: nothing is released."""
+        windows = [getattr(d, "window", None) for d in self.decoders]
+        if any(w is None for w in windows):
+            return
+        for s in self.book.live():
+            self.allocator.release_behind(s, self.book.pos[s] - max(windows) + 1)
 
     def _replayed(self) -> None:
         """Behind every replay of run(): a subclass's stream-ordered device work (no synchronisation)."""

@@ -17,7 +17,10 @@ kv_dtype="fp8_e4m3": the pools hold OCP e4m3 bytes (include/tce_matmul.h, "FP8 p
 per pool, 2^k_scale_log2 and 2^v_scale_log2, exponents in [-8, 7].  dequant(byte) is exact in binary16 and the arithmetic behind it is the fp16 kernels'.
 fp8_quantize_reference / fp8_dequantize_reference restate the format on the host.
 
-Trust: the step follows only table words 0 .. pos // page_keys of an active row; everything else in the table may hold anything (a released slot's words stay as
+window=W (PagedBatchDecodeAttention / PagedBatchedDecoder): sliding-window attention -- a row at position p weighs keys max(0, p - W + 1) .. p -- through the
+*_window entry points; the pages wholly behind every layer's window are given back with PageAllocator.release_behind (generate._GeneratorBase.run does).
+
+Trust: the step follows only table words 0 .. pos // page_keys of an active row (with a window: max(0, pos - W + 1) // page_keys .. pos // page_keys); everything else in the table may hold anything (a released slot's words stay as
 they were).  It does not validate page numbers: PageAllocator writes only numbers in [0, num_pages), and PagedBatchDecodeAttention.table_violations runs
 tce_kv_block_table_check for a caller who wants the table checked on the device before a launch.
 """
@@ -97,7 +100,8 @@ class PageAllocator:
         self.num_pages, self.page_keys, self.batch, self.max_pages_per_seq = num_pages, page_keys, batch, max_pages_per_seq
         self.free = order[::-1]  # a stack: pop() hands out order[0] first, and a released page is the next one handed out
         self.refcount = [0] * num_pages
-        self.pages: list[list[int]] = [[] for _ in range(batch)]
+        self.pages: list[list[int]] = [[] for _ in range(batch)]  # the pages a slot HOLDS, in key order: pages[slot][i] is its table word gone[slot] + i
+        self.gone = [0] * batch  # leading pages of a slot that release_behind gave back (their table words stay as they are and are never followed again)
         self.frozen = [0] * batch  # leading pages of a slot that are (or were) shared: read-only for it, never the target of an append
         self.table = torch.zeros((batch, max_pages_per_seq), dtype=torch.int32, device=device)
 
@@ -111,17 +115,24 @@ class PageAllocator:
 
     def appendable_pages(self, slot: int) -> list[int]:
         """The pages of `slot` that an append may write: those behind its shared prefix."""
-        return self.pages[slot][self.frozen[slot]:]
+        return self.pages[slot][max(0, self.frozen[slot] - self.gone[slot]):]
 
     def writable(self, slot: int, key0: int, nkeys: int) -> bool:
         """May an append write rows [key0, key0 + nkeys) of `slot`: every page they fall in exists, is held by this slot alone and lies behind its frozen prefix."""
         self._slot(slot)
         if key0 < 0 or nkeys < 1:
             return False
-        first, last = key0 // self.page_keys, (key0 + nkeys - 1) // self.page_keys
-        if first < self.frozen[slot] or last >= len(self.pages[slot]):
+        first, last = key0 // self.page_keys - self.gone[slot], (key0 + nkeys - 1) // self.page_keys - self.gone[slot]
+        if first < max(0, self.frozen[slot] - self.gone[slot]) or last >= len(self.pages[slot]):
             return False
         return all(self.refcount[p] == 1 for p in self.pages[slot][first:last + 1])
+
+    def holds(self, slot: int, key0: int, nkeys: int) -> bool:
+        """Does `slot` hold a page for every key of [key0, key0 + nkeys): reserved, and not given back by release_behind."""
+        self._slot(slot)
+        if key0 < 0 or nkeys < 1:
+            return False
+        return key0 // self.page_keys >= self.gone[slot] and (key0 + nkeys - 1) // self.page_keys < self.gone[slot] + len(self.pages[slot])
 
     # ---- operations ----
     def reserve_many(self, wanted: list[tuple[int, int]]) -> list[list[int]]:
@@ -136,7 +147,9 @@ class PageAllocator:
             need = upto_pos // self.page_keys + 1
             if upto_pos < 0 or need > self.max_pages_per_seq:
                 raise ValueError(f"key index {upto_pos} outside a slot's {self.max_keys} keys")
-            short += max(0, need - len(self.pages[slot]))
+            if need <= self.gone[slot]:
+                raise ValueError(f"slot {slot}: key {upto_pos} lies in a page that was given back")
+            short += max(0, need - self.gone[slot] - len(self.pages[slot]))
         if short > len(self.free):
             raise PagePoolExhausted(f"{short} pages needed for slots {slots}, {len(self.free)} free")
         return [self.reserve(slot, upto_pos) for slot, upto_pos in wanted]
@@ -147,7 +160,9 @@ class PageAllocator:
         need = upto_pos // self.page_keys + 1
         if upto_pos < 0 or need > self.max_pages_per_seq:
             raise ValueError(f"key index {upto_pos} outside a slot's {self.max_keys} keys")
-        have = len(self.pages[slot])
+        if need <= self.gone[slot]:
+            raise ValueError(f"slot {slot}: key {upto_pos} lies in a page that was given back")
+        have = self.gone[slot] + len(self.pages[slot])
         if need - have > len(self.free):
             raise PagePoolExhausted(f"{need - have} pages needed for slot {slot}, {len(self.free)} free")
         added = [self.free.pop() for _ in range(need - have)]
@@ -157,7 +172,7 @@ class PageAllocator:
         self.pages[slot] += added
         if added:
             self._write(slot, have, added)
-        target = self.pages[slot][upto_pos // self.page_keys]
+        target = self.pages[slot][upto_pos // self.page_keys - self.gone[slot]]
         assert self.refcount[target] == 1 and upto_pos // self.page_keys >= self.frozen[slot], f"slot {slot}: key {upto_pos} lies in a shared page ({target})"
         return added
 
@@ -174,6 +189,26 @@ class PageAllocator:
         self.free += freed[::-1]  # (the slot's first page is the next one handed out)
         self.pages[slot] = []
         self.frozen[slot] = 0
+        self.gone[slot] = 0
+        return freed
+
+    def release_behind(self, slot: int, key: int) -> list[int]:
+        """Drop the slot's references to the pages that lie WHOLLY below key index `key` (sliding-window attention: no layer weighs them any more); returns the pages
+        that went back to the free list -- a shared page only loses this slot's reference.  The table words are left as they are: a windowed row never follows a word
+        below its window's first key.  Idempotent; key <= 0 drops nothing; never more than the slot holds.  From then on the slot cannot be a fork's source."""
+        self._slot(slot)
+        drop = min(max(int(key), 0) // self.page_keys - self.gone[slot], len(self.pages[slot]))
+        if drop <= 0:
+            return []
+        freed = []
+        for p in self.pages[slot][:drop]:
+            assert self.refcount[p] > 0
+            self.refcount[p] -= 1
+            if self.refcount[p] == 0:
+                freed.append(p)
+        self.free += freed[::-1]
+        self.pages[slot] = self.pages[slot][drop:]
+        self.gone[slot] += drop
         return freed
 
     def fork(self, src_slot: int, dst_slot: int, keys: int) -> list[tuple[int, int, int]]:
@@ -182,8 +217,10 @@ class PageAllocator:
         multiple of page_keys)."""
         self._slot(src_slot)
         self._slot(dst_slot)
-        if src_slot == dst_slot or self.pages[dst_slot]:
+        if src_slot == dst_slot or self.pages[dst_slot] or self.gone[dst_slot]:
             raise ValueError("fork needs an empty destination slot other than the source")
+        if self.gone[src_slot]:
+            raise ValueError(f"slot {src_slot} gave its leading pages back (release_behind): it cannot be forked")
         if keys < 0 or keys > len(self.pages[src_slot]) * self.page_keys:
             raise ValueError(f"slot {src_slot} does not hold {keys} keys")
         full, rows = divmod(keys, self.page_keys)
@@ -219,7 +256,8 @@ class PageAllocator:
         host = self.table.cpu().numpy()
         for s, ps in enumerate(self.pages):
             assert all(self.refcount[p] == 1 for p in self.appendable_pages(s))
-            assert host[s, :len(ps)].tolist() == ps
+            assert self.gone[s] >= 0 and self.gone[s] + len(ps) <= self.max_pages_per_seq
+            assert host[s, self.gone[s]:self.gone[s] + len(ps)].tolist() == ps
 
     # ---- internals ----
     def _slot(self, slot: int) -> None:
@@ -235,9 +273,13 @@ class PagedBatchDecodeAttention:
     """One layer's K and V pools and the step's workspace, over a PageAllocator's table."""
 
     def __init__(self, allocator: PageAllocator, heads: int, kv_heads: int | None, device, cos: torch.Tensor | None = None, sin: torch.Tensor | None = None,
-                 kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
+                 kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None):
         """kv_dtype "fp16" (the default: today's pools and entry points) or "fp8_e4m3": uint8 pools of the same shape, every call through the fp8 entry points with
-        the two scale exponents (integers in [-8, 7]; ignored for fp16)."""
+        the two scale exponents (integers in [-8, 7]; ignored for fp16).  window None: every key, through today's entry points; W >= 1: step, prefill and
+        table_violations go through the *_window entry points (a row at position p weighs keys max(0, p - W + 1) .. p)."""
+        if window is not None and (int(window) != window or int(window) < 1 or int(window) > 0x7fffffff):
+            raise ValueError(f"window {window}: None or an integer >= 1")
+        self.window = None if window is None else int(window)
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"kv_dtype {kv_dtype!r}: one of {KV_DTYPES}")
         self.kv_dtype, self.fp8 = kv_dtype, kv_dtype == "fp8_e4m3"
@@ -266,6 +308,14 @@ class PagedBatchDecodeAttention:
         """The fp8 entry points' two extra arguments (in front of the stream); nothing for fp16."""
         return (self.k_scale_log2, self.v_scale_log2) if self.fp8 else ()
 
+    def _window(self) -> tuple:
+        """The *_window entry points' one extra argument (behind the scales, in front of the stream); nothing without a window."""
+        return () if self.window is None else (self.window,)
+
+    def _entry(self, name: str) -> str:
+        """`name` or, with a window, its *_window form"""
+        return name if self.window is None else name + "_window"
+
     def _table_args(self):
         t = self.allocator.table
         assert t.is_cuda and t.device == self.k_pool.device
@@ -273,10 +323,12 @@ class PagedBatchDecodeAttention:
 
     def step(self, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """BatchDecodeAttention.step on the pages: one launch; the table is read when the kernel runs."""
-        return self._step("tce_attention_decode_step_paged", None, qkv, pos_device, pos_bound, out)
+        return self._step(self._entry("tce_attention_decode_step_paged"), None, qkv, pos_device, pos_bound, out)
 
     def _step(self, entry: str, rows_per_seq: int | None, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None) -> torch.Tensor:
         """The step's assertions and call, `entry`_f16 or _fp8, for batch * rows_per_seq rows (None: one row per sequence, and an entry point without that argument)."""
+        if rows_per_seq is not None and self.window is not None:
+            raise ValueError("the multi-row step with a window is not built")
         n = self.batch * (rows_per_seq or 1)
         rw = (self.heads + 2 * self.kv_heads) * self.hd
         assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == n * rw
@@ -288,7 +340,7 @@ class PagedBatchDecodeAttention:
         fn = getattr(capi.lib(), entry + ("_fp8" if self.fp8 else "_f16"))
         rows = () if rows_per_seq is None else (rows_per_seq,)
         capi.check(fn(p(qkv), p(self.k_pool), p(self.v_pool), *self._table_args(), p(self.cos), p(self.sin), p(out), p(self.workspace), self.batch, *rows, self.heads,
-                      self.kv_heads, self.hd, p(pos_device), int(pos_bound), self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
+                      self.kv_heads, self.hd, p(pos_device), int(pos_bound), self.alpha_bits, *self._scales(), *self._window(), C.c_void_p(_stream())))
         return out
 
     def prefill(self, segments, qkv: torch.Tensor, out: torch.Tensor | None = None, causal: bool = True) -> torch.Tensor:
@@ -309,17 +361,18 @@ class PagedBatchDecodeAttention:
         t = self.allocator.table
         assert t.is_cuda and t.device == self.k_pool.device
         p = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
-        fn = L.tce_attention_prefill_paged_fp8 if self.fp8 else L.tce_attention_prefill_paged_f16
+        fn = getattr(L, self._entry("tce_attention_prefill_paged") + ("_fp8" if self.fp8 else "_f16"))
         capi.check(fn(p(qkv), 0, p(self.k_pool), p(self.v_pool), p(t), t.shape[0], t.shape[1], self.page_keys, self.num_pages, p(self.cos), p(self.sin),
                       1 if causal else 0, p(out), 0, p(self._prefill_ws), self.heads, self.kv_heads, self.hd, C.cast(segs, C.c_void_p), len(segments), total,
-                      self.alpha_bits, *self._scales(), C.c_void_p(_stream())))
+                      self.alpha_bits, *self._scales(), *self._window(), C.c_void_p(_stream())))
         return out
 
     def table_violations(self, pos_device: torch.Tensor, pos_bound: int) -> int:
         """tce_kv_block_table_check on the allocator's table, waited for: the number of words the step would follow that are not page numbers (0: sound)."""
         tab, stride, pk, n = self._table_args()
-        capi.check(capi.lib().tce_kv_block_table_check(tab, stride, pk, n, self.batch, C.c_void_p(pos_device.data_ptr()), int(pos_bound),
-                                                       C.c_void_p(self._violations.data_ptr()), C.c_void_p(_stream())))
+        fn = getattr(capi.lib(), self._entry("tce_kv_block_table_check"))
+        capi.check(fn(tab, stride, pk, n, self.batch, C.c_void_p(pos_device.data_ptr()), int(pos_bound), C.c_void_p(self._violations.data_ptr()),
+                      *self._window(), C.c_void_p(_stream())))
         return int(self._violations.item())
 
     def _row(self, slot: int) -> C.c_void_p:
@@ -333,7 +386,7 @@ class PagedBatchDecodeAttention:
         before: PageAllocator.reserve(slot, key0 + nkeys - 1))."""
         k, v = contiguous_attention.k_cache, contiguous_attention.v_cache
         assert k.dtype == v.dtype == torch.float16 and k.is_contiguous() and v.is_contiguous() and tuple(k.shape) == tuple(v.shape) and k.shape[0] == self.kv_heads
-        assert (key0 + nkeys - 1) // self.page_keys < len(self.allocator.pages[slot]), "reserve the slot's pages first"
+        assert self.allocator.holds(slot, key0, nkeys), "reserve the slot's pages first"
         p = lambda t: C.c_void_p(t.data_ptr())
         L = capi.lib()
         fn = L.tce_kv_pages_scatter_fp8 if self.fp8 else L.tce_kv_pages_scatter_f16  # (fp8: the contiguous side stays fp16, the rows are quantised on their way in)
@@ -344,7 +397,7 @@ class PagedBatchDecodeAttention:
         """The reverse of admit: the slot's rows [key0, key0 + nkeys) into a contiguous cache pair."""
         k, v = contiguous_attention.k_cache, contiguous_attention.v_cache
         assert k.dtype == v.dtype == torch.float16 and k.is_contiguous() and v.is_contiguous() and tuple(k.shape) == tuple(v.shape) and k.shape[0] == self.kv_heads
-        assert (key0 + nkeys - 1) // self.page_keys < len(self.allocator.pages[slot]), "the slot does not hold these keys"
+        assert self.allocator.holds(slot, key0, nkeys), "the slot does not hold these keys"
         p = lambda t: C.c_void_p(t.data_ptr())
         L = capi.lib()
         fn = L.tce_kv_pages_gather_fp8 if self.fp8 else L.tce_kv_pages_gather_f16  # (fp8: dequantised -- exactly -- into the fp16 pair)
@@ -386,13 +439,20 @@ class PagedBatchedDecoder(BatchedDecoder):
     prefill launches with the paged prefill in the middle.  One PageAllocator serves the decoders of all layers."""
 
     def __init__(self, block: DecoderBlock, allocator: PageAllocator, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, attention=None,
-                 rows: int | None = None):
-        """attention, rows: BatchedDecoder's (a subclass with an attention object of its own over the same allocator; the default is built here)."""
+                 rows: int | None = None, window: int | None = None):
+        """attention, rows: BatchedDecoder's (a subclass with an attention object of its own over the same allocator; the default is built here).  window: this layer's
+        sliding window (PagedBatchDecodeAttention), None for full attention."""
         self.allocator = allocator
         if attention is None:
             attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,
-                                                  k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
+                                                  k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window)
+        elif window is not None and getattr(attention, "window", None) != window:
+            raise ValueError("window: the attention object given was built with another one")
         super().__init__(block, allocator.batch, attention=attention, rows=rows)
+
+    @property
+    def window(self) -> int | None:
+        return getattr(self.attention, "window", None)
 
     def prefill_many(self, admissions) -> None:
         """Admit several sequences at once: admissions [(slot, rows, pos)], at most 16, distinct slots; rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated

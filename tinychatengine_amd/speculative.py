@@ -132,6 +132,8 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
 
     def __init__(self, allocator, heads, kv_heads, device, cos=None, sin=None, rows_per_seq: int = 1, **kw):
         _check_rows(rows_per_seq)
+        if kw.get("window") is not None:
+            raise ValueError("the multi-row step with a window is not built")
         super().__init__(allocator, heads, kv_heads, device, cos, sin, **kw)
         self.rows_per_seq = int(rows_per_seq)
         need = int(capi.lib().tce_attention_decode_batch_workspace_bytes(self.batch * self.rows_per_seq, heads, self.max_keys, self.hd))
@@ -220,6 +222,8 @@ class SpeculativeGenerator(_GeneratorBase):
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False):
         decoders = list(decoders)
+        if any(getattr(d, "window", None) is not None for d in decoders):
+            raise ValueError("SpeculativeGenerator: a decoder has a sliding window, and the multi-row step with a window is not built")
         self.rows_per_seq, self.ngram = decoders[0].rows_per_seq, int(ngram)
         _check_rows(self.rows_per_seq, self.ngram)
         assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
