@@ -411,7 +411,19 @@ TCE_API int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_po
  *               Elsewhere: a float64 evaluation over keys lo .. p within the steps' stated bound.
  *   refusals    window < 1: TCE_ERR_BAD_ARG; the prefill with causal == 0: TCE_ERR_BAD_ARG (a row's window ends at its own key).  Before any HIP call, BAD_ARG rules
  *               before UNSUPPORTED_SHAPE rules, as everywhere in the paged family.
- * NOT BUILT: the multi-row (speculative) step with a window; windows on contiguous caches and on the single-sequence step; attention sinks (first keys kept beside the
+ *   rows        tce_attention_decode_step_paged_rows_window_f16 / _fp8: the multi-row step with a window (speculative decoding on a windowed layer) -- the arguments
+ *               of tce_attention_decode_step_paged_rows_f16 / _fp8 with `int window` in front of `stream`.  Virtual row y = b * T + t at position pos = p + t weighs
+ *               keys lo_t .. pos, lo_t = max(0, pos - W + 1); its workgroups start at base_t = lo_t & ~3; the cut, the grid's chunk slots and the workgroup order are
+ *               the windowed step's (min(pos_bound + 1, W + 3) keys, the same for every row), the workspace the multi-row step's (one slice per virtual row).  Keys
+ *               in [pos - t, pos] come from the call's own q/k/v rows, never from the pool (the multi-row rule); one of them below lo_t -- possible only with W <= t,
+ *               so W < 8 -- weighs nothing.  Where the window lies wholly inside the call's rows no pool row at or beyond position p is weighted.  Of table row b
+ *               only words lo_t / page_keys .. pos / page_keys become addresses: a sequence's active rows p .. p + n - 1 follow exactly the words that
+ *               tce_kv_block_table_check_window follows for position p + n - 1 with window W + n - 1 (there is no further check entry point).
+ *               CONTRACT (no tolerance): row (b, t)'s `out` and the pool rows one call appends are bit-identical to t + 1 successive calls of
+ *               tce_attention_decode_step_paged_window_f16 / _fp8 with the same pos_bound and window; no other pool byte changes; rows_per_seq = 1 is that step;
+ *               window >= pos_bound + 1 is the unwindowed multi-row step.  Refusals: window < 1 TCE_ERR_BAD_ARG, rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS
+ *               TCE_ERR_UNSUPPORTED_SHAPE, everything else the two parents' rules.
+ * NOT BUILT: windows on contiguous caches and on the single-sequence step; attention sinks (first keys kept beside the
  * window: the pools hold ROTATED keys, so positions inside the cache would have to be re-rotated). */
 TCE_API int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len);
 TCE_API int tce_attention_decode_step_paged_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
@@ -421,6 +433,14 @@ TCE_API int tce_attention_decode_step_paged_window_fp8(const void *qkv, void *k_
                                                        const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
                                                        int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int k_scale_log2,
                                                        int v_scale_log2, int window, void *stream);
+TCE_API int tce_attention_decode_step_paged_rows_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys,
+                                                            int num_pages, const void *cos_table, const void *sin_table, void *out, void *workspace, int batch,
+                                                            int rows_per_seq, int heads, int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound,
+                                                            unsigned short alpha_half_bits, int window, void *stream);
+TCE_API int tce_attention_decode_step_paged_rows_window_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys,
+                                                            int num_pages, const void *cos_table, const void *sin_table, void *out, void *workspace, int batch,
+                                                            int rows_per_seq, int heads, int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound,
+                                                            unsigned short alpha_half_bits, int k_scale_log2, int v_scale_log2, int window, void *stream);
 TCE_API int tce_attention_prefill_paged_window_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
                                                    int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out,
                                                    void *workspace, int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments,

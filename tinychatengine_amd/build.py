@@ -44,8 +44,10 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         # buffer would turn requests that are meant to be in flight together into load -> wait -> scratch store
                                         # (the e4m3 name is a prefix of its multi-row form's; the second name is the fp16 multi-row form: both keep the paged step's double buffer)
                                         # (the third name: the fp16 windowed step; the e4m3 windowed step has the first name as a prefix.  The windowed prefill: every form, fp16 and e4m3)
+                                        # (the fourth and fifth names: the windowed multi-row step, fp16 and e4m3 -- written out, though the second and first names are their prefixes)
                                         "attention_fast.hip": ["attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1E",
-                                                               "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1E", "kv_pages_copy_fp8_kernel"],
+                                                               "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1ELb1E",
+                                                               "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1ELb1ELb1E", "kv_pages_copy_fp8_kernel"],
                                         "attention_prefill.hip": ["attn_prefill_paged_fp8_kernel", "attn_prefill_paged_window_kernel", "attn_prefill_prepare_kernelILb1ELb1E"],
                                         "w4a16_gemv_i8_token.hip": ["w4a16_gemv_i8_token_kernelILb0E"],  # (ILb1E: the lab build's instantiation with wall-clock stamps)
                                         # round 5: EVERY instantiation of the decode kernel, the general-zero-point forms included (round 4 let four of them spill 3-19 registers: each

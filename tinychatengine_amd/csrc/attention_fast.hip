@@ -75,6 +75,12 @@ struct PagedWindowAttnArgs : PagedFp8AttnArgs {
     int window;  // >= 1
 };
 
+// the windowed multi-row paged step's (speculative decoding on a sliding-window layer): both of the above -- T rows per sequence, each weighing the last W keys of ITS
+// position.  chunk / chunks were cut for min(pos_bound + 1, W + 3) keys, the same for every row
+struct PagedRowsWindowAttnArgs : PagedRowsAttnArgs {
+    int window;  // >= 1
+};
+
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
     auto dpp = [](float x, auto ctrl) {
         return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, false));
@@ -145,7 +151,7 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 // pool row, nobody waits for anybody.  The caller guarantees that a sequence's active rows are a prefix with consecutive positions (include/tce_matmul.h); all the kernel
 // does about it is to clamp t to pos, so that no address is formed from a negative position.  The key loop is the paged step's: the wave-uniform rare-block test is a
 // range overlap instead of a membership, and the work it guards is the only per-key addition.
-// WINDOW (with PAGED, not with ROWS): the row weighs keys lo .. pos only, lo = max(0, pos - W + 1) (PagedWindowAttnArgs).  The workgroup's key range starts at
+// WINDOW (with PAGED): the row weighs keys lo .. pos only, lo = max(0, pos - W + 1) (PagedWindowAttnArgs).  The workgroup's key range starts at
 // base = lo & ~3 instead of 0 -- chunk slot c covers keys base + c * chunk .. --, so the span pos - base + 1 <= W + 3 is what the grid was cut for, whatever pos is.
 // Keys base .. lo - 1 of the first group of four are loaded -- they lie in the page of key lo, a group of four never crosses a page -- and weigh nothing, exactly as
 // keys at and beyond kw1 do: excluded from the maximum and the sum by the same rare-block text.  TABLE WORDS: kw0 now depends on the position, so a wave's words
@@ -154,11 +160,17 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 // words of the row that become addresses; everything below may name a page that was given back --, lane 63 for word pos / page_keys: the page wholly invalid groups
 // are read from (word 0's page may be gone).  The appending wave, newrow, RoPE, the e4m3 round trip of the own row, both merges, the counters and the inactive rows
 // are the paged step's text.
+// ROWS && WINDOW (PagedRowsWindowAttnArgs): both texts, each as it stands -- nothing is written for the pair.  Virtual row y = b * T + t at pos = p + t has its own
+// lo_t = max(0, pos - W + 1) and base_t = lo_t & ~3, so its workgroups cover exactly the keys, chunk slots, waves and blocks of the windowed step at that position, and
+// every key in [pos - tprev, pos] comes from `newrow` whether it weighs or not: an in-call key below lo_t (possible only with W <= tprev) is taken from LDS and then
+// weighs nothing, like any key below lo.  When the window lies wholly inside the call's rows (lo_t >= pos - tprev) the pool range [lo_t, pos - tprev - 1] is empty: the
+// rows the fetch reads at and beyond position p -- other workgroups of this launch are writing them -- are all replaced from LDS or invalid, none is weighted.  The
+// table words follow the position word as in WINDOW, words lo_t / page_keys .. pos / page_keys of table row b; the workgroup order is WINDOW's (blockIdx.x alone).
 template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false, bool WINDOW = false>
 __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
-    const std::conditional_t<WINDOW, PagedWindowAttnArgs,
+    const std::conditional_t<WINDOW, std::conditional_t<ROWS, PagedRowsWindowAttnArgs, PagedWindowAttnArgs>,
                              std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>>> a) {
-    static_assert(!WINDOW || (PAGED && !ROWS && NW == 4), "a window exists on the paged step only (one row per sequence)");
+    static_assert(!WINDOW || (PAGED && NW == 4), "a window exists on the paged steps only");
     static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
     static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
     static_assert(!ROWS || (PAGED && NW == 4), "several rows per sequence exist on pages only");
@@ -900,8 +912,9 @@ static float host_pow2(int e) {
 
 // pages.fp8: the pools are e4m3 bytes and the two exponents apply; everything else is one text for both
 // rows = 0: the step; rows >= 1: the multi-row step with rows_per_seq = rows -- the same cut (pos_bound alone decides it), grid (heads x chunk slots, rows, batch)
-// s.window >= 1 (rows = 0 only): the windowed step -- the cut and the grid are made for min(pos_bound + 1, window + 3) keys.  The workspace slices stay where every
+// s.window >= 1 (with either): the windowed step -- the cut and the grid are made for min(pos_bound + 1, window + 3) keys.  The workspace slices stay where every
 // other launch on the same workspace has them (one per table row's keys): the arrival counters at their heads are zero between launches only there
+// s.window and rows: the windowed multi-row step -- the windowed cut and workgroup order, grid (padded pairs x rep, rows, batch), one workspace slice per virtual row
 int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int rows, hipStream_t stream, hipError_t *hip_err) {
     const int batch = s.batch, heads = s.heads, kv_heads = s.kv_heads, hd = s.hd, pos_bound = s.pos_bound, table_stride = pg.table_stride;
     const bool fp8 = pg.fp8;
@@ -910,7 +923,7 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         (long long)pos_bound >= ((long long)table_stride << shift))
         return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && !(fp8_log2_ok(pg.k_scale_log2) && fp8_log2_ok(pg.v_scale_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
-    if (rows < 0 || rows > TCE_SPEC_MAX_ROWS || s.window < 0 || (s.window && rows)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (rows < 0 || rows > TCE_SPEC_MAX_ROWS || s.window < 0) return TCE_ERR_UNSUPPORTED_SHAPE;
     PagedRowsAttnArgs a{};
     a.rows_per_seq = rows;
     a.qkv = static_cast<const half_t *>(s.qkv);
@@ -946,7 +959,14 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         a.k_inv = host_pow2(-pg.k_scale_log2);
         a.v_inv = host_pow2(-pg.v_scale_log2);
     }
-    if (s.window) {
+    if (s.window && rows) {
+        PagedRowsWindowAttnArgs w{};
+        static_cast<PagedRowsAttnArgs &>(w) = a;
+        w.window = s.window;
+        const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, rows, batch);  // (the windowed step's padded x, the rows step's y and z)
+        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, true, true>), grid, dim3(256), 0, stream, w);
+        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, true, true>), grid, dim3(256), 0, stream, w);
+    } else if (s.window) {
         PagedWindowAttnArgs w{};
         static_cast<PagedFp8AttnArgs &>(w) = a;
         w.window = s.window;

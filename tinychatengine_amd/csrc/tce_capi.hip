@@ -1307,7 +1307,7 @@ int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int 
 
 // rows_per_seq null: the step.  Else the multi-row form (speculative decoding), which has two rules of its own: the row count, and `out` 16-byte aligned (it stores
 // `out` in 16-byte pieces; the step never required it, and callers rely on that)
-// window null: every key.  Else the windowed step (sliding-window attention; never together with rows_per_seq), whose one rule of its own is window >= 1
+// window null: every key.  Else the windowed step (sliding-window attention; with rows_per_seq: the windowed multi-row step, both rules), whose one rule of its own is window >= 1
 static int check_window(const char *who, const int *window) {
     return window && *window < 1 ? fail(TCE_ERR_BAD_ARG, "%s: window %d (>= 1: the last `window` keys, the row's own included)", who, *window) : TCE_OK;
 }
@@ -1380,6 +1380,21 @@ int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_pool, void
                                              const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, void *stream) {
     return paged_step("tce_attention_decode_step_paged_rows_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                       {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream);
+}
+
+int tce_attention_decode_step_paged_rows_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                    const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads,
+                                                    int hd, const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int window, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_rows_window_f16", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream, &window);
+}
+
+int tce_attention_decode_step_paged_rows_window_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                    const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads,
+                                                    int hd, const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2,
+                                                    int window, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_rows_window_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream, &window);
 }
 
 // rows [key0, key0 + nkeys) between a contiguous pair and the pages of one table row (pg.table: that row)

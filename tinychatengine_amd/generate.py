@@ -385,6 +385,30 @@ def score_plan(prompts, free_slots, max_keys: int, vocab: int, chunk_rows: int =
             "chunks": [(r0, min(chunk, total - r0)) for r0 in range(0, total, chunk)], "split": split}
 
 
+def admission_chunks(lengths, chunk_rows: int, window: int | None = None) -> list[dict]:
+    """The schedule of admit(..., chunk_rows=N) for prompts of `lengths` tokens (pure: no allocator, no device).  Round r takes rows [r N, min((r + 1) N, len)) of
+    every prompt that still has some; per round, with i the prompt's index in `lengths`:
+        "reserve"   [(i, c0 + m - 1)]   reserved first, all or nothing across the round (PageAllocator.reserve_many)
+        "segments"  [(i, c0, m)]        embedded, then prefilled at position c0 through ALL layers
+        "release"   [(i, c0 + m - W)]   then PageAllocator.release_behind -- only with window = W = the largest window when EVERY layer has one (else empty):
+                                        the next chunk's first row sits at c0 + m and weighs keys from c0 + m - W + 1 on
+    A slot's keys between a round's reserve and its release span at most W + N - 1 + (page_keys - 1) rows, so it holds at most ceil((W + N) / page_keys) + 1 pages,
+    whatever the prompt's length."""
+    lengths = [int(n) for n in lengths]
+    if int(chunk_rows) != chunk_rows or int(chunk_rows) < 1:
+        raise ValueError(f"chunk_rows {chunk_rows}: None or an integer >= 1")
+    if window is not None and int(window) < 1:
+        raise ValueError(f"window {window}: None or an integer >= 1")
+    if not lengths or min(lengths) < 1:
+        raise ValueError("admission_chunks: prompts of at least one token")
+    N, rounds = int(chunk_rows), []
+    for c0 in range(0, max(lengths), N):
+        segs = [(i, c0, min(N, n - c0)) for i, n in enumerate(lengths) if n > c0]
+        rounds.append({"reserve": [(i, c + m - 1) for i, c, m in segs], "segments": segs,
+                       "release": [] if window is None else [(i, c + m - int(window)) for i, c, m in segs]})
+    return rounds
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the front
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -439,10 +463,15 @@ class _GeneratorBase:
         self.sampler.step(logits, pos, self.pos_bound)
 
     # ---- admission ----
-    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None) -> list[int]:
+    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None, chunk_rows: int | None = None) -> list[int]:
         """admit(slot, prompt_ids, params, seed, max_new), or admit([(slot, prompt_ids, params, seed, max_new), ...]) for several sequences through ONE prefill_many.
         The prompt is embedded, prefilled through every layer, the final norm and lm_head run on its last row and the first token is sampled; the slot's position
-        becomes the prompt length.  Synchronises.  Returns the slots that retired on their first token."""
+        becomes the prompt length.  Synchronises.  Returns the slots that retired on their first token.
+        chunk_rows = N >= 1 (paged decoders): the prompts go through in chunks of at most N rows (admission_chunks) -- per chunk pages are reserved through its last
+        key, all or nothing across the admissions, the chunk is embedded and prefilled at its position through ALL layers, and when every layer has a window the
+        pages wholly behind it are given back before the next chunk.  A windowed slot then never holds more than ceil((max W + N) / page_keys) + 1 pages, so a prompt
+        longer than the pool can be admitted; without windows only the activation rows are bounded.  PagePoolExhausted in a later chunk: the slots of this call are
+        released and the generator is as it was before the call.  A chunked prefill is not bit-identical to the one-shot one (the prefill's tiling differs)."""
         import torch
         adm = slot if prompt_ids is None else [(slot, prompt_ids, params, seed, max_new)]
         adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(self.sampler.log_stride if mn is None else mn)) for s, ids, p, sd, mn in adm]
@@ -458,22 +487,33 @@ class _GeneratorBase:
             p.check(self.sampler.top_k_bound)
             if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
                 raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new 1 .. {self.sampler.log_stride}")
+        if chunk_rows is not None:
+            if self.allocator is None:
+                raise ValueError("admit: chunk_rows needs paged decoders")
+            if int(chunk_rows) != chunk_rows or int(chunk_rows) < 1:
+                raise ValueError(f"chunk_rows {chunk_rows}: None or an integer >= 1")
         if self.allocator is not None:  # all or nothing, before anything changes
             if any(self.allocator.pages[s] or self.allocator.gone[s] for s, *_ in adm):
                 raise ValueError("admit: a slot still holds pages (release it first)")
-            self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])
-        rows = []
-        for s, ids, p, sd, mn in adm:
+            if chunk_rows is None:
+                self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])
+
+        def embedded(ids):
             tok = torch.tensor(ids, dtype=torch.int32).to(self.device)
             r = torch.empty((len(ids), self.hidden_size), dtype=torch.float16, device=self.device)
             embed_rows(self.embed_table, tok, r, torch.zeros(len(ids), dtype=torch.int32, device=self.device), 0, self.sampler.workspace)
-            rows.append(r)
-        for d in self.decoders:
-            if self.allocator is not None:
-                d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
-            else:
-                for (s, *_), r in zip(adm, rows):
-                    d.prefill(s, r, 0)
+            return r
+
+        if chunk_rows is not None:
+            rows = self._prefill_chunks(adm, int(chunk_rows), embedded)  # (each prompt's LAST chunk: its last row is the head's input)
+        else:
+            rows = [embedded(ids) for s, ids, *_ in adm]
+            for d in self.decoders:
+                if self.allocator is not None:
+                    d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
+                else:
+                    for (s, *_), r in zip(adm, rows):
+                        d.prefill(s, r, 0)
         self._adm_pos.fill_(-1)
         for (s, ids, p, sd, mn), r in zip(adm, rows):
             self.sampler.set_row(s, p, sd, mn, ids)
@@ -489,6 +529,28 @@ class _GeneratorBase:
         for s, ids, p, sd, mn in adm:
             self.book.admit(s, len(ids), mn)
         return self._sync()
+
+    def _prefill_chunks(self, adm, chunk_rows: int, embedded) -> list:
+        """admit's chunked prefill (admission_chunks is the schedule).  Returns every prompt's last chunk of rows, after all layers.  Nothing of the generator but the
+        allocator changes here, so on any failure releasing this call's slots restores the state before the call."""
+        windows = [getattr(d, "window", None) for d in self.decoders]
+        window = None if any(w is None for w in windows) else max(windows)
+        last = [None] * len(adm)
+        try:
+            for rnd in admission_chunks([len(ids) for _, ids, *_ in adm], chunk_rows, window):
+                self.allocator.reserve_many([(adm[i][0], upto) for i, upto in rnd["reserve"]])
+                chunk = [(adm[i][0], embedded(adm[i][1][c0:c0 + m]), c0) for i, c0, m in rnd["segments"]]
+                for d in self.decoders:
+                    d.prefill_many(chunk)
+                for (i, _, _), (_, r, _) in zip(rnd["segments"], chunk):
+                    last[i] = r
+                for i, key in rnd["release"]:
+                    self.allocator.release_behind(adm[i][0], key)
+        except Exception:
+            for s, *_ in adm:
+                self.allocator.release(s)
+            raise
+        return last
 
     def _admitted(self, admitted) -> None:
         """A subclass's own record of [(slot, prompt ids)], the first tokens sampled (sampler.next_token)."""

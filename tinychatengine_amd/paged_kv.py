@@ -18,7 +18,8 @@ per pool, 2^k_scale_log2 and 2^v_scale_log2, exponents in [-8, 7].  dequant(byte
 fp8_quantize_reference / fp8_dequantize_reference restate the format on the host.
 
 window=W (PagedBatchDecodeAttention / PagedBatchedDecoder): sliding-window attention -- a row at position p weighs keys max(0, p - W + 1) .. p -- through the
-*_window entry points; the pages wholly behind every layer's window are given back with PageAllocator.release_behind (generate._GeneratorBase.run does).
+*_window entry points; the pages wholly behind every layer's window are given back with PageAllocator.release_behind (generate._GeneratorBase.run does, and
+admit(..., chunk_rows=N) does between the chunks of a prompt).
 
 Trust: the step follows only table words 0 .. pos // page_keys of an active row (with a window: max(0, pos - W + 1) // page_keys .. pos // page_keys); everything else in the table may hold anything (a released slot's words stay as
 they were).  It does not validate page numbers: PageAllocator writes only numbers in [0, num_pages), and PagedBatchDecodeAttention.table_violations runs
@@ -326,9 +327,8 @@ class PagedBatchDecodeAttention:
         return self._step(self._entry("tce_attention_decode_step_paged"), None, qkv, pos_device, pos_bound, out)
 
     def _step(self, entry: str, rows_per_seq: int | None, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None) -> torch.Tensor:
-        """The step's assertions and call, `entry`_f16 or _fp8, for batch * rows_per_seq rows (None: one row per sequence, and an entry point without that argument)."""
-        if rows_per_seq is not None and self.window is not None:
-            raise ValueError("the multi-row step with a window is not built")
+        """The step's assertions and call, `entry`_f16 or _fp8, for batch * rows_per_seq rows (None: one row per sequence, and an entry point without that argument).
+        With a window the caller's `entry` already carries the suffix (_entry): ..._paged_window, ..._paged_rows_window."""
         n = self.batch * (rows_per_seq or 1)
         rw = (self.heads + 2 * self.kv_heads) * self.hd
         assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == n * rw

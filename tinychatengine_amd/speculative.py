@@ -126,14 +126,33 @@ class SpecSlotBook(SlotBook):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the layers at B T rows
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
+def rows_check_calls(n_active, last_pos, rows_per_seq: int, window: int | None) -> list[tuple[int | None, list[int]]]:
+    """The table checks that cover a rows step: per sequence n_active[b] rows at consecutive positions that end at last_pos[b] (n_active 0: inactive).  Returns
+    [(window argument, position words [batch])]: one tce_kv_block_table_check call each (window None: the unwindowed check), -1 for the sequences a call leaves out.
+    Unwindowed rows follow words 0 .. last // page_keys: the check at the last position.  Windowed rows p .. p + n - 1 follow the union of
+    [max(0, p + t - W + 1) // page_keys, (p + t) // page_keys], t < n -- contiguous, from row 0's first word to row n - 1's last --, which is what
+    tce_kv_block_table_check_window follows for position p + n - 1 with window W + n - 1: one call per distinct n."""
+    _check_rows(rows_per_seq)
+    n_active, last_pos = [int(n) for n in n_active], [int(p) for p in last_pos]
+    assert len(n_active) == len(last_pos) and all(0 <= n <= rows_per_seq for n in n_active)
+    if window is None:
+        return [(None, [p if n else -1 for n, p in zip(n_active, last_pos)])]
+    return [(int(window) + n - 1, [p if m == n else -1 for m, p in zip(n_active, last_pos)]) for n in sorted(set(n_active) - {0})]
+
+
 class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
     """PagedBatchDecodeAttention whose step takes rows_per_seq rows per sequence (tce_attention_decode_step_paged_rows_f16 / _fp8): a workspace slice per virtual
-    row; prefill and the copies are the parent's."""
+    row; prefill and the copies are the parent's.  window=W: tce_attention_decode_step_paged_rows_window_f16 / _fp8 -- row t of a sequence at position p weighs keys
+    max(0, p + t - W + 1) .. p + t, the call's own rows among them from the call itself.  Rejected drafts leave pool rows beyond the accepted position: the next
+    call's rows start AT that position and take every key from there on from their own q/k/v rows, and each appends its own row, so a stale row is overwritten
+    before any row weighs it -- with a window as without."""
 
     def __init__(self, allocator, heads, kv_heads, device, cos=None, sin=None, rows_per_seq: int = 1, **kw):
         _check_rows(rows_per_seq)
-        if kw.get("window") is not None:
-            raise ValueError("the multi-row step with a window is not built")
+        if kw.get("window") is not None and not allocator.table.is_cuda:
+            # (the unwindowed form may be built over a host table for bookkeeping tests; with a window every path of this class -- step, table_violations -- is a
+            # device path, and a host table would only fail later, inside a launch wrapper)
+            raise ValueError("PagedRowsDecodeAttention: a window needs the allocator's block table on the device")
         super().__init__(allocator, heads, kv_heads, device, cos, sin, **kw)
         self.rows_per_seq = int(rows_per_seq)
         need = int(capi.lib().tce_attention_decode_batch_workspace_bytes(self.batch * self.rows_per_seq, heads, self.max_keys, self.hd))
@@ -145,18 +164,36 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
     def step(self, qkv, pos_device, pos_bound: int, out=None):
         """qkv fp16 [batch * T][(heads + 2 kv_heads) * 128], pos_device int32 [batch * T]: the ROWS' positions (a prefix p, p + 1, ... per sequence, -1 behind
         it).  One launch."""
-        return self._step("tce_attention_decode_step_paged_rows", self.rows_per_seq, qkv, pos_device, pos_bound, out)
+        return self._step(self._entry("tce_attention_decode_step_paged_rows"), self.rows_per_seq, qkv, pos_device, pos_bound, out)
+
+    def table_violations(self, pos_device, pos_bound: int) -> int:
+        """The table check for a rows step: pos_device int32 [batch * T], the ROWS' positions as step() takes them.  The words the step would follow that are not page
+        numbers (0: sound), through rows_check_calls; waited for."""
+        assert pos_device.dtype == torch.int32 and pos_device.numel() == self.batch * self.rows_per_seq
+        rp = pos_device.view(self.batch, self.rows_per_seq).cpu().numpy()
+        active = (rp >= 0) & (rp <= pos_bound)
+        last = np.where(active, rp, -1).max(axis=1)
+        tab, stride, pk, n = self._table_args()
+        bad = 0
+        for w, words in rows_check_calls(active.sum(axis=1), last, self.rows_per_seq, self.window):
+            pos = torch.tensor(words, dtype=torch.int32, device=pos_device.device)
+            fn = capi.lib().tce_kv_block_table_check if w is None else capi.lib().tce_kv_block_table_check_window
+            capi.check(fn(tab, stride, pk, n, self.batch, C.c_void_p(pos.data_ptr()), int(pos_bound), C.c_void_p(self._violations.data_ptr()),
+                          *(() if w is None else (w,)), C.c_void_p(_stream())))
+            bad += int(self._violations.item())
+        return bad
 
 
 class SpeculativeDecoder(PagedBatchedDecoder):
     """PagedBatchedDecoder whose step runs batch * rows_per_seq rows: the same seven launches (BatchedDecoder.step: hidden fp16 [batch * T][hidden], the position
-    words tce_draft_ngram's row_pos int32 [batch * T]), the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill / prefill_many are the parent's."""
+    words tce_draft_ngram's row_pos int32 [batch * T]), the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill / prefill_many are the parent's.  window: this
+    layer's sliding window (the windowed rows step and the windowed prefill), None for full attention."""
 
-    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0):
+    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None):
         _check_rows(rows_per_seq)
         self.rows_per_seq = int(rows_per_seq)
         attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin,
-                                             rows_per_seq=rows_per_seq, kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2)
+                                             rows_per_seq=rows_per_seq, kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window)
         super().__init__(block, allocator, attention=attention, rows=allocator.batch * self.rows_per_seq)
 
 
@@ -217,13 +254,18 @@ class Verifier:
 class SpeculativeGenerator(_GeneratorBase):
     """decoders: one SpeculativeDecoder per layer over ONE PageAllocator, all with the same rows_per_seq.  The token step is captured once in one torch.cuda.graph;
     one replay is 1 .. rows_per_seq tokens per live sequence.  script=True (a test hook) allocates `script` int32 [batch][hist_stride], -1 everywhere, which then
-    REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t].  admit / tokens / logprobs / release are BatchedGenerator's."""
+    REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t].  admit / tokens / logprobs / release are BatchedGenerator's.
+    Decoders with sliding windows: as in BatchedGenerator, run() gives back the pages wholly behind every layer's window around each burst.  Row 0 of the next
+    replay sits at the synced position p and needs keys from p - W + 1 on, later rows and later replays only later keys, so SpecSlotBook.wanted and _release_behind
+    are the plain loop's; a slot holds at most ceil((max W + n T) / page_keys) + 1 pages through run(n)."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False):
         decoders = list(decoders)
-        if any(getattr(d, "window", None) is not None for d in decoders):
-            raise ValueError("SpeculativeGenerator: a decoder has a sliding window, and the multi-row step with a window is not built")
+        for d in decoders:  # a windowed layer must run the windowed ROWS step: its attention object carries the window (SpeculativeDecoder(..., window=W) builds it so)
+            w = getattr(d, "window", None)
+            if w is not None and getattr(getattr(d, "attention", None), "window", None) != w:
+                raise ValueError(f"SpeculativeGenerator: a decoder reports window {w} but its attention object does not carry it (build the layer as SpeculativeDecoder(..., window=W))")
         self.rows_per_seq, self.ngram = decoders[0].rows_per_seq, int(ngram)
         _check_rows(self.rows_per_seq, self.ngram)
         assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
