@@ -18,11 +18,10 @@
 //              feeds ROWS rows.
 //   * UNPACK   7 VALU instructions per 8 weights: each nibble pair is moved to mantissa bits 4..7 of the half
 //              1024.0 (3 shifts + 4 v_and_or_b32 with the mask in a VGPR -- gfx9 VOP3 reads one scalar only), giving the
-//              halves 1024 + 16q.  The zero point is NOT removed per element:
-//                  sum_k (q_k - z) x_k = ( sum_k (1024 + 16 q_k) x_k  -  (1024 + 16 z) * sum_k x_k ) / 16
-//              where sum_k x_k per 32-weight chunk is row independent (computed once per step, on the matrix pipe).
-//              The bias is only ~14x the signal at this nibble position, so the fp32 accumulation noise it adds is
-//              ~2e-6 of the output rms (DESIGN.md "GEMV numerics"), three orders below the 1e-3 budget.
+//              halves 1024 + 16q; one packed subtraction of (1024 + 16z) per two weights then leaves 16 (q - z), exactly.
+//              (Until the designed-operand tests the zero point was removed algebraically, sum (1024 + 16 q) x - (1024 + 16 z) sum x
+//              in fp32: the difference of two terms 10^3 - 10^6 times the signal on a row with a large sum or one large element,
+//              1.8 - 105 times the 1e-3 bound there)
 //   * DOT      on the otherwise idle matrix pipe: v_mfma_f32_4x4x4_16b_f16 computes, per group of 4 lanes,
 //              D[i][j] = sum_k A_i[k] B_j[k] over the 4 halves each lane supplies; with A = a lane's weights and
 //              B = the same lane's activations the DIAGONAL D[l%4][l%4] is that lane's own dot product, accumulated
@@ -287,6 +286,8 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
     unsigned mask_hi;
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
     const unsigned magic = 0x64006400u;  // (1024.0h, 1024.0h)
+    unsigned cz8_bits = 0x64806480u;  // (1152.0h, 1152.0h) = 1024 + 16 * 8, held in a scalar register: the packed subtraction reads it from there
+    asm volatile("" : "+s"(cz8_bits));
     const half4_t ones = half4_t{(half_t)1.0f, (half_t)1.0f, (half_t)1.0f, (half_t)1.0f};
 
     auto compute = [&](const Step &st, int t) {
@@ -327,6 +328,14 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
             float4_t blk[MB];
 #pragma unroll
             for (int m = 0; m < MB; ++m) blk[m] = float4_t{0.f, 0.f, 0.f, 0.f};
+            // the zero point leaves per element: (1024 + 16 q) - (1024 + 16 z) = 16 (q - z), exact in binary16 (one packed add per two weights)
+            half4_t cz4;
+            if constexpr (Z8) {
+                cz4 = __builtin_bit_cast(half4_t, uint2_t{cz8_bits, cz8_bits});
+            } else {
+                const half_t czh = (half_t)__builtin_fmaf((float)((st.z[i] >> zsh) & 0xFu), 16.0f, 1024.0f);
+                cz4 = half4_t{czh, czh, czh, czh};
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned w = st.w[i][j];
@@ -334,8 +343,8 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
                 const unsigned t1 = (w & mask_hi) | magic;         // (q1, q5)
                 const unsigned t2 = ((w >> 4) & mask_hi) | magic;  // (q2, q6)
                 const unsigned t3 = ((w >> 8) & mask_hi) | magic;  // (q3, q7)
-                const half4_t a0 = __builtin_bit_cast(half4_t, uint2_t{t0, t1});
-                const half4_t a1 = __builtin_bit_cast(half4_t, uint2_t{t2, t3});
+                const half4_t a0 = __builtin_bit_cast(half4_t, uint2_t{t0, t1}) - cz4;
+                const half4_t a1 = __builtin_bit_cast(half4_t, uint2_t{t2, t3}) - cz4;
 #pragma unroll
                 for (int m = 0; m < MB; ++m) {
                     blk[m] = __builtin_amdgcn_mfma_f32_4x4x4f16(a0, xb[m][2 * j], blk[m], 0, 0, 0);
@@ -345,13 +354,10 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
             // lanes 4b..4b+3 share a quantization group (32 weights per lane, groups of >= 32), so scaling all four
             // accumulator registers by this lane's scale is consistent; the diagonal is picked once, at the end
             const float s = (float)__builtin_bit_cast(half_t, st.s[i]);
-            const float cz = Z8 ? 1152.0f : __builtin_fmaf((float)((st.z[i] >> zsh) & 0xFu), 16.0f, 1024.0f);  // 1024 + 16 z
-            const float scz = s * cz;
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][m][r] = __builtin_fmaf(s, blk[m][r], acc[i][m][r]);
-                corr[i][m] = __builtin_fmaf(scz, xsum[m], corr[i][m]);
             }
         }
     };
@@ -597,7 +603,7 @@ int launch_w4a16_gemv(const tce_w4a16_desc *descs, int count, int forced_rows, i
     a.zeros_are_8 = 1;
     for (int i = 0; i < count; ++i)
         if (!(descs[i].flags & TCE_W4_ZERO_POINT_IS_8)) a.zeros_are_8 = 0;
-    a.shared_xsum = g_shared_xsum == 1 || (g_shared_xsum == 0 && d0.M == 1);
+    a.shared_xsum = false;  // (no zero-point term is left that needs the chunks' activation sums; the switch g_shared_xsum is kept for the ABI's tuning calls)
 
     int total_n = 0;
     for (int i = 0; i < count; ++i) total_n += descs[i].N;

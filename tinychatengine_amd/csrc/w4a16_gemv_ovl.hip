@@ -276,7 +276,8 @@ __global__ __launch_bounds__(64 * NW, 8 / (NW / 4)) void w4a16_gemv_ovl_kernel(c
     unsigned mask_hi;  // nibble mask in a VGPR (tce_common.hpp: one scalar operand per VOP3 on gfx9)
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
     const unsigned magic = 0x64006400u;  // (1024.0h, 1024.0h)
-    const half4_t ones = half4_t{(half_t)1.0f, (half_t)1.0f, (half_t)1.0f, (half_t)1.0f};
+    unsigned cz8_bits = 0x64806480u;  // (1152.0h, 1152.0h), held in a scalar register
+    asm volatile("" : "+s"(cz8_bits));
     float acc[ROWS][4];  // the 4 accumulator registers of the 4x4x4 MFMA; the lane's own dot product is [lane & 3]
     float corr[ROWS];    // sum over chunks of s * (1024 + 16 z) * sum_k x_k, z = 8
 #pragma unroll
@@ -298,20 +299,17 @@ __global__ __launch_bounds__(64 * NW, 8 / (NW / 4)) void w4a16_gemv_ovl_kernel(c
         }
         const int t = c_t;
         half4_t xb[8];
-        float4_t xs4 = float4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint4_t xp = xs[(t * 4 + j) * 64 + lane];
             xb[2 * j] = __builtin_bit_cast(half4_t, uint2_t{xp.x, xp.y});      // (x0,x4,x1,x5) of word j
             xb[2 * j + 1] = __builtin_bit_cast(half4_t, uint2_t{xp.z, xp.w});  // (x2,x6,x3,x7)
-            xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, xb[2 * j], xs4, 0, 0, 0);
-            xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, xb[2 * j + 1], xs4, 0, 0, 0);
         }
-        const float xsum = xs4[0];  // D[i][j] = sum_k B_j[k] for every i: all four registers hold this lane's sum
 #pragma unroll
         for (int i = 0; i < ROWS; ++i) {
             __builtin_amdgcn_sched_barrier(0);  // one row's unpack -> MFMA -> scale at a time (register pressure, see w4a16_gemv.hip)
             float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f};
+            const half4_t cz4 = __builtin_bit_cast(half4_t, uint2_t{cz8_bits, cz8_bits});  // 1024 + 16 * 8: removed per element, exactly (w4a16_gemv.hip)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned wj = w[i][j];
@@ -319,13 +317,12 @@ __global__ __launch_bounds__(64 * NW, 8 / (NW / 4)) void w4a16_gemv_ovl_kernel(c
                 const unsigned t1 = (wj & mask_hi) | magic;         // (q1, q5)
                 const unsigned t2 = ((wj >> 4) & mask_hi) | magic;  // (q2, q6)
                 const unsigned t3 = ((wj >> 8) & mask_hi) | magic;  // (q3, q7)
-                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t0, t1}), xb[2 * j], blk, 0, 0, 0);
-                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t2, t3}), xb[2 * j + 1], blk, 0, 0, 0);
+                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t0, t1}) - cz4, xb[2 * j], blk, 0, 0, 0);
+                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t2, t3}) - cz4, xb[2 * j + 1], blk, 0, 0, 0);
             }
             const float s = (float)__builtin_bit_cast(half_t, (unsigned short)(sbits[i] & 0xFFFFu));
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][r] = __builtin_fmaf(s, blk[r], acc[i][r]);
-            corr[i] = __builtin_fmaf(s * 1152.0f, xsum, corr[i]);  // 1024 + 16 * 8
         }
         // every LDS read of this slot has returned before the slot is handed back to the DMA engine
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

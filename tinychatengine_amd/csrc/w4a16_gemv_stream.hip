@@ -195,7 +195,6 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
     const __amdgpu_buffer_rsrc_t rs_t =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned *>(tagged_in ? L.A_tag : reinterpret_cast<const unsigned *>(A)), 0, 0x7FFFFFF0, 0x00020000);
     uint4_t *xs = reinterpret_cast<uint4_t *>(smem);                  // [T][4][64] pieces of 16 bytes (pair-permuted, lane-linear)
-    float *xsl = reinterpret_cast<float *>(smem + (size_t)T * 4096);  // [T][64]: sum of the 32 activations of (step, lane)
     const int total_pieces = T * 256;
     // x piece p -> 16 bytes of the vector.  sc0 sc1: device-coherent read -- behind a barrier the vector was written by
     // other CUs (other XCDs, other L2s) moments ago, and this CU / this L2 may still hold the previous token's lines.
@@ -339,21 +338,8 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
         }
     }
     __syncthreads();
-    {
-        // D[i][j] = sum_k A_i[k] B_j[k] with A = ones: every accumulator register of a lane holds that lane's own sum
-        const half4_t ones = half4_t{(half_t)1.0f, (half_t)1.0f, (half_t)1.0f, (half_t)1.0f};
-        for (int t = wave; t < T; t += NW) {
-            float4_t xs4 = float4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint4_t xp = xs[(t * 4 + j) * 64 + lane];
-                xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, __builtin_bit_cast(half4_t, uint2_t{xp.x, xp.y}), xs4, 0, 0, 0);
-                xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, __builtin_bit_cast(half4_t, uint2_t{xp.z, xp.w}), xs4, 0, 0, 0);
-            }
-            xsl[t * 64 + lane] = xs4[0];
-        }
-    }
-    __syncthreads();
+    // (the per-chunk activation sums the zero-point term needed used to be formed here; the zero point now leaves per element in the unpack.  Their LDS area behind
+    // the image stays in the launch's size, unused)
     if constexpr (MODE == 2) *ts_x_ready = wall_clock64();
     stamp(2);
 
@@ -371,6 +357,8 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
     unsigned mask_hi;  // nibble mask in a VGPR (tce_common.hpp: one scalar operand per VOP3 on gfx9)
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
     const unsigned magic = 0x64006400u;  // (1024.0h, 1024.0h)
+    unsigned cz8_bits = 0x64806480u;  // (1152.0h, 1152.0h) = 1024 + 16 * 8, held in a scalar register: a packed add reads it from there, no vector register is spent
+    asm volatile("" : "+s"(cz8_bits));
     float diag[4];                       // one-hot pick of the lane's diagonal accumulator and the final /16 in one factor
 #pragma unroll
     for (int q = 0; q < 4; ++q) diag[q] = (lane & 3) == q ? 0.0625f : 0.0f;
@@ -396,7 +384,6 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
                 xb[2 * j] = __builtin_bit_cast(half4_t, uint2_t{xp.x, xp.y});      // (x0,x4,x1,x5) of word j
                 xb[2 * j + 1] = __builtin_bit_cast(half4_t, uint2_t{xp.z, xp.w});  // (x2,x6,x3,x7)
             }
-            const float xsum = xsl[t * 64 + lane];
             int zsh = 0;
             if constexpr (!Z8) {
                 const int c = t * 64 + lane;
@@ -409,6 +396,14 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
                 // rows' unpacks ahead of the first MFMA and the register allocation explodes
                 __builtin_amdgcn_sched_barrier(0);
                 float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f};
+                // the zero point leaves per element: (1024 + 16 q) - (1024 + 16 z) = 16 (q - z), exact in binary16 (w4a16_gemv.hip)
+                half4_t cz4;
+                if constexpr (Z8) {
+                    cz4 = __builtin_bit_cast(half4_t, uint2_t{cz8_bits, cz8_bits});
+                } else {
+                    const half_t czh = (half_t)__builtin_fmaf((float)((st.z[i] >> zsh) & 0xFu), 16.0f, 1024.0f);
+                    cz4 = half4_t{czh, czh, czh, czh};
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const unsigned w = st.w[i][j];
@@ -416,16 +411,14 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
                     const unsigned t1 = (w & mask_hi) | magic;         // (q1, q5)
                     const unsigned t2 = ((w >> 4) & mask_hi) | magic;  // (q2, q6)
                     const unsigned t3 = ((w >> 8) & mask_hi) | magic;  // (q3, q7)
-                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t0, t1}), xb[2 * j], blk, 0, 0, 0);
-                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t2, t3}), xb[2 * j + 1], blk, 0, 0, 0);
+                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t0, t1}) - cz4, xb[2 * j], blk, 0, 0, 0);
+                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t2, t3}) - cz4, xb[2 * j + 1], blk, 0, 0, 0);
                 }
                 // lanes 4b..4b+3 share a quantization group (32 weights per lane, groups of >= 32), so scaling all four
                 // accumulator registers by this lane's scale is consistent; the diagonal is picked at the row group's end
                 const float s = (float)__builtin_bit_cast(half_t, st.s[i]);
-                const float cz = Z8 ? 1152.0f : __builtin_fmaf((float)((st.z[i] >> zsh) & 0xFu), 16.0f, 1024.0f);  // 1024 + 16 z
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][r] = __builtin_fmaf(s, blk[r], acc[i][r]);
-                corr[i] = __builtin_fmaf(s * cz, xsum, corr[i]);
             }
         }
         if (t != T - 1) {

@@ -16,9 +16,9 @@
 //     weights (4 consecutive lanes read one row's 64 bytes -- the operand fragment itself would make each quarter-wave
 //     touch 16 rows, see w8a8_gemm.hip) and the 16 x 128 activation block (4 KiB, L1/L2 hits), passes both through its
 //     own LDS slots (swizzled, conflict-free both ways) into fragment order, unpacks with the GEMV's 7-instruction bias
-//     form (halves 1024 + 16 q) and removes bias and zero point algebraically:
-//         sum_k (q - z) x = ( sum_k (1024 + 16 q) x - (1024 + 16 z) sum_k x ) / 16,
-//     where sum_k x per (batch row, group) comes from the same MFMA with A = ones;
+//     form (halves 1024 + 16 q) and subtracts the row's (1024 + 16 z) per element -- 16 (q - z), exact in binary16; one packed
+//     add per two weights, and no second MFMA for sum_k x (the algebraic removal it replaces was the difference of two terms
+//     up to 10^6 times the signal on rows with a large sum or one large element);
 //   * scales and (1024 + 16 z) of the tile's rows and the wave's groups are staged once into LDS as halves (exact).
 //
 // Same math and tolerance as the GEMV (fp32 accumulation of exact products, one fp32 scale per group); G = 128 only.
@@ -116,7 +116,6 @@ __global__ __launch_bounds__(512) void w4a16_skinny_kernel(const SkinnyArgs a) {
     unsigned mask_hi;
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
     const unsigned magic = 0x64006400u;
-    const half8_t ones = half8_t{(half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f};
 
     auto process = [&](const Regs &r, int g) {
         // registers -> LDS in fragment-friendly order.  A wave's LDS operations complete in order, so the reads below see
@@ -126,7 +125,10 @@ __global__ __launch_bounds__(512) void w4a16_skinny_kernel(const SkinnyArgs a) {
         for (int j = 0; j < 4; ++j) lds_x[x_wslot[j]] = pair_permute(r.x[j]);
         __builtin_amdgcn_wave_barrier();
         const uint4_t wq = lds_w[w_rslot];  // row r16, k-chunk kq: word s feeds MFMA step s
-        float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f}, xs = float4_t{0.f, 0.f, 0.f, 0.f};
+        float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f};
+        // the zero point leaves per element: (1024 + 16 q) - (1024 + 16 z) = 16 (q - z), exact in binary16 -- row r16's own constant for this group
+        const half_t czh = tab_c[g * 16 + r16];
+        const half8_t cz8 = half8_t{czh, czh, czh, czh, czh, czh, czh, czh};
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int pc = kq * 4 + s;
@@ -136,19 +138,14 @@ __global__ __launch_bounds__(512) void w4a16_skinny_kernel(const SkinnyArgs a) {
             const unsigned t1 = (w & mask_hi) | magic;         // (q1, q5)
             const unsigned t2 = ((w >> 4) & mask_hi) | magic;  // (q2, q6)
             const unsigned t3 = ((w >> 8) & mask_hi) | magic;  // (q3, q7)
-            const half8_t wa = __builtin_bit_cast(half8_t, uint4_t{t0, t1, t2, t3});
+            const half8_t wa = __builtin_bit_cast(half8_t, uint4_t{t0, t1, t2, t3}) - cz8;
             blk = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xb, blk, 0, 0, 0);
-            xs = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, xb, xs, 0, 0, 0);  // every row: sum_k x[m = r16][k]
         }
         __builtin_amdgcn_wave_barrier();
         // rows 4*kq .. 4*kq+3 of the tile: their scale and (1024 + 16 z) for this group
         const half4_t s4 = *reinterpret_cast<const half4_t *>(tab_s + g * 16 + 4 * kq);
-        const half4_t c4 = *reinterpret_cast<const half4_t *>(tab_c + g * 16 + 4 * kq);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float t = __builtin_fmaf(-(float)c4[i], xs[i], blk[i]);
-            acc[i] = __builtin_fmaf((float)s4[i], t, acc[i]);
-        }
+        for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf((float)s4[i], blk[i], acc[i]);
     };
 
     // ---- the wave's k-blocks, loads one block ahead (two static register sets; clamped, never predicated) ----
@@ -268,36 +265,31 @@ __global__ __launch_bounds__(512) void w4a16_skinny_shared_kernel(const SkinnyAr
     unsigned mask_hi;
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
     const unsigned magic = 0x64006400u;
-    const half8_t ones = half8_t{(half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f};
 
     // one stage: both k-blocks' weights through the wave's LDS slots, then four independent MFMA chains
     auto stage = [&](const uint4_t *xi, int g) {
         const uint4_t wq0 = lds_w[w_rslot], wq1 = lds_w[64 + w_rslot];
-        float4_t blk0 = float4_t{0.f, 0.f, 0.f, 0.f}, xs0 = blk0, blk1 = blk0, xs1 = blk0;
+        float4_t blk0 = float4_t{0.f, 0.f, 0.f, 0.f}, blk1 = blk0;
+        const half_t cz0 = tab_c[g * 16 + r16], cz1 = tab_c[g * 16 + 16 + r16];  // row r16's 1024 + 16 z of the two k-blocks: removed per element, exactly
+        const half8_t c80 = half8_t{cz0, cz0, cz0, cz0, cz0, cz0, cz0, cz0}, c81 = half8_t{cz1, cz1, cz1, cz1, cz1, cz1, cz1, cz1};
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int pc = kq * 4 + s;
             const half8_t xb0 = __builtin_bit_cast(half8_t, xi[pc * 16 + (r16 ^ pc)]);
             const half8_t xb1 = __builtin_bit_cast(half8_t, xi[256 + pc * 16 + (r16 ^ pc)]);
             const unsigned w = wq0[s], v = wq1[s];
-            const half8_t a0 = __builtin_bit_cast(half8_t, uint4_t{((w << 4) & mask_hi) | magic, (w & mask_hi) | magic, ((w >> 4) & mask_hi) | magic, ((w >> 8) & mask_hi) | magic});
-            const half8_t a1 = __builtin_bit_cast(half8_t, uint4_t{((v << 4) & mask_hi) | magic, (v & mask_hi) | magic, ((v >> 4) & mask_hi) | magic, ((v >> 8) & mask_hi) | magic});
+            const half8_t a0 = __builtin_bit_cast(half8_t, uint4_t{((w << 4) & mask_hi) | magic, (w & mask_hi) | magic, ((w >> 4) & mask_hi) | magic, ((w >> 8) & mask_hi) | magic}) - c80;
+            const half8_t a1 = __builtin_bit_cast(half8_t, uint4_t{((v << 4) & mask_hi) | magic, (v & mask_hi) | magic, ((v >> 4) & mask_hi) | magic, ((v >> 8) & mask_hi) | magic}) - c81;
             blk0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, xb0, blk0, 0, 0, 0);
             blk1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, xb1, blk1, 0, 0, 0);
-            xs0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, xb0, xs0, 0, 0, 0);
-            xs1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, xb1, xs1, 0, 0, 0);
         }
         __builtin_amdgcn_wave_barrier();
         const half4_t s40 = *reinterpret_cast<const half4_t *>(tab_s + g * 16 + 4 * kq);
-        const half4_t c40 = *reinterpret_cast<const half4_t *>(tab_c + g * 16 + 4 * kq);
         const half4_t s41 = *reinterpret_cast<const half4_t *>(tab_s + g * 16 + 16 + 4 * kq);
-        const half4_t c41 = *reinterpret_cast<const half4_t *>(tab_c + g * 16 + 16 + 4 * kq);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {  // k-block order, as the autonomous kernel
-            const float t0 = __builtin_fmaf(-(float)c40[i], xs0[i], blk0[i]);
-            acc[i] = __builtin_fmaf((float)s40[i], t0, acc[i]);
-            const float t1 = __builtin_fmaf(-(float)c41[i], xs1[i], blk1[i]);
-            acc[i] = __builtin_fmaf((float)s41[i], t1, acc[i]);
+            acc[i] = __builtin_fmaf((float)s40[i], blk0[i], acc[i]);
+            acc[i] = __builtin_fmaf((float)s41[i], blk1[i], acc[i]);
         }
     };
 
