@@ -380,10 +380,6 @@ int tce_w4a16_set_debug_mode(int mode) {
         tce::set_gemm_dma_xcd_rows(mode - 40);
         return TCE_OK;
     }
-    if (mode >= 45 && mode <= 47) {  // GEMV, the per-chunk activation sums: 46 the rule (once per workgroup for M = 1), 47 once per workgroup, 45 by every wave
-        tce::set_gemv_shared_xsum(mode == 45 ? 2 : mode - 46);
-        return TCE_OK;
-    }
     if (mode >= 80 && mode <= 87) {  // LayerNormQ + W8A8 group: 81 = the workgroup-per-8-rows form at every k; wide form: 83 no sums (wrong results), 84 no output rows, 85 phase times of workgroup 0 into the debug buffer, 86 the wide form from k = 256 on, 87 the 4-wave form's single row walked by one wave
         tce::set_lnq_form(mode - 80);
         return TCE_OK;
@@ -762,7 +758,8 @@ int tce_w4a16_describe_dispatch(const tce_w4a16_desc *d, char *buf, int buf_len)
     // which GEMV kernel: same rule as tce_w4a16_forward_group (one linear per launch here)
     const bool persistent = g_gemv_kernel == 2 || (d->rmsnorm_gamma ? (g_gemv_kernel == 0 && d->N >= kFusedNormPersistentRows)
                                                                      : (g_gemv_kernel == 0 && d->M == 1 && (long long)d->N * d->K >= kPersistentMinWeights && g_debug_mode_capi == 0));
-    std::snprintf(buf, (size_t)buf_len, "gemv passes=%d kernel=%s", (d->M + 3) / 4, persistent && d->M == 1 ? "persistent" : "row-block");
+    // (a launch the persistent kernel refuses -- M > 1, an over-long K -- goes to the row-block kernel: tce_w4a16_forward_group)
+    std::snprintf(buf, (size_t)buf_len, "gemv passes=%d kernel=%s", (d->M + 3) / 4, persistent && tce::gemv_stream_supports(d, 1) ? "persistent" : "row-block");
     return TCE_OK;
 }
 
@@ -1815,7 +1812,6 @@ int tce_layernorm_q_w8a8_group(const float *x, const float *ln_weight, const flo
 // ---------------------------------------------------------------------------------------------
 struct TunedGeometry {
     int rows = 0, wn = 0, wk = 0, depth = 0;  // all zero: the dispatcher's choice
-    int shared_xsum = 0;                      // the per-chunk activation sums (w4a16_gemv.hip): 0 the rule (once per workgroup), 2 by every wave
     int order = 0;                            // 0: the rule; 1: x staged before the first weight load; 2: weights first
 };
 
@@ -1906,11 +1902,9 @@ static int tune_plan_launches(const std::vector<tce_w4a16_desc> &descs, const st
         for (int i = 0; i < n_launches && rc == TCE_OK; ++i) {
             const bool forced = g[i].rows != 0;
             if (forced && tce_w4a16_set_gemv_config(g[i].rows, g[i].wn, g[i].wk, g[i].depth) != TCE_OK) rc = TCE_ERR_BAD_ARG;
-            tce::set_gemv_shared_xsum(g[i].shared_xsum);
             tce::set_gemv_order(g[i].order);
             if (rc == TCE_OK) rc = groups[i] == 1 ? tce_w4a16_forward(&copy[offs[i]], st) : tce_w4a16_forward_group(&copy[offs[i]], groups[i], st);
             tce::set_gemv_order(0);
-            tce::set_gemv_shared_xsum(0);
             if (forced) (void)tce_w4a16_set_gemv_config(0, 0, 0, 0);
         }
         const hipError_t ee = hipStreamEndCapture(st, &graph);
@@ -1961,16 +1955,15 @@ static int tune_plan_launches(const std::vector<tce_w4a16_desc> &descs, const st
             }
         }
     }
-    // further knobs, same acceptance rule (results bit-identical): the activation sums once per workgroup; the issue order (x staged first / weights first)
-    for (int knob = 0; knob < 3; ++knob) {
+    // one further knob, same acceptance rule (results bit-identical): the issue order, 1 = x staged first, 2 = weights first
+    for (int order = 1; order <= 2; ++order) {
         std::fill(done.begin(), done.end(), 0);
         for (int i = 0; i < n_launches && best_us > 0.f; ++i) {
             if (sig[i].empty() || done[i]) continue;
             std::vector<TunedGeometry> trial(best);
             for (int k = i; k < n_launches; ++k)
                 if (sig[k] == sig[i]) {
-                    if (knob == 0) trial[k].shared_xsum = 2;
-                    else trial[k].order = knob;
+                    trial[k].order = order;
                     done[k] = 1;
                 }
             const float us = time_plan(trial);
@@ -2064,14 +2057,10 @@ int tce_plan_create_ex(const tce_w4a16_desc *descs, const int32_t *group_sizes, 
             if (i < p->token_i8_taken) continue;  // (inside the token kernel)
             const bool forced = i < (int)p->tuned.size() && p->tuned[i].rows != 0;
             if (forced) (void)tce_w4a16_set_gemv_config(p->tuned[i].rows, p->tuned[i].wn, p->tuned[i].wk, p->tuned[i].depth);
-            if (i < (int)p->tuned.size()) {
-                tce::set_gemv_shared_xsum(p->tuned[i].shared_xsum);
-                tce::set_gemv_order(p->tuned[i].order);
-            }
+            if (i < (int)p->tuned.size()) tce::set_gemv_order(p->tuned[i].order);
             if (independent) rc = tce_w4a16_forward_independent(&p->descs[off], p->groups[i], nullptr, cap);
             else rc = p->groups[i] == 1 ? tce_w4a16_forward(&p->descs[off], cap) : tce_w4a16_forward_group(&p->descs[off], p->groups[i], cap);
             tce::set_gemv_order(0);
-            tce::set_gemv_shared_xsum(0);
             if (forced) (void)tce_w4a16_set_gemv_config(0, 0, 0, 0);
         }
     }
@@ -2122,7 +2111,7 @@ int tce_plan_launch_geometry(const tce_plan *plan, int launch, int *rows, int *w
     *rows = g.rows;
     *waves_n = g.wn;
     *waves_k = g.wk;
-    *depth = g.depth + 100 * g.shared_xsum + 1000 * g.order;  // (+ 200: the activation sums by every wave instead of once per workgroup; + 1000 / 2000: x first / weights first forced)
+    *depth = g.depth + 1000 * g.order;  // (+ 1000 / 2000: x first / weights first forced; the hundreds digit, once a knob of its own, is always 0)
     return TCE_OK;
 }
 

@@ -16,22 +16,17 @@
 //   * X        the activation vector is staged once per workgroup into LDS, permuted into the pair order the int4
 //              extraction yields, in a lane-linear image (every ds_read_b128 is bank-conflict free); one read
 //              feeds ROWS rows.
-//   * UNPACK   7 VALU instructions per 8 weights: each nibble pair is moved to mantissa bits 4..7 of the half
-//              1024.0 (3 shifts + 4 v_and_or_b32 with the mask in a VGPR -- gfx9 VOP3 reads one scalar only), giving the
-//              halves 1024 + 16q; one packed subtraction of (1024 + 16z) per two weights then leaves 16 (q - z), exactly.
-//              (Until the designed-operand tests the zero point was removed algebraically, sum (1024 + 16 q) x - (1024 + 16 z) sum x
-//              in fp32: the difference of two terms 10^3 - 10^6 times the signal on a row with a large sum or one large element,
-//              1.8 - 105 times the 1e-3 bound there)
+//   * UNPACK   7 VALU instructions per 8 weights leave the halves 16 (q - z), exactly: w4a16_unpack16.hpp has the form and why.
 //   * DOT      on the otherwise idle matrix pipe: v_mfma_f32_4x4x4_16b_f16 computes, per group of 4 lanes,
 //              D[i][j] = sum_k A_i[k] B_j[k] over the 4 halves each lane supplies; with A = a lane's weights and
 //              B = the same lane's activations the DIAGONAL D[l%4][l%4] is that lane's own dot product, accumulated
 //              in fp32 across calls (the off-diagonal cross terms are discarded at the end with a one-hot multiply).
-//   * SCALE    the fp16 group scale is applied in fp32 once per 32 weights (4 fma for the accumulator, 2 for the
-//              zero-point term).
+//   * SCALE    the fp16 group scale is applied in fp32 once per 32 weights (4 fma for the accumulator).
 //   * REDUCE   64-lane shuffle tree (+ an LDS hop when WK waves split K).
 //   * GROUP    up to TCE_MAX_GROUP linears that share the activation (q/k/v, gate/up) run as ONE launch.
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "w4a16_unpack16.hpp"
 
 #include <type_traits>
 
@@ -250,45 +245,20 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
         for (int d = 0; d < DEPTH; ++d) issue(st[d], d);
     }
     if constexpr (MODE == 2) ts1 = wall_clock64();
-    // The sum of a chunk's 32 activations (the zero-point term's factor) does not depend on the row: all WN waves along N used to form it for every
-    // step with 8 MFMAs (A = ones) -- a third of the launch's MFMAs at two rows per wave.  With `shared_xsum` wave wn forms it for the steps
-    // t = wn, wn + WN, ... only (the same 8 MFMAs in the same order: the same bits), the table goes through LDS behind the trash slots.
-    float *sxt = reinterpret_cast<float *>(smem + (size_t)total_pieces * 16 + (size_t)NTHREADS * 16);  // [MB][T][WK][64]
-    if (args.shared_xsum) {
-        const half4_t ones_t = half4_t{(half_t)1.0f, (half_t)1.0f, (half_t)1.0f, (half_t)1.0f};
-        for (int t = wn; t < T; t += WN) {
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-                float4_t xs4 = float4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint4_t xp = xs[(((m * T + t) * WK + wk) * 4 + j) * 64 + lane];
-                    xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones_t, __builtin_bit_cast(half4_t, uint2_t{xp.x, xp.y}), xs4, 0, 0, 0);
-                    xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones_t, __builtin_bit_cast(half4_t, uint2_t{xp.z, xp.w}), xs4, 0, 0, 0);
-                }
-                sxt[((m * T + t) * WK + wk) * 64 + lane] = xs4[0];
-            }
-        }
-        lds_barrier();
-    }
 
     float acc[ROWS][MB][4];  // the 4 accumulator registers of the 4x4x4 MFMA; the lane's own dot product is [lane & 3]
-    float corr[ROWS][MB];    // sum over chunks of s * (1024 + 16 z) * sum_k x_k
 #pragma unroll
     for (int i = 0; i < ROWS; ++i)
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
-            corr[i][m] = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][m][r] = 0.f;
         }
-    // nibble mask in a VGPR (see tce_common.hpp: one scalar operand per VOP3 on gfx9)
+    // the unpack's nibble mask in a VGPR, its zero-point-8 constant in a scalar register (w4a16_unpack16.hpp)
     unsigned mask_hi;
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
-    const unsigned magic = 0x64006400u;  // (1024.0h, 1024.0h)
-    unsigned cz8_bits = 0x64806480u;  // (1152.0h, 1152.0h) = 1024 + 16 * 8, held in a scalar register: the packed subtraction reads it from there
+    unsigned cz8_bits = unpack16::kCz8Bits;
     asm volatile("" : "+s"(cz8_bits));
-    const half4_t ones = half4_t{(half_t)1.0f, (half_t)1.0f, (half_t)1.0f, (half_t)1.0f};
 
     auto compute = [&](const Step &st, int t) {
         if constexpr (MODE == 1) {
@@ -296,9 +266,8 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
             for (int i = 0; i < ROWS; ++i) acc[i][0][0] += (float)((st.w[i].x ^ st.w[i].y ^ st.w[i].z ^ st.w[i].w) & 0xFFu);
             return;
         }
-        // activations of this lane's chunk, as MFMA B operands, and their sum (A = ones) on the matrix pipe
+        // activations of this lane's chunk, as MFMA B operands
         half4_t xb[MB][8];
-        float xsum[MB];
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
 #pragma unroll
@@ -306,17 +275,6 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
                 const uint4_t xp = xs[(((m * T + t) * WK + wk) * 4 + j) * 64 + lane];
                 xb[m][2 * j] = __builtin_bit_cast(half4_t, uint2_t{xp.x, xp.y});      // (x0,x4,x1,x5) of word j
                 xb[m][2 * j + 1] = __builtin_bit_cast(half4_t, uint2_t{xp.z, xp.w});  // (x2,x6,x3,x7)
-            }
-            if (args.shared_xsum) {  // wave-uniform
-                xsum[m] = sxt[((m * T + t) * WK + wk) * 64 + lane];
-            } else {
-                float4_t xs4 = float4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, xb[m][2 * j], xs4, 0, 0, 0);
-                    xs4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, xb[m][2 * j + 1], xs4, 0, 0, 0);
-                }
-                xsum[m] = xs4[0];  // D[i][j] = sum_k B_j[k] for every i: all four registers hold this lane's sum
             }
         }
         const int zsh = (st.g & 7) * 4;
@@ -328,23 +286,11 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
             float4_t blk[MB];
 #pragma unroll
             for (int m = 0; m < MB; ++m) blk[m] = float4_t{0.f, 0.f, 0.f, 0.f};
-            // the zero point leaves per element: (1024 + 16 q) - (1024 + 16 z) = 16 (q - z), exact in binary16 (one packed add per two weights)
-            half4_t cz4;
-            if constexpr (Z8) {
-                cz4 = __builtin_bit_cast(half4_t, uint2_t{cz8_bits, cz8_bits});
-            } else {
-                const half_t czh = (half_t)__builtin_fmaf((float)((st.z[i] >> zsh) & 0xFu), 16.0f, 1024.0f);
-                cz4 = half4_t{czh, czh, czh, czh};
-            }
+            const half4_t cz4 = Z8 ? unpack16::cz4_of_8(cz8_bits) : unpack16::cz4_of((st.z[i] >> zsh) & 0xFu);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const unsigned w = st.w[i][j];
-                const unsigned t0 = ((w << 4) & mask_hi) | magic;  // (1024+16 q0, 1024+16 q4)
-                const unsigned t1 = (w & mask_hi) | magic;         // (q1, q5)
-                const unsigned t2 = ((w >> 4) & mask_hi) | magic;  // (q2, q6)
-                const unsigned t3 = ((w >> 8) & mask_hi) | magic;  // (q3, q7)
-                const half4_t a0 = __builtin_bit_cast(half4_t, uint2_t{t0, t1}) - cz4;
-                const half4_t a1 = __builtin_bit_cast(half4_t, uint2_t{t2, t3}) - cz4;
+                const half4_t a0 = unpack16::operand_lo(st.w[i][j], mask_hi, cz4);  // 16 (q - z) of (q0,q4,q1,q5)
+                const half4_t a1 = unpack16::operand_hi(st.w[i][j], mask_hi, cz4);  // (q2,q6,q3,q7)
 #pragma unroll
                 for (int m = 0; m < MB; ++m) {
                     blk[m] = __builtin_amdgcn_mfma_f32_4x4x4f16(a0, xb[m][2 * j], blk[m], 0, 0, 0);
@@ -403,7 +349,7 @@ __global__ __launch_bounds__(64 * WN * WK, (MB * ROWS * DEPTH >= 8 ? 2 : (MB * R
         for (int m = 0; m < MB; ++m) {
             // diagonal pick as multiply-adds with a one-hot lane mask: a select chain on (lane & 3) is turned by hipcc
             // into a dynamically indexed private array, i.e. scratch memory traffic (off-diagonal terms are finite)
-            float v = corr[i][m] * -0.0625f;
+            float v = -0.0f;  // the additive identity (a chain started from +0 would turn a -0 result into +0)
             v = __builtin_fmaf(acc[i][m][0], diag[0], v);
             v = __builtin_fmaf(acc[i][m][1], diag[1], v);
             v = __builtin_fmaf(acc[i][m][2], diag[2], v);
@@ -477,7 +423,7 @@ hipError_t launch_one(const GemvArgs &a, int total_blocks, int m_blocks, hipStre
     const int nchunks = a.K >> 5;
     const int LS = 64 * WK;
     const int T = (nchunks + LS - 1) / LS;
-    size_t lds = (size_t)MB * T * LS * 64 + (size_t)64 * WN * WK * 16 + (size_t)MB * T * LS * sizeof(float);  // x image + trash slots + the shared activation-sum table
+    size_t lds = (size_t)MB * T * LS * 64 + (size_t)64 * WN * WK * 16;  // x image + one 16-byte trash slot per thread (NORM: the first 4 KiB of them are part[])
     const size_t red = (size_t)WN * WK * ROWS * MB * sizeof(float);
     if (lds < red) lds = red;
     auto kfn = w4a16_gemv_kernel<MB, ROWS, WN, WK, DEPTH, XB, MODE, Z8, NORM>;
@@ -566,11 +512,6 @@ hipError_t launch_mb(const Variant &v, const GemvArgs &a, int total_blocks, int 
 
 void set_gemv_debug_mode(int mode) { g_debug_mode = mode; }
 void set_gemv_order(int force) { g_order_force = force >= 0 && force <= 2 ? force : 0; }
-// 0: the rule -- ON for a decode launch (M = 1): 2-3 % on each of the token's four launch shapes (7.31 -> 7.09, 4.22 -> 4.09, 10.79 -> 10.47, 7.73 -> 7.60 us,
-// profiles/r3/gemv_shared_xsum_ab.jsonl; the round's first A/B of this switch compared a kernel with itself -- its debug mode was shadowed -- and is withdrawn);
-// 1 on, 2 off
-thread_local int g_shared_xsum = 0;
-void set_gemv_shared_xsum(int on) { g_shared_xsum = on == 1 || on == 2 ? on : 0; }
 void set_gemv_debug_buffer(void *p) { g_debug_buf = static_cast<unsigned long long *>(p); }
 
 bool gemv_variant_exists(int rows, int wn, int wk, int depth) {
@@ -603,7 +544,6 @@ int launch_w4a16_gemv(const tce_w4a16_desc *descs, int count, int forced_rows, i
     a.zeros_are_8 = 1;
     for (int i = 0; i < count; ++i)
         if (!(descs[i].flags & TCE_W4_ZERO_POINT_IS_8)) a.zeros_are_8 = 0;
-    a.shared_xsum = false;  // (no zero-point term is left that needs the chunks' activation sums; the switch g_shared_xsum is kept for the ABI's tuning calls)
 
     int total_n = 0;
     for (int i = 0; i < count; ++i) total_n += descs[i].N;
@@ -674,10 +614,11 @@ int launch_w4a16_gemv(const tce_w4a16_desc *descs, int count, int forced_rows, i
     // M rows are processed MB at a time by gridDim.y; MB in {1,2,4}
     int mb = d0.M >= 4 ? 4 : (d0.M >= 2 ? 2 : 1);
     {
-        // the x image of mb rows must fit the CU's 160 KiB of LDS (launch_one's formula): fewer rows per pass for a long K,
-        // and a clear refusal -- not a generic HIP launch error -- when even one row does not fit (K > ~80k)
+        // the x image of mb rows must fit the CU's 160 KiB of LDS: fewer rows per pass for a long K, and a clear refusal -- not a generic
+        // HIP launch error -- when even one row does not fit (K > ~77k).  The bound charges 68 bytes per lane and step, launch_one's 64 plus
+        // the 4 of a table the kernel no longer has: those are the cut-offs the suite knows, and admitting more is a change of its own.
         const int LS = 64 * v.wk, T = (nchunks + LS - 1) / LS;
-        auto need = [&](int m) { return (size_t)m * T * LS * 64 + (size_t)64 * v.wn * v.wk * 16 + (size_t)m * T * LS * 4; };  // (launch_one's formula: x image, trash slots, sum table)
+        auto need = [&](int m) { return (size_t)m * T * LS * 68 + (size_t)64 * v.wn * v.wk * 16; };
         while (mb > 1 && need(mb) > 160 * 1024) mb >>= 1;
         if (need(mb) > 160 * 1024) return TCE_ERR_UNSUPPORTED_SHAPE;
     }

@@ -34,6 +34,7 @@
 // therefore read through the constant address space (scalar loads).
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "w4a16_unpack16.hpp"
 
 #include <type_traits>
 
@@ -273,16 +274,13 @@ __global__ __launch_bounds__(64 * NW, 8 / (NW / 4)) void w4a16_gemv_ovl_kernel(c
     stamp(2);
 
     // ---- 4. the row groups of this wave ----
-    unsigned mask_hi;  // nibble mask in a VGPR (tce_common.hpp: one scalar operand per VOP3 on gfx9)
+    unsigned mask_hi;  // the unpack's nibble mask in a VGPR, its zero-point-8 constant in a scalar register (w4a16_unpack16.hpp)
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
-    const unsigned magic = 0x64006400u;  // (1024.0h, 1024.0h)
-    unsigned cz8_bits = 0x64806480u;  // (1152.0h, 1152.0h), held in a scalar register
+    unsigned cz8_bits = unpack16::kCz8Bits;
     asm volatile("" : "+s"(cz8_bits));
     float acc[ROWS][4];  // the 4 accumulator registers of the 4x4x4 MFMA; the lane's own dot product is [lane & 3]
-    float corr[ROWS];    // sum over chunks of s * (1024 + 16 z) * sum_k x_k, z = 8
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
-        corr[i] = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
     }
@@ -309,16 +307,11 @@ __global__ __launch_bounds__(64 * NW, 8 / (NW / 4)) void w4a16_gemv_ovl_kernel(c
         for (int i = 0; i < ROWS; ++i) {
             __builtin_amdgcn_sched_barrier(0);  // one row's unpack -> MFMA -> scale at a time (register pressure, see w4a16_gemv.hip)
             float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f};
-            const half4_t cz4 = __builtin_bit_cast(half4_t, uint2_t{cz8_bits, cz8_bits});  // 1024 + 16 * 8: removed per element, exactly (w4a16_gemv.hip)
+            const half4_t cz4 = unpack16::cz4_of_8(cz8_bits);  // (this kernel takes zero point 8 only)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned wj = w[i][j];
-                const unsigned t0 = ((wj << 4) & mask_hi) | magic;  // (1024+16 q0, 1024+16 q4)
-                const unsigned t1 = (wj & mask_hi) | magic;         // (q1, q5)
-                const unsigned t2 = ((wj >> 4) & mask_hi) | magic;  // (q2, q6)
-                const unsigned t3 = ((wj >> 8) & mask_hi) | magic;  // (q3, q7)
-                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t0, t1}) - cz4, xb[2 * j], blk, 0, 0, 0);
-                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t2, t3}) - cz4, xb[2 * j + 1], blk, 0, 0, 0);
+            for (int j = 0; j < 4; ++j) {  // 16 (q - 8) of (q0,q4,q1,q5), then of (q2,q6,q3,q7)
+                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(unpack16::operand_lo(w[i][j], mask_hi, cz4), xb[2 * j], blk, 0, 0, 0);
+                blk = __builtin_amdgcn_mfma_f32_4x4x4f16(unpack16::operand_hi(w[i][j], mask_hi, cz4), xb[2 * j + 1], blk, 0, 0, 0);
             }
             const float s = (float)__builtin_bit_cast(half_t, (unsigned short)(sbits[i] & 0xFFFFu));
 #pragma unroll
@@ -333,12 +326,11 @@ __global__ __launch_bounds__(64 * NW, 8 / (NW / 4)) void w4a16_gemv_ovl_kernel(c
         // ---- end of a row group: reduce over the 64 lanes, park the results in LDS, reset (wave-uniform branch) ----
 #pragma unroll
         for (int i = 0; i < ROWS; ++i) {
-            float v = corr[i] * -0.0625f;
+            float v = -0.0f;  // the additive identity (a chain started from +0 would turn a -0 result into +0)
 #pragma unroll
             for (int q = 0; q < 4; ++q) v = __builtin_fmaf(acc[i][q], (lane & 3) == q ? 0.0625f : 0.0f, v);  // one-hot pick of the diagonal and the final /16
             v = wave_sum_dpp_lane63(v);  // total in lane 63
             if (lane == 63) obuf[(c_k * NW + wave) * ROWS + i] = (half_t)v;
-            corr[i] = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
         }

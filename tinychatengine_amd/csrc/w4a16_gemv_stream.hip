@@ -13,9 +13,7 @@
 //                      shares wave slots 0-3 of a 16-wave workgroup finished at 34 us and slots 12-15 at 51 us on the
 //                      128k-row lm_head (profiles/r1/timeline_stream.jsonl) -- the launch ended with one wave per SIMD
 //                      and nothing to overlap its HBM latency with.
-//   * ONE X IMAGE      the activation vector is staged into LDS once per workgroup (not once per 32 rows), together
-//                      with the per-lane sums sum_k x_k of every 32-weight chunk that the zero-point correction needs
-//                      (computed once on the matrix pipe instead of 8 MFMAs per step).
+//   * ONE X IMAGE      the activation vector is staged into LDS once per workgroup (not once per 32 rows).
 //   * RING             a wave keeps DEPTH steps (ROWS x 1 KiB of weights + scales/zeros each) in flight across row-group
 //                      boundaries; the issue side and the compute side each walk their own (row group, step) cursor with
 //                      "sticky" per-linear state in SGPRs, so nothing but the loaded registers travels through the ring.
@@ -34,6 +32,7 @@
 //                      vs 0.995 ms: DESIGN.md 3.1b has the per-launch timeline (profiles/r2/token_kernel_timeline.jsonl).
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "w4a16_unpack16.hpp"
 
 #include <new>
 #include <vector>
@@ -83,8 +82,8 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
     const int rowbytes = nchunks * 16;
     const int n_rg = L.n_rg;
     const half_t *A = L.A;
-    // LDS: x image [T][4][64] x 16 B, chunk sums [T][64] floats, the workgroup's row-group counter
-    int *rg_counter = reinterpret_cast<int *>(smem + (size_t)T * (4096 + 256));  // [64]; word 0 is the counter
+    // LDS (lds_bytes): x image [T][4][64] x 16 B, the workgroup's row-group counter, the RMSNorm partials
+    int *rg_counter = reinterpret_cast<int *>(smem + (size_t)T * 4096);  // [64]; word 0 is the counter
     auto stamp = [&](int i) {
         if constexpr (CHAIN != 0) {
             if (bar.stamps && tid == 0) bar.stamps[i] = wall_clock64();
@@ -302,7 +301,7 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
             }
             return __builtin_bit_cast(half8_t, __builtin_amdgcn_raw_buffer_load_b128(rs_a, lin * 16, 0, /*sc0|sc1*/ 17));
         };
-        const float rs = rmsnorm_rs_block(raw_piece, K, L.eps, wave, NW, lane, reinterpret_cast<float *>(smem + (size_t)T * (4096 + 256) + 256));
+        const float rs = rmsnorm_rs_block(raw_piece, K, L.eps, wave, NW, lane, reinterpret_cast<float *>(smem + (size_t)T * 4096 + 256));
         for (int p = tid; p < total_pieces; p += nthreads) {
             const int c = (p >> 8) * 64 + (p & 63), j = (p >> 6) & 3;
             uint4_t o = uint4_t{0u, 0u, 0u, 0u};
@@ -338,8 +337,6 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
         }
     }
     __syncthreads();
-    // (the per-chunk activation sums the zero-point term needed used to be formed here; the zero point now leaves per element in the unpack.  Their LDS area behind
-    // the image stays in the launch's size, unused)
     if constexpr (MODE == 2) *ts_x_ready = wall_clock64();
     stamp(2);
 
@@ -347,17 +344,14 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
     // compute side
     // ---------------------------------------------------------------------------------------------------------------
     float acc[ROWS][4];  // the 4 accumulator registers of the 4x4x4 MFMA; the lane's own dot product is [lane & 3]
-    float corr[ROWS];    // sum over chunks of s * (1024 + 16 z) * sum_k x_k
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
-        corr[i] = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
     }
-    unsigned mask_hi;  // nibble mask in a VGPR (tce_common.hpp: one scalar operand per VOP3 on gfx9)
+    unsigned mask_hi;  // the unpack's nibble mask in a VGPR, its zero-point-8 constant in a scalar register (w4a16_unpack16.hpp)
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
-    const unsigned magic = 0x64006400u;  // (1024.0h, 1024.0h)
-    unsigned cz8_bits = 0x64806480u;  // (1152.0h, 1152.0h) = 1024 + 16 * 8, held in a scalar register: a packed add reads it from there, no vector register is spent
+    unsigned cz8_bits = unpack16::kCz8Bits;
     asm volatile("" : "+s"(cz8_bits));
     float diag[4];                       // one-hot pick of the lane's diagonal accumulator and the final /16 in one factor
 #pragma unroll
@@ -396,23 +390,11 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
                 // rows' unpacks ahead of the first MFMA and the register allocation explodes
                 __builtin_amdgcn_sched_barrier(0);
                 float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f};
-                // the zero point leaves per element: (1024 + 16 q) - (1024 + 16 z) = 16 (q - z), exact in binary16 (w4a16_gemv.hip)
-                half4_t cz4;
-                if constexpr (Z8) {
-                    cz4 = __builtin_bit_cast(half4_t, uint2_t{cz8_bits, cz8_bits});
-                } else {
-                    const half_t czh = (half_t)__builtin_fmaf((float)((st.z[i] >> zsh) & 0xFu), 16.0f, 1024.0f);
-                    cz4 = half4_t{czh, czh, czh, czh};
-                }
+                const half4_t cz4 = Z8 ? unpack16::cz4_of_8(cz8_bits) : unpack16::cz4_of((st.z[i] >> zsh) & 0xFu);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned w = st.w[i][j];
-                    const unsigned t0 = ((w << 4) & mask_hi) | magic;  // (1024+16 q0, 1024+16 q4)
-                    const unsigned t1 = (w & mask_hi) | magic;         // (q1, q5)
-                    const unsigned t2 = ((w >> 4) & mask_hi) | magic;  // (q2, q6)
-                    const unsigned t3 = ((w >> 8) & mask_hi) | magic;  // (q3, q7)
-                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t0, t1}) - cz4, xb[2 * j], blk, 0, 0, 0);
-                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, uint2_t{t2, t3}) - cz4, xb[2 * j + 1], blk, 0, 0, 0);
+                for (int j = 0; j < 4; ++j) {  // 16 (q - z) of (q0,q4,q1,q5), then of (q2,q6,q3,q7)
+                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(unpack16::operand_lo(st.w[i][j], mask_hi, cz4), xb[2 * j], blk, 0, 0, 0);
+                    blk = __builtin_amdgcn_mfma_f32_4x4x4f16(unpack16::operand_hi(st.w[i][j], mask_hi, cz4), xb[2 * j + 1], blk, 0, 0, 0);
                 }
                 // lanes 4b..4b+3 share a quantization group (32 weights per lane, groups of >= 32), so scaling all four
                 // accumulator registers by this lane's scale is consistent; the diagonal is picked at the row group's end
@@ -442,7 +424,7 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
         half_t outv[ROWS];
 #pragma unroll
         for (int i = 0; i < ROWS; ++i) {
-            float v = corr[i] * -0.0625f;
+            float v = -0.0f;  // the additive identity (a chain started from +0 would turn a -0 result into +0)
             v = __builtin_fmaf(acc[i][0], diag[0], v);
             v = __builtin_fmaf(acc[i][1], diag[1], v);
             v = __builtin_fmaf(acc[i][2], diag[2], v);
@@ -450,7 +432,6 @@ __device__ __forceinline__ void gemv_launch_body(const StreamLaunch &L, const Ba
             if constexpr (MODE == 1) v = acc[i][0];
             v = wave_sum_dpp_lane63(v);  // total in lane 63
             outv[i] = (half_t)v;
-            corr[i] = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
         }
@@ -561,7 +542,11 @@ int num_cus() {
     return g_num_cus;
 }
 
-size_t lds_bytes(int K) { return (size_t)(((K >> 5) + 63) / 64) * (4096 + 256) + 256 + 4096; }  // x image, chunk sums, ticket words, RMSNorm partials
+int steps_of(int K) { return ((K >> 5) + 63) / 64; }
+size_t lds_bytes(int K) { return (size_t)steps_of(K) * 4096 + 256 + 4096; }  // x image, ticket words, RMSNorm partials
+// Admission: at most 18 steps (K <= 36864).  That is where an 84 KiB gate on the launch's LDS cut while every step also carried 256 bytes of
+// chunk sums; the sums are gone, the cut-off the suite knows stays -- admitting a longer K is a change of its own.
+constexpr int kMaxSteps = 18;
 
 template <typename KFn>
 hipError_t set_lds(KFn kfn, size_t lds) {
@@ -645,7 +630,7 @@ void set_gemv_stream_config(int rows, int nw, int depth) {
 
 bool gemv_stream_supports(const tce_w4a16_desc *descs, int count) {
     if (descs[0].M != 1) return false;
-    if (lds_bytes(descs[0].K) > 84 * 1024) return false;
+    if (steps_of(descs[0].K) > kMaxSteps) return false;
     StreamLaunch tmp;
     bool z8 = true;
     return fill_launch(descs, count, 1, &tmp, &z8);

@@ -24,7 +24,6 @@ struct GemvArgs {
     int zeros_are_8;          // every linear of the launch carries TCE_W4_ZERO_POINT_IS_8
     const float *gamma;       // non-null: stage RMSNorm(A) * gamma instead of A (fused prologue, M = 1)
     float eps;
-    int shared_xsum;          // the per-chunk activation sums are computed once per workgroup (table in LDS) instead of by every wave in every step
     GemvSeg seg[TCE_MAX_GROUP];
 };
 
@@ -56,7 +55,6 @@ void set_w8a8_kslice(int code);    // W8A8, the whole tile in every wave (round 
 void set_w8a8_big(int b);           // W8A8 128-row tiles: 0 the rule, 1 / 2 forced (128 / 64 columns), 9 off
 void set_lnq_stamps(void *p);
 void set_lnq_form(int f);           // 1: the workgroup-per-8-rows form of the LayerNormQ + W8A8 launch at every k
-void set_gemv_shared_xsum(int on);  // 0 the rule (on for M = 1), 1 on, 2 off
 void set_gemv_debug_buffer(void *p);
 
 // persistent form, w4a16_gemv_stream.hip

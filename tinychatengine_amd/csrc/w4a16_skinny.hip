@@ -15,15 +15,14 @@
 //   * every wave is autonomous (no workgroup barrier in the k-loop): per 128-wide k-block it loads 1 KiB of packed
 //     weights (4 consecutive lanes read one row's 64 bytes -- the operand fragment itself would make each quarter-wave
 //     touch 16 rows, see w8a8_gemm.hip) and the 16 x 128 activation block (4 KiB, L1/L2 hits), passes both through its
-//     own LDS slots (swizzled, conflict-free both ways) into fragment order, unpacks with the GEMV's 7-instruction bias
-//     form (halves 1024 + 16 q) and subtracts the row's (1024 + 16 z) per element -- 16 (q - z), exact in binary16; one packed
-//     add per two weights, and no second MFMA for sum_k x (the algebraic removal it replaces was the difference of two terms
-//     up to 10^6 times the signal on rows with a large sum or one large element);
+//     own LDS slots (swizzled, conflict-free both ways) into fragment order and unpacks with the GEMV's 7-instruction
+//     form to 16 (q - z), exactly (w4a16_unpack16.hpp);
 //   * scales and (1024 + 16 z) of the tile's rows and the wave's groups are staged once into LDS as halves (exact).
 //
 // Same math and tolerance as the GEMV (fp32 accumulation of exact products, one fp32 scale per group); G = 128 only.
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
+#include "w4a16_unpack16.hpp"
 
 namespace tce {
 
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(512) void w4a16_skinny_kernel(const SkinnyArgs a) {
         tab_s[idx] = a.scales[(size_t)n * a.scales_stride + kb];
         unsigned z = 8u;
         if constexpr (!Z8) z = (a.zeros[(size_t)n * a.zeros_stride + (kb >> 3)] >> ((kb & 7) * 4)) & 0xFu;
-        tab_c[idx] = (half_t)(float)(1024u + 16u * z);  // exact in binary16
+        tab_c[idx] = (half_t)(float)(1024u + 16u * z);  // cz of w4a16_unpack16.hpp, staged once per (row, group): in integers, exact in binary16
     }
 
     // ---- lane roles ----
@@ -113,9 +112,8 @@ __global__ __launch_bounds__(512) void w4a16_skinny_kernel(const SkinnyArgs a) {
     };
 
     float4_t acc = float4_t{0.f, 0.f, 0.f, 0.f};  // D[n = 4*kq + i][m = r16], i = 0..3
-    unsigned mask_hi;
+    unsigned mask_hi;  // the unpack's nibble mask in a VGPR (w4a16_unpack16.hpp)
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
-    const unsigned magic = 0x64006400u;
 
     auto process = [&](const Regs &r, int g) {
         // registers -> LDS in fragment-friendly order.  A wave's LDS operations complete in order, so the reads below see
@@ -126,20 +124,12 @@ __global__ __launch_bounds__(512) void w4a16_skinny_kernel(const SkinnyArgs a) {
         __builtin_amdgcn_wave_barrier();
         const uint4_t wq = lds_w[w_rslot];  // row r16, k-chunk kq: word s feeds MFMA step s
         float4_t blk = float4_t{0.f, 0.f, 0.f, 0.f};
-        // the zero point leaves per element: (1024 + 16 q) - (1024 + 16 z) = 16 (q - z), exact in binary16 -- row r16's own constant for this group
-        const half_t czh = tab_c[g * 16 + r16];
-        const half8_t cz8 = half8_t{czh, czh, czh, czh, czh, czh, czh, czh};
+        const half8_t cz8 = unpack16::cz8_splat(tab_c[g * 16 + r16]);  // row r16's 1024 + 16 z of this group
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int pc = kq * 4 + s;
             const half8_t xb = __builtin_bit_cast(half8_t, lds_x[pc * 16 + (r16 ^ pc)]);  // batch row r16, its piece pc
-            const unsigned w = wq[s];
-            const unsigned t0 = ((w << 4) & mask_hi) | magic;  // (1024+16 q0, 1024+16 q4)
-            const unsigned t1 = (w & mask_hi) | magic;         // (q1, q5)
-            const unsigned t2 = ((w >> 4) & mask_hi) | magic;  // (q2, q6)
-            const unsigned t3 = ((w >> 8) & mask_hi) | magic;  // (q3, q7)
-            const half8_t wa = __builtin_bit_cast(half8_t, uint4_t{t0, t1, t2, t3}) - cz8;
-            blk = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xb, blk, 0, 0, 0);
+            blk = __builtin_amdgcn_mfma_f32_16x16x32_f16(unpack16::operand8(wq[s], mask_hi, cz8), xb, blk, 0, 0, 0);
         }
         __builtin_amdgcn_wave_barrier();
         // rows 4*kq .. 4*kq+3 of the tile: their scale and (1024 + 16 z) for this group
@@ -246,7 +236,7 @@ __global__ __launch_bounds__(512) void w4a16_skinny_shared_kernel(const SkinnyAr
         tab_s[idx] = g < nkb ? sv : (half_t)0.f;
         unsigned z = 8u;
         if constexpr (!Z8) z = (a.zeros[(size_t)n * a.zeros_stride + (gc >> 3)] >> ((gc & 7) * 4)) & 0xFu;
-        tab_c[idx] = (half_t)(float)(1024u + 16u * z);
+        tab_c[idx] = (half_t)(float)(1024u + 16u * z);  // cz of w4a16_unpack16.hpp, staged once per (row, group): in integers, exact in binary16
     }
 
     const int r16 = lane & 15, kq = lane >> 4;
@@ -262,24 +252,20 @@ __global__ __launch_bounds__(512) void w4a16_skinny_shared_kernel(const SkinnyAr
     const int x_wslot = xh * 256 + xpc * 16 + (xm ^ xpc);
 
     float4_t acc = float4_t{0.f, 0.f, 0.f, 0.f};
-    unsigned mask_hi;
+    unsigned mask_hi;  // the unpack's nibble mask in a VGPR (w4a16_unpack16.hpp)
     asm volatile("v_mov_b32 %0, 0x00F000F0" : "=v"(mask_hi));
-    const unsigned magic = 0x64006400u;
 
     // one stage: both k-blocks' weights through the wave's LDS slots, then four independent MFMA chains
     auto stage = [&](const uint4_t *xi, int g) {
         const uint4_t wq0 = lds_w[w_rslot], wq1 = lds_w[64 + w_rslot];
         float4_t blk0 = float4_t{0.f, 0.f, 0.f, 0.f}, blk1 = blk0;
-        const half_t cz0 = tab_c[g * 16 + r16], cz1 = tab_c[g * 16 + 16 + r16];  // row r16's 1024 + 16 z of the two k-blocks: removed per element, exactly
-        const half8_t c80 = half8_t{cz0, cz0, cz0, cz0, cz0, cz0, cz0, cz0}, c81 = half8_t{cz1, cz1, cz1, cz1, cz1, cz1, cz1, cz1};
+        const half8_t c80 = unpack16::cz8_splat(tab_c[g * 16 + r16]), c81 = unpack16::cz8_splat(tab_c[g * 16 + 16 + r16]);  // row r16's 1024 + 16 z of the two k-blocks
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int pc = kq * 4 + s;
             const half8_t xb0 = __builtin_bit_cast(half8_t, xi[pc * 16 + (r16 ^ pc)]);
             const half8_t xb1 = __builtin_bit_cast(half8_t, xi[256 + pc * 16 + (r16 ^ pc)]);
-            const unsigned w = wq0[s], v = wq1[s];
-            const half8_t a0 = __builtin_bit_cast(half8_t, uint4_t{((w << 4) & mask_hi) | magic, (w & mask_hi) | magic, ((w >> 4) & mask_hi) | magic, ((w >> 8) & mask_hi) | magic}) - c80;
-            const half8_t a1 = __builtin_bit_cast(half8_t, uint4_t{((v << 4) & mask_hi) | magic, (v & mask_hi) | magic, ((v >> 4) & mask_hi) | magic, ((v >> 8) & mask_hi) | magic}) - c81;
+            const half8_t a0 = unpack16::operand8(wq0[s], mask_hi, c80), a1 = unpack16::operand8(wq1[s], mask_hi, c81);
             blk0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, xb0, blk0, 0, 0, 0);
             blk1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, xb1, blk1, 0, 0, 0);
         }
