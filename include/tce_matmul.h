@@ -474,7 +474,7 @@ TCE_API int tce_kv_block_table_check_window(const int32_t *block_table, int tabl
  * passed); prompt tokens are pushed by the host at admission (ring[ring_pushed % 64], ring_pushed += 1).  A row's top_k outside [1, top_k_bound] is clamped (it lives
  * on the device: the host cannot refuse it at the call).
  * NOT BUILT: tfs_z, typical_p, mirostat (the call accepts only their disabled values 1.0, 1.0, 0), top_k <= 0 = "whole vocabulary", k > 256: TCE_ERR_UNSUPPORTED_SHAPE
- * before any launch.  Also refused there: vocab > ld (TCE_ERR_BAD_ARG), vocab > 2^20, logits not 16-byte aligned or ld % 8 != 0, and ceil(vocab / 4096) * top_k_bound
+ * before any launch.  (Token masks, automata and logit_bias ARE built: tce_sample_constrained_f16 below; this entry point applies none.)  Also refused there: vocab > ld (TCE_ERR_BAD_ARG), vocab > 2^20, logits not 16-byte aligned or ld % 8 != 0, and ceil(vocab / 4096) * top_k_bound
  * > 8192 (the second launch holds the chunks' survivors in registers: 131072 entries at k = 256, 838k at k = 40).
  * workspace: tce_sample_workspace_bytes(batch, vocab) bytes (0 for a bad shape), zeroed once; word 0 counts the ids tce_embed_rows_f16 refused, the rest carries the
  * first launch's survivors to the second -- the kernel boundary is the only ordering, there is no counter to reset.  The logits are not modified.
@@ -578,6 +578,61 @@ TCE_API size_t tce_logprobs_workspace_bytes(int rows, int vocab);
 TCE_API int tce_sample_logprobs_f16(const tce_sample_call *call, const tce_logprob_out *lp, void *stream);
 TCE_API int tce_sample_verify_logprobs_f16(const tce_sample_verify_call *call, const tce_logprob_out *lp, void *stream);
 TCE_API int tce_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, void *stream);
+/* Constrained decoding on the device (csrc/sampling.hip; additive within ABI 113, no existing struct or entry point changes): which tokens a row may draw is a TOKEN
+ * AUTOMATON that lives on the device and advances in the sampler's tail, plus up to TCE_BIAS_MAX (id, value) logit-bias pairs per row -- the reference carries
+ * logit_bias in its generation config (llm/include/Generate.h:59) and never applies it.  A captured replay stays one token per live slot with no host round trip.
+ * tce_sample_constrained_f16 is tce_sample_f16 (with lp: tce_sample_logprobs_f16) with, per ACTIVE row, c->rows[b] = (fsm, state, bias):
+ *   1. BIAS.  The row's first min(max(n_bias, 0), 16) pairs; for each pair with 0 <= id < vocab, x_id = float(fp16 logit) + bias_val: one fp32 add, BEFORE any penalty;
+ *      an id that occurs twice has the later pair added on top of the earlier one, in index order.  tce_sample_f16's step 1 (the penalties) acts on the biased value.
+ *   2. MASK.  fsm >= 0: token t is a candidate only if bit (t & 31) of word mask[state][t >> 5] is set (a word at or past mask_words counts as 0).  A masked token is
+ *      "no element", like an entry past the vocabulary, whatever its logit; an allowed token whose logit is -inf IS a candidate.  fsm < 0: every token is allowed.
+ *   3. THE CHAIN.  Greedy, top-k, softmax, top-p, temperature and the draw run unchanged over the candidates, in the same order (descending penalised logit, ascending id
+ *      among equals); with fewer than k candidates, k becomes their number.
+ *   4. TAIL.  next = edge_next[e] of the edge e in [edge_begin[state], edge_begin[state + 1]) with edge_token[e] == token (binary search: ascending), else
+ *      default_next[state].  next == TCE_FSM_DONE: the token is emitted, then the row retires (pos_device[b] = -1) exactly as for a stop id; the state word stays.
+ *      Otherwise state = next -- also when a stop id or max_new retires the row in the same call.
+ *   5. LOG-PROBABILITIES (lp != NULL) stay what they are: x_t - LSE(x) on the RAW logits; neither the mask nor the bias enters.
+ *   6. INVALID STATE (the row lives on the device: the host cannot refuse it at the call; ONE defined path).  A constrained row is invalid when fsm >= n_fsm, when state
+ *      lies outside [0, states), when the chosen token's next lies outside [-1, states), or when its state leaves no candidate inside the vocabulary.  An invalid row
+ *      emits NOTHING -- token, log, ring, generated, state and debug record stay untouched --, retires (pos_device[b] = -1) and adds 1 to *violations.  The state changes
+ *      only in the tail.
+ *   7. fsm < 0 and n_bias <= 0: everything tce_sample_f16 (tce_sample_logprobs_f16) writes comes out bit for bit.
+ * tce_sample_verify_constrained_f16: c->rows is per SEQUENCE; virtual row t is sampled in the state delta*(state, row_token[(b, 1)] .. row_token[(b, t)]), known in advance
+ *   for the reason the penalty window is (thread 0 of the select workgroup walks the <= TCE_SPEC_MAX_ROWS - 1 transitions).  A draft that is forbidden, or whose
+ *   transition is DONE or invalid, makes its row and every row behind it unreachable -- the token sampled in front of it is allowed and so differs from the draft --:
+ *   they are not sampled and their candidate word is -1.  The chain launch advances the state once per EMITTED token and applies 4's retirement and 6 (an invalid row t
+ *   emits nothing and retires the sequence behind the t tokens already emitted).  LOSSLESS: the emitted tokens, the state words and *violations are those of
+ *   tce_sample_constrained_f16 called once per token.
+ * tce_fsm (56 bytes) and its arrays are DEVICE memory written by the host, stream-ordered; a captured graph keeps c->fsms, c->rows and c->violations.  The arrays'
+ * contents are trusted as far as rule 6 does not name them (edge_begin ascending within [0, edges], mask [states][mask_words]).
+ * Refusals, before any launch: tce_sample_f16's / tce_sample_verify_f16's own, the logprob forms' for a non-NULL lp; TCE_ERR_BAD_ARG for a NULL c, rows or violations,
+ * n_fsm outside 0 .. TCE_FSM_MAX, n_fsm > 0 with NULL fsms; TCE_ERR_UNSUPPORTED_SHAPE for fsms not 8-byte or rows / violations not 4-byte aligned.
+ * NOT BUILT: log-probabilities renormalised over the allowed set, constraints in scoring, cutting tce_draft_ngram's drafts at the first forbidden token. */
+#define TCE_FSM_DONE      (-1)   /* a transition to it: the token is emitted, then the sequence retires */
+#define TCE_FSM_MAX       64     /* automata resident at once */
+#define TCE_BIAS_MAX      16     /* (id, value) pairs per row */
+typedef struct tce_fsm {          /* one token automaton, all arrays on the DEVICE */
+    const uint32_t *mask;         /* [states][mask_words]; bit (t & 31) of word t >> 5 set: token t allowed in the state; bits at t >= vocab are ignored */
+    const int32_t *edge_begin;    /* [states + 1] */
+    const int32_t *edge_token;    /* [edges], strictly ascending within a state */
+    const int32_t *edge_next;     /* [edges] */
+    const int32_t *default_next;  /* [states]: next state of an allowed token that has no edge */
+    int32_t states, mask_words, start, reserved0;
+} tce_fsm;
+typedef struct tce_constraint_row { /* per slot (144 bytes); changes hands by one copy, like tce_sample_row */
+    int32_t fsm;                  /* index into fsms, -1: unconstrained */
+    int32_t state;
+    int32_t n_bias, reserved0;
+    int32_t bias_id[TCE_BIAS_MAX];
+    float bias_val[TCE_BIAS_MAX];
+} tce_constraint_row;
+typedef struct tce_constraint {
+    const tce_fsm *fsms; int32_t n_fsm, reserved0;   /* DEVICE array; a captured graph keeps the pointer, the host rewrites entries stream-ordered */
+    tce_constraint_row *rows;                        /* DEVICE [batch] (per SEQUENCE in the verifier) */
+    uint32_t *violations;                            /* DEVICE, one word, zeroed once */
+} tce_constraint;
+TCE_API int tce_sample_constrained_f16(const tce_sample_call *call, const tce_constraint *c, const tce_logprob_out *lp /* may be NULL */, void *stream);
+TCE_API int tce_sample_verify_constrained_f16(const tce_sample_verify_call *call, const tce_constraint *c, const tce_logprob_out *lp /* may be NULL */, void *stream);
 /* The next step's input rows, one launch: row token[b] of an fp16 table [vocab][hidden] into out[b] ([batch][hidden]) for every active row (pos_device / pos_bound as
  * above; inactive rows are left as they are).  The reference looks an fp32 table up and rounds with float2half (Int4llamaDecoder: Embedding + float2half); a table
  * rounded once to fp16 gives the same bits.  A token outside [0, vocab) is not followed: the row is written as zeros and word 0 of `workspace` (tce_sample_f16's, or

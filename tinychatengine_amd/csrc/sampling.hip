@@ -22,6 +22,12 @@
 // already holds the chunk's 16 logits per thread and stores the chunk's pair (m_c, s_c = sum expf(x_i - m_c)) before it patches the penalties in; the draw launch
 // merges the row's <= 256 pairs and subtracts.  The summation order is FIXED (chunk_lse_pair, merge_lse below), so a value does not depend on the batch, the slot or
 // the entry point: scoring (logprobs_partials_kernel -> logprobs_merge_kernel) calls the same two device functions.  The LSE = false forms are the code they were.
+//
+// CONSTRAINED DECODING (tce_sample_constrained_f16, tce_sample_verify_constrained_f16; the rules are in include/tce_matmul.h): the CON = true forms of the three sampler
+// kernels.  Select tests a bit of mask[state] before a logit becomes a key and patches the row's <= 16 bias pairs in beside the penalties; draw treats "no survivor" and
+// an invalid transition as one path (nothing emitted, the row retires, *violations += 1) and stores the next state in the tail; the verifier walks the drafts' transitions
+// to know each virtual row's state in advance.  fsm_next is the one edge lookup of all three.  The CON = false forms declare nothing new and compile to the instructions
+// they were (profiles/constrained/).
 #include "tce_common.hpp"
 
 #include <type_traits>
@@ -126,19 +132,71 @@ __device__ __forceinline__ float merge_lse(const float2_t *pairs, int nchunks, i
     return M + logf(S);
 }
 
+// ---- constrained decoding (tce_sample_constrained_f16, tce_sample_verify_constrained_f16): the CON = true forms ----
+// The automaton's transition: the edge of state s that carries tok (binary search: edge_token ascends within a state), else the state's default.  The ONE lookup of
+// the select launch's walk, the draw launch's tail and the chain launch.  The caller has checked s against [0, states) and checks the result against [-1, states).
+__device__ __forceinline__ int fsm_next(const tce_fsm &f, int s, int tok) {
+    int lo = f.edge_begin[s];
+    const int end = f.edge_begin[s + 1];
+    int hi = end;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (f.edge_token[mid] < tok) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && f.edge_token[lo] == tok ? f.edge_next[lo] : f.default_next[s];
+}
+__device__ __forceinline__ bool fsm_state_ok(const tce_constraint &con, int fsm, int s) { return fsm < con.n_fsm && s >= 0 && s < con.fsms[fsm].states; }
+__device__ __forceinline__ bool fsm_allows(const tce_fsm &f, int s, int tok, int vocab) {
+    if (tok < 0 || tok >= vocab || (tok >> 5) >= f.mask_words) return false;
+    return (f.mask[(size_t)s * f.mask_words + (tok >> 5)] >> (tok & 31)) & 1u;
+}
+// The state virtual row vt of a constrained sequence is sampled in: delta*(state, drafts 1 .. vt) (drafts[j] = draft j + 1), or -1 where the row cannot be reached (the
+// base state is invalid -- row 0 then carries rule 6 --, or a draft is forbidden or its transition DONE or invalid).  At most TCE_SPEC_MAX_ROWS - 1 transitions.
+__device__ __forceinline__ int fsm_walk(const tce_constraint &con, int fsm, int s, const int32_t *drafts, int vt, int vocab) {
+    if (!fsm_state_ok(con, fsm, s)) return -1;
+    const tce_fsm &f = con.fsms[fsm];
+    for (int j = 0; j < vt; ++j) {
+        const int d = drafts[j];
+        if (!fsm_allows(f, s, d, vocab)) return -1;
+        s = fsm_next(f, s, d);
+        if (s < 0 || s >= f.states) return -1;
+    }
+    return s;
+}
+__device__ __forceinline__ int &con_next_word() {  // the draw launch's LDS word for thread 0's lookup (only the CON = true forms instantiate it)
+    __shared__ int word;
+    return word;
+}
+// the chain launch's state of a sequence's automaton; the CON = false forms hold an empty struct instead, so that they declare nothing new
+struct ChainCon {
+    int fsm = -1, state = 0, nx = 0;
+    bool invalid = false;
+};
+struct NoCon {};
+template <class Base>
+struct ConArgs : Base {  // the CON = true forms' arguments: the base form's, then the constraint (the CON = false instantiations keep their argument layout)
+    tce_constraint con;
+};
+
 // SPEC (tce_sample_verify_f16): blockIdx.y is a VIRTUAL row y = seq * RT + t -- logits row, position word (row_pos) and survivors are y's, the sampling row is seq's.
 // Row t is only ever used when drafts 1 .. t were all accepted, so the window it must be sampled with is known now: the ring as it stands with row_token[(seq, 1)] ..
 // row_token[(seq, t)] pushed behind it.
 // LSE: the chunk's pair of the RAW logits goes to partials[row][chunk] (one 8-byte store) before the penalties are patched in.
-template <bool SPEC, bool LSE>
+// CON: the thread's 16 logits are one half of one word of mask[state]; a cleared bit gives key 0 ("no element").  The row -> descriptor -> mask word loads are issued
+// in front of the logits loads (three dependent round trips that should hide under them; SPEC rows behind row 0 wait for thread 0's walk instead).  The row's bias ids
+// join the patch path (<= 64 + 16 ids): an id both biased and penalised is patched by its window thread with penalty(raw + bias).  An invalid or unreachable row
+// writes k "no element" entries per chunk and searches nothing: the draw launch finds no candidate and takes rule 6's path (SPEC: cand = -1).
+template <bool SPEC, bool LSE, bool CON>
 __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *logits, int ld, int vocab, const tce_sample_row *rows, const int32_t *pos, int pos_bound,
                                                                   int kbound, uint2_t *entries, int nchunks, int RT, const int32_t *row_token,
-                                                                  [[maybe_unused]] float2_t *partials) {
+                                                                  [[maybe_unused]] float2_t *partials, [[maybe_unused]] tce_constraint con) {
     const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(pos, b, pos_bound)) return;
     [[maybe_unused]] const int seq = SPEC ? b / RT : b, vt = SPEC ? b - seq * RT : 0;
-    __shared__ int win_id[64], pen_id[64];
-    __shared__ float pen_val[64];
+    constexpr int kPatch = CON ? 64 + TCE_BIAS_MAX : 64;
+    __shared__ int win_id[64], pen_id[kPatch];
+    __shared__ float pen_val[kPatch];
     __shared__ unsigned mask[kThreads];
     __shared__ int cnt[2][4];
     __shared__ int nsel;
@@ -147,6 +205,32 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
     const half_t *row = logits + (size_t)b * ld;
     const int base = c * kChunk, i0 = base + tid * 16;
 
+    [[maybe_unused]] unsigned allow = 0xFFFFu;  // CON: bit e = entry i0 + e may be a candidate
+    [[maybe_unused]] int nbias = 0;
+    [[maybe_unused]] bool dead = false;          // CON: an invalid or unreachable row
+    if constexpr (CON) {
+        __shared__ int walked;
+        const tce_constraint_row &cr = con.rows[seq];
+        const int fsm = cr.fsm;
+        int s = cr.state;
+        nbias = cr.n_bias < 0 ? 0 : (cr.n_bias > TCE_BIAS_MAX ? TCE_BIAS_MAX : cr.n_bias);
+        if (fsm >= 0) {
+            if (SPEC && vt > 0) {  // (uniform) the state behind drafts 1 .. vt: one thread walks, the workgroup waits
+                if (tid == 0) walked = fsm_walk(con, fsm, s, row_token + b - vt + 1, vt, vocab);
+                __syncthreads();
+                s = walked;
+                dead = s < 0;
+            } else {
+                dead = !fsm_state_ok(con, fsm, s);
+            }
+            allow = 0u;
+            if (!dead && i0 < vocab) {
+                const tce_fsm &f = con.fsms[fsm];
+                if ((i0 >> 5) < f.mask_words) allow = (f.mask[(size_t)s * f.mask_words + (i0 >> 5)] >> (i0 & 16)) & 0xFFFFu;
+            }
+        }
+    }
+
     float x[16];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -154,6 +238,17 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
         if (i0 + 8 * h < vocab) v = *reinterpret_cast<const half8_t *>(row + i0 + 8 * h);  // (a piece across `vocab` stays inside the row: vocab <= ld, ld % 8 == 0)
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[8 * h + j] = (float)v[j];
+    }
+    if constexpr (CON) {
+        if (dead) {  // (uniform) k "no element" entries and nothing else
+            if (tid < k) {
+                uint2_t ent;
+                ent.x = 0u;
+                ent.y = 0u;
+                entries[((size_t)b * nchunks + c) * kMaxK + tid] = ent;
+            }
+            return;
+        }
     }
     if constexpr (LSE) {
         const float2_t pair = chunk_lse_pair(x, i0, vocab, wave, lane);
@@ -171,7 +266,31 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
         else win_id[tid] = tid < nwin ? r.ring[(r.ring_pushed - 1u - (unsigned)tid) & 63u] : -1;
         pen_id[tid] = -1;
     }
+    if constexpr (CON) {
+        if (tid >= 64 && tid < kPatch) pen_id[tid] = -1;
+    }
     __syncthreads();
+    if constexpr (CON) {  // thread 64 + j: bias pair j, where its id lies in this chunk, is the id's first pair and no window thread patches the id
+        const int j = tid - 64;
+        if (j >= 0 && j < nbias) {
+            const tce_constraint_row &cr = con.rows[seq];
+            const int id = cr.bias_id[j];
+            if (id >= base && id < base + kChunk && id < vocab) {
+                bool mine = true;
+                for (int i = 0; i < j; ++i) mine = mine && cr.bias_id[i] != id;
+                if (rp != 1.0f || freq_on)
+                    for (int i = 0; i < nwin; ++i) mine = mine && win_id[i] != id;
+                if (mine) {
+                    float v = (float)row[id];
+                    for (int i = j; i < nbias; ++i)
+                        if (cr.bias_id[i] == id) v = v + cr.bias_val[i];
+                    pen_id[tid] = id;
+                    pen_val[tid] = v;
+                    atomicOr(&mask[(id - base) >> 4], 1u << ((id - base) & 15));
+                }
+            }
+        }
+    }
     if ((rp != 1.0f || freq_on) && tid < nwin) {
         const int id = win_id[tid];
         if (id >= base && id < base + kChunk && id < vocab) {
@@ -184,6 +303,11 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
             }
             if (first) {
                 float v = (float)row[id];
+                if constexpr (CON) {
+                    const tce_constraint_row &cr = con.rows[seq];
+                    for (int i = 0; i < nbias; ++i)
+                        if (cr.bias_id[i] == id) v = v + cr.bias_val[i];
+                }
                 if (rp != 1.0f) v = v <= 0.0f ? v * rp : v / rp;                   // sample_repetition_penalty (Generate.cc:26-30)
                 if (freq_on) v = v - ((float)count * af + 1.0f * ap);             // sample_frequency_and_presence_penalties (:56)
                 pen_id[tid] = id;
@@ -198,7 +322,7 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             if ((m >> e) & 1u) {
-                for (int j = 0; j < 64; ++j)
+                for (int j = 0; j < kPatch; ++j)
                     if (pen_id[j] == i0 + e) x[e] = pen_val[j];
             }
         }
@@ -208,7 +332,8 @@ __global__ __launch_bounds__(kThreads) void sample_select_kernel(const half_t *l
     u64 comp[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const unsigned key = i0 + e < vocab ? order_key(x[e]) : 0u;
+        unsigned key = i0 + e < vocab ? order_key(x[e]) : 0u;
+        if constexpr (CON) key = (allow >> e) & 1u ? key : 0u;
         comp[e] = ((u64)key << 12) | (u64)(0xFFF - (tid * 16 + e));
     }
     u64 T = 0;
@@ -289,8 +414,14 @@ struct VerifyArgs {
 
 // SPEC: blockIdx.x is a virtual row y = seq * RT + t (a.pos = row_pos): the draw of token generated + t of the sequence, into cand[y]; no state is written
 // LSE: the row's log-sum-exp from the select launch's pairs (merge_lse); logprob = the RAW logit of the token drawn - lse, written beside the token.
-template <bool SPEC, bool LSE>
-__global__ __launch_bounds__(kThreads) void sample_draw_kernel(std::conditional_t<LSE, DrawLseArgs, DrawArgs> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
+// CON: no survivor at all (V == 0: an invalid or unreachable row, or a state that allows nothing inside the vocabulary) is rule 6 -- the row retires, *violations += 1,
+// nothing else is written (SPEC: cand = -1, the chain launch applies the rule).  Otherwise thread 0 looks the drawn token's transition up (fsm_next) BEFORE anything
+// is written: a next outside [-1, states) is rule 6 again; DONE retires the row behind the token like a stop id; any other next is stored as the state, in the tail.
+template <bool LSE, bool CON>
+using DrawArgsOf = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, DrawLseArgs, DrawArgs>>, std::conditional_t<LSE, DrawLseArgs, DrawArgs>>;
+
+template <bool SPEC, bool LSE, bool CON>
+__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, CON> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(a.pos, b, a.pos_bound)) return;
     [[maybe_unused]] float lse = 0.0f;
@@ -322,6 +453,19 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(std::conditional_
     if (tid == 0) nsel = 0;
     const int V = block_total(valid, cnt, 0, wave, lane);
     const int kk = V < k ? V : k;  // (>= 1: the vocabulary is not empty)
+    if constexpr (CON) {
+        if (V == 0) {  // (uniform) rule 6: nothing is emitted
+            if (tid == 0) {
+                if constexpr (SPEC) {
+                    cand[b] = -1;
+                } else {
+                    a.pos[b] = -1;
+                    atomicAdd(a.con.violations, 1u);
+                }
+            }
+            return;
+        }
+    }
     const int nj = (E + kThreads - 1) / kThreads;
     u64 T = 0;
     for (int bit = 51; bit >= 0; --bit) {
@@ -392,6 +536,30 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(std::conditional_
             }
         }
     }
+    if constexpr (CON && !SPEC) {  // the drawn token's next state, through one LDS word (0 for an unconstrained row: unused)
+        int &con_next = con_next_word();
+        if (tid == 0) {
+            const tce_constraint_row &cr = a.con.rows[b];
+            int v = 0;
+            if (cr.fsm >= 0) {
+                v = -2;  // invalid
+                if (fsm_state_ok(a.con, cr.fsm, cr.state)) {
+                    const tce_fsm &f = a.con.fsms[cr.fsm];
+                    v = fsm_next(f, cr.state, ids[choice]);
+                    if (v < TCE_FSM_DONE || v >= f.states) v = -2;
+                }
+            }
+            con_next = v;
+        }
+        __syncthreads();
+        if (con_next == -2) {  // (uniform) rule 6
+            if (tid == 0) {
+                a.pos[b] = -1;
+                atomicAdd(a.con.violations, 1u);
+            }
+            return;
+        }
+    }
     if (a.debug) {
         tce_sample_debug &d = a.debug[b];
         if (tid < kMaxK) {
@@ -439,6 +607,14 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(std::conditional_
         r.generated = gen + 1u;
         bool stop = (int)(gen + 1u) >= r.max_new || gen + 1u >= (unsigned)a.log_stride;
         for (int i = 0; i < a.n_stop; ++i) stop = stop || tok == a.stop_ids[i];
+        if constexpr (CON) {
+            tce_constraint_row &cr = a.con.rows[b];
+            const int nx = con_next_word();
+            if (cr.fsm >= 0) {
+                if (nx == TCE_FSM_DONE) stop = true;
+                else cr.state = nx;
+            }
+        }
         a.pos[b] = stop ? -1 : a.pos[b] + 1;
     }
 }
@@ -450,8 +626,13 @@ struct VerifyLseArgs : VerifyArgs {
     float *out_logprob, *last_lse;
 };
 
-template <bool LSE>
-__global__ __launch_bounds__(64) void sample_verify_chain_kernel(std::conditional_t<LSE, VerifyLseArgs, VerifyArgs> a) {
+// CON: the sequence's state advances once per emitted token (fsm_next); DONE retires the sequence behind the token; a row that is invalid (rule 6: the base state, no
+// candidate -- cand < 0 --, or the token's next outside [-1, states)) emits nothing, retires the sequence behind the tokens already emitted and counts one violation.
+template <bool LSE, bool CON>
+using VerifyArgsOf = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, VerifyLseArgs, VerifyArgs>>, std::conditional_t<LSE, VerifyLseArgs, VerifyArgs>>;
+
+template <bool LSE, bool CON>
+__global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgsOf<LSE, CON> a) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.batch) return;
     if (!row_active(a.d.pos, b, a.d.pos_bound)) {
@@ -465,7 +646,24 @@ __global__ __launch_bounds__(64) void sample_verify_chain_kernel(std::conditiona
     const unsigned g = r.generated;
     unsigned pushed = r.ring_pushed;
     int t = 0, tok = 0, newpos = -1;
+    [[maybe_unused]] std::conditional_t<CON, ChainCon, NoCon> cs;
+    if constexpr (CON) {
+        cs.fsm = a.con.rows[b].fsm;
+        cs.state = a.con.rows[b].state;
+        cs.invalid = cs.fsm >= 0 && !fsm_state_ok(a.con, cs.fsm, cs.state);
+    }
     for (; t < n; ++t) {
+        if constexpr (CON) {
+            const int ct = a.cand[y0 + t];
+            if (cs.fsm >= 0 && !cs.invalid) {
+                cs.nx = ct < 0 ? -2 : fsm_next(a.con.fsms[cs.fsm], cs.state, ct);
+                cs.invalid = cs.nx < TCE_FSM_DONE || cs.nx >= a.con.fsms[cs.fsm].states;
+            }
+            if (cs.invalid) {
+                newpos = -1;
+                break;
+            }
+        }
         tok = a.cand[y0 + t];
         if (g + t < (unsigned)a.d.log_stride) a.d.out_log[(size_t)b * a.d.log_stride + g + t] = tok;
         if constexpr (LSE) {
@@ -476,6 +674,12 @@ __global__ __launch_bounds__(64) void sample_verify_chain_kernel(std::conditiona
         if (p + 1 + t < a.hist_stride) a.history[(size_t)b * a.hist_stride + p + 1 + t] = tok;
         bool stop = (int)(g + t + 1u) >= r.max_new || g + t + 1u >= (unsigned)a.d.log_stride;
         for (int i = 0; i < a.d.n_stop; ++i) stop = stop || tok == a.d.stop_ids[i];
+        if constexpr (CON) {
+            if (cs.fsm >= 0) {
+                if (cs.nx == TCE_FSM_DONE) stop = true;
+                else cs.state = cs.nx;
+            }
+        }
         if (stop) {
             ++t;
             break;
@@ -487,6 +691,13 @@ __global__ __launch_bounds__(64) void sample_verify_chain_kernel(std::conditiona
         }
     }
     // (n == 0 cannot happen for an active sequence -- row 0 is its own position --; it would emit nothing and leave the sequence where it is)
+    if constexpr (CON) {
+        if (cs.fsm >= 0 && t > 0) a.con.rows[b].state = cs.state;
+        if (cs.invalid) {
+            a.d.pos[b] = -1;
+            atomicAdd(a.con.violations, 1u);
+        }
+    }
     if (t > 0) {
         a.d.next_token[b] = tok;
         r.ring_pushed = pushed;
@@ -608,16 +819,40 @@ size_t logprobs_workspace_bytes(int rows, int vocab) {
     return (logprobs_cand_offset(rows, vocab) + (size_t)rows * 2 * sizeof(float) + 255) & ~(size_t)255;
 }
 
+// con == null: the CON = false forms, the launches they were.  Otherwise f(true_type) picks the CON = true form and con_args appends the constraint to its arguments.
+template <class F>
+static void with_con(const tce_constraint *con, F f) {
+    if (con) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <bool CON, class Base>
+static auto con_args(const Base &base, const tce_constraint *con) {
+    if constexpr (CON) {
+        ConArgs<Base> x;
+        static_cast<Base &>(x) = base;
+        x.con = *con;
+        return x;
+    } else {
+        return base;
+    }
+}
+
 // lp == null: tce_sample_f16, the launches they were
-int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err) {
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err) {
+    const tce_constraint cv = con ? *con : tce_constraint{};
     const int nchunks = sample_chunks(c.vocab);
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
-    if (lp)
-        hipLaunchKernelGGL((sample_select_kernel<false, true>), dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
-                           c.pos_device, c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr), static_cast<float2_t *>(lp->partials));
-    else
-        hipLaunchKernelGGL((sample_select_kernel<false, false>), dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
-                           c.pos_device, c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr), static_cast<float2_t *>(nullptr));
+    with_con(con, [&](auto tag) {
+        constexpr bool CON = decltype(tag)::value;
+        if (lp)
+            hipLaunchKernelGGL((sample_select_kernel<false, true, CON>), dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab,
+                               c.rows, c.pos_device, c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr),
+                               static_cast<float2_t *>(lp->partials), cv);
+        else
+            hipLaunchKernelGGL((sample_select_kernel<false, false, CON>), dim3(nchunks, c.batch), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab,
+                               c.rows, c.pos_device, c.pos_bound, c.top_k_bound, entries, nchunks, 1, static_cast<const int32_t *>(nullptr), static_cast<float2_t *>(nullptr),
+                               cv);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         DrawArgs a;
@@ -644,9 +879,15 @@ int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, hipSt
             la.out_logprob = lp->out_logprob;
             la.last_lse = lp->last_lse;
             la.cand_logprob = la.cand_lse = nullptr;
-            hipLaunchKernelGGL((sample_draw_kernel<false, true>), dim3(c.batch), dim3(kThreads), 0, stream, la, 1, static_cast<int32_t *>(nullptr));
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                hipLaunchKernelGGL((sample_draw_kernel<false, true, CON>), dim3(c.batch), dim3(kThreads), 0, stream, con_args<CON>(la, con), 1, static_cast<int32_t *>(nullptr));
+            });
         } else {
-            hipLaunchKernelGGL((sample_draw_kernel<false, false>), dim3(c.batch), dim3(kThreads), 0, stream, a, 1, static_cast<int32_t *>(nullptr));
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                hipLaunchKernelGGL((sample_draw_kernel<false, false, CON>), dim3(c.batch), dim3(kThreads), 0, stream, con_args<CON>(a, con), 1, static_cast<int32_t *>(nullptr));
+            });
         }
         e = hipGetLastError();
     }
@@ -665,8 +906,9 @@ size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
     return verify_cand_offset(batch, rows_per_seq, vocab) + (((size_t)batch * rows_per_seq * 4 + 255) & ~(size_t)255);
 }
 
-int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err) {
+int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err) {
     const tce_sample_call &c = v.s;
+    const tce_constraint cv = con ? *con : tce_constraint{};
     const int nchunks = sample_chunks(c.vocab), T = v.rows_per_seq, vrows = c.batch * T;
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
     VerifyArgs a;
@@ -707,19 +949,31 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
         la.cand_lse = cl + vrows;
         la.out_logprob = lp->out_logprob;
         la.last_lse = lp->last_lse;
-        hipLaunchKernelGGL((sample_select_kernel<true, true>), dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
-                           v.row_pos, c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token, static_cast<float2_t *>(lp->partials));
+        with_con(con, [&](auto tag) {
+            constexpr bool CON = decltype(tag)::value;
+            hipLaunchKernelGGL((sample_select_kernel<true, true, CON>), dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab,
+                               c.rows, v.row_pos, c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token, static_cast<float2_t *>(lp->partials), cv);
+        });
     } else {
-        hipLaunchKernelGGL((sample_select_kernel<true, false>), dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab, c.rows,
-                           v.row_pos, c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token, static_cast<float2_t *>(nullptr));
+        with_con(con, [&](auto tag) {
+            constexpr bool CON = decltype(tag)::value;
+            hipLaunchKernelGGL((sample_select_kernel<true, false, CON>), dim3(nchunks, vrows), dim3(kThreads), 0, stream, static_cast<const half_t *>(c.logits), c.ld, c.vocab,
+                               c.rows, v.row_pos, c.pos_bound, c.top_k_bound, entries, nchunks, T, v.row_token, static_cast<float2_t *>(nullptr), cv);
+        });
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         if (lp) {
             static_cast<DrawArgs &>(ld) = a.d;
-            hipLaunchKernelGGL((sample_draw_kernel<true, true>), dim3(vrows), dim3(kThreads), 0, stream, ld, T, a.cand);
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                hipLaunchKernelGGL((sample_draw_kernel<true, true, CON>), dim3(vrows), dim3(kThreads), 0, stream, con_args<CON>(ld, con), T, a.cand);
+            });
         } else {
-            hipLaunchKernelGGL((sample_draw_kernel<true, false>), dim3(vrows), dim3(kThreads), 0, stream, a.d, T, a.cand);
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                hipLaunchKernelGGL((sample_draw_kernel<true, false, CON>), dim3(vrows), dim3(kThreads), 0, stream, con_args<CON>(a.d, con), T, a.cand);
+            });
         }
         e = hipGetLastError();
     }
@@ -727,9 +981,15 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
         a.d.pos = c.pos_device;
         if (lp) {
             static_cast<VerifyArgs &>(la) = a;
-            hipLaunchKernelGGL(sample_verify_chain_kernel<true>, dim3((c.batch + 63) / 64), dim3(64), 0, stream, la);
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                hipLaunchKernelGGL((sample_verify_chain_kernel<true, CON>), dim3((c.batch + 63) / 64), dim3(64), 0, stream, con_args<CON>(la, con));
+            });
         } else {
-            hipLaunchKernelGGL(sample_verify_chain_kernel<false>, dim3((c.batch + 63) / 64), dim3(64), 0, stream, a);
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                hipLaunchKernelGGL((sample_verify_chain_kernel<false, CON>), dim3((c.batch + 63) / 64), dim3(64), 0, stream, con_args<CON>(a, con));
+            });
         }
         e = hipGetLastError();
     }

@@ -21,14 +21,14 @@ size_t w8a8_scratch_bytes();
 void set_w8a8_xsplit(int xs);
 int sample_chunks(int vocab);
 size_t sample_workspace_bytes(int batch, int vocab);
-int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err);
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err);
 size_t logprobs_workspace_bytes(int rows, int vocab);
 int launch_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, hipStream_t stream,
                         hipError_t *hip_err);
 int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos, int pos_bound, void *workspace,
                           hipStream_t stream, hipError_t *hip_err);
 size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
-int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, hipStream_t stream, hipError_t *hip_err);
+int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err);
 int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
                        int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err);
 }
@@ -1485,7 +1485,7 @@ static int check_sample_call(const char *who, const tce_sample_call *c, long lon
 int tce_sample_f16(const tce_sample_call *c, void *stream) {
     if (const int rc = check_sample_call("tce_sample_f16", c, c ? c->batch : 0)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_sample_f16(*c, nullptr, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_sample_f16(*c, nullptr, nullptr, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
 }
 
@@ -1505,7 +1505,7 @@ int tce_sample_logprobs_f16(const tce_sample_call *c, const tce_logprob_out *lp,
     if (const int rc = check_sample_call(who, c, c ? c->batch : 0)) return rc;
     if (const int rc = check_logprob_out(who, lp)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_sample_f16(*c, lp, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_sample_f16(*c, lp, nullptr, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
 }
 
@@ -1544,7 +1544,7 @@ static int check_verify_call(const char *who, const tce_sample_verify_call *v) {
 int tce_sample_verify_f16(const tce_sample_verify_call *v, void *stream) {
     if (const int rc = check_verify_call("tce_sample_verify_f16", v)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_sample_verify_f16(*v, nullptr, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_sample_verify_f16(*v, nullptr, nullptr, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
 }
 
@@ -1553,7 +1553,40 @@ int tce_sample_verify_logprobs_f16(const tce_sample_verify_call *v, const tce_lo
     if (const int rc = check_verify_call(who, v)) return rc;
     if (const int rc = check_logprob_out(who, lp)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_sample_verify_f16(*v, lp, static_cast<hipStream_t>(stream), &he);
+    const int rc = tce::launch_sample_verify_f16(*v, lp, nullptr, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
+}
+
+// the constrained forms' own refusals (after the sampling call's)
+static int check_constraint(const char *who, const tce_constraint *con) {
+    if (!con) return fail(TCE_ERR_BAD_ARG, "%s: null tce_constraint", who);
+    if (!con->rows || !con->violations) return fail(TCE_ERR_BAD_ARG, "%s: null pointer (rows, violations)", who);
+    if (con->n_fsm < 0 || con->n_fsm > TCE_FSM_MAX) return fail(TCE_ERR_BAD_ARG, "%s: n_fsm %d (0 .. %d)", who, con->n_fsm, TCE_FSM_MAX);
+    if (con->n_fsm > 0 && !con->fsms) return fail(TCE_ERR_BAD_ARG, "%s: n_fsm %d with null fsms", who, con->n_fsm);
+    if (reinterpret_cast<uintptr_t>(con->fsms) % 8 != 0 || (reinterpret_cast<uintptr_t>(con->rows) | reinterpret_cast<uintptr_t>(con->violations)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: fsms 8-byte aligned, rows / violations 4-byte aligned", who);
+    return TCE_OK;
+}
+
+int tce_sample_constrained_f16(const tce_sample_call *c, const tce_constraint *con, const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_constrained_f16";
+    if (const int rc = check_sample_call(who, c, c ? c->batch : 0)) return rc;
+    if (const int rc = check_constraint(who, con)) return rc;
+    if (lp)
+        if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_f16(*c, lp, con, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+int tce_sample_verify_constrained_f16(const tce_sample_verify_call *v, const tce_constraint *con, const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_verify_constrained_f16";
+    if (const int rc = check_verify_call(who, v)) return rc;
+    if (const int rc = check_constraint(who, con)) return rc;
+    if (lp)
+        if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_verify_f16(*v, lp, con, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
 }
 

@@ -8,6 +8,8 @@ The batched / paged decoders (batch_decode.py, paged_kv.py) run a "step" = the l
     1        tce_w4a16_forward       lm_head at M = B -> logits fp16 [B][vocab]
     2        tce_sample_f16          penalties, top-k, softmax, top-p, temperature, draw; token -> next_token, log, ring; pos += 1 or -1 (retired)
                                      (logprobs=True: tce_sample_logprobs_f16, the same two launches, which also write the token's log-probability)
+                                     (constraints=True: tce_sample_constrained_f16, the same two launches under a token automaton and a logit bias per slot:
+                                     constrain.py)
 
 7 L + 5 launches, captured once in one torch.cuda.graph: ONE REPLAY IS ONE TOKEN for all B sequences, with no host round trip.  Everything a replay needs lives
 on the device (positions, sampling parameters, recent-token rings, generator counters, output logs), so a slot changes hands without recapture.
@@ -93,7 +95,11 @@ class SamplingParams:
 def penalised_logits(logits_f16_row: np.ndarray, recent, params: SamplingParams) -> np.ndarray:
     """fp32 logits after sample_repetition_penalty and sample_frequency_and_presence_penalties over the window `recent` (Generate.cc:14-60)."""
     assert logits_f16_row.dtype == np.float16 and logits_f16_row.ndim == 1
-    x = logits_f16_row.astype(np.float32)  # half2float: exact
+    return _penalise(logits_f16_row.astype(np.float32), recent, params)  # half2float: exact
+
+
+def _penalise(x: np.ndarray, recent, params: SamplingParams) -> np.ndarray:
+    """The two penalties on fp32 values, in place (penalised_logits on the widened row; constrain.constrained_reference on the biased one)."""
     recent = np.asarray(recent, dtype=np.int64).reshape(-1)
     recent = recent[(recent >= 0) & (recent < x.size)]
     if recent.size == 0:
@@ -137,19 +143,26 @@ def sample_reference(logits_f16_row: np.ndarray, recent, params: SamplingParams,
     Ordering rule: descending penalised logit, ascending id among equals.  Returns ids / logits (the k sorted candidates), p (first softmax), n (kept by top-p),
     final_p (after temperature, n entries), choice and token."""
     x = penalised_logits(logits_f16_row, recent, params)
-    V = x.size
+    return _chain(x, np.arange(x.size), params, u)
+
+
+def _chain(x: np.ndarray, among: np.ndarray, params: SamplingParams, u) -> dict:
+    """sample_reference behind the penalties, over the ids `among` (ascending) of the penalised fp32 row x: every id (sample_reference) or the allowed ones
+    (constrain.constrained_reference).  The ids keep their values: ties go to the lowest id, and fewer than k ids make k their number."""
+    xa = x[among]
+    V = xa.size
     if params.temp <= 0:
-        tok = int(np.argmax(x))  # the first maximum: std::max_element
+        tok = int(among[int(np.argmax(xa))])  # the first maximum: std::max_element
         return {"ids": np.array([tok], np.int32), "logits": x[tok:tok + 1].copy(), "p": np.zeros(1, np.float32), "n": 1, "final_p": np.zeros(1, np.float32),
                 "choice": 0, "token": tok}
     k = min(max(int(params.top_k), 1), V)
     if k < V:
-        kth = np.partition(x, V - k)[V - k]
-        gt = np.nonzero(x > kth)[0]
-        eq = np.nonzero(x == kth)[0][:k - gt.size]  # the lowest ids of the boundary's tie class
-        cand = np.concatenate([gt, eq])
+        kth = np.partition(xa, V - k)[V - k]
+        gt = np.nonzero(xa > kth)[0]
+        eq = np.nonzero(xa == kth)[0][:k - gt.size]  # the lowest ids of the boundary's tie class
+        cand = among[np.concatenate([gt, eq])]
     else:
-        cand = np.arange(V)
+        cand = among
     order = np.lexsort((cand, -x[cand].astype(np.float64)))
     ids = cand[order].astype(np.int32)
     l = (x[ids] + np.float32(0.0)).astype(np.float32)  # (-0 -> +0, as the device returns it)
@@ -212,10 +225,13 @@ class Sampler:
     """The per-row device state of tce_sample_f16 for `batch` rows: rows (parameters, ring, counters), next_token, the output log [batch][log_stride], the workspace
     (zeroed once).  debug=True keeps the sorted candidates of the last call (tests).  logprobs=True: step() calls tce_sample_logprobs_f16 -- the same two launches --
     and out_logprob fp32 [batch][log_stride] holds, beside every token of out_log, its log-probability under the raw logits (NaN where nothing was written yet); last_lse
-    [batch] the log-sum-exp of the row each slot's last token was drawn from.  logprobs=False: the call, the launches and a captured graph are what they were."""
+    [batch] the log-sum-exp of the row each slot's last token was drawn from.  logprobs=False: the call, the launches and a captured graph are what they were.
+    constraints=True: the sampler owns the constraint rows [batch] (struct tce_constraint_row: automaton, state, logit bias), the automaton table (constrain.
+    AutomatonTable) and the violations word, and step() calls tce_sample_constrained_f16 -- still two launches; set_row(..., automaton=, logit_bias=) gives a slot its
+    automaton (an index from table.register) and bias.  constraints=False: the existing entry points, untouched."""
 
     def __init__(self, batch: int, vocab: int, log_stride: int, device, top_k_bound: int = 40, stop_ids=(), debug: bool = False, tfs_z: float = 1.0,
-                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False):
+                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False, constraints: bool = False):
         import torch
         if len(stop_ids) > 4:
             raise ValueError("at most 4 stop ids")
@@ -236,20 +252,56 @@ class Sampler:
             self.out_logprob = torch.full((batch, self.log_stride), float("nan"), dtype=torch.float32, device=device)
             self.last_lse = torch.full((batch,), float("nan"), dtype=torch.float32, device=device)
             self.partials = torch.empty(int(capi.lib().tce_logprobs_workspace_bytes(batch, vocab)), dtype=torch.uint8, device=device)  # (need not be zeroed)
+        self.constraints = bool(constraints)
+        self.crows = self.table = self.violations_word = None
+        if self.constraints:
+            from .constrain import AutomatonTable
+            self.crows = torch.zeros((batch, C.sizeof(capi.ConstraintRow) // 4), dtype=torch.int32, device=device)
+            self.crows[:, 0] = -1  # every row unconstrained
+            self.table = AutomatonTable(vocab, device)
+            self.violations_word = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def constraint(self) -> capi.Constraint:
+        """struct tce_constraint over this sampler's table, rows and violations word (n_fsm is the table's size: a free entry has no states and is refused on the device)."""
+        return capi.Constraint(fsms=self.table.fsms.data_ptr(), n_fsm=capi.TCE_FSM_MAX, rows=self.crows.data_ptr(), violations=self.violations_word.data_ptr())
+
+    def check_constraint(self, automaton, logit_bias) -> list:
+        """set_row's refusals for automaton / logit_bias, without a write: returns the bias as [(id, value)]."""
+        from .constrain import check_bias
+        if not self.constraints:
+            if automaton is not None or logit_bias:
+                raise ValueError("automaton / logit_bias: the sampler was built without constraints=True")
+            return []
+        if automaton is not None:
+            self.table.start(automaton)
+        return check_bias(logit_bias, self.vocab)
+
+    def violations(self) -> int:
+        """Rows the device found in an invalid constraint state (rule 6) since the sampler was made: 0 unless a row or a descriptor was written from outside."""
+        return int(self.violations_word.cpu().numpy().view(np.uint32)[0]) if self.constraints else 0
 
     def logprob_out(self, partials=None) -> capi.LogprobOut:
         """struct tce_logprob_out over this sampler's arrays (partials: another workspace -- the verifier's, for batch * rows_per_seq rows)."""
         return capi.LogprobOut(out_logprob=self.out_logprob.data_ptr(), last_lse=self.last_lse.data_ptr(), partials=(self.partials if partials is None else partials).data_ptr())
 
-    def set_row(self, slot: int, params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> None:
-        """The slot changes hands: one stream-ordered copy of its row (parameters, a fresh ring with the prompt pushed, counters at zero)."""
+    def set_row(self, slot: int, params: SamplingParams, seed: int, max_new: int, prompt_ids=(), automaton: int | None = None, logit_bias=None) -> None:
+        """The slot changes hands: one stream-ordered copy of its row (parameters, a fresh ring with the prompt pushed, counters at zero) and, with constraints=True,
+        one of its constraint row: automaton (an index of table.register, None: unconstrained) in its start state, logit_bias ({id: value} or [(id, value)], <= 16)."""
         import torch
         params.check(self.top_k_bound)
         if not 1 <= max_new <= self.log_stride:
             raise ValueError(f"max_new {max_new}: 1 .. {self.log_stride}")
+        bias = self.check_constraint(automaton, logit_bias)
         row = make_row(params, seed, max_new, prompt_ids)
         host = torch.from_numpy(np.frombuffer(bytes(row), dtype=np.int32).copy())
         self.rows[slot].copy_(host)
+        if self.constraints:
+            from .constrain import constraint_row
+            cr = constraint_row(-1 if automaton is None else automaton, 0 if automaton is None else self.table.start(automaton), bias)
+            self.crows[slot].copy_(torch.from_numpy(np.frombuffer(bytes(cr), dtype=np.int32).copy()))
+            self.table.users.pop(slot, None)
+            if automaton is not None:
+                self.table.users[slot] = int(automaton)
 
     def step(self, logits, pos_device, pos_bound: int) -> None:
         """tce_sample_f16 on logits fp16 [batch][ld] (two launches on the current stream).  pos_device int32 [batch] is READ (activity) and WRITTEN (+1, or -1)."""
@@ -259,7 +311,9 @@ class Sampler:
         assert pos_device.dtype == torch.int32 and pos_device.is_contiguous() and pos_device.numel() == self.batch
         assert logits.is_cuda and pos_device.is_cuda
         c = self.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound)
-        if self.logprobs:
+        if self.constraints:
+            capi.check(capi.sample_constrained_f16(c, self.constraint(), self.logprob_out() if self.logprobs else None, _stream()))
+        elif self.logprobs:
             capi.check(capi.sample_logprobs_f16(c, self.logprob_out(), _stream()))
         else:
             capi.check(capi.sample_f16(c, _stream()))
@@ -277,6 +331,9 @@ class Sampler:
     # ---- reading state back (each synchronises) ----
     def row(self, slot: int) -> capi.SampleRow:
         return capi.SampleRow.from_buffer_copy(self.rows[slot].cpu().numpy().tobytes())
+
+    def constraint_row(self, slot: int) -> capi.ConstraintRow:
+        return capi.ConstraintRow.from_buffer_copy(self.crows[slot].cpu().numpy().tobytes())
 
     def debug_row(self, slot: int) -> capi.SampleDebug:
         return capi.SampleDebug.from_buffer_copy(self.debug[slot].cpu().numpy().tobytes())
@@ -463,7 +520,8 @@ class _GeneratorBase:
         self.sampler.step(logits, pos, self.pos_bound)
 
     # ---- admission ----
-    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None, chunk_rows: int | None = None) -> list[int]:
+    def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None, chunk_rows: int | None = None,
+              automaton: int | None = None, logit_bias=None, constraints: dict | None = None) -> list[int]:
         """admit(slot, prompt_ids, params, seed, max_new), or admit([(slot, prompt_ids, params, seed, max_new), ...]) for several sequences through ONE prefill_many.
         The prompt is embedded, prefilled through every layer, the final norm and lm_head run on its last row and the first token is sampled; the slot's position
         becomes the prompt length.  Synchronises.  Returns the slots that retired on their first token.
@@ -471,8 +529,13 @@ class _GeneratorBase:
         key, all or nothing across the admissions, the chunk is embedded and prefilled at its position through ALL layers, and when every layer has a window the
         pages wholly behind it are given back before the next chunk.  A windowed slot then never holds more than ceil((max W + N) / page_keys) + 1 pages, so a prompt
         longer than the pool can be admitted; without windows only the activation rows are bounded.  PagePoolExhausted in a later chunk: the slots of this call are
-        released and the generator is as it was before the call.  A chunked prefill is not bit-identical to the one-shot one (the prefill's tiling differs)."""
+        released and the generator is as it was before the call.  A chunked prefill is not bit-identical to the one-shot one (the prefill's tiling differs).
+        constraints=True generators: automaton= (an index of sampler.table.register) and logit_bias= ({id: value} or [(id, value)]) for the single form, constraints=
+        {slot: (automaton index or None, bias or None)} for the list form; the slot starts in the automaton's start state and the FIRST token is already constrained."""
         import torch
+        if prompt_ids is not None and constraints is not None or prompt_ids is None and (automaton is not None or logit_bias):
+            raise ValueError("admit: automaton= / logit_bias= go with the single form, constraints={slot: (automaton, bias)} with the list form")
+        cons = {int(slot): (automaton, logit_bias)} if prompt_ids is not None else {int(k): tuple(v) for k, v in (constraints or {}).items()}
         adm = slot if prompt_ids is None else [(slot, prompt_ids, params, seed, max_new)]
         adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(self.sampler.log_stride if mn is None else mn)) for s, ids, p, sd, mn in adm]
         if len({s for s, *_ in adm}) != len(adm):
@@ -485,6 +548,8 @@ class _GeneratorBase:
             if any(not 0 <= t < self.vocab for t in ids):
                 raise ValueError("a prompt token lies outside the vocabulary")
             p.check(self.sampler.top_k_bound)
+            if any(c is not None for c in cons.get(s, ())):  # (the existing call forms read nothing new of the sampler)
+                self.sampler.check_constraint(*cons[s])
             if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
                 raise ValueError(f"a prompt of 1 .. {self.max_keys - 1} tokens and max_new 1 .. {self.sampler.log_stride}")
         if chunk_rows is not None:
@@ -516,7 +581,7 @@ class _GeneratorBase:
                         d.prefill(s, r, 0)
         self._adm_pos.fill_(-1)
         for (s, ids, p, sd, mn), r in zip(adm, rows):
-            self.sampler.set_row(s, p, sd, mn, ids)
+            self.sampler.set_row(s, p, sd, mn, ids, *(cons[s] if any(c is not None for c in cons.get(s, ())) else ()))
             self.sampler.out_log[s].fill_(-1)
             if self.sampler.logprobs:
                 self.sampler.out_logprob[s].fill_(float("nan"))
@@ -610,6 +675,10 @@ class _GeneratorBase:
         self.book.clear(slot)
         return self.allocator.release(slot) if self.allocator is not None else []
 
+    def violations(self) -> int:
+        """Rows the sampler found in an invalid constraint state (Sampler.violations; 0 without constraints=True)."""
+        return self.sampler.violations()
+
     def embed_violations(self) -> int:
         """Token ids tce_embed_rows_f16 refused since the workspace was made (0 unless something wrote next_token from outside)."""
         return int(self.sampler.workspace[:4].cpu().numpy().view(np.uint32)[0])
@@ -621,8 +690,8 @@ class BatchedGenerator(_GeneratorBase):
     inactive) and run() replays it: one replay is one token for every live slot."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
-                 debug: bool = False, logprobs: bool = False):
-        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs)
+                 debug: bool = False, logprobs: bool = False, constraints: bool = False):
+        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints)
         self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
         self.score_logits: list = []
         self.launches_per_token = 1 + self.decoders[0].LAUNCHES * len(self.decoders) + 1 + 1 + 2

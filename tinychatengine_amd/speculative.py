@@ -242,7 +242,9 @@ class Verifier:
         c.debug = self.debug.data_ptr() if self.debug is not None else None
         v = capi.SampleVerifyCall(s=c, rows_per_seq=self.rows_per_seq, hist_stride=history.shape[1], row_token=row_token.data_ptr(), row_pos=row_pos.data_ptr(),
                                   history=history.data_ptr(), emitted=self.emitted.data_ptr())
-        if s.logprobs:
+        if s.constraints:
+            capi.check(capi.sample_verify_constrained_f16(v, s.constraint(), s.logprob_out(self.partials) if s.logprobs else None, _stream()))
+        elif s.logprobs:
             capi.check(capi.sample_verify_logprobs_f16(v, s.logprob_out(self.partials), _stream()))
         else:
             capi.check(capi.sample_verify_f16(v, _stream()))
@@ -260,7 +262,8 @@ class SpeculativeGenerator(_GeneratorBase):
     are the plain loop's; a slot holds at most ceil((max W + n T) / page_keys) + 1 pages through run(n)."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
-                 graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False):
+                 graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False,
+                 constraints: bool = False):
         decoders = list(decoders)
         for d in decoders:  # a windowed layer must run the windowed ROWS step: its attention object carries the window (SpeculativeDecoder(..., window=W) builds it so)
             w = getattr(d, "window", None)
@@ -269,7 +272,8 @@ class SpeculativeGenerator(_GeneratorBase):
         self.rows_per_seq, self.ngram = decoders[0].rows_per_seq, int(ngram)
         _check_rows(self.rows_per_seq, self.ngram)
         assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
-        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, rows_per_seq=self.rows_per_seq, logprobs=logprobs)
+        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, rows_per_seq=self.rows_per_seq, logprobs=logprobs,
+                         constraints=constraints)
         B, T, dev = self.batch, self.rows_per_seq, self.device
         self.verifier = Verifier(self.sampler, T)
         self.book = SpecSlotBook(B, self.max_keys, T)
