@@ -69,6 +69,7 @@ for n, parts in rows.items():
     first = np.concatenate([p[p[:, 0] - p[:, 0].min() < 50] for p in parts])  # workgroups that entered within 0.5 us of the launch's first: the first generation's front
     rec = {"label": args.label, "launch": n, "workgroups_per_launch": len(parts[0]), "launches": len(parts), "ns_p10_p50_p90_from_wave_entry": {
         "requests_issued": q((a[:, 1] - a[:, 0]) * 10), "x_staged": q((a[:, 2] - a[:, 0]) * 10), "contraction_done": q((a[:, 3] - a[:, 0]) * 10), "stored": q((a[:, 4] - a[:, 0]) * 10)},
+        "ns_p10_p50_p90_contraction_done_to_stored": q((a[:, 4] - a[:, 3]) * 10),  # the tail of the launch, per workgroup (profiles/decode_tail/)
         "head_shader_cycles_p10_p50_p90": q(a[:, 6] - a[:, 5]),
         "first_front_requests_issued_ns_p10_p50_p90": q((first[:, 1] - first[:, 0]) * 10), "first_front_head_shader_cycles_p10_p50_p90": q(first[:, 6] - first[:, 5]),
         "first_front_stored_ns_p10_p50_p90": q((first[:, 4] - first[:, 0]) * 10),

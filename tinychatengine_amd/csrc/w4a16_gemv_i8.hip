@@ -163,6 +163,7 @@ template <typename T>
 __device__ __forceinline__ void keep_scalar(T &v) {
     asm volatile("" : "+s"(v));
 }
+typedef __attribute__((address_space(1))) half_t c16_t;  // an output element, as device memory
 
 // The body: everything behind the choice of the workgroup's linear.  `seg`, `A_` ... are VALUES (registers, or scalar loads still in flight: waited for at the first use);
 // `args` is the launch's tail (I8Tail) or the mixed launch's struct, for the prologue / epilogue fields.
@@ -453,13 +454,42 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
     // the residual epilogue's old values (TCE_W4_ADD_TO_C): requested by the lanes that will add to them, BEHIND the weight requests and the conversion (the flags, C and
     // ldc are tail arguments: asking here, not in front of the weights, keeps every scalar wait out of the head; loads return in order, and the value is needed behind
     // the K reduction's barrier only -- where a load issued there was a memory round trip at the very end of every o_proj / down_proj launch)
+    // What the store needs is formed HERE as well, where the wave is parked on its weight loads and the issue slots are free (decode-tail round; profiles/decode_tail/):
+    // whether the thread's output row exists, its member's epilogue, and its element as a scalar base per tile plus one 32-bit byte offset per lane.  Behind the K
+    // reduction's barrier wave 0 then does only what needs the contraction's result: the sum over the waves, the rounding, the epilogue its flags name, one store -- no
+    // select, no bounds compare, no multiply.
+    // Thread tid of wave 0 finishes output (tile t_r, activation row t_m, tile row t_i16): tid = (t_r * MB + t_m) * 16 + t_i16.
+    const int t_i16 = tid & 15, t_m = (tid >> 4) % MB, t_r = tid / (16 * MB);
+    const int t_row = (tile0 + t_r) * 16 + t_i16;  // (unclamped: a surplus tile's rows are >= N)
+    const bool t_live = wk == 0 && tid < ROWS * MB * 16 && m0 + t_m < M_ && t_row < seg.N;
+    c16_t *cbase[ROWS];  // the element of (activation row m0, the tile's first row) in the tile's member: C is device memory, addressed as such (a scalar base + a lane's offset in ONE instruction)
+    int any_pair = 0;    // (wave-uniform: the SiLU arithmetic sits behind a scalar branch)
+    int pshift[ROWS];    // 1: the tile's member stores pairs
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        keep_scalar(mepi[r]);  // (the flags stay in their registers from here on: nothing behind the barrier waits on scalar memory)
+        const int first = (tile0 + r) * 16 - mrow0[r];  // the tile's first row inside its member (a group copy; otherwise in the linear): a multiple of 16
+        // the pair epilogue: rows 2n, 2n + 1 -> element n
+        cbase[r] = (c16_t *)mC[r] + ((size_t)m0 * mldc[r] + ((mepi[r] & TCE_W4_SILU_MUL_PAIRS) ? first >> 1 : first));
+        keep_scalar(cbase[r]);
+        pshift[r] = (mepi[r] & TCE_W4_SILU_MUL_PAIRS) ? 1 : 0;
+        keep_scalar(pshift[r]);
+        any_pair |= mepi[r] & TCE_W4_SILU_MUL_PAIRS;
+    }
+    const int t_epi = of_tile(mepi, t_r);
+    const bool t_pair = (t_epi & TCE_W4_SILU_MUL_PAIRS) != 0;
+    const bool t_add = !t_pair && (t_epi & TCE_W4_ADD_TO_C);
+    const bool t_store = t_live && !(t_pair && (t_i16 & 1));  // (the pair is stored by the even row's lane)
+    // thread t's element of tile r: bytes from the tile's base -- its activation row's ldc (nothing for one row per pass) and the tile row, halved by a pair member
+    auto c_at = [&](int r, int t) {
+        const unsigned off = (unsigned)(((t >> 4) % MB) * mldc[r] + ((t & 15) >> pshift[r])) * 2u;
+        return reinterpret_cast<c16_t *>(reinterpret_cast<__attribute__((address_space(1))) unsigned char *>(cbase[r]) + off);
+    };
     half_t c_old = (half_t)0.0f;
     if constexpr (!RNORM) {
-        if (wk == 0 && tid < ROWS * MB * 16) {
-            const int i16 = tid & 15, m = (tid >> 4) % MB, r = tid / (16 * MB);
-            const int row = (tile0 + r) * 16 + i16;
-            if ((of_tile(mepi, r) & TCE_W4_ADD_TO_C) && m0 + m < M_ && row < seg.N) c_old = of_tile(mC, r)[(size_t)(m0 + m) * of_tile(mldc, r) + (row - of_tile(mrow0, r))];
-        }
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+            if (t_live && t_add && (ROWS == 1 || t_r == r)) c_old = *c_at(r, tid);
     }
 
     // ---- 3. contraction.  B set uu: the operand of unit uu of the pass in the lanes of ITS columns, zeros in the others (never written) ----
@@ -565,23 +595,29 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
     const float cj = bad_l ? __builtin_nanf("") : __builtin_bit_cast(float, (unsigned)(127 + 8 * p_l - sh_l - 4) << 23);
     float *red = reinterpret_cast<float *>(smem + (size_t)WK * UW * MB * 512);  // [WK][ROWS][MB][16]
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float v = acc[r][q] * cj;
-            v = dpp_add_f32<0xB1>(v);  // quad_perm [1,0,3,2]: planes
-            v = dpp_add_f32<0x4E>(v);  // quad_perm [2,3,0,1]
-            if constexpr (MB <= 2) v = dpp_add_f32<0x128>(v);  // row_ror 8
-            if constexpr (MB == 1) v = dpp_add_f32<0x124>(v);  // row_ror 4
-            if (p_l == 0 && (j >> 2) < MB) red[((wk * ROWS + r) * MB + m_l) * 16 + kq * 4 + q] = v;
-        }
-    // nothing behind the barrier waits on scalar memory: what the store needs is in registers by now
-#pragma unroll
     for (int r = 0; r < ROWS; ++r) {
-        keep_scalar(mC[r]);
-        keep_scalar(mldc[r]);
-        keep_scalar(mepi[r]);
-        keep_scalar(mrow0[r]);
+        // (step by step over the four registers: four independent chains, so that no DPP step waits on the add in front of it; each chain's own order is what it was)
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = acc[r][q] * cj;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = dpp_add_f32<0xB1>(v[q]);  // quad_perm [1,0,3,2]: planes
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = dpp_add_f32<0x4E>(v[q]);  // quad_perm [2,3,0,1]
+        if constexpr (MB <= 2) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = dpp_add_f32<0x128>(v[q]);  // row_ror 8
+        }
+        if constexpr (MB == 1) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = dpp_add_f32<0x124>(v[q]);  // row_ror 4
+        }
+        // (the chains end as four scalars: seen from the 16-byte write the vectoriser pairs them up -- a zeroing move, a DPP move and a packed add per step and pair
+        //  where the scalar form is ONE v_add_f32 with a DPP operand)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(v[q]));
+        // a lane that holds a finished partial row holds four consecutive floats of it: one 16-byte LDS write
+        if (p_l == 0 && (j >> 2) < MB) *reinterpret_cast<float4_t *>(red + ((wk * ROWS + r) * MB + m_l) * 16 + kq * 4) = float4_t{v[0], v[1], v[2], v[3]};
     }
     keep_scalar(seg.N);
     keep_scalar(M_);
@@ -602,44 +638,95 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
     }
     __syncthreads();
     if (tid < ROWS * MB * 16) {
-        float part[16];
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) part[k2] = red[(k2 < WK ? k2 : 0) * (ROWS * MB * 16) + tid];
+        // The sum over the WK waves that exist (wave-uniform, 1..16): exactly their partial rows, at one address plus immediate offsets, chosen by scalar branches.
+        // Added in wave order starting from 0.f, as ever: what the sixteen-slot form added for the waves that do not exist was `+ 0.f` on a value that is never -0
+        // (the chain starts at +0, and +0 plus anything is not -0), so every output bit is what it was.
+        constexpr int S = ROWS * MB * 16;  // floats per set of partial rows
+        const float *part = red + tid;
         float v = 0.f;
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) v += k2 < WK ? part[k2] : 0.f;
-        const int i16 = tid & 15, m = (tid >> 4) % MB, r = tid / (16 * MB);
-        const int row = (tile0 + r) * 16 + i16;  // (unclamped: a surplus tile's rows are >= N)
-        const half_t y = (half_t)v;
-        // the (gate, up) neighbour of the pair epilogue: rows 2n, 2n + 1 are adjacent lanes
-        const half_t y_other = __builtin_bit_cast(half_t, (unsigned short)__builtin_amdgcn_update_dpp(0, (int)__builtin_bit_cast(unsigned short, y), 0xB1, 0xF, 0xF, false));
-        half_t hnew = (half_t)0.0f;
-        (void)hnew;
-        if (m0 + m < M_ && row < seg.N) {
-            const int epi = of_tile(mepi, r), mrow = row - of_tile(mrow0, r);  // the row inside its member (a group copy; otherwise the row itself)
-            half_t *crow = of_tile(mC, r) + (size_t)(m0 + m) * of_tile(mldc, r);
-            if (epi & TCE_W4_SILU_MUL_PAIRS) {
-                if ((i16 & 1) == 0) crow[mrow >> 1] = silu_mul_half(y, y_other);
-            } else if (epi & TCE_W4_ADD_TO_C) {
-                if constexpr (RNORM) hnew = crow[mrow] + y;  // (stored below, write-through)
-                else crow[mrow] = c_old + y;
+        if (WK <= 4) {
+            // K <= 4096, four of the token's five launch shapes: straight-line, the reads issued together
+            if (WK == 4) {
+                const float p0 = part[0], p1 = part[S], p2 = part[2 * S], p3 = part[3 * S];
+                v += p0;
+                v += p1;
+                v += p2;
+                v += p3;
+            } else if (WK == 3) {
+                const float p0 = part[0], p1 = part[S], p2 = part[2 * S];
+                v += p0;
+                v += p1;
+                v += p2;
+            } else if (WK == 2) {
+                const float p0 = part[0], p1 = part[S];
+                v += p0;
+                v += p1;
             } else {
-                crow[mrow] = y;
+                v += part[0];
             }
-            if constexpr (MIX) {
-                if (gathers) {
-                    // (a) the tile's 16 values into EVERY rank's window -- buffer (slot, parity of the epoch), this rank's slice -- past every cache (comm.hip's protocol)
-                    const half_t outv = (epi & TCE_W4_ADD_TO_C) ? (half_t)(c_old + y) : y;
-                    const size_t off = ((size_t)args.g.slot * 2 + (g_epoch & 1u)) * args.g.vec_bytes + ((size_t)args.g.rank * args.g.slice_elems + (size_t)row) * 2;
+        } else {
+            // 5 .. 16 waves: four rows per trip, then the 0 .. 3 rows that are left.  (Written with the next trip's reads in front of this trip's adds; the compiler
+            //  reuses the four registers and issues them behind the adds, so a trip still costs an LDS round trip: profiles/decode_tail/instruction_budget.md)
+            float p0 = part[0], p1 = part[S], p2 = part[2 * S], p3 = part[3 * S];
+            int left = WK - 4;
+            part += 4 * S;
+#pragma unroll 1
+            while (left >= 4) {
+                const float q0 = part[0], q1 = part[S], q2 = part[2 * S], q3 = part[3 * S];
+                v += p0;
+                v += p1;
+                v += p2;
+                v += p3;
+                p0 = q0, p1 = q1, p2 = q2, p3 = q3;
+                left -= 4;
+                part += 4 * S;
+            }
+            float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+            if (left >= 1) r0 = part[0];
+            if (left >= 2) r1 = part[S];
+            if (left >= 3) r2 = part[2 * S];
+            v += p0;
+            v += p1;
+            v += p2;
+            v += p3;
+            if (left >= 1) v += r0;
+            if (left >= 2) v += r1;
+            if (left >= 3) v += r2;
+        }
+        const half_t y = (half_t)v;
+        half_t out = y, hnew = (half_t)0.0f;
+        (void)hnew;
+        if (any_pair) {  // (wave-uniform)
+            // the (gate, up) neighbour of the pair epilogue: rows 2n, 2n + 1 are adjacent lanes
+            const half_t y_other = __builtin_bit_cast(half_t, (unsigned short)__builtin_amdgcn_update_dpp(0, (int)__builtin_bit_cast(unsigned short, y), 0xB1, 0xF, 0xF, false));
+            if (t_pair) out = silu_mul_half(y, y_other);
+        }
+        if constexpr (RNORM) {
+            if (t_live && t_add) hnew = *c_at(0, tid) + y;  // (stored below, write-through)
+            else if (t_store) *c_at(0, tid) = out;
+        } else {
+            if (t_add) out = c_old + y;
+            // (several tiles per wave are the forms short of registers: there the lane's offset -- two shifts -- is formed again here and not carried through the contraction)
+            int t_late = tid;
+            if constexpr (ROWS > 1) asm volatile("" : "+v"(t_late));
 #pragma unroll
-                    for (int p = 0; p < kCommMaxRanks; ++p)
-                        if (p < args.g.world)
-                            __hip_atomic_store(reinterpret_cast<unsigned short *>(args.g.peer[p] + off), __builtin_bit_cast(unsigned short, outv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+            for (int r = 0; r < ROWS; ++r)
+                if (t_store && (ROWS == 1 || t_r == r)) *c_at(r, t_late) = out;
+        }
+        if constexpr (MIX) {
+            if (gathers && t_live) {
+                // (a) the tile's 16 values into EVERY rank's window -- buffer (slot, parity of the epoch), this rank's slice -- past every cache (comm.hip's protocol)
+                const half_t outv = (t_epi & TCE_W4_ADD_TO_C) ? (half_t)(c_old + y) : y;
+                const size_t off = ((size_t)args.g.slot * 2 + (g_epoch & 1u)) * args.g.vec_bytes + ((size_t)args.g.rank * args.g.slice_elems + (size_t)t_row) * 2;
+#pragma unroll
+                for (int p = 0; p < kCommMaxRanks; ++p)
+                    if (p < args.g.world)
+                        __hip_atomic_store(reinterpret_cast<unsigned short *>(args.g.peer[p] + off), __builtin_bit_cast(unsigned short, outv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
         if constexpr (RNORM) {
             // the tile's 16 updated values -> memory, past every cache (the last workgroup reads them from another XCD); their two piece sums likewise
+            const int row = t_row;
             if (row < seg.N) __hip_atomic_store(reinterpret_cast<unsigned short *>(seg.C) + row, __builtin_bit_cast(unsigned short, hnew), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             const float hf = row < seg.N ? (float)hnew : 0.f;
             float s0 = 0.f, s1 = 0.f;  // fmaf chains over the two pieces' 8 values, in order (rmsnorm_piece_sum), formed by every lane from broadcasts
