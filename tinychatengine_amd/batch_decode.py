@@ -15,6 +15,9 @@ A layer is SEVEN launches for the B rows:
     5  post_attention_layernorm                  tce_rmsnorm_half
     6  gate/up + SiLU*mul                        tce_w4a16_forward, M = B, TCE_W4_SILU_MUL_PAIRS (gate, up and tce_silu_mul_half where the pairs are refused)
     7  down_proj + residual add                  tce_w4a16_forward, M = B, TCE_W4_ADD_TO_C
+
+lora=<a LoraLayer> (lora.py): q/k/v, o_proj and down_proj are ADAPTED linears -- tce_lora_shrink_f16 once the linear's input exists, tce_lora_expand_add_f16 directly
+behind the base launch, each row on the adapter its row_adapter word names -- 7 + 6 launches.  lora=None: every code path and launch is the one above.
 """
 from __future__ import annotations
 
@@ -82,12 +85,19 @@ class BatchDecodeAttention:
 class BatchedDecoder:
     """`batch` sequences through one decoder block: the linears and gammas of `block` (nothing in the block changes), caches of its own."""
 
-    LAUNCHES = 7  # per layer and step, with the SiLU*mul pairs accepted (9 otherwise)
+    LAUNCHES = 7  # per layer and step, with the SiLU*mul pairs accepted (9 otherwise); with lora=: 7 + 6 (9 + 6 where the pairs are refused: the figure does not follow _gate_up's fallback)
 
-    def __init__(self, block: DecoderBlock, batch: int, attention=None, rows: int | None = None):
+    def __init__(self, block: DecoderBlock, batch: int, attention=None, rows: int | None = None, lora=None):
         """attention: the step's attention object (default: a BatchDecodeAttention with contiguous caches of its own); rows: the rows one step carries, where that is
-        not `batch` (the speculative step's batch * rows_per_seq)."""
+        not `batch` (the speculative step's batch * rows_per_seq); lora: this layer's view of a LoraPool (LoraPool.layer(i)), None for the base model alone."""
         self.block, self.batch, self.rows = block, batch, batch if rows is None else rows
+        self.lora, self._lora_t = lora, None
+        if lora is not None:
+            if self.rows != batch:
+                raise ValueError("lora: one row per slot only (speculative rows are not adapted)")
+            lora.pool.bind(batch)  # the shared row_adapter words, one per slot
+            self._lora_t = lora.workspace(batch)
+            self.LAUNCHES = BatchedDecoder.LAUNCHES + 6
         dev = block.gamma1.device
         self.attention = attention if attention is not None else BatchDecodeAttention(batch, block.heads, block.attention.max_keys, dev, block.attention.cos,
                                                                                       block.attention.sin, kv_heads=block.kv_heads)
@@ -103,13 +113,26 @@ class BatchedDecoder:
         blk = self.block
         assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.rows, blk.hidden)
         st = _stream()
+        lora, t = self.lora, self._lora_t
         rmsnorm_half(hidden, blk.gamma1, blk.eps, out=self.xn)
+        if lora is not None:
+            lora.shrink("qkv", self.xn, t["qkv"])
         capi.check(capi.w4a16_forward(blk.qkv.desc(self.xn, self.qkv_out), st))
+        if lora is not None:
+            lora.expand_add("qkv", t["qkv"], self.qkv_out)
         self.attention.step(self.qkv_out, pos_device, pos_bound, out=self.attn_out)
+        if lora is not None:
+            lora.shrink("o", self.attn_out, t["o"])
         capi.check(capi.w4a16_forward(blk.o.desc(self.attn_out, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+        if lora is not None:
+            lora.expand_add("o", t["o"], hidden)
         rmsnorm_half(hidden, blk.gamma2, blk.eps, out=self.xn)
         self._gate_up(self.xn, st)
+        if lora is not None:
+            lora.shrink("down", self.act, t["down"])
         capi.check(capi.w4a16_forward(blk.down.desc(self.act, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
+        if lora is not None:
+            lora.expand_add("down", t["down"], hidden)
 
     def _gate_up(self, xn: torch.Tensor, st: int) -> None:
         blk = self.block
@@ -127,20 +150,39 @@ class BatchedDecoder:
     def prefill(self, slot: int, rows: torch.Tensor, pos: int) -> None:
         """Admit a sequence into `slot`: rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated in place -- DecoderBlock.prefill's launches on the
         slot's caches."""
-        self._prefill_rows(rows, lambda qkv, attn: self.attention.slot(slot).prefill(qkv, pos, out=attn, causal=True))
+        self._prefill_rows(rows, lambda qkv, attn: self.attention.slot(slot).prefill(qkv, pos, out=attn, causal=True), self._row_words([(slot, rows.shape[0])]))
 
-    def _prefill_rows(self, rows: torch.Tensor, attend) -> None:
-        """prefill's launches over `rows`; attend(qkv, attn) is the attention in the middle (the paged decoder's serves several sequences' rows at once)."""
+    def _row_words(self, segments) -> torch.Tensor | None:
+        """The prefill's per-row adapter words for segments [(slot, m)]: every row of an admission carries its SLOT's word, gathered on the device from the shared
+        row_adapter tensor (written before the prefill; device-side copies only: nothing is read back and no host tensor is sent over).  None without a pool."""
+        if self.lora is None:
+            return None
+        ra = self.lora.row_adapter
+        return torch.cat([ra[slot:slot + 1].expand(m) for slot, m in segments])
+
+    def _prefill_rows(self, rows: torch.Tensor, attend, row_words: torch.Tensor | None = None) -> None:
+        """prefill's launches over `rows`; attend(qkv, attn) is the attention in the middle (the paged decoder's serves several sequences' rows at once).  row_words
+        (with a pool): int32 [m], the adapter of every row -- the three adapted linears get their shrink and expand as in step()."""
         blk = self.block
         m = rows.shape[0]
+        lora = self.lora if row_words is not None else None
+        t = lora.workspace(m) if lora is not None else None
         assert rows.dtype == torch.float16 and rows.is_contiguous() and rows.shape[1] == blk.hidden
         st = _stream()
         e = lambda n: torch.empty((m, n), dtype=torch.float16, device=rows.device)
         xn, qkv, attn, g, u = e(blk.hidden), e((blk.heads + 2 * blk.kv_heads) * 128), e(blk.hidden), e(blk.ffn), e(blk.ffn)
         rmsnorm_half(rows, blk.gamma1, blk.eps, out=xn)
+        if lora is not None:
+            lora.shrink("qkv", xn, t["qkv"], row_words)
         capi.check(capi.w4a16_forward(blk.qkv.desc(xn, qkv), st))
+        if lora is not None:
+            lora.expand_add("qkv", t["qkv"], qkv, row_words)
         attend(qkv, attn)
+        if lora is not None:
+            lora.shrink("o", attn, t["o"], row_words)
         capi.check(capi.w4a16_forward(blk.o.desc(attn, rows, flags=capi.TCE_W4_ADD_TO_C), st))
+        if lora is not None:
+            lora.expand_add("o", t["o"], rows, row_words)
         rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
         if m > 128 and blk.gate_up.packed is not None:
             capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, g, flags=capi.TCE_W4_SILU_MUL_PAIRS), st))
@@ -148,4 +190,8 @@ class BatchedDecoder:
             capi.check(capi.w4a16_forward(blk.gate.desc(xn, g), st))
             capi.check(capi.w4a16_forward(blk.up.desc(xn, u), st))
             capi.check(capi.lib().tce_silu_mul_half(g.data_ptr(), u.data_ptr(), g.numel(), st))
+        if lora is not None:
+            lora.shrink("down", g, t["down"], row_words)
         capi.check(capi.w4a16_forward(blk.down.desc(g, rows, flags=capi.TCE_W4_ADD_TO_C), st))
+        if lora is not None:
+            lora.expand_add("down", t["down"], rows, row_words)

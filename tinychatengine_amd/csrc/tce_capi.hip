@@ -31,6 +31,10 @@ size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
 int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err);
 int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
                        int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err);
+int launch_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, hipStream_t stream,
+                           hipError_t *hip_err);
+int launch_lora_expand_add_f16(const float *t, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int R, int n_adapters,
+                               hipStream_t stream, hipError_t *hip_err);
 }
 
 namespace {
@@ -1618,6 +1622,40 @@ int tce_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *
     hipError_t he = hipSuccess;
     const int rc = tce::launch_embed_rows_f16(table, vocab, hidden, token, out, batch, pos_device, pos_bound, workspace, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "embedding launch") : rc;
+}
+
+// the shape rules both LoRA entry points share (csrc/lora.hip): after every argument refusal
+static int check_lora_shape(const char *who, int rows, int R, int n_adapters) {
+    if (R % 8 != 0 || R > TCE_LORA_MAX_RANK) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: R %d (a multiple of 8, 8 .. %d)", who, R, TCE_LORA_MAX_RANK);
+    if (n_adapters > TCE_LORA_MAX_ADAPTERS) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d adapters (at most %d)", who, n_adapters, TCE_LORA_MAX_ADAPTERS);
+    if (rows > 65535 * 4) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d rows (at most %d per call)", who, rows, 65535 * 4);
+    return TCE_OK;
+}
+
+int tce_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, void *stream) {
+    if (!x || !A || !row_adapter || !t) return fail(TCE_ERR_BAD_ARG, "tce_lora_shrink_f16: null pointer");
+    if (rows < 1 || K < 1 || R < 1 || n_adapters < 1 || ldx < K) return fail(TCE_ERR_BAD_ARG, "tce_lora_shrink_f16: need rows, K, R, n_adapters >= 1 and ldx >= K");
+    if (K % 8 != 0 || ldx % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_shrink_f16: K %d, ldx %d (multiples of 8)", K, ldx);
+    if (const int rc = check_lora_shape("tce_lora_shrink_f16", rows, R, n_adapters)) return rc;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(A)) % 16 != 0 || (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_shrink_f16: 16-byte aligned x / A, 4-byte aligned row_adapter / t");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_shrink_f16(x, ldx, A, row_adapter, t, rows, K, R, n_adapters, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA shrink launch") : rc;
+}
+
+int tce_lora_expand_add_f16(const float *t, const void *B, const float *scale, const int32_t *row_adapter, void *Cm, int ldc, int rows, int N, int R, int n_adapters,
+                            void *stream) {
+    if (!t || !B || !scale || !row_adapter || !Cm) return fail(TCE_ERR_BAD_ARG, "tce_lora_expand_add_f16: null pointer");
+    if (rows < 1 || N < 1 || R < 1 || n_adapters < 1 || ldc < N) return fail(TCE_ERR_BAD_ARG, "tce_lora_expand_add_f16: need rows, N, R, n_adapters >= 1 and ldc >= N");
+    if (N % 8 != 0 || ldc % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_expand_add_f16: N %d, ldc %d (multiples of 8)", N, ldc);
+    if (const int rc = check_lora_shape("tce_lora_expand_add_f16", rows, R, n_adapters)) return rc;
+    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(Cm)) % 16 != 0 ||
+        (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(scale)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_expand_add_f16: 16-byte aligned B / C, 4-byte aligned row_adapter / t / scale");
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_expand_add_f16(t, B, scale, row_adapter, Cm, ldc, rows, N, R, n_adapters, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA expand launch") : rc;
 }
 
 int tce_attention_decode_step_deferred_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace, int heads,

@@ -473,6 +473,8 @@ class _GeneratorBase:
     """What BatchedGenerator and speculative.SpeculativeGenerator share: the construction, the graph, admission, the replay loop and the read-outs.  A subclass gives
     token_step() (what one replay runs) and launches_per_token, and calls _capture() once its own buffers exist."""
 
+    lora = None  # a LoraPool (BatchedGenerator(..., lora=pool)): admit(..., adapter=) writes the slot's row_adapter word, release() writes -1
+
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None, top_k_bound: int, stop_ids, rows_per_seq: int | None = None,
                  **sampler_kw):
         """rows_per_seq None: the token step carries one row per slot, and admission runs its head on the step's xn / logits.  An integer: hidden / xn / logits are
@@ -521,7 +523,7 @@ class _GeneratorBase:
 
     # ---- admission ----
     def admit(self, slot, prompt_ids=None, params: SamplingParams | None = None, seed: int = 0, max_new: int | None = None, chunk_rows: int | None = None,
-              automaton: int | None = None, logit_bias=None, constraints: dict | None = None) -> list[int]:
+              automaton: int | None = None, logit_bias=None, constraints: dict | None = None, adapter: int | None = None, adapters: dict | None = None) -> list[int]:
         """admit(slot, prompt_ids, params, seed, max_new), or admit([(slot, prompt_ids, params, seed, max_new), ...]) for several sequences through ONE prefill_many.
         The prompt is embedded, prefilled through every layer, the final norm and lm_head run on its last row and the first token is sampled; the slot's position
         becomes the prompt length.  Synchronises.  Returns the slots that retired on their first token.
@@ -531,8 +533,19 @@ class _GeneratorBase:
         longer than the pool can be admitted; without windows only the activation rows are bounded.  PagePoolExhausted in a later chunk: the slots of this call are
         released and the generator is as it was before the call.  A chunked prefill is not bit-identical to the one-shot one (the prefill's tiling differs).
         constraints=True generators: automaton= (an index of sampler.table.register) and logit_bias= ({id: value} or [(id, value)]) for the single form, constraints=
-        {slot: (automaton index or None, bias or None)} for the list form; the slot starts in the automaton's start state and the FIRST token is already constrained."""
+        {slot: (automaton index or None, bias or None)} for the list form; the slot starts in the automaton's start state and the FIRST token is already constrained.
+        lora=pool generators: adapter= (an index of the pool, None: the base model) for the single form, adapters={slot: index} for the list form (a slot it does not
+        name runs the base model).  The slot's row_adapter word is written BEFORE the prefill, so the prompt's rows and the first token already run on the adapter; the
+        captured graph reads the word, so no admission captures again."""
         import torch
+        if prompt_ids is not None and adapters is not None or prompt_ids is None and adapter is not None:
+            raise ValueError("admit: adapter= goes with the single form, adapters={slot: index} with the list form")
+        lora_of = {int(slot): adapter} if prompt_ids is not None else {int(k): v for k, v in (adapters or {}).items()}
+        if self.lora is None and any(a is not None for a in lora_of.values()):
+            raise ValueError("admit: adapter= / adapters=: the generator was built without lora=pool")
+        for a in lora_of.values():
+            if a is not None and (int(a) != a or not 0 <= int(a) < self.lora.max_adapters):
+                raise ValueError(f"admit: adapter {a} of {self.lora.max_adapters} (None: the base model)")
         if prompt_ids is not None and constraints is not None or prompt_ids is None and (automaton is not None or logit_bias):
             raise ValueError("admit: automaton= / logit_bias= go with the single form, constraints={slot: (automaton, bias)} with the list form")
         cons = {int(slot): (automaton, logit_bias)} if prompt_ids is not None else {int(k): tuple(v) for k, v in (constraints or {}).items()}
@@ -540,6 +553,8 @@ class _GeneratorBase:
         adm = [(int(s), [int(t) for t in ids], p or SamplingParams(), int(sd), int(self.sampler.log_stride if mn is None else mn)) for s, ids, p, sd, mn in adm]
         if len({s for s, *_ in adm}) != len(adm):
             raise ValueError("admit: a slot is named twice")
+        if any(s not in {sl for sl, *_ in adm} for s in lora_of):
+            raise ValueError("admit: adapters names a slot that is not admitted")
         for s, ids, p, sd, mn in adm:
             if not 0 <= s < self.batch:
                 raise IndexError(f"slot {s} of {self.batch}")
@@ -562,6 +577,10 @@ class _GeneratorBase:
                 raise ValueError("admit: a slot still holds pages (release it first)")
             if chunk_rows is None:
                 self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])
+        if self.lora is not None:
+            for s, *_ in adm:  # every admitted slot's word, -1 included: before the prefill
+                a = lora_of.get(s)
+                self.lora.row_adapter[s] = -1 if a is None else int(a)
 
         def embedded(ids):
             tok = torch.tensor(ids, dtype=torch.int32).to(self.device)
@@ -597,7 +616,8 @@ class _GeneratorBase:
 
     def _prefill_chunks(self, adm, chunk_rows: int, embedded) -> list:
         """admit's chunked prefill (admission_chunks is the schedule).  Returns every prompt's last chunk of rows, after all layers.  Nothing of the generator but the
-        allocator changes here, so on any failure releasing this call's slots restores the state before the call."""
+        allocator changes here (and, with a pool, the admitted slots' adapter words, which admit wrote just before), so on any failure releasing this call's slots
+        and writing their words back to -1 restores the state before the call."""
         windows = [getattr(d, "window", None) for d in self.decoders]
         window = None if any(w is None for w in windows) else max(windows)
         last = [None] * len(adm)
@@ -614,6 +634,8 @@ class _GeneratorBase:
         except Exception:
             for s, *_ in adm:
                 self.allocator.release(s)
+                if self.lora is not None:  # (admit wrote the slot's word in front of the prefill: a free slot's word is -1)
+                    self.lora.row_adapter[s] = -1
             raise
         return last
 
@@ -672,6 +694,8 @@ class _GeneratorBase:
     def release(self, slot: int) -> list[int]:
         """The slot is free again: its position word is -1 and (paged) its pages go back to the pool; returns them."""
         self.pos[slot] = -1
+        if self.lora is not None:
+            self.lora.row_adapter[slot] = -1
         self.book.clear(slot)
         return self.allocator.release(slot) if self.allocator is not None else []
 
@@ -690,8 +714,17 @@ class BatchedGenerator(_GeneratorBase):
     inactive) and run() replays it: one replay is one token for every live slot."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
-                 debug: bool = False, logprobs: bool = False, constraints: bool = False):
+                 debug: bool = False, logprobs: bool = False, constraints: bool = False, lora=None):
+        """lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  lm_head
+        and the embedding are not adapted."""
         super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints)
+        pools = [getattr(getattr(d, "lora", None), "pool", None) for d in self.decoders]
+        if lora is None and any(p is not None for p in pools):
+            raise ValueError("the decoders carry LoRA views: pass their pool as lora=")
+        if lora is not None:
+            if any(p is not lora for p in pools) or [d.lora.index for d in self.decoders] != list(range(len(self.decoders))) or lora.layers != len(self.decoders):
+                raise ValueError("lora=pool: decoder i must be built with lora=pool.layer(i), one layer of the pool per decoder")
+            self.lora = lora
         self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
         self.score_logits: list = []
         self.launches_per_token = 1 + self.decoders[0].LAUNCHES * len(self.decoders) + 1 + 1 + 2
@@ -710,16 +743,19 @@ class BatchedGenerator(_GeneratorBase):
         """Slots that are neither live nor still holding pages."""
         return [s for s in range(self.batch) if self.book.pos[s] < 0 and not (self.allocator is not None and self.allocator.pages[s])]
 
-    def score(self, prompts, chunk_rows: int = 256) -> list[np.ndarray]:
+    def score(self, prompts, chunk_rows: int = 256, adapter: int | None = None) -> list[np.ndarray]:
         """For each prompt of n tokens the n - 1 values logprob(token[i + 1] | token[.. i]) (fp32; empty for a 1-token prompt), logprob_reference's definition on the
         logits this call produces.  The prompts take free slots and pages, all or nothing (PagePoolExhausted, or ValueError when there are fewer free slots than
         prompts: nothing changed), are embedded and run through every layer by ONE prefill_many; then, in chunks of at most chunk_rows rows: final norm -> lm_head at
         M = chunk -> tce_logprobs_f16 with the next tokens as targets (-1 for a prompt's last row), so at most chunk_rows * ld * 2 bytes of logits exist and none leave
-        the device.  Slots and pages are released afterwards; ONE synchronise.  Live sequences are not disturbed.  Paged decoders only (fp16 or fp8_e4m3 pages)."""
+        the device.  Slots and pages are released afterwards; ONE synchronise.  Live sequences are not disturbed.  Paged decoders only (fp16 or fp8_e4m3 pages).
+        adapter (lora=pool generators): ALL the prompts are scored under that adapter of the pool (None: the base model); the slots' words are -1 again afterwards."""
         import torch
         from .linear import _stream, rmsnorm_half
         if self.allocator is None:
             raise ValueError("score: paged decoders only")
+        if adapter is not None and (self.lora is None or int(adapter) != adapter or not 0 <= int(adapter) < self.lora.max_adapters):
+            raise ValueError("score: adapter= needs a generator built with lora=pool and an index of that pool")
         plan = score_plan(prompts, self.free_slots(), self.max_keys, self.vocab, chunk_rows)
         prompts, work, slots = plan["prompts"], plan["work"], plan["slots"]
         if not work:
@@ -735,6 +771,9 @@ class BatchedGenerator(_GeneratorBase):
             for i in work:
                 rows.append(hidden[r0:r0 + len(prompts[i])])
                 r0 += len(prompts[i])
+            if self.lora is not None:  # every slot it uses, -1 included, as admit does: nothing is assumed of a free slot's word
+                for s in slots:
+                    self.lora.row_adapter[s] = -1 if adapter is None else int(adapter)
             for d in self.decoders:
                 d.prefill_many([(s, r, 0) for s, r in zip(slots, rows)])
             chunk = plan["chunk"]
@@ -753,6 +792,8 @@ class BatchedGenerator(_GeneratorBase):
         finally:
             for s in slots:
                 self.allocator.release(s)
+                if self.lora is not None:
+                    self.lora.row_adapter[s] = -1
         return plan["split"](values.cpu().numpy())  # (synchronises)
 
 

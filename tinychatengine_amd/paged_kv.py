@@ -439,16 +439,17 @@ class PagedBatchedDecoder(BatchedDecoder):
     prefill launches with the paged prefill in the middle.  One PageAllocator serves the decoders of all layers."""
 
     def __init__(self, block: DecoderBlock, allocator: PageAllocator, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, attention=None,
-                 rows: int | None = None, window: int | None = None):
+                 rows: int | None = None, window: int | None = None, lora=None):
         """attention, rows: BatchedDecoder's (a subclass with an attention object of its own over the same allocator; the default is built here).  window: this layer's
-        sliding window (PagedBatchDecodeAttention), None for full attention."""
+        sliding window (PagedBatchDecodeAttention), None for full attention.  lora: BatchedDecoder's (this layer's view of a LoraPool: q/k/v, o_proj and down_proj
+        become adapted linears in step, prefill and prefill_many)."""
         self.allocator = allocator
         if attention is None:
             attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,
                                                   k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window)
         elif window is not None and getattr(attention, "window", None) != window:
             raise ValueError("window: the attention object given was built with another one")
-        super().__init__(block, allocator.batch, attention=attention, rows=rows)
+        super().__init__(block, allocator.batch, attention=attention, rows=rows, lora=lora)
 
     @property
     def window(self) -> int | None:
@@ -468,7 +469,7 @@ class PagedBatchedDecoder(BatchedDecoder):
         for slot, pos, m in segments:
             assert self.allocator.writable(slot, pos, m), f"slot {slot}: a chunk at key {pos} starts inside a shared page"
         packed = admissions[0][1] if len(admissions) == 1 else torch.cat([rows for _, rows, _ in admissions])
-        self._prefill_rows(packed, lambda qkv, attn: self.attention.prefill(segments, qkv, out=attn, causal=True))
+        self._prefill_rows(packed, lambda qkv, attn: self.attention.prefill(segments, qkv, out=attn, causal=True), self._row_words([(slot, m) for slot, _, m in segments]))
         if len(admissions) > 1:
             row0 = 0
             for _, rows, _ in admissions:

@@ -263,7 +263,9 @@ class SpeculativeGenerator(_GeneratorBase):
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False,
-                 constraints: bool = False):
+                 constraints: bool = False, lora=None):
+        if lora is not None:
+            raise ValueError("SpeculativeGenerator: LoRA adapters on speculative rows are not built (lora=None only)")
         decoders = list(decoders)
         for d in decoders:  # a windowed layer must run the windowed ROWS step: its attention object carries the window (SpeculativeDecoder(..., window=W) builds it so)
             w = getattr(d, "window", None)
