@@ -53,9 +53,23 @@ def classify(i):
     return "addressing / other vector"
 
 
+def section3(ins):
+    """the contraction: from the first read of a B operand (ds_read_b128) to the last MFMA, in the listing's order"""
+    first = next(i for i, t in enumerate(ins) if t.startswith("ds_read_b128"))
+    last = max(i for i, t in enumerate(ins) if t.startswith("v_mfma"))
+    return ins[first:last + 1]
+
+
 if __name__ == "__main__":
-    ins = listing(sys.argv[1])
+    argv = [a for a in sys.argv[1:] if a != "--section3"]
+    ins = listing(argv[0])
+    label = argv[1] if len(argv) > 1 else os.path.basename(argv[0])
+    if "--section3" in sys.argv:  # profiles/decode_occupancy/: the contraction alone, by mnemonic
+        sec = section3(ins)
+        c = collections.Counter(i.split()[0] for i in sec)
+        vec = sum(v for k, v in c.items() if k.startswith(("v_", "ds_")))
+        print(f"| {label} | {len(sec)} | {vec} | " + ", ".join(f"{k} {v}" for k, v in sorted(c.items(), key=lambda kv: (-kv[1], kv[0]))) + " |")
+        sys.exit(0)
     c = collections.Counter(classify(i) for i in ins)
-    label = sys.argv[2] if len(sys.argv) > 2 else os.path.basename(sys.argv[1])
     order = ["unpack", "conversion", "epilogue", "addressing / other vector", "loads", "MFMA", "scalar / control"]
     print(f"| {label} | " + " | ".join(str(c[k]) for k in order) + f" | {sum(v for k, v in c.items() if k != 'scalar / control')} | {len(ins)} |")

@@ -11,7 +11,7 @@ g = torch.Generator(device=dev).manual_seed(5)
 K = 4096
 x = torch.randn(1, K, device=dev).to(torch.float16)
 gamma = (1 + 0.1 * torch.randn(K, device=dev)).float()
-for N in (8192, 12288, 14336, 16384, 20480, 24576, 28672, 32000, 65536, 128256):
+for N in [int(a) for a in sys.argv[1:]] or (8192, 12288, 14336, 16384, 20480, 24576, 28672, 32000, 65536, 128256):  # (rows on the command line: those instead)
     nsets = max(2, min(24, int(4e8 // (N * K // 2))))
     lins = [Linear_half_int4.from_float(torch.empty(N, K, device=dev).normal_(0, 0.02, generator=g), 128).prepack() for _ in range(nsets)]
     outs = torch.empty(1, N, dtype=torch.float16, device=dev)

@@ -13,7 +13,8 @@
 //              base-256 digit planes ((I + 0x808080) ^ 0x808080: 2 instructions), byte-transposed into the B operand image in the wave's OWN LDS region: no
 //              workgroup barrier in front of the contraction.  The planes are COLUMNS of B: one MFMA contracts all four at once, products and sums exact.
 //   * COLUMNS  M = 1 uses 4 of the 16 output columns per 128-k unit, so four units (four quantization groups) share one accumulator: unit c of a pass presents
-//              its planes in columns 4c..4c+3 and zeros elsewhere (the B registers of the other lanes are never written).  One v_cvt_f32_i32 + one v_fma_mix
+//              its planes in columns 4c..4c+3 and zeros elsewhere (the B registers of the other lanes are never written -- or, in the ring of two sets that
+//              keeps the plain forms at seven or eight waves per SIMD, read from a block of zeros: section 3).  One v_cvt_f32_i32 + one v_fma_mix
 //              (fp16 scale) per output register then serve FOUR groups; M = 2 / 4 rows of A take the columns instead (2 / 1 units per pass).
 //   * STREAM   a wave owns ROWS tiles x UW units: every weight byte it will use is requested at once (after the few x / scale bytes: loads retire in order,
 //              a wait for x must not be a wait for the weights), 1 KiB of consecutive memory per load instruction, non-temporal.
@@ -165,6 +166,13 @@ __device__ __forceinline__ void keep_scalar(T &v) {
 }
 typedef __attribute__((address_space(1))) half_t c16_t;  // an output element, as device memory
 
+// The forms whose contraction stages the B operand in a ring of two register sets (section 3 of the body): four units per pass -- one decode row, groups of 128 -- of
+// the ordinary launch.  They end the workgroup's LDS with two 16-byte blocks of zeros 256 bytes apart (kI8ZeroBlock; ONE rule for the body and for launch_i8).  The other forms hold two
+// sets or one per pass as it is; the mixed launch and the deferred-attention prologue keep the whole pass (their waves per SIMD are set by the workgroup's width and by
+// the prologue's registers, not by the contraction).
+constexpr bool i8_ring_staging(int MB, int GPU, bool MIX, int COMB) { return MB * GPU == 1 && !MIX && COMB == 0; }
+constexpr int kI8ZeroBlock = 256 + 16;
+
 // The body: everything behind the choice of the workgroup's linear.  `seg`, `A_` ... are VALUES (registers, or scalar loads still in flight: waited for at the first use);
 // `args` is the launch's tail (I8Tail) or the mixed launch's struct, for the prologue / epilogue fields.
 template <int MB, int GPU, int ROWS, int UW, bool Z8, bool NORM, bool RNORM, int COMB, bool MIX, typename ARGS, bool STAMPS = false>
@@ -315,6 +323,10 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
     }
     // ---- 2. the wave's activations -> digit planes, image [unit][lo/hi][m][plane][kq][word s] in its own LDS region ----
     unsigned *planes = reinterpret_cast<unsigned *>(smem) + wk * (UW * MB * 128);
+    // the workgroup's two blocks of zeros (section 3's ring; bytes 0 .. 15 and 256 .. 271), behind everything else in LDS.  Every wave writes them -- the same zeros -- in front of its own wave barrier:
+    // what a wave reads there follows its own write in program order, whatever the other waves are doing
+    unsigned char *zero_blk = smem + (size_t)WK * UW * MB * 512 + (size_t)WK * ROWS * MB * 16 * sizeof(float) + (NORM ? (size_t)(K_ >> 3) * sizeof(float) + 1024 : 0);
+    if constexpr (i8_ring_staging(MB, GPU, MIX, COMB)) reinterpret_cast<unsigned *>(zero_blk)[(lane & 3) + (lane & 4) * 16] = 0u;
     if constexpr (NORM) {
         // slot[p] = the sum of squares of the row's p-th 16-byte piece (fmaf chain over its 8 values); K <= 16384: at most two pieces per slot of the
         // 1024-slot order, and a two-term sum does not depend on which wave wrote which
@@ -493,9 +505,29 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
     }
 
     // ---- 3. contraction.  B set uu: the operand of unit uu of the pass in the lanes of ITS columns, zeros in the others (never written) ----
-    int4_t B[UPP][2];
+    // RING (four units per pass: one decode row, groups of 128): the sets are a ring of TWO -- unit t's operand is read into set t & 1 behind the MFMAs of unit t - 2,
+    // two units ahead of its own -- where a whole pass of four sets (32 registers, refilled a pass ahead) was what kept the kernel at five waves per SIMD
+    // (profiles/decode_occupancy/).  A reused set must hold zeros again in the lanes of the other units' columns: those lanes READ zeros, through the same two
+    // instructions, from the workgroup's zero blocks -- two of 16 bytes, as far apart (256 bytes) as a unit's low and high image, so that ONE select on the address
+    // serves both reads of a unit: an add and a select per unit, 16 vector instructions per wave.  (Re-zeroing a set instead: four 64-bit moves and a second exec mask
+    // per reuse, 24 moves per wave; a select per read with the offset in the instruction: a move of the scalar operand on top of every select, 31.)
+    // Same LDS image, same addresses, same columns, the same MFMAs in the same order per accumulator: the integer sums are what they were.
+    constexpr bool RING = i8_ring_staging(MB, GPU, MIX, COMB);
+    constexpr int NB = RING ? 2 : UPP;
+    int4_t B[NB][2];
+    if constexpr (!RING) {
 #pragma unroll
-    for (int uu = 0; uu < UPP; ++uu) B[uu][0] = B[uu][1] = int4_t{0, 0, 0, 0};
+        for (int uu = 0; uu < UPP; ++uu) B[uu][0] = B[uu][1] = int4_t{0, 0, 0, 0};
+    }
+    typedef __attribute__((address_space(3))) const uint4_t lds_u4_t;
+    // (LDS byte addresses; RING only: MB == 1 and GPU == 1, the lane's part of a unit's image is (plane, k-quarter))
+    const unsigned lane_a = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) unsigned *)planes + (unsigned)((p_l * 4 + kq) * 16);
+    const unsigned zero_a = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) unsigned char *)zero_blk;
+    auto read_unit = [&](int t) {  // unit t of the wave (t = ps * UPP + uu) -> set t & 1
+        const unsigned a = uu_l == t % UPP ? lane_a + (unsigned)t * 512u : zero_a;  // the unit's low image, or the first zero block
+#pragma unroll
+        for (int h = 0; h < 2; ++h) B[t & 1][h] = __builtin_bit_cast(int4_t, *reinterpret_cast<lds_u4_t *>(a + (unsigned)h * 256u));
+    };
     auto read_b = [&](int ps) {
 #pragma unroll
         for (int uu = 0; uu < UPP; ++uu)
@@ -517,7 +549,14 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
                     }
                 }
     };
-    read_b(0);
+    (void)read_unit;
+    (void)read_b;
+    if constexpr (RING) {
+        read_unit(0);
+        read_unit(1);
+    } else {
+        read_b(0);
+    }
 
     float acc[ROWS][4];
 #pragma unroll
@@ -538,9 +577,10 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
 #pragma unroll
         for (int uu = 0; uu < UPP; ++uu) {
             const int t = ps * UPP + uu;
+            const int bs = RING ? (t & 1) : uu;  // the unit's B set
             if constexpr (!Z8) {
-                dz = __builtin_amdgcn_mfma_i32_16x16x64_i8(sixteens, B[uu][0], dz, 0, 0, 0);
-                dz = __builtin_amdgcn_mfma_i32_16x16x64_i8(sixteens, B[uu][1], dz, 0, 0, 0);
+                dz = __builtin_amdgcn_mfma_i32_16x16x64_i8(sixteens, B[bs][0], dz, 0, 0, 0);
+                dz = __builtin_amdgcn_mfma_i32_16x16x64_i8(sixteens, B[bs][1], dz, 0, 0, 0);
             }
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
@@ -553,9 +593,15 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
                     ahi[q] = (int)((wq & 0xF0F0F0F0u) ^ 0x80808080u);
                     alo[q] = (int)(((wq << 4) & 0xF0F0F0F0u) ^ 0x80808080u);
                 }
-                dd[r][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(alo, B[uu][0], dd[r][0], 0, 0, 0);
-                if constexpr (Z8) dd[r][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, B[uu][1], dd[r][1], 0, 0, 0);
-                else dd[r][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, B[uu][1], dd[r][0], 0, 0, 0);  // (one accumulator chain: integer sums, the same value; four registers fewer beside dz and the sixteens)
+                dd[r][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(alo, B[bs][0], dd[r][0], 0, 0, 0);
+                if constexpr (Z8) dd[r][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, B[bs][1], dd[r][1], 0, 0, 0);
+                else dd[r][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, B[bs][1], dd[r][0], 0, 0, 0);  // (one accumulator chain: integer sums, the same value; four registers fewer beside dz and the sixteens)
+            }
+            if constexpr (RING) {
+                // the set is free once this unit's MFMAs have been issued: the read of unit t + 2 stays BEHIND them (left alone the scheduler hoists every read to the
+                // top of the pass -- one set per unit again) and in front of the next unit's
+                __builtin_amdgcn_sched_barrier(0);
+                if (t + 2 < UW) read_unit(t + 2);
             }
         }
 #pragma unroll
@@ -575,7 +621,9 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
             acc[r][2] = __builtin_fmaf((float)tot[2], (float)s2, acc[r][2]);
             acc[r][3] = __builtin_fmaf((float)tot[3], (float)s3, acc[r][3]);
         }
-        if (ps + 1 < NP) read_b(ps + 1);
+        if constexpr (!RING) {
+            if (ps + 1 < NP) read_b(ps + 1);
+        }
     }
 
     // ---- 4. planes and groups -> the wave's partial rows (fixed lane order), waves -> rows (wave order), store ----
@@ -933,7 +981,8 @@ struct I8Launch {
 
 template <int MB, int GPU, int ROWS, int UW, bool Z8, int MAXT, bool NORM = false, bool RNORM = false, int COMB = 0, bool STAMPS = false>
 hipError_t launch_i8(const I8Launch &a, int blocks, int m_blocks, int wk, hipStream_t stream) {
-    const size_t lds = (size_t)wk * UW * MB * 512 + (size_t)wk * ROWS * MB * 16 * sizeof(float) + (NORM ? (size_t)(a.K >> 3) * sizeof(float) + 1024 : 0);  // the row's piece sums (+ the ragged last wave's zero pieces)
+    const size_t lds = (size_t)wk * UW * MB * 512 + (size_t)wk * ROWS * MB * 16 * sizeof(float) + (NORM ? (size_t)(a.K >> 3) * sizeof(float) + 1024 : 0)  // the row's piece sums (+ the ragged last wave's zero pieces)
+                       + (i8_ring_staging(MB, GPU, false, COMB) ? kI8ZeroBlock : 0);                                                           // the ring's blocks of zeros, last
     auto kfn = w4a16_gemv_i8_kernel<MB, GPU, ROWS, UW, Z8, MAXT, NORM, RNORM, COMB, STAMPS>;
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1033,6 +1082,10 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
     // the arithmetic: same bits.)
     int rows = 1;
     const bool two_ok = mb == 1 && gpu == 1 && uw == 8 && wk <= 8;
+    // Those figures are of the prologue kernel at five waves per SIMD.  With the B operand staged two units deep (section 3 of the body) it holds seven, and all of the
+    // window's workgroups are resident at once -- and two tiles per wave STILL win there (profiles/decode_occupancy/norm_tiles_ab.jsonl, one tile / two tiles:
+    // 1280 tiles 10.28 / 10.48 us, 1376: 11.26 / 10.77, 1536: 11.68 / 11.35, 1792: 13.17 / 13.19): what they save is the conversion per byte, not a generation.  The
+    // window is a measured one and stays as it is; `resident` is its anchor, no longer the number of workgroups the chip holds.
     const long long resident = 256LL * (20 / wk);
     if (gamma && two_ok && total_tiles > resident && total_tiles * 5 <= resident * 6) rows = 2;
     if (g_i8_rows && two_ok) rows = g_i8_rows;
