@@ -47,7 +47,7 @@ extern "C" {
 
 #define TCE_API __attribute__((visibility("default")))
 
-#define TCE_VERSION 113 /* additive, unversioned: tce_lora_shrink_f16, tce_lora_expand_add_f16 (per-row fp16 LoRA adapters beside a W4A16 linear: the rows of one launch pick their adapter by a word on the device); tce_w4a16_prepack_group_bytes, tce_w4a16_prepack_group (one packed copy for linears that are always launched together; a member's descriptor names the copy, its first tile and the copy's rows in `prepacked`, `reserved`, `reserved2` -- fields that were zero before, and zero still means an individual copy.  BEHAVIOUR CHANGE under the unchanged number: the two reserved fields are now READ, so a caller that left them uninitialised -- non-zero, with no packed copy or not describing N rows of one -- gets TCE_ERR_BAD_ARG from every W4A16 entry point where it ran before; zero them); tce_sample_workspace_bytes, tce_sample_f16, tce_embed_rows_f16 (device-side sampling and the embedding lookup: one graph replay is one token); tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
+#define TCE_VERSION 113 /* additive, unversioned: tce_lora_shrink_f16, tce_lora_expand_add_f16 (per-row fp16 LoRA adapters beside a W4A16 linear: the rows of one launch pick their adapter by a word on the device), tce_lora_expand_silu_mul_f16 (the gate/up form: the delta in front of SiLU * mul); tce_w4a16_prepack_group_bytes, tce_w4a16_prepack_group (one packed copy for linears that are always launched together; a member's descriptor names the copy, its first tile and the copy's rows in `prepacked`, `reserved`, `reserved2` -- fields that were zero before, and zero still means an individual copy.  BEHAVIOUR CHANGE under the unchanged number: the two reserved fields are now READ, so a caller that left them uninitialised -- non-zero, with no packed copy or not describing N rows of one -- gets TCE_ERR_BAD_ARG from every W4A16 entry point where it ran before; zero them); tce_sample_workspace_bytes, tce_sample_f16, tce_embed_rows_f16 (device-side sampling and the embedding lookup: one graph replay is one token); tce_kv_pages_pool_bytes, tce_attention_decode_step_paged_f16, tce_attention_decode_describe_paged, tce_kv_pages_scatter_f16, tce_kv_pages_gather_f16, tce_kv_block_table_check (the batched step on a paged KV cache); tce_attention_decode_batch_workspace_bytes, tce_attention_decode_describe_batch, tce_attention_decode_step_batch_f16 (B sequences per attention launch); 0.1.13: tce_w8a8_describe_dispatch; 0.1.12: tce_w4a16_forward_independent (up to TCE_MAX_INDEPENDENT decode linears with their own activations and K as one launch: the sharded block); 0.1.11: tce_w4a16_gemm_scratch_faults (a k-cut exchange that gives up stores NaN and poisons its counter: loud, sticky), TCE_PLAN_TAGGED on packed copies runs the int8-contraction token kernel (tce_plan_is_chained = 4), TCE_DESC_V2_MAX_BYTES; 0.1.10: tce_attention_decode_step_deferred_f16 + tce_w4a16_forward_deferred_attention (the attention combine in o_proj's prologue); size-prefixed descriptors (tce_w4a16_desc_v2 / tce_w8a8_desc_v2 + the *_v2 entry points; the plain ones stay), TCE_ERR_RCCL, the tuning setters act on the CALLING THREAD only; 0.1.9: tce_w4a16_check_zero_point_8_async, tce_host_alloc / tce_host_free (the adapter no longer synchronises); 0.1.8: per-family tuning setters (tce_attention_set_tuning, tce_w8a8_set_tuning); 0.1.7: decode on the pre-packed copy (int8 contraction), tce_w4a16_set_gemv_i8; 0.1.6: TCE_PLAN_TUNED; 0.1.5: tce_opt_attention_decode; 0.1.4: tce_attention_prefill_f16 (0.1.3: tce_attention_decode_step_gqa_f16, TCE_PLAN_OVERLAPPED; 0.1.2: tce_w4a16_desc.scratch; 0.1.1: .prepacked, tce_w4a16_prepack*) */
 
 /* error codes (return values) */
 #define TCE_OK 0
@@ -656,12 +656,30 @@ TCE_API int tce_embed_rows_f16(const void *table, int vocab, int hidden, const i
  * Refusals, before any HIP call, arguments before shapes: TCE_ERR_BAD_ARG for a NULL pointer, rows / K / N / R / n_adapters < 1, ldx < K, ldc < N;
  * TCE_ERR_UNSUPPORTED_SHAPE for K, N, ldx or ldc not a multiple of 8, R not a multiple of 8 or above TCE_LORA_MAX_RANK, n_adapters above TCE_LORA_MAX_ADAPTERS, more than
  * 262140 rows, x / A / B / C not 16-byte aligned, t / scale / row_adapter not 4-byte aligned.
- * NOT BUILT: a segmented expand for a fused q/k/v (its B is block-structured with zeros off the blocks), an MFMA shrink for long prefills, quantised adapters. */
+ * Gate / up.  The decode path runs gate, up and SiLU * mul as ONE launch (TCE_W4_SILU_MUL_PAIRS), and a delta has to land in front of the nonlinearity.  An adapted
+ * gate/up is three launches: tce_lora_shrink_f16 on the shared input with gate's and up's A stacked (rows 0 .. R-1 gate's, R .. 2R-1 up's: t fp32 [rows][2R]); the
+ * base gate_up linear WITHOUT the pair flag (y fp16 [rows][2N], column 2n = gate n, column 2n + 1 = up n); and
+ * tce_lora_expand_silu_mul_f16   Bg, Bu fp16 [n_adapters][R][N]; y with row stride ldy, only read; C fp16 [rows][N] with row stride ldc.  For a row whose word a lies in
+ *                          [0, n_adapters):  g = fp16(fmaf(scale[a], sum_{j<R} t[i][j] * Bg[a][j][n], float(y[i][2n]))),
+ *                                            u = fp16(fmaf(scale[a], sum_{j<R} t[i][R + j] * Bu[a][j][n], float(y[i][2n+1])))
+ *                          (j ascends, one fmaf per step in fp32 from +0: tce_lora_expand_add_f16's order); any other word: g = y[i][2n], u = y[i][2n+1], and nothing of
+ *                          the pool or of t is read.  EVERY row below `rows` then gets C[i][n] = silu_mul_half(g, u), the pair epilogue's function.  The sums are
+ *                          SEGMENTED (gate's walk gate's R rows, up's walk up's: no zero block is read) and bit-identical, for finite t, to tce_lora_expand_add_f16 on y
+ *                          with the block-structured B' [2R][2N] followed by tce_silu_mul_half on the de-interleaved columns.  No atomics; a row's bits depend only on
+ *                          that row's y and t and its adapter; rows of one 4-row block that share an adapter share one read of Bg and Bu.
+ *                          Refusals as above: TCE_ERR_BAD_ARG for a NULL pointer, rows / N / R / n_adapters < 1, ldy < 2 N, ldc < N, C overlapping y;
+ *                          TCE_ERR_UNSUPPORTED_SHAPE for N, ldy or ldc not a multiple of 8, R not a multiple of 8, 2 R above TCE_LORA_MAX_RANK, n_adapters above
+ *                          TCE_LORA_MAX_ADAPTERS, more than 262140 rows, Bg / Bu / y / C not 16-byte aligned, t / scale / row_adapter not 4-byte aligned.
+ * Speculative rows need nothing here: the T rows of a slot carry the slot's word (row_adapter int32 [batch * T], written by the host).
+ * NOT BUILT: a segmented expand for a fused q/k/v (its B is block-structured with zeros off the blocks), an MFMA shrink for long prefills, quantised adapters, adapters on
+ * lm_head and the embedding. */
 #define TCE_LORA_MAX_RANK     192   /* padded rank R of a pool: 8 .. 192 in steps of 8 (a fused q/k/v at r = 64) */
 #define TCE_LORA_MAX_ADAPTERS 64    /* adapters resident in one pool */
 TCE_API int tce_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, void *stream);
 TCE_API int tce_lora_expand_add_f16(const float *t, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int R, int n_adapters,
                                     void *stream);
+TCE_API int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C,
+                                         int ldc, int rows, int N, int R, int n_adapters, void *stream);
 /* Reads [ptr, ptr + bytes) with at most `workgroups` workgroups (0 = as many as the range needs) and discards the data: the
  * range then sits in the memory-side cache (256 MiB) for the launch that needs it.  Meant for a side stream / graph branch
  * next to the launch BEFORE that one (no reference counterpart: cudaMallocManaged prefetching is the closest idea). */

@@ -18,6 +18,9 @@ A layer is SEVEN launches for the B rows:
 
 lora=<a LoraLayer> (lora.py): q/k/v, o_proj and down_proj are ADAPTED linears -- tce_lora_shrink_f16 once the linear's input exists, tce_lora_expand_add_f16 directly
 behind the base launch, each row on the adapter its row_adapter word names -- 7 + 6 launches.  lora=None: every code path and launch is the one above.
+A view of a gate_up=True pool: launch 6 becomes three -- the shrink on xn with gate's and up's A stacked, the gate_up linear WITHOUT the pair flag into [rows][2 * ffn]
+and tce_lora_expand_silu_mul_f16 (both deltas in front of the nonlinearity, SiLU * mul for every row) -- 7 + 8 launches.  A pool built with rows_per_seq=T serves the
+speculative step: rows = batch * T, a slot's word stands T times in row_adapter.
 """
 from __future__ import annotations
 
@@ -85,19 +88,22 @@ class BatchDecodeAttention:
 class BatchedDecoder:
     """`batch` sequences through one decoder block: the linears and gammas of `block` (nothing in the block changes), caches of its own."""
 
-    LAUNCHES = 7  # per layer and step, with the SiLU*mul pairs accepted (9 otherwise); with lora=: 7 + 6 (9 + 6 where the pairs are refused: the figure does not follow _gate_up's fallback)
+    LAUNCHES = 7  # per layer and step, with the SiLU*mul pairs accepted (9 otherwise); with lora=: 7 + 6 (9 + 6 where the pairs are refused: the figure does not follow _gate_up's fallback);
+    # with a gate_up=True pool: 7 + 8 (the adapted gate/up never asks for the pairs)
 
     def __init__(self, block: DecoderBlock, batch: int, attention=None, rows: int | None = None, lora=None):
         """attention: the step's attention object (default: a BatchDecodeAttention with contiguous caches of its own); rows: the rows one step carries, where that is
-        not `batch` (the speculative step's batch * rows_per_seq); lora: this layer's view of a LoraPool (LoraPool.layer(i)), None for the base model alone."""
+        not `batch` (the speculative step's batch * rows_per_seq); lora: this layer's view of a LoraPool (LoraPool.layer(i)), None for the base model alone.  The
+        pool's rows_per_seq must be the step's: None for rows == batch, T for rows == batch * T."""
         self.block, self.batch, self.rows = block, batch, batch if rows is None else rows
-        self.lora, self._lora_t = lora, None
+        self.lora, self._lora_t, self._gate_up_y = lora, None, None
         if lora is not None:
-            if self.rows != batch:
-                raise ValueError("lora: one row per slot only (speculative rows are not adapted)")
-            lora.pool.bind(batch)  # the shared row_adapter words, one per slot
-            self._lora_t = lora.workspace(batch)
-            self.LAUNCHES = BatchedDecoder.LAUNCHES + 6
+            if self.rows != batch * (lora.pool.rows_per_seq or 1):
+                raise ValueError(f"lora: a step of {self.rows} rows for {batch} slots, but the pool was built with rows_per_seq={lora.pool.rows_per_seq} "
+                                 "(speculative rows take LoraPool(..., rows_per_seq=T), one row per slot the default pool)")
+            lora.pool.bind(batch)  # the shared row_adapter words: one per slot, or one per row of a slot
+            self._lora_t = lora.workspace(self.rows)
+            self.LAUNCHES = BatchedDecoder.LAUNCHES + (8 if lora.gate_up else 6)
         dev = block.gamma1.device
         self.attention = attention if attention is not None else BatchDecodeAttention(batch, block.heads, block.attention.max_keys, dev, block.attention.cos,
                                                                                       block.attention.sin, kv_heads=block.kv_heads)
@@ -105,6 +111,8 @@ class BatchedDecoder:
         self.xn, self.qkv_out, self.attn_out = e(block.hidden), e((block.heads + 2 * block.kv_heads) * 128), e(block.hidden)
         self.act = e(block.ffn)
         self._up = None  # gate / up / SiLU*mul as three launches: up's output rows (only where the dispatcher refuses the pairs at M = rows)
+        if lora is not None and lora.gate_up:
+            self._gate_up_y = e(2 * block.ffn)  # the adapted gate/up: the base linear's pairs, in front of tce_lora_expand_silu_mul_f16
 
     def step(self, hidden: torch.Tensor, pos_device: torch.Tensor, pos_bound: int) -> None:
         """hidden fp16 [rows][hidden], updated in place (each row is its sequence's residual stream); pos_device int32 [rows], -1 for an inactive slot: its
@@ -127,7 +135,12 @@ class BatchedDecoder:
         if lora is not None:
             lora.expand_add("o", t["o"], hidden)
         rmsnorm_half(hidden, blk.gamma2, blk.eps, out=self.xn)
-        self._gate_up(self.xn, st)
+        if self._gate_up_y is not None:
+            lora.shrink("gate_up", self.xn, t["gate_up"])
+            capi.check(capi.w4a16_forward(blk.gate_up.desc(self.xn, self._gate_up_y), st))
+            lora.expand_silu_mul(t["gate_up"], self._gate_up_y, self.act)
+        else:
+            self._gate_up(self.xn, st)
         if lora is not None:
             lora.shrink("down", self.act, t["down"])
         capi.check(capi.w4a16_forward(blk.down.desc(self.act, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
@@ -157,8 +170,8 @@ class BatchedDecoder:
         row_adapter tensor (written before the prefill; device-side copies only: nothing is read back and no host tensor is sent over).  None without a pool."""
         if self.lora is None:
             return None
-        ra = self.lora.row_adapter
-        return torch.cat([ra[slot:slot + 1].expand(m) for slot, m in segments])
+        ra, T = self.lora.row_adapter, self.lora.pool.rows_per_seq or 1  # (a pool built for rows: the slot's FIRST word)
+        return torch.cat([ra[slot * T:slot * T + 1].expand(m) for slot, m in segments])
 
     def _prefill_rows(self, rows: torch.Tensor, attend, row_words: torch.Tensor | None = None) -> None:
         """prefill's launches over `rows`; attend(qkv, attn) is the attention in the middle (the paged decoder's serves several sequences' rows at once).  row_words
@@ -184,7 +197,12 @@ class BatchedDecoder:
         if lora is not None:
             lora.expand_add("o", t["o"], rows, row_words)
         rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
-        if m > 128 and blk.gate_up.packed is not None:
+        if lora is not None and lora.gate_up:  # the adapted gate/up: shrink, the pairs unfused, both deltas + SiLU * mul
+            y = e(2 * blk.ffn)
+            lora.shrink("gate_up", xn, t["gate_up"], row_words)
+            capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, y), st))
+            lora.expand_silu_mul(t["gate_up"], y, g, row_words)
+        elif m > 128 and blk.gate_up.packed is not None:
             capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, g, flags=capi.TCE_W4_SILU_MUL_PAIRS), st))
         else:
             capi.check(capi.w4a16_forward(blk.gate.desc(xn, g), st))

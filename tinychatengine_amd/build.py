@@ -40,7 +40,8 @@ EXTRA_FLAGS: dict[str, list[str]] = {"w4a16_gemv_i8.hip": ["-mllvm", "-amdgpu-ke
 NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_kernel"],
                                         "w4a16_gemv_stream.hip": ["w4a16_gemv_token_kernel"],
                                         # the adapter kernels hold a pass's accumulators (4 rows; the expand: 4 x 8 columns) beside the loads in flight: in scratch every step would re-read them
-                                        "lora.hip": ["lora_shrink_kernel", "lora_expand_add_kernel"],
+                                        # (the gate/up expand: one segment's 4 x 8 accumulators, both segments' y and gate's finished halves)
+                                        "lora.hip": ["lora_shrink_kernel", "lora_expand_add_kernel", "lora_expand_silu_mul_kernel"],
                                         # the sampler's two kernels keep 16 / 32 64-bit numbers per thread in registers through ~50 counting rounds: in scratch every round would re-read them
                                         # (every instantiation, the logprob forms included; the two scoring kernels hold the same 16 logits per thread)
                                         "sampling.hip": ["sample_select_kernel", "sample_draw_kernel", "logprobs_partials_kernel", "logprobs_merge_kernel"],

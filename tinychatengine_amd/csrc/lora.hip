@@ -1,4 +1,4 @@
-// lora.hip -- per-row fp16 LoRA adapters beside the W4A16 linears (include/tce_matmul.h: tce_lora_shrink_f16, tce_lora_expand_add_f16).
+// lora.hip -- per-row fp16 LoRA adapters beside the W4A16 linears (include/tce_matmul.h: tce_lora_shrink_f16, tce_lora_expand_add_f16, tce_lora_expand_silu_mul_f16).
 //
 // The base weights are packed int4, so an adapter cannot be merged into them: it is a run-time path of two launches per adapted linear,
 //
@@ -19,6 +19,16 @@
 //           share the pass (every count of rows per pass is the same instructions per row).
 //   expand: a lane owns 8 adjacent columns; j ascends into one accumulator per column; then fmaf(scale, acc, float(C)) and ONE rounding to fp16.
 // No atomics: a row has exactly one adapter, so one workgroup owns each element it writes.
+//
+// Gate / up (tce_lora_expand_silu_mul_f16): the project runs gate, up and SiLU * mul as ONE launch, and a delta has to land in front of the nonlinearity.  An adapted
+// gate/up is the shrink on the shared input (A stacked: t fp32 [rows][2R], gate's sums in front), the base gate_up linear WITHOUT the pair flag (y fp16 [rows][2N],
+// column 2n = gate n, column 2n + 1 = up n) and
+//     expand   g = fp16(float(y[i][2n]) + scale[a] * sum_j t[i][j] * Bg[a][j][n]),  u = fp16(float(y[i][2n+1]) + scale[a] * sum_j t[i][R + j] * Bu[a][j][n]),
+//              C[i][n] = silu_mul_half(g, u)                                          -- every row; a row without an adapter takes g and u from y as they are
+// The expand is SEGMENTED: gate's sum walks gate's R rows of t and Bg, up's sum up's -- the zero blocks of the block-structured form (B' [2R][2N], gate in the even
+// columns of the first R rows, up in the odd columns of the last R) are never read.  It is that form's result bit for bit all the same: a sum that starts at +0 never
+// becomes -0, so the steps fmaf(t, 0, acc) it leaves out change no bit of acc (finite t).  Grid (piece of N, adapter, block of 4 rows) as above, with ONE PLANE MORE:
+// plane n_adapters serves the block's rows without an adapter.  An adapter's plane serves the block's rows on it with ONE read of Bg and Bu, gate's pass in front of up's.
 #include "tce_common.hpp"
 
 namespace tce {
@@ -160,6 +170,101 @@ __global__ __launch_bounds__(64) void lora_expand_add_kernel(const float *__rest
         expand_pass<4>(t, Ba, s, C, ldc, r, n, row0, col, N, R);
 }
 
+// one segment (gate's or up's) of the rows r[0 .. n): out[p] = fp16(fmaf(s, sum_j t[r[p]][j] * Ba[j][:], float(yv[p]))) -- expand_pass's sums and its one rounding
+template <int NR>
+__device__ __forceinline__ void segment_pass(const float *__restrict__ t, int ldt, const half_t *__restrict__ Ba, float s, const half8_t (&yv)[NR], half8_t (&out)[NR],
+                                             const int (&r)[kRowBlock], int n, int row0, int N, int R) {
+    const float *tr[NR];
+#pragma unroll
+    for (int p = 0; p < NR; ++p) tr[p] = t + (size_t)(row0 + r[p]) * ldt;
+    float acc[NR][8];
+#pragma unroll
+    for (int p = 0; p < NR; ++p)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[p][e] = 0.f;
+#pragma unroll 2
+    for (int j0 = 0; j0 < R; j0 += 8) {  // (R % 8 == 0)
+        half8_t bh[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) bh[u] = __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4_t *>(Ba + (size_t)(j0 + u) * N));
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int p = 0; p < NR; ++p) {
+                const float tj = p < n ? tr[p][j0 + u] : 0.f;  // (a repeated slot adds nothing and is not stored)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[p][e] = fmaf(tj, (float)bh[u][e], acc[p][e]);
+            }
+    }
+#pragma unroll
+    for (int p = 0; p < NR; ++p)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[p][e] = (half_t)fmaf(s, acc[p][e], (float)yv[p][e]);
+}
+
+// a lane's 16 columns of one row of y (8 gate / up pairs), de-interleaved
+__device__ __forceinline__ void load_pairs(const half_t *__restrict__ yp, half8_t &g, half8_t &u) {
+    const half8_t lo = __builtin_bit_cast(half8_t, reinterpret_cast<const uint4_t *>(yp)[0]), hi = __builtin_bit_cast(half8_t, reinterpret_cast<const uint4_t *>(yp)[1]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        g[e] = lo[2 * e];
+        u[e] = lo[2 * e + 1];
+        g[4 + e] = hi[2 * e];
+        u[4 + e] = hi[2 * e + 1];
+    }
+}
+
+__device__ __forceinline__ void store_silu_mul(half_t *__restrict__ cp, const half8_t &g, const half8_t &u) {
+    half8_t out;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e] = silu_mul_half(g[e], u[e]);
+    *reinterpret_cast<uint4_t *>(cp) = __builtin_bit_cast(uint4_t, out);
+}
+
+template <int NR>
+__device__ __forceinline__ void gate_up_pass(const float *__restrict__ t, const half_t *__restrict__ Bga, const half_t *__restrict__ Bua, float s, const half_t *__restrict__ y,
+                                             long long ldy, half_t *__restrict__ C, long long ldc, const int (&r)[kRowBlock], int n, int row0, int col, int N, int R) {
+    half8_t yg[NR], yu[NR], g[NR], u[NR];
+#pragma unroll
+    for (int p = 0; p < NR; ++p) load_pairs(y + (size_t)(row0 + r[p]) * (size_t)ldy + 2 * (size_t)col, yg[p], yu[p]);
+    segment_pass<NR>(t, 2 * R, Bga, s, yg, g, r, n, row0, N, R);
+    segment_pass<NR>(t + R, 2 * R, Bua, s, yu, u, r, n, row0, N, R);
+#pragma unroll
+    for (int p = 0; p < NR; ++p) {
+        if (p >= n) break;
+        store_silu_mul(C + (size_t)(row0 + r[p]) * (size_t)ldc + col, g[p], u[p]);
+    }
+}
+
+__global__ __launch_bounds__(64) void lora_expand_silu_mul_kernel(const float *__restrict__ t, const half_t *__restrict__ Bg, const half_t *__restrict__ Bu,
+                                                                  const float *__restrict__ scale, const int32_t *__restrict__ row_adapter, const half_t *__restrict__ y,
+                                                                  long long ldy, half_t *__restrict__ C, long long ldc, int rows, int N, int R, int n_adapters) {
+    const int a = blockIdx.y, row0 = blockIdx.z * kRowBlock;  // plane n_adapters: the block's rows without an adapter
+    const int col = blockIdx.x * kExpandCols + threadIdx.x * 8;
+    if (a == n_adapters) {
+        if (col >= N) return;  // (N % 8 == 0: a lane's 8 columns -- 8 pairs of y -- are all inside or all outside)
+        for (int i = 0; i < kRowBlock && row0 + i < rows; ++i) {
+            const int w = row_adapter[row0 + i];
+            if (w >= 0 && w < n_adapters) continue;
+            half8_t g, u;  // g and u are y's bits
+            load_pairs(y + (size_t)(row0 + i) * (size_t)ldy + 2 * (size_t)col, g, u);
+            store_silu_mul(C + (size_t)(row0 + i) * (size_t)ldc + col, g, u);
+        }
+        return;
+    }
+    int r[kRowBlock] = {0, 0, 0, 0};
+    const int n = matching_rows(row_adapter, row0, rows, a, r);
+    if (n == 0 || col >= N) return;
+    const half_t *Bga = Bg + (size_t)a * R * (size_t)N + col, *Bua = Bu + (size_t)a * R * (size_t)N + col;
+    const float s = scale[a];
+    if (n == 1)
+        gate_up_pass<1>(t, Bga, Bua, s, y, ldy, C, ldc, r, n, row0, col, N, R);
+    else if (n == 2)
+        gate_up_pass<2>(t, Bga, Bua, s, y, ldy, C, ldc, r, n, row0, col, N, R);
+    else  // (three rows run the 4-row form, as in lora_expand_add_kernel)
+        gate_up_pass<4>(t, Bga, Bua, s, y, ldy, C, ldc, r, n, row0, col, N, R);
+}
+
 }  // namespace
 
 int launch_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, hipStream_t stream,
@@ -178,6 +283,19 @@ int launch_lora_expand_add_f16(const float *t, const void *B, const float *scale
                                hipStream_t stream, hipError_t *hip_err) {
     hipLaunchKernelGGL(lora_expand_add_kernel, dim3((N + kExpandCols - 1) / kExpandCols, n_adapters, (rows + kRowBlock - 1) / kRowBlock), dim3(64), 0, stream, t,
                        static_cast<const half_t *>(B), scale, row_adapter, static_cast<half_t *>(C), (long long)ldc, rows, N, R);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (hip_err) *hip_err = e;
+        return TCE_ERR_HIP;
+    }
+    return TCE_OK;
+}
+
+int launch_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C, int ldc,
+                                    int rows, int N, int R, int n_adapters, hipStream_t stream, hipError_t *hip_err) {
+    hipLaunchKernelGGL(lora_expand_silu_mul_kernel, dim3((N + kExpandCols - 1) / kExpandCols, n_adapters + 1, (rows + kRowBlock - 1) / kRowBlock), dim3(64), 0, stream, t,
+                       static_cast<const half_t *>(Bg), static_cast<const half_t *>(Bu), scale, row_adapter, static_cast<const half_t *>(y), (long long)ldy,
+                       static_cast<half_t *>(C), (long long)ldc, rows, N, R, n_adapters);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (hip_err) *hip_err = e;

@@ -35,6 +35,8 @@ int launch_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t 
                            hipError_t *hip_err);
 int launch_lora_expand_add_f16(const float *t, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int R, int n_adapters,
                                hipStream_t stream, hipError_t *hip_err);
+int launch_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C, int ldc,
+                                    int rows, int N, int R, int n_adapters, hipStream_t stream, hipError_t *hip_err);
 }
 
 namespace {
@@ -1656,6 +1658,29 @@ int tce_lora_expand_add_f16(const float *t, const void *B, const float *scale, c
     hipError_t he = hipSuccess;
     const int rc = tce::launch_lora_expand_add_f16(t, B, scale, row_adapter, Cm, ldc, rows, N, R, n_adapters, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA expand launch") : rc;
+}
+
+int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *Cm, int ldc,
+                                 int rows, int N, int R, int n_adapters, void *stream) {
+    const char *who = "tce_lora_expand_silu_mul_f16";
+    if (!t || !Bg || !Bu || !scale || !row_adapter || !y || !Cm) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (rows < 1 || N < 1 || R < 1 || n_adapters < 1 || ldy < 2 * (long long)N || ldc < N)
+        return fail(TCE_ERR_BAD_ARG, "%s: need rows, N, R, n_adapters >= 1, ldy >= 2 N and ldc >= N", who);
+    {  // y is only read and C is written by other lanes than those that read the pair: the two ranges must not meet
+        const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), c0 = reinterpret_cast<uintptr_t>(Cm);
+        const uintptr_t y1 = y0 + ((uintptr_t)(rows - 1) * (uintptr_t)ldy + 2 * (uintptr_t)N) * 2, c1 = c0 + ((uintptr_t)(rows - 1) * (uintptr_t)ldc + (uintptr_t)N) * 2;
+        if (y0 < c1 && c0 < y1) return fail(TCE_ERR_BAD_ARG, "%s: C overlaps y", who);
+    }
+    if (N % 8 != 0 || ldy % 8 != 0 || ldc % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d, ldy %d, ldc %d (multiples of 8)", who, N, ldy, ldc);
+    if (R % 8 != 0 || R > TCE_LORA_MAX_RANK / 2)  // (t carries gate's and up's sums: 2 R <= TCE_LORA_MAX_RANK, the shrink's bound)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: R %d (a multiple of 8, 8 .. %d: gate's and up's rows share the shrink's %d)", who, R, TCE_LORA_MAX_RANK / 2, TCE_LORA_MAX_RANK);
+    if (const int rc = check_lora_shape(who, rows, 2 * R, n_adapters)) return rc;
+    if ((reinterpret_cast<uintptr_t>(Bg) | reinterpret_cast<uintptr_t>(Bu) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(Cm)) % 16 != 0 ||
+        (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(scale)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned Bg / Bu / y / C, 4-byte aligned row_adapter / t / scale", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_expand_silu_mul_f16(t, Bg, Bu, scale, row_adapter, y, ldy, Cm, ldc, rows, N, R, n_adapters, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA gate/up expand launch") : rc;
 }
 
 int tce_attention_decode_step_deferred_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace, int heads,

@@ -473,7 +473,8 @@ class _GeneratorBase:
     """What BatchedGenerator and speculative.SpeculativeGenerator share: the construction, the graph, admission, the replay loop and the read-outs.  A subclass gives
     token_step() (what one replay runs) and launches_per_token, and calls _capture() once its own buffers exist."""
 
-    lora = None  # a LoraPool (BatchedGenerator(..., lora=pool)): admit(..., adapter=) writes the slot's row_adapter word, release() writes -1
+    lora = None  # a LoraPool (BatchedGenerator / SpeculativeGenerator(..., lora=pool)): admit(..., adapter=) writes the slot's row_adapter word (LoraPool.set_slot: once per
+    # row of the slot in a pool built for speculative rows), release() writes -1
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None, top_k_bound: int, stop_ids, rows_per_seq: int | None = None,
                  **sampler_kw):
@@ -503,6 +504,16 @@ class _GeneratorBase:
         self._adm_hidden = h(self.batch, self.hidden_size)
         self._adm_xn, self._adm_logits = (self.xn, self.logits) if rows_per_seq is None else (h(self.batch, self.hidden_size), h(self.batch, lm_head.out_features))
         self._graph = None
+
+    def _take_pool(self, lora) -> None:
+        """lora=pool of a generator: the decoders' views must be this pool's layers, in order (None: no decoder may carry one)."""
+        pools = [getattr(getattr(d, "lora", None), "pool", None) for d in self.decoders]
+        if lora is None and any(p is not None for p in pools):
+            raise ValueError("the decoders carry LoRA views: pass their pool as lora=")
+        if lora is not None:
+            if any(p is not lora for p in pools) or [d.lora.index for d in self.decoders] != list(range(len(self.decoders))) or lora.layers != len(self.decoders):
+                raise ValueError("lora=pool: decoder i must be built with lora=pool.layer(i), one layer of the pool per decoder")
+            self.lora = lora
 
     def _capture(self) -> None:
         """token_step once eagerly -- the warm-up: every row inactive, so nothing is embedded, appended or sampled; the gate/up form is settled --, then once into the
@@ -579,8 +590,7 @@ class _GeneratorBase:
                 self.allocator.reserve_many([(s, len(ids) - 1) for s, ids, *_ in adm])
         if self.lora is not None:
             for s, *_ in adm:  # every admitted slot's word, -1 included: before the prefill
-                a = lora_of.get(s)
-                self.lora.row_adapter[s] = -1 if a is None else int(a)
+                self.lora.set_slot(s, lora_of.get(s))
 
         def embedded(ids):
             tok = torch.tensor(ids, dtype=torch.int32).to(self.device)
@@ -635,7 +645,7 @@ class _GeneratorBase:
             for s, *_ in adm:
                 self.allocator.release(s)
                 if self.lora is not None:  # (admit wrote the slot's word in front of the prefill: a free slot's word is -1)
-                    self.lora.row_adapter[s] = -1
+                    self.lora.set_slot(s, None)
             raise
         return last
 
@@ -695,7 +705,7 @@ class _GeneratorBase:
         """The slot is free again: its position word is -1 and (paged) its pages go back to the pool; returns them."""
         self.pos[slot] = -1
         if self.lora is not None:
-            self.lora.row_adapter[slot] = -1
+            self.lora.set_slot(slot, None)
         self.book.clear(slot)
         return self.allocator.release(slot) if self.allocator is not None else []
 
@@ -715,16 +725,10 @@ class BatchedGenerator(_GeneratorBase):
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
                  debug: bool = False, logprobs: bool = False, constraints: bool = False, lora=None):
-        """lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  lm_head
-        and the embedding are not adapted."""
+        """lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  A
+        gate_up=True pool adapts gate/up too (15 L + 5 launches per token instead of 13 L + 5).  lm_head and the embedding are not adapted."""
         super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints)
-        pools = [getattr(getattr(d, "lora", None), "pool", None) for d in self.decoders]
-        if lora is None and any(p is not None for p in pools):
-            raise ValueError("the decoders carry LoRA views: pass their pool as lora=")
-        if lora is not None:
-            if any(p is not lora for p in pools) or [d.lora.index for d in self.decoders] != list(range(len(self.decoders))) or lora.layers != len(self.decoders):
-                raise ValueError("lora=pool: decoder i must be built with lora=pool.layer(i), one layer of the pool per decoder")
-            self.lora = lora
+        self._take_pool(lora)
         self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
         self.score_logits: list = []
         self.launches_per_token = 1 + self.decoders[0].LAUNCHES * len(self.decoders) + 1 + 1 + 2
@@ -773,7 +777,7 @@ class BatchedGenerator(_GeneratorBase):
                 r0 += len(prompts[i])
             if self.lora is not None:  # every slot it uses, -1 included, as admit does: nothing is assumed of a free slot's word
                 for s in slots:
-                    self.lora.row_adapter[s] = -1 if adapter is None else int(adapter)
+                    self.lora.set_slot(s, adapter)
             for d in self.decoders:
                 d.prefill_many([(s, r, 0) for s, r in zip(slots, rows)])
             chunk = plan["chunk"]
@@ -793,7 +797,7 @@ class BatchedGenerator(_GeneratorBase):
             for s in slots:
                 self.allocator.release(s)
                 if self.lora is not None:
-                    self.lora.row_adapter[s] = -1
+                    self.lora.set_slot(s, None)
         return plan["split"](values.cpu().numpy())  # (synchronises)
 
 

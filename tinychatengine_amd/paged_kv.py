@@ -442,7 +442,7 @@ class PagedBatchedDecoder(BatchedDecoder):
                  rows: int | None = None, window: int | None = None, lora=None):
         """attention, rows: BatchedDecoder's (a subclass with an attention object of its own over the same allocator; the default is built here).  window: this layer's
         sliding window (PagedBatchDecodeAttention), None for full attention.  lora: BatchedDecoder's (this layer's view of a LoraPool: q/k/v, o_proj and down_proj
-        become adapted linears in step, prefill and prefill_many)."""
+        become adapted linears in step, prefill and prefill_many; gate/up too with a gate_up=True pool)."""
         self.allocator = allocator
         if attention is None:
             attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,

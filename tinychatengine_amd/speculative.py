@@ -8,6 +8,7 @@ spread over up to T tokens of the SAME sequence: the linears run at M = B T and 
                                           sequence's most recent n-gram in its own history (prompt lookup; no second model)
     1        tce_embed_rows_f16           B T rows (inactive rows skipped)
     7 x L    the layers                   SpeculativeDecoder: BatchedDecoder.step's seven launches at B T rows, tce_attention_decode_step_paged_rows_* as launch 3
+                                          (lora=: + 6 per layer, + 8 with a gate_up=True pool; the T rows of a slot carry the slot's adapter word)
     1        tce_rmsnorm_half             the final norm
     1        tce_w4a16_forward            lm_head at M = B T
     3        tce_sample_verify_f16        select for all rows, draw per row, walk the chain: 1 .. T tokens per sequence
@@ -189,12 +190,14 @@ class SpeculativeDecoder(PagedBatchedDecoder):
     words tce_draft_ngram's row_pos int32 [batch * T]), the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill / prefill_many are the parent's.  window: this
     layer's sliding window (the windowed rows step and the windowed prefill), None for full attention."""
 
-    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None):
+    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None, lora=None):
+        """lora: this layer's view of a LoraPool built with the same rows_per_seq (LoraPool(..., rows_per_seq=T).layer(i)): the T rows of a slot run on the slot's
+        adapter -- 7 + 6 launches, 7 + 8 with a gate_up=True pool."""
         _check_rows(rows_per_seq)
         self.rows_per_seq = int(rows_per_seq)
         attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin,
                                              rows_per_seq=rows_per_seq, kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window)
-        super().__init__(block, allocator, attention=attention, rows=allocator.batch * self.rows_per_seq)
+        super().__init__(block, allocator, attention=attention, rows=allocator.batch * self.rows_per_seq, lora=lora)
 
 
 def draft_ngram(history, script, pos_device, pos_bound: int, rows_per_seq: int, ngram: int, row_token, row_pos) -> None:
@@ -264,8 +267,12 @@ class SpeculativeGenerator(_GeneratorBase):
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False,
                  constraints: bool = False, lora=None):
-        if lora is not None:
-            raise ValueError("SpeculativeGenerator: LoRA adapters on speculative rows are not built (lora=None only)")
+        if lora is not None:  # first: a pool that was not built for rows, or for another T, is refused before anything else of the constructor runs
+            T = getattr(lora, "rows_per_seq", None)
+            decoders = list(decoders) if T is not None and decoders is not None else None
+            if T is None or not decoders or T != getattr(decoders[0], "rows_per_seq", None):
+                raise ValueError(f"SpeculativeGenerator: lora= takes a pool built for its speculative rows, LoraPool(..., rows_per_seq=T) with the decoders' T "
+                                 f"(this pool: rows_per_seq={T})")
         decoders = list(decoders)
         for d in decoders:  # a windowed layer must run the windowed ROWS step: its attention object carries the window (SpeculativeDecoder(..., window=W) builds it so)
             w = getattr(d, "window", None)
@@ -276,6 +283,7 @@ class SpeculativeGenerator(_GeneratorBase):
         assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
         super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, rows_per_seq=self.rows_per_seq, logprobs=logprobs,
                          constraints=constraints)
+        self._take_pool(lora)
         B, T, dev = self.batch, self.rows_per_seq, self.device
         self.verifier = Verifier(self.sampler, T)
         self.book = SpecSlotBook(B, self.max_keys, T)
