@@ -6,7 +6,8 @@ slice.  Every active row computes, bit for bit, what tce_attention_decode_step_p
 whose position word is < 0 or > pos_bound is inactive (zero output row, caches and counters untouched), so a fixed-B captured graph is a slot pool
 in which a finished sequence is retired by writing -1.
 
-A layer is SEVEN launches for the B rows:
+A layer is SEVEN launches for the B rows, issued by ONE function, decoder_block.layer_body -- step() runs it on the decoder's persistent rows with the batched step as
+launch 3 and _gate_up as launch 6, _prefill_rows (prefill, prefill_many) on per-call rows with the prefill attention and gate_up_by_rule, DecoderBlock.prefill on its own:
 
     1  input_layernorm                           tce_rmsnorm_half over B rows (the fused RMSNorm prologue is an M = 1 form)
     2  q/k/v projection                          tce_w4a16_forward, M = B
@@ -16,8 +17,8 @@ A layer is SEVEN launches for the B rows:
     6  gate/up + SiLU*mul                        tce_w4a16_forward, M = B, TCE_W4_SILU_MUL_PAIRS (gate, up and tce_silu_mul_half where the pairs are refused)
     7  down_proj + residual add                  tce_w4a16_forward, M = B, TCE_W4_ADD_TO_C
 
-lora=<a LoraLayer> (lora.py): q/k/v, o_proj and down_proj are ADAPTED linears -- tce_lora_shrink_f16 once the linear's input exists, tce_lora_expand_add_f16 directly
-behind the base launch, each row on the adapter its row_adapter word names -- 7 + 6 launches.  lora=None: every code path and launch is the one above.
+lora=<a LoraLayer> (lora.py): q/k/v, o_proj and down_proj are ADAPTED linears (layer_body's `linear`) -- tce_lora_shrink_f16 once the linear's input exists,
+tce_lora_expand_add_f16 directly behind the base launch, each row on the adapter its row_adapter word names -- 7 + 6 launches.  lora=None: every launch is the one above.
 A view of a gate_up=True pool: launch 6 becomes three -- the shrink on xn with gate's and up's A stacked, the gate_up linear WITHOUT the pair flag into [rows][2 * ffn]
 and tce_lora_expand_silu_mul_f16 (both deltas in front of the nonlinearity, SiLU * mul for every row) -- 7 + 8 launches.  A pool built with rows_per_seq=T serves the
 speculative step: rows = batch * T, a slot's word stands T times in row_adapter.
@@ -31,8 +32,8 @@ import torch
 
 from . import capi
 from .attention_ops import DecodeAttention
-from .decoder_block import DecoderBlock
-from .linear import _stream, rmsnorm_half
+from .decoder_block import DecoderBlock, gate_up_by_rule, gate_up_three, layer_body
+from .linear import _stream
 
 
 class _SlotAttention(DecodeAttention):
@@ -120,50 +121,30 @@ class BatchedDecoder:
         torch.cuda.graph and replayable token after token with pos_device advanced on the device."""
         blk = self.block
         assert hidden.dtype == torch.float16 and hidden.is_contiguous() and tuple(hidden.shape) == (self.rows, blk.hidden)
-        st = _stream()
-        lora, t = self.lora, self._lora_t
-        rmsnorm_half(hidden, blk.gamma1, blk.eps, out=self.xn)
-        if lora is not None:
-            lora.shrink("qkv", self.xn, t["qkv"])
-        capi.check(capi.w4a16_forward(blk.qkv.desc(self.xn, self.qkv_out), st))
-        if lora is not None:
-            lora.expand_add("qkv", t["qkv"], self.qkv_out)
-        self.attention.step(self.qkv_out, pos_device, pos_bound, out=self.attn_out)
-        if lora is not None:
-            lora.shrink("o", self.attn_out, t["o"])
-        capi.check(capi.w4a16_forward(blk.o.desc(self.attn_out, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
-        if lora is not None:
-            lora.expand_add("o", t["o"], hidden)
-        rmsnorm_half(hidden, blk.gamma2, blk.eps, out=self.xn)
-        if self._gate_up_y is not None:
-            lora.shrink("gate_up", self.xn, t["gate_up"])
-            capi.check(capi.w4a16_forward(blk.gate_up.desc(self.xn, self._gate_up_y), st))
-            lora.expand_silu_mul(t["gate_up"], self._gate_up_y, self.act)
-        else:
-            self._gate_up(self.xn, st)
-        if lora is not None:
-            lora.shrink("down", self.act, t["down"])
-        capi.check(capi.w4a16_forward(blk.down.desc(self.act, hidden, flags=capi.TCE_W4_ADD_TO_C), st))
-        if lora is not None:
-            lora.expand_add("down", t["down"], hidden)
+        layer_body(blk, hidden, self.xn, self.qkv_out, self.attn_out, self.act, lambda qkv, attn: self.attention.step(qkv, pos_device, pos_bound, out=attn),
+                   self._gate_up, lora=self.lora, t=self._lora_t, y=self._gate_up_y)  # (row_words None: the pool's own row_adapter, one word per row of the step)
 
     def _gate_up(self, xn: torch.Tensor, st: int) -> None:
-        blk = self.block
+        """The step's gate/up policy: ask for the SiLU*mul pairs, and where the dispatcher refuses them at M = rows fall back to the three launches FOR GOOD."""
         if self._up is None:
-            rc = capi.w4a16_forward(blk.gate_up.desc(xn, self.act, flags=capi.TCE_W4_SILU_MUL_PAIRS), st)
+            rc = capi.w4a16_forward(self.block.gate_up.desc(xn, self.act, flags=capi.TCE_W4_SILU_MUL_PAIRS), st)
             if rc == capi.TCE_OK:
                 return
             if rc == capi.TCE_ERR_HIP:
                 capi.check(rc)
             self._up = torch.empty_like(self.act)  # refused before any launch: the three-launch form from now on
-        capi.check(capi.w4a16_forward(blk.gate.desc(xn, self.act), st))
-        capi.check(capi.w4a16_forward(blk.up.desc(xn, self._up), st))
-        capi.check(capi.lib().tce_silu_mul_half(self.act.data_ptr(), self._up.data_ptr(), self.act.numel(), st))
+        gate_up_three(self.block, xn, self.act, self._up, st)
 
     def prefill(self, slot: int, rows: torch.Tensor, pos: int) -> None:
         """Admit a sequence into `slot`: rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated in place -- DecoderBlock.prefill's launches on the
         slot's caches."""
         self._prefill_rows(rows, lambda qkv, attn: self.attention.slot(slot).prefill(qkv, pos, out=attn, causal=True), self._row_words([(slot, rows.shape[0])]))
+
+    def prefill_many(self, admissions) -> None:
+        """admissions [(slot, rows, pos)]: prefill once per sequence, in order (a contiguous cache takes one sequence per attention call; the paged decoder's
+        prefill_many serves them all at M = all rows)."""
+        for slot, rows, pos in admissions:
+            self.prefill(slot, rows, pos)
 
     def _row_words(self, segments) -> torch.Tensor | None:
         """The prefill's per-row adapter words for segments [(slot, m)]: every row of an admission carries its SLOT's word, gathered on the device from the shared
@@ -174,42 +155,13 @@ class BatchedDecoder:
         return torch.cat([ra[slot * T:slot * T + 1].expand(m) for slot, m in segments])
 
     def _prefill_rows(self, rows: torch.Tensor, attend, row_words: torch.Tensor | None = None) -> None:
-        """prefill's launches over `rows`; attend(qkv, attn) is the attention in the middle (the paged decoder's serves several sequences' rows at once).  row_words
-        (with a pool): int32 [m], the adapter of every row -- the three adapted linears get their shrink and expand as in step()."""
+        """prefill's launches over `rows` -- layer_body on rows of this call's own; attend(qkv, attn) is the attention in the middle (the paged decoder's serves several
+        sequences' rows at once).  row_words (with a pool): int32 [m], the adapter of every row -- the linears are adapted as in step()."""
         blk = self.block
         m = rows.shape[0]
         lora = self.lora if row_words is not None else None
-        t = lora.workspace(m) if lora is not None else None
         assert rows.dtype == torch.float16 and rows.is_contiguous() and rows.shape[1] == blk.hidden
-        st = _stream()
         e = lambda n: torch.empty((m, n), dtype=torch.float16, device=rows.device)
         xn, qkv, attn, g, u = e(blk.hidden), e((blk.heads + 2 * blk.kv_heads) * 128), e(blk.hidden), e(blk.ffn), e(blk.ffn)
-        rmsnorm_half(rows, blk.gamma1, blk.eps, out=xn)
-        if lora is not None:
-            lora.shrink("qkv", xn, t["qkv"], row_words)
-        capi.check(capi.w4a16_forward(blk.qkv.desc(xn, qkv), st))
-        if lora is not None:
-            lora.expand_add("qkv", t["qkv"], qkv, row_words)
-        attend(qkv, attn)
-        if lora is not None:
-            lora.shrink("o", attn, t["o"], row_words)
-        capi.check(capi.w4a16_forward(blk.o.desc(attn, rows, flags=capi.TCE_W4_ADD_TO_C), st))
-        if lora is not None:
-            lora.expand_add("o", t["o"], rows, row_words)
-        rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
-        if lora is not None and lora.gate_up:  # the adapted gate/up: shrink, the pairs unfused, both deltas + SiLU * mul
-            y = e(2 * blk.ffn)
-            lora.shrink("gate_up", xn, t["gate_up"], row_words)
-            capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, y), st))
-            lora.expand_silu_mul(t["gate_up"], y, g, row_words)
-        elif m > 128 and blk.gate_up.packed is not None:
-            capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, g, flags=capi.TCE_W4_SILU_MUL_PAIRS), st))
-        else:
-            capi.check(capi.w4a16_forward(blk.gate.desc(xn, g), st))
-            capi.check(capi.w4a16_forward(blk.up.desc(xn, u), st))
-            capi.check(capi.lib().tce_silu_mul_half(g.data_ptr(), u.data_ptr(), g.numel(), st))
-        if lora is not None:
-            lora.shrink("down", g, t["down"], row_words)
-        capi.check(capi.w4a16_forward(blk.down.desc(g, rows, flags=capi.TCE_W4_ADD_TO_C), st))
-        if lora is not None:
-            lora.expand_add("down", t["down"], rows, row_words)
+        t, y = (lora.workspace(m), e(2 * blk.ffn) if lora.gate_up else None) if lora else (None, None)
+        layer_body(blk, rows, xn, qkv, attn, g, attend, lambda x, st: gate_up_by_rule(blk, x, g, u, st), lora=lora, t=t, row_words=row_words, y=y)

@@ -24,7 +24,7 @@ import torch
 
 from . import capi
 from .attention_ops import DecodeAttention
-from .linear import Linear_half_int4, _stream
+from .linear import Linear_half_int4, _stream, rmsnorm_half
 
 
 class DecoderBlock:
@@ -98,32 +98,69 @@ class DecoderBlock:
         """hidden_rows fp16 [m][hidden], updated in place; the m rows take positions pos .. pos + m - 1.  EIGHT launches where the reference issues its ~20 + the
         per-head copies: RMSNorm, q/k/v GEMM, [rotation + KV append], attention, o_proj GEMM + residual, RMSNorm, gate/up GEMM with the SiLU*mul pair epilogue,
         down_proj GEMM + residual (the GEMMs have no fused norm prologue: that is a decode form)."""
-        from .linear import rmsnorm_half
         m = hidden_rows.shape[0]
         assert hidden_rows.dtype == torch.float16 and hidden_rows.is_contiguous() and hidden_rows.shape[1] == self.hidden
-        st = _stream()
-        buf = getattr(self, "_pf", None)
+        buf = getattr(self, "_pf", None)  # the working rows are kept between calls (and grow with m): a timed loop of prefills allocates nothing
         if buf is None or buf[0].shape[0] < m:
             e = lambda n: torch.empty((m, n), dtype=torch.float16, device=hidden_rows.device)
             buf = self._pf = (e(self.hidden), e((self.heads + 2 * self.kv_heads) * 128), e(self.hidden), e(self.ffn), e(self.ffn))
         xn, qkv, attn, g, u = (t[:m] for t in buf)
-        rmsnorm_half(hidden_rows, self.gamma1, self.eps, out=xn)
-        capi.check(capi.w4a16_forward(self.qkv.desc(xn, qkv), st))
-        self.attention.prefill(qkv, pos, out=attn, causal=True)
-        capi.check(capi.w4a16_forward(self.o.desc(attn, hidden_rows, flags=capi.TCE_W4_ADD_TO_C), st))
-        rmsnorm_half(hidden_rows, self.gamma2, self.eps, out=xn)
-        if m > 128 and self.gate_up.packed is not None:  # gate + up + SiLU*mul as ONE GEMM launch on the interleaved rows (pair epilogue of the 128-row GEMM)
-            capi.check(capi.w4a16_forward(self.gate_up.desc(xn, g, flags=capi.TCE_W4_SILU_MUL_PAIRS), st))
-        else:
-            capi.check(capi.w4a16_forward(self.gate.desc(xn, g), st))
-            capi.check(capi.w4a16_forward(self.up.desc(xn, u), st))
-            capi.check(capi.lib().tce_silu_mul_half(g.data_ptr(), u.data_ptr(), g.numel(), st))
-        capi.check(capi.w4a16_forward(self.down.desc(g, hidden_rows, flags=capi.TCE_W4_ADD_TO_C), st))
+        layer_body(self, hidden_rows, xn, qkv, attn, g, lambda q, a: self.attention.prefill(q, pos, out=a, causal=True),
+                   lambda x, st: gate_up_by_rule(self, x, g, u, st))
 
     PREFILL_LAUNCHES = 8  # with pre-packed weights and m > 128 (otherwise 10: gate, up and SiLU*mul as three launches)
 
     def linear_bytes(self) -> int:
         return sum(capi.algorithmic_bytes(1, l.out_features, l.in_features, l.group_size) for l in (self.qkv, self.o, self.gate_up, self.down))
+
+
+# ---- the layer over m rows: ONE body for DecoderBlock.prefill, BatchedDecoder.step and BatchedDecoder._prefill_rows (step / step_chained above are other launches) ----
+def layer_body(blk: DecoderBlock, rows: torch.Tensor, xn, qkv, attn, act, attend, gate_up, lora=None, t=None, row_words=None, y=None) -> None:
+    """The seven stages of a decoder layer over rows fp16 [m][hidden], updated in place: RMSNorm, q/k/v, attend(qkv, attn), o_proj + residual, RMSNorm, gate/up with
+    SiLU * mul into act, down_proj + residual.  The caller owns the working rows (xn [m][hidden], qkv [m][(heads + 2 kv_heads) * 128], attn [m][hidden], act [m][ffn])
+    and the two things that differ between callers: attend, the attention in the middle, and gate_up(xn, st), the policy that leaves SiLU(gate) * up in act
+    (BatchedDecoder._gate_up, or gate_up_by_rule).
+    lora: the layer's LoraLayer, with t = lora.workspace(m) and row_words int32 [m] (None: the pool's own row_adapter).  q/k/v, o_proj and down_proj are then adapted
+    linears.  A view of a gate_up=True pool adapts gate/up too, the one linear that does not follow the rule: the delta belongs in front of the nonlinearity, so the base
+    gate_up linear runs WITHOUT the pair flag into y [m][2 * ffn] and tce_lora_expand_silu_mul_f16 adds both deltas and applies SiLU * mul; the policy is not asked."""
+    st = _stream()
+
+    def linear(target, lin, x, out, flags=0):
+        """a linear that may carry an adapter: the shrink once the linear's input exists, the expand directly behind the base launch"""
+        if lora is not None:
+            lora.shrink(target, x, t[target], row_words)
+        capi.check(capi.w4a16_forward(lin.desc(x, out, flags=flags), st))
+        if lora is not None:
+            lora.expand_add(target, t[target], out, row_words)
+
+    rmsnorm_half(rows, blk.gamma1, blk.eps, out=xn)
+    linear("qkv", blk.qkv, xn, qkv)
+    attend(qkv, attn)
+    linear("o", blk.o, attn, rows, capi.TCE_W4_ADD_TO_C)
+    rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
+    if lora is not None and lora.gate_up:
+        lora.shrink("gate_up", xn, t["gate_up"], row_words)
+        capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, y), st))
+        lora.expand_silu_mul(t["gate_up"], y, act, row_words)
+    else:
+        gate_up(xn, st)
+    linear("down", blk.down, act, rows, capi.TCE_W4_ADD_TO_C)
+
+
+def gate_up_three(blk: DecoderBlock, xn, act, up, st: int) -> None:
+    """gate, up and SiLU * mul as three launches: act = SiLU(gate(xn)) * up(xn), `up` the second linear's output rows"""
+    capi.check(capi.w4a16_forward(blk.gate.desc(xn, act), st))
+    capi.check(capi.w4a16_forward(blk.up.desc(xn, up), st))
+    capi.check(capi.lib().tce_silu_mul_half(act.data_ptr(), up.data_ptr(), act.numel(), st))
+
+
+def gate_up_by_rule(blk: DecoderBlock, xn, act, up, st: int) -> None:
+    """The prefill's gate/up policy: more than 128 rows on pre-packed weights are ONE GEMM launch on the interleaved rows (the pair epilogue of the 128-row GEMM),
+    anything else the three launches."""
+    if xn.shape[0] > 128 and blk.gate_up.packed is not None:
+        capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, act, flags=capi.TCE_W4_SILU_MUL_PAIRS), st))
+    else:
+        gate_up_three(blk, xn, act, up, st)
 
 
 def dequantize(lin: Linear_half_int4) -> np.ndarray:

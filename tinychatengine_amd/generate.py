@@ -603,11 +603,7 @@ class _GeneratorBase:
         else:
             rows = [embedded(ids) for s, ids, *_ in adm]
             for d in self.decoders:
-                if self.allocator is not None:
-                    d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
-                else:
-                    for (s, *_), r in zip(adm, rows):
-                        d.prefill(s, r, 0)
+                d.prefill_many([(s, r, 0) for (s, *_), r in zip(adm, rows)])
         self._adm_pos.fill_(-1)
         for (s, ids, p, sd, mn), r in zip(adm, rows):
             self.sampler.set_row(s, p, sd, mn, ids, *(cons[s] if any(c is not None for c in cons.get(s, ())) else ()))
@@ -852,11 +848,7 @@ class HostDrivenLoop:
         adm = [(int(s), [int(t) for t in ids], int(mn)) for s, ids, mn in adm]
         rows = [self.table_host[torch.tensor(ids, dtype=torch.int64)].to(self.device).contiguous() for _, ids, _ in adm]
         for d in self.decoders:
-            if self.allocator is not None:
-                d.prefill_many([(s, r, 0) for (s, _, _), r in zip(adm, rows)])
-            else:
-                for (s, _, _), r in zip(adm, rows):
-                    d.prefill(s, r, 0)
+            d.prefill_many([(s, r, 0) for (s, _, _), r in zip(adm, rows)])
         last = torch.zeros_like(self.hidden)
         for (s, _, _), r in zip(adm, rows):
             last[s].copy_(r[-1])
