@@ -423,8 +423,8 @@ TCE_API int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_po
  *               tce_attention_decode_step_paged_window_f16 / _fp8 with the same pos_bound and window; no other pool byte changes; rows_per_seq = 1 is that step;
  *               window >= pos_bound + 1 is the unwindowed multi-row step.  Refusals: window < 1 TCE_ERR_BAD_ARG, rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS
  *               TCE_ERR_UNSUPPORTED_SHAPE, everything else the two parents' rules.
- * NOT BUILT: windows on contiguous caches and on the single-sequence step; attention sinks (first keys kept beside the
- * window: the pools hold ROTATED keys, so positions inside the cache would have to be re-rotated). */
+ * NOT BUILT: windows on contiguous caches and on the single-sequence step; attention sinks on the multi-row step (below: the one-row step and the prefill have them); a
+ * ring table for unbounded streams -- positions stay bounded by table_stride * page_keys. */
 TCE_API int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len);
 TCE_API int tce_attention_decode_step_paged_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                                        const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
@@ -451,6 +451,53 @@ TCE_API int tce_attention_prefill_paged_window_fp8(const void *qkv, int ld_qkv, 
                                                    int total_rows, unsigned short alpha_half_bits, int k_scale_log2, int v_scale_log2, int window, void *stream);
 TCE_API int tce_kv_block_table_check_window(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
                                             uint32_t *violations, int window, void *stream);
+
+/* ATTENTION SINKS beside the sliding window (StreamingLLM: a model that was not trained with a window fails once the first keys of the sequence leave it; keeping them
+ * beside the window is the remedy).  window = W >= 1, sinks = S, 1 <= S <= 16: the smallest page holds 16 keys, so the sinks always lie in table word 0's page.  Each entry
+ * point below is its *_window namesake with `int sinks` behind `window`; everything not said here is the namesake's.
+ * A row at position p BINDS iff p >= S + W.
+ *   not binding  the row is the unwindowed row: it weighs keys 0 .. p, every score with q rotated with cos / sin row p.
+ *   binding      lo = p - W + 1.  Keys 0 .. S - 1 are scored with q rotated by cos / sin row S + W - 1, keys lo .. p with q rotated by row p; ONE softmax runs over these
+ *                S + W scores; keys S .. lo - 1 weigh nothing.  check_inf_half, alpha and the value handling are the step's.
+ *   appended key rotated with row p, as always: the pools after any sequence of sink calls equal the pools after the unwindowed calls on the same inputs -- no pool byte
+ *                depends on window or sinks, so forks, prefill and decode stay interchangeable.
+ *   no RoPE      with cos = sin = NULL both queries are the raw q.
+ * Why a second rotation of q is all it takes: StreamingLLM scores with positions INSIDE the cache, and a RoPE score depends on the position difference alone.  For a window
+ * key j the difference is p - j in both numberings; for a sink key i < S it is (S + W - 1) - i, which is what q rotated with row S + W - 1 gives against the key as the
+ * pool holds it (rotated with row i).  The definition is in terms of table ROWS, not angles: any cos / sin table is valid input.
+ *   key range   the step's workgroups walk a virtual key sequence: S4 = (S + 3) & ~3 keys for the sinks (virtual v < S4 is key v, valid iff v < S), then the windowed
+ *               step's keys from base2 = lo & ~3 on (valid iff >= lo); a row that does not bind walks keys 0 .. p.  Rows S .. S4 - 1 of word 0's page and rows base2 ..
+ *               lo - 1 are loaded and weigh nothing.  The prefill: a query block's window pass is the windowed block's (a row that does not bind has lo = 0; the block
+ *               starts at the lo of its first row, 0 if that row does not bind), and a block whose last row binds makes one more pass over keys 0 .. S - 1.
+ *   cut         the batched step's fitted rule for the virtual keys: pos_bound + 1 while S + W > pos_bound (no row can bind: the unwindowed step's cut), else
+ *               min(pos_bound + 1 + d, S4 + W + 3) with d = S4 - ((S + 1) & ~3), 0 or 4: the keys by which a binding row's virtual sequence can exceed pos + 1
+ *               (tce_attention_decode_describe_paged_sink).  Workspace: the unwindowed step's.
+ *   trust       of an active binding row only table word 0 and words lo / page_keys .. pos / page_keys become addresses (prefill, per block: word 0 if a row of the block
+ *               binds, and the words from klo / page_keys on); of a row that does not bind words 0 .. pos / page_keys.  tce_kv_block_table_check_sink checks those words.
+ *               The caller keeps the first ceil(S / page_keys) = 1 page of a sequence alive (PageAllocator.release_behind(..., keep_pages=1)).
+ *   identities  (no tolerance) 1. NEVER BINDING: with S + W >= pos_bound + 1 (prefill: >= pos + m of every segment) `out` and every pool byte equal the unwindowed entry
+ *               point's.  2. COMPACTION: with cos = sin = NULL, S a multiple of 4 and lo % 4 == 0 the step at a binding pos equals the unwindowed step at position
+ *               S + W - 1 under pos_bound S + W + 2 on a pool that holds keys [0, S) ++ [lo, pos) -- both launches use the same cut.  Elsewhere: the float64 evaluation
+ *               of the definition (two binary16 rotations of q) within the steps' stated bound.
+ *   refusals    the *_window entry point's, in its order, then sinks < 1 || sinks > 16: TCE_ERR_BAD_ARG.  Before any HIP call.  The prefill is causal only. */
+TCE_API int tce_attention_decode_describe_paged_sink(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, int sinks, char *buf, int buf_len);
+TCE_API int tce_attention_decode_step_paged_sink_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                     const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
+                                                     int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int window, int sinks, void *stream);
+TCE_API int tce_attention_decode_step_paged_sink_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                     const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,
+                                                     int head_dim, const int32_t *pos_device, int pos_bound, unsigned short alpha_half_bits, int k_scale_log2,
+                                                     int v_scale_log2, int window, int sinks, void *stream);
+TCE_API int tce_attention_prefill_paged_sink_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                                 int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out,
+                                                 void *workspace, int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments,
+                                                 int total_rows, unsigned short alpha_half_bits, int window, int sinks, void *stream);
+TCE_API int tce_attention_prefill_paged_sink_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                                 int page_keys, int num_pages, const void *cos_table, const void *sin_table, int causal, void *out, int ld_out,
+                                                 void *workspace, int heads, int kv_heads, int head_dim, const tce_prefill_segment *segments, int num_segments,
+                                                 int total_rows, unsigned short alpha_half_bits, int k_scale_log2, int v_scale_log2, int window, int sinks, void *stream);
+TCE_API int tce_kv_block_table_check_sink(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                                          uint32_t *violations, int window, int sinks, void *stream);
 
 /* Device-side sampling: what the reference does on the host between Int4LlamaForCausalLM::forward and the next token's Embedding (llm/src/Generate.cc driven by
  * LLaMA3Generate.cc:127-198), for `batch` rows of fp16 logits [batch][ld] (lm_head's output at M = batch; vocab <= ld) in TWO launches (csrc/sampling.hip), so that a

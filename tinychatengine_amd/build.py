@@ -52,8 +52,11 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         # (the fourth and fifth names: the windowed multi-row step, fp16 and e4m3 -- written out, though the second and first names are their prefixes)
                                         "attention_fast.hip": ["attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1E",
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1ELb1E",
-                                                               "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1ELb1ELb1E", "kv_pages_copy_fp8_kernel"],
-                                        "attention_prefill.hip": ["attn_prefill_paged_fp8_kernel", "attn_prefill_paged_window_kernel", "attn_prefill_prepare_kernelILb1ELb1E"],
+                                                               "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1ELb1ELb1E", "kv_pages_copy_fp8_kernel",
+                                                               # (the sink step, fp16 -- the e4m3 one has the first name as a prefix.  SINK is the kernel's LAST template parameter: every
+                                                               #  name above is still a prefix of the instantiation it was written for)
+                                                               "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1ELb1E"],
+                                        "attention_prefill.hip": ["attn_prefill_paged_fp8_kernel", "attn_prefill_paged_window_kernel", "attn_prefill_paged_sink_kernel", "attn_prefill_prepare_kernelILb1ELb1E"],
                                         "w4a16_gemv_i8_token.hip": ["w4a16_gemv_i8_token_kernelILb0E"],  # (ILb1E: the lab build's instantiation with wall-clock stamps)
                                         # round 5: EVERY instantiation of the decode kernel, the general-zero-point forms included (round 4 let four of them spill 3-19 registers: each
                                         # spilled scale / zero-point load became load -> wait -> scratch store, i.e. the wave's requests went out one at a time)

@@ -81,6 +81,14 @@ struct PagedRowsWindowAttnArgs : PagedRowsAttnArgs {
     int window;  // >= 1
 };
 
+// the windowed paged step with attention sinks: the windowed step's arguments and S = sinks, 1 .. 16.  A row at position p BINDS iff p >= S + W: it then weighs keys
+// 0 .. S - 1, scored with q rotated by cos / sin row S + W - 1, and keys p - W + 1 .. p, scored with q rotated by row p; a row that does not bind weighs keys 0 .. p
+// (include/tce_matmul.h, "Attention sinks").  chunk / chunks were cut by attention_sink_cut_keys
+struct PagedSinkAttnArgs : PagedWindowAttnArgs {
+    int sinks;     // 1 .. 16
+    int sink_row;  // min(S + W - 1, pos_bound): the cos / sin row of the second rotation (beyond pos_bound no row binds and the rotation is not used)
+};
+
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
     auto dpp = [](float x, auto ctrl) {
         return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, false));
@@ -166,10 +174,21 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 // weighs nothing, like any key below lo.  When the window lies wholly inside the call's rows (lo_t >= pos - tprev) the pool range [lo_t, pos - tprev - 1] is empty: the
 // rows the fetch reads at and beyond position p -- other workgroups of this launch are writing them -- are all replaced from LDS or invalid, none is weighted.  The
 // table words follow the position word as in WINDOW, words lo_t / page_keys .. pos / page_keys of table row b; the workgroup order is WINDOW's (blockIdx.x alone).
-template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false, bool WINDOW = false>
-__global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
-    const std::conditional_t<WINDOW, std::conditional_t<ROWS, PagedRowsWindowAttnArgs, PagedWindowAttnArgs>,
-                             std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>>> a) {
+// SINK (with WINDOW, PAGED, !ROWS; PagedSinkAttnArgs): a binding row weighs keys 0 .. S - 1 (the sinks) beside its window, the sinks scored with a SECOND rotation of q (cos /
+// sin row S + W - 1, a launch constant requested with the prologue batch: R * 4 registers and two 16-byte loads).  The workgroups walk a VIRTUAL key sequence: with
+// S4 = (S + 3) & ~3 and base2 = lo & ~3, virtual index v < S4 is key v (valid iff v < S) and v >= S4 is key base2 + (v - S4) (valid iff >= lo); for a row that does not
+// bind S4 = lo = base2 = 0 and virtual equals actual: the unwindowed row.  Chunk slots, waves, blocks, both merges and the counters are the text above applied to v; only
+// the fetch turns v into a key.  A group of four is wholly sink or wholly window (S4 is a multiple of 4), and S4 <= 16 = a block, so sink groups lie in the FIRST block of
+// the waves whose run starts below S4 (wave 0 of chunk slot 0 when a wave's run is 16 keys or more): every wave's first block takes consume()'s sink form, which picks the
+// query per step, wave-uniformly; every other block is the windowed text.  TABLE WORDS: word 0 (lane 62: S <= 16 <= page_keys, the sinks lie in its page) and lo / page_keys .. pos /
+// page_keys, indices clamped into that set.  Rows S .. S4 - 1 of word 0's page and rows base2 .. lo - 1 are loaded and weigh nothing (value rows zeroed: the rare-block text).
+template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false, bool WINDOW = false, bool SINK = false>
+// (waves per SIMD: the sink forms are pinned to the windowed step's 4 -- left alone the fp16 one takes 141 registers for the second copy of consume() and runs 3; 1 .. 8
+//  leaves every other form alone)
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SINK ? 4 : 1, SINK ? 4 : 8))) void attn_decode_fast_kernel(
+    const std::conditional_t<SINK, PagedSinkAttnArgs, std::conditional_t<WINDOW, std::conditional_t<ROWS, PagedRowsWindowAttnArgs, PagedWindowAttnArgs>,
+                             std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>>>> a) {
+    static_assert(!SINK || (WINDOW && !ROWS), "sinks exist beside a window, on the one-row step");
     static_assert(!WINDOW || (PAGED && NW == 4), "a window exists on the paged steps only");
     static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
     static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
@@ -231,13 +250,29 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
             return;
         }
     }
-    const int keys = pos + 1;
+    int keys = pos + 1;  // (SINK: the virtual keys, below)
     // WINDOW: the first key that weighs, and the first key of the workgroups' range (a multiple of four: the groups of four stay aligned); else 0
+    // SINK: of a binding row; a row that does not bind is the unwindowed row
     [[maybe_unused]] const int lo = [&]() -> int {
-        if constexpr (WINDOW) return pos - a.window + 1 > 0 ? pos - a.window + 1 : 0;
+        if constexpr (SINK) return pos - a.window >= a.sinks ? pos - a.window + 1 : 0;
+        else if constexpr (WINDOW) return pos - a.window + 1 > 0 ? pos - a.window + 1 : 0;
         else return 0;
     }();
-    const int base = WINDOW ? lo & ~3 : 0;
+    const int base = WINDOW && !SINK ? lo & ~3 : 0;
+    // SINK: S and S4 of a binding row (else 0); what turns a virtual index at or beyond S4 into its key; the virtual index of key lo.  The range below (keys, key0, kw0,
+    // kw1 ..) is virtual, kpos the row's own virtual index
+    [[maybe_unused]] const int snk = [&]() -> int {
+        if constexpr (SINK) return pos - a.window >= a.sinks ? a.sinks : 0;
+        else return 0;
+    }();
+    [[maybe_unused]] const int s4 = (snk + 3) & ~3;
+    [[maybe_unused]] const int vshift = SINK ? (lo & ~3) - s4 : 0;
+    [[maybe_unused]] const int vlo = SINK ? lo - vshift : lo;
+    int kpos = pos;
+    if constexpr (SINK) {
+        kpos = pos - vshift;
+        keys = kpos + 1;
+    }
     // ROWS: the rows of this sequence in front of this one, all in flight in this launch (keys pos - tprev .. pos - 1)
     [[maybe_unused]] const int tprev = ROWS ? ((int)blockIdx.y < pos ? (int)blockIdx.y : pos) : 0;
     const int chunks = a.pos_dev ? (keys - base + a.chunk - 1) / a.chunk : a.chunks;  // active chunks (<= the grid's chunk slots)
@@ -246,9 +281,15 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         // the table words, behind the position (see above): of an active row, words lo / page_keys .. pos / page_keys and no other
         const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l_ = threadIdx.x & 63;
         const int e_lo = lo >> a.page_shift, e_hi = pos >> a.page_shift;
-        tab_e0 = (base + c * a.chunk + w_ * (a.chunk / NW)) >> a.page_shift;
+        if constexpr (SINK) {  // (the wave's first window key; lane 62: word 0, the sinks' page -- a wave's run spans at most 17 words)
+            const int v0 = c * a.chunk + w_ * (a.chunk / NW);
+            tab_e0 = ((v0 < s4 ? s4 : v0) + vshift) >> a.page_shift;
+        } else {
+            tab_e0 = (base + c * a.chunk + w_ * (a.chunk / NW)) >> a.page_shift;
+        }
         int e = l_ == 63 ? e_hi : tab_e0 + l_;
         e = e < e_lo ? e_lo : (e > e_hi ? e_hi : e);
+        if constexpr (SINK) e = l_ == 62 ? 0 : e;
         tabw = a.table[(size_t)tseq * a.table_stride + e];
     }
     const int head = (grp * R) / a.rep;  // the key / value head
@@ -289,10 +330,17 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
                 // is clamped to keys - 1, which then lies in the same group (kw1 is a multiple of 4 or keys itself) and so in the same page.  g >= kw1: nothing of
                 // the group is weighted; it is read from rows 0 .. 3 of word 0's page (lane 63) -- never from a word past pos / page_keys.
                 // WINDOW: g >= base, so g / page_keys >= lo / page_keys too (base and lo share a group of four, hence a page); lane 63 holds word pos / page_keys.
+                // SINK: g is virtual.  A sink group (g < s4 <= kw1's group: never clamped) is keys g .. g + 3 of word 0's page (lane 62); a window group is keys
+                // g + vshift .., and a slot clamped to keys - 1 = kpos stays in its group as above
                 const int g = kw0 + it0 + u * 4;
                 const bool live = g < kw1;
-                const int page = __builtin_amdgcn_readlane(tabw, __builtin_amdgcn_readfirstlane(live ? (g >> a.page_shift) - tab_e0 : 63));
-                const size_t off = page_row(page, live ? (kk & ((1 << a.page_shift) - 1)) : slot) + piece * 8;
+                const int page = [&]() -> int {
+                    if constexpr (SINK)
+                        return __builtin_amdgcn_readlane(tabw, __builtin_amdgcn_readfirstlane(live ? (g < s4 ? 62 : ((g + vshift) >> a.page_shift) - tab_e0) : 63));
+                    else return __builtin_amdgcn_readlane(tabw, __builtin_amdgcn_readfirstlane(live ? (g >> a.page_shift) - tab_e0 : 63));
+                }();
+                const int krow = SINK ? (g < s4 ? kk : kk + vshift) : kk;
+                const size_t off = page_row(page, live ? (krow & ((1 << a.page_shift) - 1)) : slot) + piece * 8;
                 if constexpr (FP8) {  // (an element is a byte: the same offset counts bytes)
                     kd[u] = *reinterpret_cast<const uint2_t *>(reinterpret_cast<const unsigned char *>(a.kc) + off);
                     vd[u] = *reinterpret_cast<const uint2_t *>(reinterpret_cast<const unsigned char *>(a.vc) + off);
@@ -340,6 +388,11 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         cck = ld8(cpk + piece * 8);
         ssk = ld8(spk + piece * 8);
     }
+    [[maybe_unused]] half8_t ccs, sss;  // SINK: the pieces of cos / sin row S + W - 1
+    if constexpr (SINK) {
+        ccs = ld8((rope ? a.cosv + (size_t)a.sink_row * kHD : xq) + piece * 8);
+        sss = ld8((rope ? a.sinv + (size_t)a.sink_row * kHD : xq) + piece * 8);
+    }
     __builtin_amdgcn_sched_barrier(0);
     fetch(kbuf[0], vbuf[0], mbuf[0], 0);  // (the row at index pos may not be in the cache yet: consume() takes it from LDS)
     // (Round 4, tried: the SECOND block requested here too, so that a wave's first 32 keys cost one memory round trip instead of two.  Slower at every context, in
@@ -351,6 +404,11 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
     half8_t qh[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) qh[r] = rope ? rope_apply(q_v[r], q_p[r], cc, ss, piece) : q_v[r];
+    [[maybe_unused]] half8_t qs[R];  // SINK: the same raw q rotated with row S + W - 1, for the sink keys
+    if constexpr (SINK) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) qs[r] = rope ? rope_apply(q_v[r], q_p[r], ccs, sss, piece) : q_v[r];
+    }
     // ---- the new key / value of this head: into LDS for this workgroup's use, into the cache by the workgroup that owns index pos ----
     if (ROWS ? wave * 4 + slot <= tprev : wave == 0) {
         half8_t kh;
@@ -367,7 +425,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         if (ROWS || slot == 0) {
             *reinterpret_cast<half8_t *>(&newrow[nj][0][piece * 8]) = kh;
             *reinterpret_cast<half8_t *>(&newrow[nj][1][piece * 8]) = vh;
-            if ((!ROWS || nj == tprev) && appends && pos >= key0 && pos < key1) {
+            if ((!ROWS || nj == tprev) && appends && kpos >= key0 && kpos < key1) {
                 if constexpr (PAGED) {
                     // the page that holds index pos: word pos / page_keys, the last one the row owns (a wave-uniform load that depends on the position word, beside
                     // the cos / sin pieces which do too: it delays this store, not the cache requests)
@@ -400,7 +458,9 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
     // of the accumulators, then the four weighted value rows as fused multiply-adds that take the binary16 value straight from its register (v_fma_mix_f32).  The
     // step-by-step form this replaces -- a rescale, two exponentials and 8 conversions per step -- was bound by exactly that arithmetic: 58 vector instructions per
     // step, one wave per SIMD, 0.62 us per block against a memory round trip of about the same length (profiles/r4/attention_block_softmax_ab.jsonl).
-    auto consume = [&](const row_t (&kd)[BLK], const row_t (&vd)[BLK], const half_t (&md)[BLK], int it0) {
+    // sink_blk (SINK; a constant at each call: true for a wave's first block alone): step u takes the second query when its group is a sink group -- the scores' text
+    // twice, everything else once
+    auto consume = [&](const bool sink_blk, const row_t (&kd)[BLK], const row_t (&vd)[BLK], const half_t (&md)[BLK], int it0) {
         half8_t kk[BLK], vv[BLK];
         float sco[R][BLK];
         bool valid[BLK];
@@ -418,18 +478,19 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         // the rare blocks -- the one that runs past the wave's range, the one that holds the token's own row -- are told apart by a wave-uniform test, so the
         // others carry no per-slot validity arithmetic at all
         const int b0 = kw0 + it0;
-        if (b0 + BLK * 4 > kw1 || (pos >= b0 && pos - tprev < b0 + BLK * 4) || (WINDOW && b0 < lo)) {  // (tprev: 0 unless ROWS; WINDOW: the block of keys base .. lo - 1)
+        if (b0 + BLK * 4 > kw1 || (ROWS ? (pos >= b0 && pos - tprev < b0 + BLK * 4) : (kpos >= b0 && kpos < b0 + BLK * 4)) || (WINDOW && b0 < vlo)) {  // (tprev: 0 unless ROWS; WINDOW: the block of keys base .. lo - 1; SINK: and of the sinks)
 #pragma unroll
             for (int u = 0; u < BLK; ++u) {
                 const int key = b0 + u * 4 + slot;
                 valid[u] = key < kw1;
-                if constexpr (WINDOW) valid[u] = valid[u] && key >= lo;
+                if constexpr (SINK) valid[u] = valid[u] && (key >= vlo || key < snk);
+                else if constexpr (WINDOW) valid[u] = valid[u] && key >= lo;
                 if constexpr (ROWS) {
                     if (key >= pos - tprev && key <= pos) {  // this launch's rows of the sequence: in LDS, in the pool only once their workgroups have run
                         kk[u] = *reinterpret_cast<const half8_t *>(&newrow[key - (pos - tprev)][0][piece * 8]);
                         vv[u] = *reinterpret_cast<const half8_t *>(&newrow[key - (pos - tprev)][1][piece * 8]);
                     }
-                } else if (key == pos) {  // the token's own row: not necessarily visible in the cache yet
+                } else if (key == kpos) {  // the token's own row: not necessarily visible in the cache yet
                     kk[u] = *reinterpret_cast<const half8_t *>(&newrow[0][0][piece * 8]);
                     vv[u] = *reinterpret_cast<const half8_t *>(&newrow[0][1][piece * 8]);
                 }
@@ -438,19 +499,41 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
                 if (!valid[u]) vv[u] = half8_t{(half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0};
             }
         }
+        if (SINK && sink_blk) {  // (the loop below with the step's query picked; SINK only)
+            if constexpr (SINK) {
 #pragma unroll
-        for (int u = 0; u < BLK; ++u) {
+                for (int u = 0; u < BLK; ++u) {
+                    const bool sg = b0 + u * 4 < s4;  // (wave-uniform)
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                float d = 0.f;
+                    for (int r = 0; r < R; ++r) {
+                        const half8_t qq = sg ? qs[r] : qh[r];
+                        float d = 0.f;
 #pragma unroll
-                for (int e = 0; e < 8; e += 2) d = __builtin_amdgcn_fdot2(half2_t{qh[r][e], qh[r][e + 1]}, half2_t{kk[u][e], kk[u][e + 1]}, d, false);
-                d = row16_sum(d);
-                float sv = a.alpha * d;
-                if constexpr (MASK) sv += (float)md[u];
-                if (!(__builtin_fabsf(sv) <= 65504.0f)) sv = -65504.0f;  // check_inf_half (Int4llamaAttention.cu:105-115): inf / nan / beyond binary16 -> -65504
-                if (!valid[u]) sv = kNegBig;
-                sco[r][u] = sv;
+                        for (int e = 0; e < 8; e += 2) d = __builtin_amdgcn_fdot2(half2_t{qq[e], qq[e + 1]}, half2_t{kk[u][e], kk[u][e + 1]}, d, false);
+                        d = row16_sum(d);
+                        float sv = a.alpha * d;
+                        if constexpr (MASK) sv += (float)md[u];
+                        if (!(__builtin_fabsf(sv) <= 65504.0f)) sv = -65504.0f;  // check_inf_half (Int4llamaAttention.cu:105-115): inf / nan / beyond binary16 -> -65504
+                        if (!valid[u]) sv = kNegBig;
+                        sco[r][u] = sv;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < BLK; ++u) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    float d = 0.f;
+#pragma unroll
+                    for (int e = 0; e < 8; e += 2) d = __builtin_amdgcn_fdot2(half2_t{qh[r][e], qh[r][e + 1]}, half2_t{kk[u][e], kk[u][e + 1]}, d, false);
+                    d = row16_sum(d);
+                    float sv = a.alpha * d;
+                    if constexpr (MASK) sv += (float)md[u];
+                    if (!(__builtin_fabsf(sv) <= 65504.0f)) sv = -65504.0f;  // check_inf_half (Int4llamaAttention.cu:105-115): inf / nan / beyond binary16 -> -65504
+                    if (!valid[u]) sv = kNegBig;
+                    sco[r][u] = sv;
+                }
             }
         }
 #pragma unroll
@@ -477,12 +560,27 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fast_kernel(
         }
     };
     // per_wave is a multiple of 4 (steps); blocks of 4 steps, the last one possibly past the range (clamped loads, zero weights)
-    for (int it = 0; it < per_wave; it += 2 * BLK * 4) {
-        fetch(kbuf[1], vbuf[1], mbuf[1], it + BLK * 4);
-        consume(kbuf[0], vbuf[0], mbuf[0], it);
-        if (it + BLK * 4 >= per_wave) break;
-        fetch(kbuf[0], vbuf[0], mbuf[0], it + 2 * BLK * 4);
-        consume(kbuf[1], vbuf[1], mbuf[1], it + BLK * 4);
+    // SINK: sink groups lie in a wave's FIRST block only (s4 <= 16), so that block is peeled off the loop and takes the sink form in every wave -- a wave-uniform select
+    // of the query per step; the loop behind it carries nothing for the sinks.  (Measured against a wave-uniform branch on the first block inside the loop: the same
+    // time, 7 registers fewer -- profiles/sink/sink_time.jsonl and DESIGN.md section 5 say what the sink step costs over the windowed one, and that the cause is not found.)
+    if constexpr (SINK) {
+        fetch(kbuf[1], vbuf[1], mbuf[1], BLK * 4);
+        consume(true, kbuf[0], vbuf[0], mbuf[0], 0);
+        for (int it = BLK * 4; it < per_wave; it += 2 * BLK * 4) {  // (the loop below, one block on: the buffers have changed places)
+            fetch(kbuf[0], vbuf[0], mbuf[0], it + BLK * 4);
+            consume(false, kbuf[1], vbuf[1], mbuf[1], it);
+            if (it + BLK * 4 >= per_wave) break;
+            fetch(kbuf[1], vbuf[1], mbuf[1], it + 2 * BLK * 4);
+            consume(false, kbuf[0], vbuf[0], mbuf[0], it + BLK * 4);
+        }
+    } else {
+        for (int it = 0; it < per_wave; it += 2 * BLK * 4) {
+            fetch(kbuf[1], vbuf[1], mbuf[1], it + BLK * 4);
+            consume(false, kbuf[0], vbuf[0], mbuf[0], it);
+            if (it + BLK * 4 >= per_wave) break;
+            fetch(kbuf[0], vbuf[0], mbuf[0], it + 2 * BLK * 4);
+            consume(false, kbuf[1], vbuf[1], mbuf[1], it + BLK * 4);
+        }
     }
     // ---- merge the workgroup's 4 * NW states, per query head ----
 #pragma unroll
@@ -770,6 +868,21 @@ void describe_attention_decode_window(int heads, int kv_heads, int pos_bound, in
     describe_attention_decode_batch(heads, kv_heads, attention_window_cut_keys(pos_bound, window) - 1, chunk, chunks, waves);
 }
 
+// the sink step's cut: the same rule for the VIRTUAL keys a workgroup group can span (no HIP call).  A binding row's are S4 + (pos - base2 + 1) <= S4 + window + 3; a row
+// that does not bind has its pos + 1 <= pos_bound + 1 keys.  While no row of the launch can bind (sinks + window > pos_bound) that is the unwindowed step's cut, chunk for
+// chunk.  Else min(pos_bound + 1, S4 + window + 3) -- plus the S4 - ((S + 1) & ~3) keys (0 or 4) by which a binding row's virtual sequence can be LONGER than pos + 1: its
+// first window group may start below S4 (S = 5, lo = 6: sinks in groups 0 and 4, the window's first group is 4 again)
+int attention_sink_cut_keys(int pos_bound, int window, int sinks) {
+    const long long s4 = (sinks + 3) & ~3, all = (long long)pos_bound + 1;
+    if ((long long)sinks + window > pos_bound) return (int)all;
+    const long long bound = all + (s4 - ((sinks + 1) & ~3)), span = s4 + window + 3;
+    const long long cut = span < bound ? span : bound;
+    return (int)(cut < 0x7fffffffLL ? cut : 0x7fffffffLL);
+}
+void describe_attention_decode_sink(int heads, int kv_heads, int pos_bound, int window, int sinks, int *chunk, int *chunks, int *waves) {
+    describe_attention_decode_batch(heads, kv_heads, attention_sink_cut_keys(pos_bound, window, sinks) - 1, chunk, chunks, waves);
+}
+
 size_t attention_decode_batch_workspace_bytes(int batch, int heads, int max_keys, int hd) {
     if (batch <= 0) return 0;
     return (size_t)batch * attention_decode_workspace_bytes(heads, max_keys, hd);
@@ -857,9 +970,11 @@ __global__ __launch_bounds__(256) void kv_pages_copy_fp8_kernel(half_t *k_lin, h
 // *violations = the number of table words an active row would follow that are not page numbers, plus the active rows whose position needs a word past the row
 // (one workgroup: the tables are a few thousand words)
 // WINDOW: of the words a WINDOWED row would follow, lo / page_keys .. pos / page_keys (lo = max(0, pos - window + 1)); else from word 0 (`window` unused)
-template <bool WINDOW>
+// SINK (with WINDOW): of the words a sink row would follow -- one that binds (pos >= sinks + window) word 0 and lo / page_keys .. pos / page_keys, one that does not
+// words 0 .. pos / page_keys
+template <bool WINDOW, bool SINK = false>
 __global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *table, int table_stride, int page_shift, int num_pages, int batch, const int *pos_dev,
-                                                                    int pos_bound, unsigned *violations, int window) {
+                                                                    int pos_bound, unsigned *violations, int window, int sinks = 0) {
     __shared__ unsigned bad;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
@@ -872,7 +987,13 @@ __global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *t
             if (threadIdx.x == 0) ++mine;
             last = table_stride - 1;
         }
-        const int first = WINDOW && pos - window + 1 > 0 ? (pos - window + 1) >> page_shift : 0;
+        const int first = WINDOW && (SINK ? pos - window >= sinks : pos - window + 1 > 0) ? (pos - window + 1) >> page_shift : 0;
+        if constexpr (SINK) {
+            if (first > 0 && threadIdx.x == 0) {
+                const int page = table[(size_t)b * table_stride];
+                if (page < 0 || page >= num_pages) ++mine;
+            }
+        }
         for (int e = first + threadIdx.x; e <= last; e += 1024) {
             const int page = table[(size_t)b * table_stride + e];
             if (page < 0 || page >= num_pages) ++mine;
@@ -946,8 +1067,10 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
     a.table = pg.table;
     a.table_stride = table_stride;
     a.page_shift = shift;
+    if (s.sinks && (!s.window || rows || s.sinks < 1 || s.sinks > 16)) return TCE_ERR_UNSUPPORTED_SHAPE;
     int nw = 4;
-    if (s.window) describe_attention_decode_window(heads, kv_heads, pos_bound, s.window, &a.chunk, &a.chunks, &nw);
+    if (s.sinks) describe_attention_decode_sink(heads, kv_heads, pos_bound, s.window, s.sinks, &a.chunk, &a.chunks, &nw);
+    else if (s.window) describe_attention_decode_window(heads, kv_heads, pos_bound, s.window, &a.chunk, &a.chunks, &nw);
     else describe_attention_decode_batch(heads, kv_heads, pos_bound, &a.chunk, &a.chunks, &nw);
     if (a.chunks > 1024 || nw != 4) return TCE_ERR_UNSUPPORTED_SHAPE;
     half_t ah;
@@ -966,6 +1089,15 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, rows, batch);  // (the windowed step's padded x, the rows step's y and z)
         if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, true, true>), grid, dim3(256), 0, stream, w);
         else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, true, true>), grid, dim3(256), 0, stream, w);
+    } else if (s.sinks) {
+        PagedSinkAttnArgs w{};
+        static_cast<PagedFp8AttnArgs &>(w) = a;
+        w.window = s.window;
+        w.sinks = s.sinks;
+        w.sink_row = (long long)s.sinks + s.window - 1 < (long long)pos_bound ? s.sinks + s.window - 1 : pos_bound;
+        const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, batch);  // (the windowed step's grid)
+        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, false, true, true>), grid, dim3(256), 0, stream, w);
+        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, false, true, true>), grid, dim3(256), 0, stream, w);
     } else if (s.window) {
         PagedWindowAttnArgs w{};
         static_cast<PagedFp8AttnArgs &>(w) = a;
@@ -1012,10 +1144,12 @@ int launch_kv_pages_copy(const KvPages &pg, const KvLinear &lin, bool gather, in
     return TCE_OK;
 }
 
-int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err, int window) {
+int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err, int window,
+                                int sinks) {
     const int shift = page_shift_of(pg.page_keys);
-    if (shift < 0 || pg.table_stride < 1 || batch < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
-    if (window > 0) hipLaunchKernelGGL(kv_block_table_check_kernel<true>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, window);
+    if (shift < 0 || pg.table_stride < 1 || batch < 1 || (sinks && window < 1)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (sinks > 0) hipLaunchKernelGGL((kv_block_table_check_kernel<true, true>), dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, window, sinks);
+    else if (window > 0) hipLaunchKernelGGL(kv_block_table_check_kernel<true>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, window);
     else hipLaunchKernelGGL(kv_block_table_check_kernel<false>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, 0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -253,6 +253,15 @@ struct PagedBlockWindowArgs : PagedBlockFp8Args {
     int window;  // >= 1
 };
 
+// the sink form's (attention sinks beside the window): row i at p = pos + i BINDS iff p >= sinks + window and then weighs keys 0 .. sinks - 1, scored with its raw q rotated
+// by cos / sin row sinks + window - 1, beside keys p - window + 1 .. p; a row that does not bind weighs keys 0 .. p
+struct PagedBlockSinkArgs : PagedBlockWindowArgs {
+    int sinks;                    // 1 .. 16
+    const half_t *qkv;            // the launch's raw rows [total_rows][ld_qkv]: the second rotation is made from them in registers
+    int ld_qkv;
+    const half_t *cos_s, *sin_s;  // row sinks + window - 1 of the tables, or null (no rotation: the second query is the first)
+};
+
 // what differs between the forms in the statements they share: the row count and first row of the segment inside qrot / out, and a key / value head's base
 __device__ __forceinline__ int qrows(const PrefillArgs &a) { return a.m; }
 __device__ __forceinline__ int qrows(const PagedBlockArgs &a) { return a.total_rows; }
@@ -277,6 +286,8 @@ struct TileWords<true> {
         const int e = (kt * kBK + 16 * (lane & 3)) >> a.page_shift;
         v = a.trow[e < lastw ? e : lastw];
     }
+    // SINK: the sink pass's tile -- keys 0 .. sinks - 1 <= 15, all in word 0's page
+    __device__ __forceinline__ void request_word0(const PagedBlockArgs &a) { v = a.trow[0]; }
     // WINDOW: additionally clamped from below to the word of the block's first visible key, `firstw`: words under it may name pages that were given back
     __device__ __forceinline__ void request_from(const PagedBlockArgs &a, int kt, int kend, int lane, int firstw) {
         const int lastw = (kend - 1) >> a.page_shift;
@@ -294,8 +305,14 @@ struct TileWords<true> {
 // WINDOW (with PAGED, causal launches only): sliding-window attention (PagedBlockWindowArgs).  The block walks key tiles from the tile of klo = lo(its first row) to the
 // tile of its last row's position; tiles wholly below are neither requested nor computed, and keys below klo -- which may lie in pages that were given back -- are staged
 // as zeros like the keys at and beyond kend.  The lower bound is tested on the tiles that hold a key below the lo of one of the wave's rows: the causal diagonal's `edge`.
-template <bool MASK, int NW, int RT, bool PAGED = false, bool FP8 = false, bool WINDOW = false>
-__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WINDOW, PagedBlockWindowArgs, std::conditional_t<FP8, PagedBlockFp8Args, std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs>>> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+// SINK (with WINDOW; PagedBlockSinkArgs): the window pass is the windowed block's with lo_r = 0 for a row that does not bind (klo: the lo of the block's FIRST row, 0 if that
+// row does not bind).  A block whose last row binds then makes one SINK PASS, the loop's last iteration (index ntiles): key tile 0 with keys >= sinks staged as zeros, scored
+// against Q_s -- the rows' raw q rotated with row sinks + window - 1, made in registers from qkv at the head of that iteration with the prepare kernel's binary16 statement
+// (a fragment's partner half qf[t][s ^ 2] is in the same lane) and put where Q was: no register is held for it through the window pass.  Keys >= sinks and rows that do not
+// bind are cut; a fully cut tile leaves a row's state as it was.  A block none of whose rows binds walks exactly the windowed block's tiles.
+template <bool MASK, int NW, int RT, bool PAGED = false, bool FP8 = false, bool WINDOW = false, bool SINK = false>
+__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<SINK, PagedBlockSinkArgs, std::conditional_t<WINDOW, PagedBlockWindowArgs, std::conditional_t<FP8, PagedBlockFp8Args, std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs>>>> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+    static_assert(!SINK || WINDOW, "sinks exist beside a window");
     static_assert(!PAGED || !MASK, "the paged form takes no additive mask");
     static_assert(!WINDOW || PAGED, "a window exists on pages only");
     static_assert(!FP8 || PAGED, "e4m3 caches exist as pages only");
@@ -313,10 +330,14 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
     const int ntiles = (kend + kBK - 1) / kBK;
     // WINDOW: the first key the block's first row weighs -- no row of the block weighs an earlier one -- and its tile; else 0
     [[maybe_unused]] const int klo = [&]() -> int {
-        if constexpr (WINDOW) return a.pos + qb * kBQ - a.window + 1 > 0 ? a.pos + qb * kBQ - a.window + 1 : 0;
+        if constexpr (SINK) return a.pos + qb * kBQ - a.window >= a.sinks ? a.pos + qb * kBQ - a.window + 1 : 0;
+        else if constexpr (WINDOW) return a.pos + qb * kBQ - a.window + 1 > 0 ? a.pos + qb * kBQ - a.window + 1 : 0;
         else return 0;
     }();
     const int kt0 = WINDOW ? klo / kBK : 0;
+    // SINK: the tiles of the loop, the sink pass (index ntiles) included when the block's last row binds
+    int nt_all = ntiles;
+    if constexpr (SINK) nt_all += a.pos + last_row - a.window >= a.sinks ? 1 : 0;
     const float scale2 = a.alpha * kLog2e;  // scores in units of log2: exp(x) = exp2(x * log2 e), one v_exp_f32 per probability
 
     // Q fragments of row tile t: row r0 + 16 t + n16 (clamped), head dimensions 32 s + 8 quad ..; that row is also the lane's softmax row
@@ -348,7 +369,14 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
     using piece_t = std::conditional_t<FP8, uint2_t, half8_t>;  // a lane's 8 elements of a row between request and LDS write
     piece_t kreg[KI], vreg[KI];
     auto fetch_tile = [&](int kt) {
-        const int key0 = kt * kBK;
+        const bool sink_tile = [&]() -> bool {  // (SINK: the sink pass reads tile 0, keys 0 .. sinks - 1 of it)
+            if constexpr (SINK) return kt == ntiles;
+            else return false;
+        }();
+        const int key0 = [&]() -> int {
+            if constexpr (SINK) return sink_tile ? 0 : kt * kBK;
+            else return kt * kBK;
+        }();
 #pragma unroll
         for (int i = 0; i < KI; ++i) {
             const int idx = tid + NT * i, gk = key0 + (idx >> 4);
@@ -359,7 +387,11 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
                 kreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
                 vreg[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
             }
-            if (gk < kend && (!WINDOW || gk >= klo)) {
+            const bool wanted = [&]() -> bool {
+                if constexpr (SINK) return sink_tile ? gk < a.sinks : (gk < kend && gk >= klo);
+                else return gk < kend && (!WINDOW || gk >= klo);
+            }();
+            if (wanted) {
                 if constexpr (PAGED) {
                     // the piece's run of the tile: i with 4 waves (a pass of 256 pieces is 16 keys), 2 i + wave / 4 with 8 -- wave-uniform, so the page is a scalar
                     const int page = NT == 256 ? tw.w[i] : (wave >= 4 ? tw.w[(2 * i + 1) & 3] : tw.w[(2 * i) & 3]);
@@ -382,7 +414,10 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
         }
     };
     [[maybe_unused]] auto request_words = [&](int kt) {
-        if constexpr (WINDOW) tw.request_from(a, kt, kend, lane, klo >> a.page_shift);
+        if constexpr (SINK) {
+            if (kt == ntiles) tw.request_word0(a);
+            else tw.request_from(a, kt, kend, lane, klo >> a.page_shift);
+        } else if constexpr (WINDOW) tw.request_from(a, kt, kend, lane, klo >> a.page_shift);
         else if constexpr (PAGED) tw.request(a, kt, kend, lane);
     };
     if constexpr (PAGED) {
@@ -393,8 +428,30 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
     if constexpr (PAGED) request_words(kt0 + 1);
     // this lane's piece of a [4 keys][16 head dimensions] block for the transpose read: key 4 quad + n16 / 4, head dimensions 4 (n16 % 4) ..
     const unsigned char *vfrag = vs + (4 * quad + (n16 >> 2)) * kVStride + (n16 & 3) * 8;
-    for (int kt = kt0; kt < ntiles; ++kt) {
-        const int key0 = kt * kBK;
+    for (int kt = kt0; kt < nt_all; ++kt) {
+        [[maybe_unused]] const bool sink_pass = SINK && kt == ntiles;
+        const int key0 = sink_pass ? 0 : kt * kBK;
+        if constexpr (SINK) {
+            if (sink_pass && a.cos_s) {  // Q becomes Q_s
+#pragma unroll
+                for (int t = 0; t < RT; ++t) {
+                    const half_t *qraw = a.qkv + (size_t)(qrow0(a) + rowc[t]) * a.ld_qkv + (size_t)head * kHD;
+                    half8_t raw[4];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) raw[s] = *reinterpret_cast<const half8_t *>(qraw + 32 * s + 8 * quad);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const half8_t c = *reinterpret_cast<const half8_t *>(a.cos_s + 32 * s + 8 * quad), sn = *reinterpret_cast<const half8_t *>(a.sin_s + 32 * s + 8 * quad);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const half_t rot = s < 2 ? (half_t)(-raw[s ^ 2][e]) : raw[s ^ 2][e];
+                            const half_t tt = rot * sn[e];                         // hmul
+                            qf[t][s][e] = __builtin_fmaf16(raw[s][e], c[e], tt);   // hfma, one rounding (the prepare kernel's statement)
+                        }
+                    }
+                }
+            }
+        }
         __syncthreads();  // everybody has read the previous tiles
         // ---- both tiles as they lie ----
 #pragma unroll
@@ -410,7 +467,7 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
         }
         if constexpr (PAGED) tw.latch();  // tile kt + 1's words arrived with tile kt's rows
         __syncthreads();
-        if (kt + 1 < ntiles) fetch_tile(kt + 1);
+        if (kt + 1 < nt_all) fetch_tile(kt + 1);
         if constexpr (PAGED) request_words(kt + 2);  // behind tile kt + 1's row requests, for the fetch a tile from now
         // ---- S^T = K Q^T (64 keys x this wave's 16 RT rows): a K fragment feeds the RT row tiles ----
         float4_t sacc[RT][4];
@@ -428,7 +485,8 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
         // does this tile hold keys some row of the wave must not see?  (wave-uniform; the last tile, and the tiles on the wave's causal diagonal)
         const bool edge = [&]() -> bool {
             const bool e = key0 + kBK > tgz || (a.causal && key0 + kBK - 1 > a.pos + r0);
-            if constexpr (WINDOW) return e || key0 < a.pos + r0 + 16 * RT - 1 - a.window + 1;  // (the lo of the wave's last row)
+            if constexpr (SINK) return sink_pass || e || (a.pos + r0 + 16 * RT - 1 - a.window >= a.sinks && key0 < a.pos + r0 + 16 * RT - 1 - a.window + 1);  // (if it binds)
+            else if constexpr (WINDOW) return e || key0 < a.pos + r0 + 16 * RT - 1 - a.window + 1;  // (the lo of the wave's last row)
             else return e;
         }();
         // ---- scale, mask, cut; online softmax: the lane's row is rowc[t], its keys key0 + 16 j + 4 quad + r ----
@@ -460,7 +518,10 @@ __device__ __forceinline__ void attn_prefill_block(const std::conditional_t<WIND
                     if (MASK || edge) {
                         const int key = key0 + 16 * j + 4 * quad + r;
                         cut = edge && !(key < tgz && !(a.causal && key > a.pos + rowc[t]));
-                        if constexpr (WINDOW) cut = cut || key < a.pos + rowc[t] - a.window + 1;
+                        if constexpr (SINK) {
+                            const bool binds = a.pos + rowc[t] - a.window >= a.sinks;
+                            cut = sink_pass ? !(binds && key < a.sinks) : (cut || (binds && key < a.pos + rowc[t] - a.window + 1));
+                        } else if constexpr (WINDOW) cut = cut || key < a.pos + rowc[t] - a.window + 1;
                     }
                     s = cut ? kNegBig : (in_range ? s : -65504.0f * kLog2e);
                     sacc[t][j][r] = s;
@@ -641,6 +702,41 @@ void attn_prefill_paged_window_kernel(const PagedPrefillWindowArgs a) {
     }
 }
 
+// The sink launch, fp16 and e4m3 pools: the same workgroups, block list and pairs.  (waves per SIMD: every form is pinned to its windowed counterpart's.)
+struct PagedPrefillSinkArgs : PagedPrefillWindowArgs {
+    int sinks;
+    const half_t *qkv;
+    int ld_qkv;
+    const half_t *cos_s, *sin_s;
+};
+template <bool FP8>
+__device__ __forceinline__ PagedBlockSinkArgs paged_block_args_sink(const PagedPrefillSinkArgs &a, const PrefillSegment sg) {
+    PagedBlockSinkArgs b;
+    static_cast<PagedBlockWindowArgs &>(b) = paged_block_args_window<FP8>(a, sg);
+    b.sinks = a.sinks;
+    b.qkv = a.qkv;
+    b.ld_qkv = a.ld_qkv;
+    b.cos_s = a.cos_s;
+    b.sin_s = a.sin_s;
+    return b;
+}
+template <int NW, int RT, bool PAIR, bool FP8>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FP8_WAVES(NW, RT, PAIR), FP8_WAVES(NW, RT, PAIR))))
+void attn_prefill_paged_sink_kernel(const PagedPrefillSinkArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile
+    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
+    const int i = (int)blockIdx.x;
+    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
+    attn_prefill_block<false, NW, RT, true, FP8, true, true>(paged_block_args_sink<FP8>(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
+    if constexpr (PAIR) {
+        const int j = a.nblocks - 1 - i;
+        if (i < j) {
+            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
+            attn_prefill_block<false, NW, RT, true, FP8, true, true>(paged_block_args_sink<FP8>(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
+        }
+    }
+}
+
 #undef FP8_WAVES
 
 thread_local int g_prefill_pair = 0;   // 0: by the rule; 1 / 2: pairing forced on / off
@@ -752,7 +848,10 @@ int prefill_page_shift(int page_keys) {  // log2 of a power of two in [16, 256],
 
 // form, pairing and the block list (heaviest first; ties: in segment order, a segment's later blocks first) of a paged launch; false: more blocks than the list holds
 // window >= 1 (causal): a block walks the tiles from the one of its first row's first visible key on -- those are what it is weighed by
-bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int nseg, int *form_out, int *pair_out, int *nblocks_out, unsigned short *order, int window = 0) {
+// sinks >= 1 (with a window): a row binds from position sinks + window on -- a block whose first row does not bind walks from tile 0, one whose last row binds walks the
+// sink pass's tile besides
+bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int nseg, int *form_out, int *pair_out, int *nblocks_out, unsigned short *order, int window = 0,
+                        int sinks = 0) {
     auto blocks = [&](int rows) {
         long long n = 0;
         for (int s = 0; s < nseg; ++s) n += (seg[s].m + rows - 1) / rows;
@@ -777,7 +876,8 @@ bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int ns
             tiles[n] = (kend + kBK - 1) / kBK;
             if (window > 0) {
                 const long long klo = (long long)seg[s].pos + (long long)qb * rows - window + 1;
-                tiles[n] -= klo > 0 ? (int)(klo / kBK) : 0;
+                tiles[n] -= klo > sinks ? (int)(klo / kBK) : 0;  // (sinks = 0: klo > 0; else the first row binds iff its lo >= sinks + 1)
+                if (sinks > 0 && (long long)seg[s].pos + last_row - window >= sinks) ++tiles[n];
             }
             order[n++] = (unsigned short)(s << 12 | qb);
         }
@@ -795,11 +895,11 @@ bool plan_paged_prefill(int heads, int causal, const PrefillSegment *seg, int ns
 
 size_t attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd) { return attention_prefill_workspace_bytes(heads, total_rows, hd); }
 
-int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups, int window) {
+int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups, int window, int sinks) {
     PrefillSegment seg[kMaxSegments];
     if (nseg < 1 || nseg > kMaxSegments || heads < 1) return TCE_ERR_BAD_ARG;
     __builtin_memcpy(seg, segments, sizeof(PrefillSegment) * nseg);
-    if (!plan_paged_prefill(heads, causal, seg, nseg, form, pair, nblocks, nullptr, window)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (!plan_paged_prefill(heads, causal, seg, nseg, form, pair, nblocks, nullptr, window, sinks)) return TCE_ERR_UNSUPPORTED_SHAPE;
     *workgroups = (*pair ? (*nblocks + 1) / 2 : *nblocks) * heads;
     return TCE_OK;
 }
@@ -823,13 +923,15 @@ int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, con
     if (shift < 0 || nseg < 1 || nseg > kMaxSegments || !table || table_stride < 1 || kv_heads <= 0 || heads % kv_heads != 0 || total_rows < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && (k_log2 < kFp8ScaleLog2Min || k_log2 > kFp8ScaleLog2Max || v_log2 < kFp8ScaleLog2Min || v_log2 > kFp8ScaleLog2Max)) return TCE_ERR_UNSUPPORTED_SHAPE;
     const int window = s.window;
-    if (window < 0 || (window && !causal)) return TCE_ERR_UNSUPPORTED_SHAPE;
-    PagedPrefillWindowArgs a{};
+    const int sinks = s.sinks;
+    if (window < 0 || (window && !causal) || sinks < 0 || sinks > 16 || (sinks && !window)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    PagedPrefillSinkArgs a{};
     a.window = window;
+    a.sinks = sinks;
     __builtin_memcpy(a.seg, r.segments, sizeof(PrefillSegment) * nseg);
     int form = 0;
     unsigned short order[kMaxListedBlocks] = {};
-    if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order, window)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (!plan_paged_prefill(heads, causal, a.seg, nseg, &form, &a.pair, &a.nblocks, order, window, sinks)) return TCE_ERR_UNSUPPORTED_SHAPE;
     for (int i = 0; i < a.nblocks; ++i) a.order[i >> 1] |= (unsigned)order[i] << ((i & 1) * 16);
     PagedPrepareFp8Args p{};
     p.qkv = static_cast<const half_t *>(s.qkv);
@@ -861,6 +963,12 @@ int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, con
     a.kc = p.kc;
     a.vc = p.vc;
     a.out = static_cast<half_t *>(s.out);
+    if (sinks) {  // (a row binds only at a position >= sinks + window: the tables then hold row sinks + window - 1; the pointers are followed by binding blocks alone)
+        a.qkv = p.qkv;
+        a.ld_qkv = p.ld_qkv;
+        a.cos_s = p.cosv ? p.cosv + ((size_t)sinks + window - 1) * kHD : nullptr;
+        a.sin_s = p.sinv ? p.sinv + ((size_t)sinks + window - 1) * kHD : nullptr;
+    }
     a.table = table;
     a.ld_out = r.ld_out;
     a.heads = heads;
@@ -876,13 +984,22 @@ int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, con
     auto go = [&](auto nw_c, auto rt_c) {
         constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
         const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
-        if (window) {
+        if (sinks) {
             if (fp8) {
-                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, true>), grid, dim3(64 * NW), 0, stream, a);
-                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, true>), grid, dim3(64 * NW), 0, stream, a);
+                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, true, true>), grid, dim3(64 * NW), 0, stream, a);
+                else hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, false, true>), grid, dim3(64 * NW), 0, stream, a);
             } else {
-                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, false>), grid, dim3(64 * NW), 0, stream, a);
-                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, false>), grid, dim3(64 * NW), 0, stream, a);
+                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, true, false>), grid, dim3(64 * NW), 0, stream, a);
+                else hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, false, false>), grid, dim3(64 * NW), 0, stream, a);
+            }
+        } else if (window) {
+            const PagedPrefillWindowArgs &w = a;
+            if (fp8) {
+                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, true>), grid, dim3(64 * NW), 0, stream, w);
+                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, true>), grid, dim3(64 * NW), 0, stream, w);
+            } else {
+                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, false>), grid, dim3(64 * NW), 0, stream, w);
+                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, false>), grid, dim3(64 * NW), 0, stream, w);
             }
         } else if (fp8) {
             if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillFp8Args &>(a));

@@ -1315,7 +1315,12 @@ static int check_window(const char *who, const int *window) {
     return window && *window < 1 ? fail(TCE_ERR_BAD_ARG, "%s: window %d (>= 1: the last `window` keys, the row's own included)", who, *window) : TCE_OK;
 }
 
-static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, const int *rows_per_seq, void *stream, const int *window = nullptr) {
+// sinks null: none.  Else the sink step (attention sinks beside the window): its one rule of its own, 1 <= sinks <= 16, is tested behind every rule of the windowed entry point
+static int check_sinks(const char *who, const int *sinks) {
+    return sinks && (*sinks < 1 || *sinks > 16) ? fail(TCE_ERR_BAD_ARG, "%s: sinks %d (1 .. 16: the first keys of the sequence, all in the first page)", who, *sinks) : TCE_OK;
+}
+
+static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, const int *rows_per_seq, void *stream, const int *window = nullptr, const int *sinks = nullptr) {
     if (const int rc = check_pages(who, pg)) return rc;
     if (const int rc = check_row_keys(who, pg)) return rc;
     if (const int rc = check_window(who, window)) return rc;
@@ -1327,6 +1332,8 @@ static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs
                                                {"out", rows_per_seq ? s.out : nullptr}}))
         return rc;
     if (const int rc = check_aligned(who, 4, {{"pos_device", s.pos_device}, {"block_table", pg.table}})) return rc;
+    if (const int rc = check_sinks(who, sinks)) return rc;
+    s.sinks = sinks ? *sinks : 0;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_attention_decode_paged(pg, s, rows_per_seq ? *rows_per_seq : 0, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "paged attention decode step launch") : rc;
@@ -1369,6 +1376,32 @@ int tce_attention_decode_step_paged_window_fp8(const void *qkv, void *k_pool, vo
                                                void *stream) {
     return paged_step("tce_attention_decode_step_paged_window_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                       {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream, &window);
+}
+
+int tce_attention_decode_describe_paged_sink(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, int sinks, char *buf, int buf_len) {
+    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys) || window < 1)
+        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_paged_sink: bad argument");
+    if (const int rc = check_sinks("tce_attention_decode_describe_paged_sink", &sinks)) return rc;
+    int chunk = 0, chunks = 0, waves = 0;
+    tce::describe_attention_decode_sink(heads, kv_heads, pos_bound, window, sinks, &chunk, &chunks, &waves);
+    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
+                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
+    return TCE_OK;
+}
+
+int tce_attention_decode_step_paged_sink_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                             const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                             const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int window, int sinks, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_sink_f16", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream, &window, &sinks);
+}
+
+int tce_attention_decode_step_paged_sink_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                             const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
+                                             const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2, int window, int sinks,
+                                             void *stream) {
+    return paged_step("tce_attention_decode_step_paged_sink_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream, &window, &sinks);
 }
 
 int tce_attention_decode_step_paged_rows_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
@@ -1442,15 +1475,16 @@ int tce_kv_pages_gather_fp8(const void *k_pool, const void *v_pool, void *k_dst,
 }
 
 static int table_check(const char *who, const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
-                       uint32_t *violations, const int *window, void *stream) {
+                       uint32_t *violations, const int *window, void *stream, const int *sinks = nullptr) {
     const tce::KvPages pg{nullptr, nullptr, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0};
     if (!pos_device || !violations) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
     if (const int rc = check_pages(who, pg, false)) return rc;
     if (const int rc = check_window(who, window)) return rc;
     if (batch < 1 || pos_bound < 0) return fail(TCE_ERR_BAD_ARG, "%s: need batch >= 1 and pos_bound >= 0", who);
     if (const int rc = check_aligned(who, 4, {{"block_table", block_table}, {"pos_device", pos_device}, {"violations", violations}})) return rc;
+    if (const int rc = check_sinks(who, sinks)) return rc;
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_kv_block_table_check(pg, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he, window ? *window : 0);
+    const int rc = tce::launch_kv_block_table_check(pg, batch, pos_device, pos_bound, violations, static_cast<hipStream_t>(stream), &he, window ? *window : 0, sinks ? *sinks : 0);
     return rc == TCE_ERR_HIP ? hip_fail(he, "block table check launch") : rc;
 }
 
@@ -1462,6 +1496,11 @@ int tce_kv_block_table_check(const int32_t *block_table, int table_stride, int p
 int tce_kv_block_table_check_window(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
                                     uint32_t *violations, int window, void *stream) {
     return table_check("tce_kv_block_table_check_window", block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, &window, stream);
+}
+
+int tce_kv_block_table_check_sink(const int32_t *block_table, int table_stride, int page_keys, int num_pages, int batch, const int32_t *pos_device, int pos_bound,
+                                  uint32_t *violations, int window, int sinks, void *stream) {
+    return table_check("tce_kv_block_table_check_sink", block_table, table_stride, page_keys, num_pages, batch, pos_device, pos_bound, violations, &window, stream, &sinks);
 }
 
 size_t tce_sample_workspace_bytes(int batch, int vocab) { return batch < 1 || batch > 65535 || vocab < 1 || vocab > (1 << 20) ? 0 : tce::sample_workspace_bytes(batch, vocab); }
@@ -1812,7 +1851,7 @@ const char *tce_attention_prefill_describe_paged(int heads, int kv_heads, int ca
 
 // r: ld_qkv / ld_out 0 = dense.  The only entry point that knows the table's row count: a segment names its slot.
 // window null: every key a row may see.  Else the windowed prefill: window >= 1, causal launches only
-static int paged_prefill(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, tce::PrefillRows r, void *stream, const int *window = nullptr) {
+static int paged_prefill(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, tce::PrefillRows r, void *stream, const int *window = nullptr, const int *sinks = nullptr) {
     const tce_prefill_segment *segments = reinterpret_cast<const tce_prefill_segment *>(r.segments);
     if (!s.qkv || !s.out || !s.workspace || !segments) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
     if (const int rc = check_pages(who, pg)) return rc;
@@ -1836,6 +1875,10 @@ static int paged_prefill(const char *who, const tce::KvPages &pg, tce::AttnStepA
     if (const int rc = check_aligned(who, 4, {{"block_table", pg.table}})) return rc;
     int form = 0, pair = 0, blocks = 0, wgs = 0;
     if (tce::describe_attention_prefill_paged(s.heads, r.causal, r.segments, r.nseg, &form, &pair, &blocks, &wgs, s.window) != TCE_OK)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
+    if (const int rc = check_sinks(who, sinks)) return rc;
+    s.sinks = sinks ? *sinks : 0;
+    if (tce::describe_attention_prefill_paged(s.heads, r.causal, r.segments, r.nseg, &form, &pair, &blocks, &wgs, s.window, s.sinks) != TCE_OK)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d query blocks: one launch lists at most 1024 (several calls)", who, blocks);
     hipError_t he = hipSuccess;
     const int rc = tce::launch_attention_prefill_paged(pg, s, r, static_cast<hipStream_t>(stream), &he);
@@ -1876,6 +1919,24 @@ int tce_attention_prefill_paged_window_fp8(const void *qkv, int ld_qkv, void *k_
     return paged_prefill("tce_attention_prefill_paged_window_fp8", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                          {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
                          {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream, &window);
+}
+
+int tce_attention_prefill_paged_sink_f16(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                         int page_keys, int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads,
+                                         int kv_heads, int hd, const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits, int window,
+                                         int sinks, void *stream) {
+    return paged_prefill("tce_attention_prefill_paged_sink_f16", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, false, 0, 0},
+                         {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
+                         {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream, &window, &sinks);
+}
+
+int tce_attention_prefill_paged_sink_fp8(const void *qkv, int ld_qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_rows, int table_stride,
+                                         int page_keys, int num_pages, const void *cosv, const void *sinv, int causal, void *out, int ld_out, void *workspace, int heads,
+                                         int kv_heads, int hd, const tce_prefill_segment *segments, int num_segments, int total_rows, unsigned short alpha_bits,
+                                         int k_scale_log2, int v_scale_log2, int window, int sinks, void *stream) {
+    return paged_prefill("tce_attention_prefill_paged_sink_fp8", {k_pool, v_pool, block_table, table_rows, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                         {qkv, cosv, sinv, out, workspace, 0, heads, kv_heads, hd, nullptr, 0, alpha_bits},
+                         {ld_qkv, ld_out, causal ? 1 : 0, reinterpret_cast<const int *>(segments), num_segments, total_rows}, stream, &window, &sinks);
 }
 
 int tce_layernorm_q_w8a8_group(const float *x, const float *ln_weight, const float *ln_bias, int m, int k, const tce_w8a8_desc *lin, int count,

@@ -270,6 +270,8 @@ struct AttnStepArgs {  // what every batched step (contiguous, paged, multi-row)
     int pos_bound;
     unsigned short alpha_bits;
     int window = 0;  // the paged step and the paged prefill: >= 1 = sliding-window attention, a row at position p weighs keys max(0, p - window + 1) .. p; 0: every key
+    int sinks = 0;   // with a window, 1 .. 16 = attention sinks: a row at p >= sinks + window also weighs keys 0 .. sinks - 1, scored with q rotated by row sinks + window - 1;
+                     // a row below that weighs keys 0 .. p
 };
 struct PrefillRows {  // the paged prefill's rows: up to 16 segments {slot, pos, m, row0} (int32 x 4 each: tce_prefill_segment) of total_rows rows
     int ld_qkv, ld_out, causal;
@@ -283,7 +285,7 @@ struct KvLinear {  // a contiguous single-sequence cache pair fp16 [kv_heads][ma
 // the paged prefill: both launches on the pools and block table; UNSUPPORTED_SHAPE: more query blocks than one launch lists (1024), or an exponent outside [-8, 7].
 // describe: the form (4 / 8 / 14 / 18), pairing, query blocks and workgroups; no HIP call.
 size_t attention_prefill_paged_workspace_bytes(int heads, int total_rows, int hd);
-int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups, int window = 0);
+int describe_attention_prefill_paged(int heads, int causal, const int *segments, int nseg, int *form, int *pair, int *nblocks, int *workgroups, int window = 0, int sinks = 0);
 int launch_attention_prefill_paged(const KvPages &pages, const AttnStepArgs &step, const PrefillRows &rows, hipStream_t stream, hipError_t *hip_err);
 // what a deferred attention step leaves for its consumer (tce_attention_deferred of the C ABI, field for field)
 struct AttnDeferred {
@@ -309,7 +311,10 @@ size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int h
 int launch_attention_decode_paged(const KvPages &pages, const AttnStepArgs &step, int rows_per_seq, hipStream_t stream, hipError_t *hip_err);
 int launch_kv_pages_copy(const KvPages &pages, const KvLinear &lin, bool gather, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err);
 int launch_kv_block_table_check(const KvPages &pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err,
-                                int window = 0);  // window >= 1: only the words a windowed row follows
+                                int window = 0, int sinks = 0);  // window >= 1: only the words a windowed row follows; sinks >= 1: a sink row
+// the sink step's cut (AttnStepArgs::sinks >= 1): the batched rule for the virtual keys a workgroup group can span (attention_fast.hip)
+int attention_sink_cut_keys(int pos_bound, int window, int sinks);
+void describe_attention_decode_sink(int heads, int kv_heads, int pos_bound, int window, int sinks, int *chunk, int *chunks, int *waves);
 // the windowed paged step's cut (AttnStepArgs::window >= 1): the batched rule for min(pos_bound + 1, window + 3) keys
 void describe_attention_decode_window(int heads, int kv_heads, int pos_bound, int window, int *chunk, int *chunks, int *waves);
 int launch_rope_half(void *q, void *k, const void *cosv, const void *sinv, int heads, int len, int hd, int start_idx, hipStream_t stream, hipError_t *hip_err);

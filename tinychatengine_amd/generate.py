@@ -442,7 +442,7 @@ def score_plan(prompts, free_slots, max_keys: int, vocab: int, chunk_rows: int =
             "chunks": [(r0, min(chunk, total - r0)) for r0 in range(0, total, chunk)], "split": split}
 
 
-def admission_chunks(lengths, chunk_rows: int, window: int | None = None) -> list[dict]:
+def admission_chunks(lengths, chunk_rows: int, window: int | None = None, sinks: int | None = None) -> list[dict]:
     """The schedule of admit(..., chunk_rows=N) for prompts of `lengths` tokens (pure: no allocator, no device).  Round r takes rows [r N, min((r + 1) N, len)) of
     every prompt that still has some; per round, with i the prompt's index in `lengths`:
         "reserve"   [(i, c0 + m - 1)]   reserved first, all or nothing across the round (PageAllocator.reserve_many)
@@ -450,7 +450,10 @@ def admission_chunks(lengths, chunk_rows: int, window: int | None = None) -> lis
         "release"   [(i, c0 + m - W)]   then PageAllocator.release_behind -- only with window = W = the largest window when EVERY layer has one (else empty):
                                         the next chunk's first row sits at c0 + m and weighs keys from c0 + m - W + 1 on
     A slot's keys between a round's reserve and its release span at most W + N - 1 + (page_keys - 1) rows, so it holds at most ceil((W + N) / page_keys) + 1 pages,
-    whatever the prompt's length."""
+    whatever the prompt's length.  sinks = S (the largest of the layers' sink counts; needs a window): the schedule is the same -- the caller's release_behind keeps
+    the first ceil(S / page_keys) = 1 page besides, so the bound is ceil((W + N) / page_keys) + 2 pages."""
+    if sinks is not None and (window is None or not 1 <= int(sinks) <= 16):
+        raise ValueError(f"sinks {sinks}: None, or an integer 1 .. 16 beside a window")
     lengths = [int(n) for n in lengths]
     if int(chunk_rows) != chunk_rows or int(chunk_rows) < 1:
         raise ValueError(f"chunk_rows {chunk_rows}: None or an integer >= 1")
@@ -626,9 +629,10 @@ class _GeneratorBase:
         and writing their words back to -1 restores the state before the call."""
         windows = [getattr(d, "window", None) for d in self.decoders]
         window = None if any(w is None for w in windows) else max(windows)
+        keep = self._keep_pages()
         last = [None] * len(adm)
         try:
-            for rnd in admission_chunks([len(ids) for _, ids, *_ in adm], chunk_rows, window):
+            for rnd in admission_chunks([len(ids) for _, ids, *_ in adm], chunk_rows, window, self._max_sinks() if window is not None else None):
                 self.allocator.reserve_many([(adm[i][0], upto) for i, upto in rnd["reserve"]])
                 chunk = [(adm[i][0], embedded(adm[i][1][c0:c0 + m]), c0) for i, c0, m in rnd["segments"]]
                 for d in self.decoders:
@@ -636,7 +640,7 @@ class _GeneratorBase:
                 for (i, _, _), (_, r, _) in zip(rnd["segments"], chunk):
                     last[i] = r
                 for i, key in rnd["release"]:
-                    self.allocator.release_behind(adm[i][0], key)
+                    self.allocator.release_behind(adm[i][0], key, keep_pages=keep)
         except Exception:
             for s, *_ in adm:
                 self.allocator.release(s)
@@ -668,6 +672,16 @@ class _GeneratorBase:
             self._release_behind()
         return retired
 
+    def _max_sinks(self) -> int | None:
+        """The largest sink count of the layers (None: no layer has attention sinks)."""
+        sinks = [s for s in (getattr(d, "sinks", None) for d in self.decoders) if s is not None]
+        return max(sinks) if sinks else None
+
+    def _keep_pages(self) -> int:
+        """release_behind's keep_pages: the pages that hold the layers' sinks, ceil(max S / page_keys) (0: no layer has any)."""
+        s = self._max_sinks()
+        return 0 if s is None or self.allocator is None else -(-s // self.allocator.page_keys)
+
     def _release_behind(self) -> None:
         """Sliding windows: when EVERY layer has one, no layer weighs a key below pos - max(windows) + 1 of a live slot at position pos again -- the pages wholly below
         go back to the pool (PageAllocator.release_behind; host bookkeeping only: the table words stay, so the captured graph stays valid).  Between bursts a slot then
@@ -676,7 +690,7 @@ class _GeneratorBase:
         if any(w is None for w in windows):
             return
         for s in self.book.live():
-            self.allocator.release_behind(s, self.book.pos[s] - max(windows) + 1)
+            self.allocator.release_behind(s, self.book.pos[s] - max(windows) + 1, keep_pages=self._keep_pages())
 
     def _replayed(self) -> None:
         """Behind every replay of run(): a subclass's stream-ordered device work (no synchronisation)."""

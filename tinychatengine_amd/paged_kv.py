@@ -103,6 +103,8 @@ class PageAllocator:
         self.refcount = [0] * num_pages
         self.pages: list[list[int]] = [[] for _ in range(batch)]  # the pages a slot HOLDS, in key order: pages[slot][i] is its table word gone[slot] + i
         self.gone = [0] * batch  # leading pages of a slot that release_behind gave back (their table words stay as they are and are never followed again)
+        self.kept: list[list[int]] = [[] for _ in range(batch)]  # release_behind(..., keep_pages=k): the slot's first k pages (table words 0 .. k - 1), still held though
+                                                                  # they lie below `gone` -- the attention sinks' pages; between them and pages[slot][0] is the hole
         self.frozen = [0] * batch  # leading pages of a slot that are (or were) shared: read-only for it, never the target of an append
         self.table = torch.zeros((batch, max_pages_per_seq), dtype=torch.int32, device=device)
 
@@ -129,11 +131,15 @@ class PageAllocator:
         return all(self.refcount[p] == 1 for p in self.pages[slot][first:last + 1])
 
     def holds(self, slot: int, key0: int, nkeys: int) -> bool:
-        """Does `slot` hold a page for every key of [key0, key0 + nkeys): reserved, and not given back by release_behind."""
+        """Does `slot` hold a page for every key of [key0, key0 + nkeys): reserved, and not given back by release_behind.  With kept pages (release_behind(...,
+        keep_pages=k)): inside the kept pages or inside the tail, never across the hole between them."""
         self._slot(slot)
         if key0 < 0 or nkeys < 1:
             return False
-        return key0 // self.page_keys >= self.gone[slot] and (key0 + nkeys - 1) // self.page_keys < self.gone[slot] + len(self.pages[slot])
+        first, last = key0 // self.page_keys, (key0 + nkeys - 1) // self.page_keys
+        if last < len(self.kept[slot]):
+            return True
+        return first >= self.gone[slot] and last < self.gone[slot] + len(self.pages[slot])
 
     # ---- operations ----
     def reserve_many(self, wanted: list[tuple[int, int]]) -> list[list[int]]:
@@ -182,32 +188,44 @@ class PageAllocator:
         never followed)."""
         self._slot(slot)
         freed = []
-        for p in self.pages[slot]:
+        for p in self.kept[slot] + self.pages[slot]:
             assert self.refcount[p] > 0
             self.refcount[p] -= 1
             if self.refcount[p] == 0:
                 freed.append(p)
         self.free += freed[::-1]  # (the slot's first page is the next one handed out)
         self.pages[slot] = []
+        self.kept[slot] = []
         self.frozen[slot] = 0
         self.gone[slot] = 0
         return freed
 
-    def release_behind(self, slot: int, key: int) -> list[int]:
+    def release_behind(self, slot: int, key: int, keep_pages: int = 0) -> list[int]:
         """Drop the slot's references to the pages that lie WHOLLY below key index `key` (sliding-window attention: no layer weighs them any more); returns the pages
         that went back to the free list -- a shared page only loses this slot's reference.  The table words are left as they are: a windowed row never follows a word
-        below its window's first key.  Idempotent; key <= 0 drops nothing; never more than the slot holds.  From then on the slot cannot be a fork's source."""
+        below its window's first key.  Idempotent; key <= 0 drops nothing; never more than the slot holds.  From then on the slot cannot be a fork's source.
+        keep_pages = k > 0 (attention sinks): the slot's first k pages stay held -- they move to kept[slot], the pages between them and `key` go back; gone[slot] is
+        still the table index of pages[slot][0].  The kept pages can only be established while nothing has been given back (gone == 0): a later call that asks for
+        more than is kept raises ValueError (one that asks for fewer, or 0, keeps what is kept).  keep_pages=0 on a slot without kept pages: as it always was."""
         self._slot(slot)
+        k = int(keep_pages)
+        if k < 0:
+            raise ValueError(f"keep_pages {keep_pages}: an integer >= 0")
+        if self.gone[slot] and k > len(self.kept[slot]):
+            raise ValueError(f"slot {slot}: keep_pages {k}, but it gave pages back while {len(self.kept[slot])} were kept (kept pages are established by the first release)")
         drop = min(max(int(key), 0) // self.page_keys - self.gone[slot], len(self.pages[slot]))
-        if drop <= 0:
+        keep = k if self.gone[slot] == 0 else 0  # (the first release: the first k pages of the tail are the ones to keep)
+        if drop <= keep:
             return []
         freed = []
-        for p in self.pages[slot][:drop]:
+        for p in self.pages[slot][keep:drop]:
             assert self.refcount[p] > 0
             self.refcount[p] -= 1
             if self.refcount[p] == 0:
                 freed.append(p)
         self.free += freed[::-1]
+        if keep:
+            self.kept[slot] = self.pages[slot][:keep]
         self.pages[slot] = self.pages[slot][drop:]
         self.gone[slot] += drop
         return freed
@@ -247,9 +265,9 @@ class PageAllocator:
     def check_invariants(self) -> None:
         """No page both free and referenced, counts equal to the slot lists, no shared page appendable, the table's live words equal to the slot lists."""
         counts = [0] * self.num_pages
-        for ps in self.pages:
-            assert len(ps) <= self.max_pages_per_seq and len(set(ps)) == len(ps)
-            for p in ps:
+        for ps, kp in zip(self.pages, self.kept):
+            assert len(ps) <= self.max_pages_per_seq and len(set(kp + ps)) == len(kp) + len(ps)
+            for p in kp + ps:
                 counts[p] += 1
         assert counts == self.refcount
         assert len(set(self.free)) == len(self.free) and all(self.refcount[p] == 0 for p in self.free)
@@ -259,6 +277,7 @@ class PageAllocator:
             assert all(self.refcount[p] == 1 for p in self.appendable_pages(s))
             assert self.gone[s] >= 0 and self.gone[s] + len(ps) <= self.max_pages_per_seq
             assert host[s, self.gone[s]:self.gone[s] + len(ps)].tolist() == ps
+            assert len(self.kept[s]) <= self.gone[s] and host[s, :len(self.kept[s])].tolist() == self.kept[s]
 
     # ---- internals ----
     def _slot(self, slot: int) -> None:
@@ -274,13 +293,18 @@ class PagedBatchDecodeAttention:
     """One layer's K and V pools and the step's workspace, over a PageAllocator's table."""
 
     def __init__(self, allocator: PageAllocator, heads: int, kv_heads: int | None, device, cos: torch.Tensor | None = None, sin: torch.Tensor | None = None,
-                 kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None):
+                 kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None, sinks: int | None = None):
         """kv_dtype "fp16" (the default: today's pools and entry points) or "fp8_e4m3": uint8 pools of the same shape, every call through the fp8 entry points with
         the two scale exponents (integers in [-8, 7]; ignored for fp16).  window None: every key, through today's entry points; W >= 1: step, prefill and
-        table_violations go through the *_window entry points (a row at position p weighs keys max(0, p - W + 1) .. p)."""
+        table_violations go through the *_window entry points (a row at position p weighs keys max(0, p - W + 1) .. p).  sinks None: as above; S in 1 .. 16 (needs a
+        window): attention sinks, through the *_sink entry points -- a row at p >= S + W weighs keys 0 .. S - 1 (q rotated with row S + W - 1) beside its window, a row
+        below weighs keys 0 .. p (include/tce_matmul.h).  The caller keeps the sequence's first page: PageAllocator.release_behind(..., keep_pages=1)."""
         if window is not None and (int(window) != window or int(window) < 1 or int(window) > 0x7fffffff):
             raise ValueError(f"window {window}: None or an integer >= 1")
         self.window = None if window is None else int(window)
+        if sinks is not None and (window is None or int(sinks) != sinks or not 1 <= int(sinks) <= 16):
+            raise ValueError(f"sinks {sinks}: None, or an integer 1 .. 16 beside a window")
+        self.sinks = None if sinks is None else int(sinks)
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"kv_dtype {kv_dtype!r}: one of {KV_DTYPES}")
         self.kv_dtype, self.fp8 = kv_dtype, kv_dtype == "fp8_e4m3"
@@ -310,12 +334,12 @@ class PagedBatchDecodeAttention:
         return (self.k_scale_log2, self.v_scale_log2) if self.fp8 else ()
 
     def _window(self) -> tuple:
-        """The *_window entry points' one extra argument (behind the scales, in front of the stream); nothing without a window."""
-        return () if self.window is None else (self.window,)
+        """The *_window entry points' one extra argument (behind the scales, in front of the stream), the *_sink entry points' two; nothing without a window."""
+        return () if self.window is None else ((self.window,) if self.sinks is None else (self.window, self.sinks))
 
     def _entry(self, name: str) -> str:
-        """`name` or, with a window, its *_window form"""
-        return name if self.window is None else name + "_window"
+        """`name` or, with a window, its *_window form; with sinks, its *_sink form"""
+        return name if self.window is None else name + ("_window" if self.sinks is None else "_sink")
 
     def _table_args(self):
         t = self.allocator.table
@@ -439,21 +463,27 @@ class PagedBatchedDecoder(BatchedDecoder):
     prefill launches with the paged prefill in the middle.  One PageAllocator serves the decoders of all layers."""
 
     def __init__(self, block: DecoderBlock, allocator: PageAllocator, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, attention=None,
-                 rows: int | None = None, window: int | None = None, lora=None):
+                 rows: int | None = None, window: int | None = None, lora=None, sinks: int | None = None):
         """attention, rows: BatchedDecoder's (a subclass with an attention object of its own over the same allocator; the default is built here).  window: this layer's
         sliding window (PagedBatchDecodeAttention), None for full attention.  lora: BatchedDecoder's (this layer's view of a LoraPool: q/k/v, o_proj and down_proj
         become adapted linears in step, prefill and prefill_many; gate/up too with a gate_up=True pool)."""
         self.allocator = allocator
         if attention is None:
             attention = PagedBatchDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin, kv_dtype=kv_dtype,
-                                                  k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window)
+                                                  k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window, sinks=sinks)
         elif window is not None and getattr(attention, "window", None) != window:
             raise ValueError("window: the attention object given was built with another one")
+        elif sinks is not None and getattr(attention, "sinks", None) != sinks:
+            raise ValueError("sinks: the attention object given was built with another count")
         super().__init__(block, allocator.batch, attention=attention, rows=rows, lora=lora)
 
     @property
     def window(self) -> int | None:
         return getattr(self.attention, "window", None)
+
+    @property
+    def sinks(self) -> int | None:
+        return getattr(self.attention, "sinks", None)
 
     def prefill_many(self, admissions) -> None:
         """Admit several sequences at once: admissions [(slot, rows, pos)], at most 16, distinct slots; rows fp16 [m][hidden] at positions pos .. pos + m - 1, updated

@@ -150,6 +150,8 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
 
     def __init__(self, allocator, heads, kv_heads, device, cos=None, sin=None, rows_per_seq: int = 1, **kw):
         _check_rows(rows_per_seq)
+        if kw.get("sinks") is not None:
+            raise ValueError("PagedRowsDecodeAttention: attention sinks are not built on the multi-row step (sinks=None)")
         if kw.get("window") is not None and not allocator.table.is_cuda:
             # (the unwindowed form may be built over a host table for bookkeeping tests; with a window every path of this class -- step, table_violations -- is a
             # device path, and a host table would only fail later, inside a launch wrapper)
@@ -190,9 +192,12 @@ class SpeculativeDecoder(PagedBatchedDecoder):
     words tce_draft_ngram's row_pos int32 [batch * T]), the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill / prefill_many are the parent's.  window: this
     layer's sliding window (the windowed rows step and the windowed prefill), None for full attention."""
 
-    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None, lora=None):
+    def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None, lora=None,
+                 sinks: int | None = None):
         """lora: this layer's view of a LoraPool built with the same rows_per_seq (LoraPool(..., rows_per_seq=T).layer(i)): the T rows of a slot run on the slot's
-        adapter -- 7 + 6 launches, 7 + 8 with a gate_up=True pool."""
+        adapter -- 7 + 6 launches, 7 + 8 with a gate_up=True pool.  sinks: refused (ValueError) unless None -- attention sinks exist on the one-row step only."""
+        if sinks is not None:
+            raise ValueError("SpeculativeDecoder: attention sinks are not built on the multi-row step (sinks=None)")
         _check_rows(rows_per_seq)
         self.rows_per_seq = int(rows_per_seq)
         attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin,
@@ -274,6 +279,9 @@ class SpeculativeGenerator(_GeneratorBase):
                 raise ValueError(f"SpeculativeGenerator: lora= takes a pool built for its speculative rows, LoraPool(..., rows_per_seq=T) with the decoders' T "
                                  f"(this pool: rows_per_seq={T})")
         decoders = list(decoders)
+        for d in decoders:  # (attention sinks exist on the one-row step only)
+            if getattr(d, "sinks", None) is not None or getattr(getattr(d, "attention", None), "sinks", None) is not None:
+                raise ValueError("SpeculativeGenerator: a decoder has attention sinks, which are not built on the multi-row step")
         for d in decoders:  # a windowed layer must run the windowed ROWS step: its attention object carries the window (SpeculativeDecoder(..., window=W) builds it so)
             w = getattr(d, "window", None)
             if w is not None and getattr(getattr(d, "attention", None), "window", None) != w:
