@@ -45,18 +45,18 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         # the sampler's two kernels keep 16 / 32 64-bit numbers per thread in registers through ~50 counting rounds: in scratch every round would re-read them
                                         # (every instantiation, the logprob forms included; the two scoring kernels hold the same 16 logits per thread)
                                         "sampling.hip": ["sample_select_kernel", "sample_draw_kernel", "logprobs_partials_kernel", "logprobs_merge_kernel"],
-                                        # the e4m3 forms of the paged step, the paged prefill (every block form) and the copies: a spilled piece of a tile or of the double
-                                        # buffer would turn requests that are meant to be in flight together into load -> wait -> scratch store
-                                        # (the e4m3 name is a prefix of its multi-row form's; the second name is the fp16 multi-row form: both keep the paged step's double buffer)
-                                        # (the third name: the fp16 windowed step; the e4m3 windowed step has the first name as a prefix.  The windowed prefill: every form, fp16 and e4m3)
-                                        # (the fourth and fifth names: the windowed multi-row step, fp16 and e4m3 -- written out, though the second and first names are their prefixes)
+                                        # the paged steps, the paged prefill (every form and block form) and the e4m3 copies and prepare: a spilled piece of a tile or of
+                                        # the double buffer would turn requests that are meant to be in flight together into load -> wait -> scratch store
+                                        # (attention_fast.hip: every paged instantiation but the plain fp16 step, written out by their mangled prefixes -- the kernel's
+                                        #  flags are <MASK, NW, R, BATCH, PAGED, FP8, ROWS, WINDOW, SINK> and a name matches every instantiation whose flags begin with its own:
+                                        #  e4m3, any form; fp16 rows; fp16 window; fp16 rows + window; e4m3 rows + window; fp16 sink.  The flags' order is part of these names)
                                         "attention_fast.hip": ["attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1E",
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1ELb1E",
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1ELb1ELb1E", "kv_pages_copy_fp8_kernel",
-                                                               # (the sink step, fp16 -- the e4m3 one has the first name as a prefix.  SINK is the kernel's LAST template parameter: every
-                                                               #  name above is still a prefix of the instantiation it was written for)
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1ELb1E"],
-                                        "attention_prefill.hip": ["attn_prefill_paged_fp8_kernel", "attn_prefill_paged_window_kernel", "attn_prefill_paged_sink_kernel", "attn_prefill_prepare_kernelILb1ELb1E"],
+                                        # (attention_prefill.hip: one paged kernel, guarded by name -- the plain fp16 forms too, which spill nothing either:
+                                        #  profiles/attn_forms/kernel_resources_parent.txt)
+                                        "attention_prefill.hip": ["attn_prefill_paged_kernel", "attn_prefill_prepare_kernelILb1ELb1E"],
                                         "w4a16_gemv_i8_token.hip": ["w4a16_gemv_i8_token_kernelILb0E"],  # (ILb1E: the lab build's instantiation with wall-clock stamps)
                                         # round 5: EVERY instantiation of the decode kernel, the general-zero-point forms included (round 4 let four of them spill 3-19 registers: each
                                         # spilled scale / zero-point load became load -> wait -> scratch store, i.e. the wave's requests went out one at a time)

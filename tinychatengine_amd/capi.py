@@ -388,26 +388,27 @@ def last_error() -> str:
     return lib().tce_last_error().decode()
 
 
+def _parse_pairs(text: str) -> dict:
+    """The describe entry points' "key=value key=value ..." text as a dict; a value of digits becomes an int."""
+    out = {}
+    for tok in text.split():
+        k, v = tok.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
+
+
 def describe_attention_step(heads: int, keys: int, kv_heads: int | None = None) -> dict:
     """How tce_attention_decode_step_f16 / _gqa_f16 cuts a context of `keys` keys: {"chunks", "keys-per-chunk", "waves", "workgroups", "combine"} (no GPU needed)."""
     buf = C.create_string_buffer(160)
     check(lib().tce_attention_decode_describe_gqa(heads, heads if kv_heads is None else kv_heads, keys, buf, len(buf)))
-    out = {}
-    for tok in buf.value.decode().split():
-        k, v = tok.split("=")
-        out[k] = int(v) if v.isdigit() else v
-    return out
+    return _parse_pairs(buf.value.decode())
 
 
 def describe_attention_paged(batch: int, heads: int, kv_heads: int, pos_bound: int, page_keys: int) -> dict:
     """How tce_attention_decode_step_paged_f16 cuts the launch: describe_attention_batch's keys plus "page-keys" (no GPU needed)."""
     buf = C.create_string_buffer(192)
     check(lib().tce_attention_decode_describe_paged(batch, heads, kv_heads, pos_bound, page_keys, buf, len(buf)))
-    out = {}
-    for tok in buf.value.decode().split():
-        k, v = tok.split("=")
-        out[k] = int(v) if v.isdigit() else v
-    return out
+    return _parse_pairs(buf.value.decode())
 
 
 def describe_attention_paged_sink(batch: int, heads: int, kv_heads: int, pos_bound: int, page_keys: int, window: int, sinks: int) -> dict:
@@ -415,22 +416,14 @@ def describe_attention_paged_sink(batch: int, heads: int, kv_heads: int, pos_bou
     (no GPU needed)."""
     buf = C.create_string_buffer(192)
     check(lib().tce_attention_decode_describe_paged_sink(batch, heads, kv_heads, pos_bound, page_keys, window, sinks, buf, len(buf)))
-    out = {}
-    for tok in buf.value.decode().split():
-        k, v = tok.split("=")
-        out[k] = int(v) if v.isdigit() else v
-    return out
+    return _parse_pairs(buf.value.decode())
 
 
 def describe_attention_paged_window(batch: int, heads: int, kv_heads: int, pos_bound: int, page_keys: int, window: int) -> dict:
     """How tce_attention_decode_step_paged_window_f16 cuts the launch -- for min(pos_bound + 1, window + 3) keys: describe_attention_paged's keys (no GPU needed)."""
     buf = C.create_string_buffer(192)
     check(lib().tce_attention_decode_describe_paged_window(batch, heads, kv_heads, pos_bound, page_keys, window, buf, len(buf)))
-    out = {}
-    for tok in buf.value.decode().split():
-        k, v = tok.split("=")
-        out[k] = int(v) if v.isdigit() else v
-    return out
+    return _parse_pairs(buf.value.decode())
 
 
 TCE_PREFILL_MAX_SEGMENTS = 16
@@ -457,22 +450,14 @@ def describe_prefill_paged(heads: int, kv_heads: int, causal: bool, segments) ->
     text = lib().tce_attention_prefill_describe_paged(heads, kv_heads, 1 if causal else 0, C.cast(arr, C.c_void_p), len(segments))
     if text is None:
         raise TceError(TCE_ERR_BAD_ARG, last_error())
-    out = {}
-    for tok in text.decode().split():
-        k, v = tok.split("=")
-        out[k] = int(v) if v.isdigit() else v
-    return out
+    return _parse_pairs(text.decode())
 
 
 def describe_attention_batch(batch: int, heads: int, kv_heads: int, pos_bound: int) -> dict:
     """How tce_attention_decode_step_batch_f16 cuts `batch` sequences bounded by pos_bound: describe_attention_step's keys plus "batch" (no GPU needed)."""
     buf = C.create_string_buffer(160)
     check(lib().tce_attention_decode_describe_batch(batch, heads, kv_heads, pos_bound, buf, len(buf)))
-    out = {}
-    for tok in buf.value.decode().split():
-        k, v = tok.split("=")
-        out[k] = int(v) if v.isdigit() else v
-    return out
+    return _parse_pairs(buf.value.decode())
 
 
 def describe_dispatch(desc: W4A16Desc) -> str:

@@ -27,6 +27,7 @@
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
 #include "fp8_kv.hpp"
+#include "attn_dispatch.hpp"
 
 namespace tce {
 
@@ -88,6 +89,11 @@ struct PagedSinkAttnArgs : PagedWindowAttnArgs {
     int sinks;     // 1 .. 16
     int sink_row;  // min(S + W - 1, pos_bound): the cos / sin row of the second rotation (beyond pos_bound no row binds and the rotation is not used)
 };
+
+// a form's arguments (the kernel's static_asserts say which forms exist)
+template <bool PAGED, bool FP8, bool ROWS, bool WINDOW, bool SINK>
+using step_args_t = std::conditional_t<SINK, PagedSinkAttnArgs, std::conditional_t<WINDOW, std::conditional_t<ROWS, PagedRowsWindowAttnArgs, PagedWindowAttnArgs>,
+                                       std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>>>>;
 
 __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, result in every lane of the row
     auto dpp = [](float x, auto ctrl) {
@@ -185,9 +191,7 @@ __host__ __device__ inline size_t attn_workspace_words(int heads, int max_keys) 
 template <bool MASK, int NW, int R, bool BATCH = false, bool PAGED = false, bool FP8 = false, bool ROWS = false, bool WINDOW = false, bool SINK = false>
 // (waves per SIMD: the sink forms are pinned to the windowed step's 4 -- left alone the fp16 one takes 141 registers for the second copy of consume() and runs 3; 1 .. 8
 //  leaves every other form alone)
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SINK ? 4 : 1, SINK ? 4 : 8))) void attn_decode_fast_kernel(
-    const std::conditional_t<SINK, PagedSinkAttnArgs, std::conditional_t<WINDOW, std::conditional_t<ROWS, PagedRowsWindowAttnArgs, PagedWindowAttnArgs>,
-                             std::conditional_t<ROWS, PagedRowsAttnArgs, std::conditional_t<FP8, PagedFp8AttnArgs, std::conditional_t<PAGED, PagedAttnArgs, FastAttnArgs>>>>> a) {
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SINK ? 4 : 1, SINK ? 4 : 8))) void attn_decode_fast_kernel(const step_args_t<PAGED, FP8, ROWS, WINDOW, SINK> a) {
     static_assert(!SINK || (WINDOW && !ROWS), "sinks exist beside a window, on the one-row step");
     static_assert(!WINDOW || (PAGED && NW == 4), "a window exists on the paged steps only");
     static_assert(!PAGED || (BATCH && !MASK && R == 1), "the paged form is a form of the batched step");
@@ -847,12 +851,7 @@ int launch_attention_decode_fast(const void *qkv, void *kc, void *vc, const void
     };
     if (a.mask) go(std::true_type{});
     else go(std::false_type{});
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    return launch_status(hip_err);
 }
 
 // the batched step's cut: the single step's fitted rule for pos_bound + 1 keys, one query head per workgroup (no HIP call)
@@ -916,12 +915,7 @@ int launch_attention_decode_batch(const AttnStepArgs &s, void *kc, void *vc, int
     __builtin_memcpy(&ah, &s.alpha_bits, 2);
     a.alpha = (float)ah;
     hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    return launch_status(hip_err);
 }
 
 // ---- pages <-> a contiguous single-sequence cache pair, and the block-table check (the paged step's companions) ----
@@ -1007,12 +1001,6 @@ __global__ __launch_bounds__(1024) void kv_block_table_check_kernel(const int *t
 }  // namespace
 
 // ---- the paged step: the batched step on pools of pages.  The cut, the grid, the workspace layout and every row's arithmetic are the batched step's ----
-static int page_shift_of(int page_keys) {  // log2 of a power of two in [16, 256], or -1
-    for (int s = 4; s <= 8; ++s)
-        if (page_keys == 1 << s) return s;
-    return -1;
-}
-
 size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) {
     if (num_pages <= 0 || kv_heads <= 0 || hd != kHD || page_shift_of(page_keys) < 0) return 0;
     return (size_t)num_pages * kv_heads * page_keys * kHD * sizeof(half_t);
@@ -1021,14 +1009,6 @@ size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) {
 size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd) {
     if (num_pages <= 0 || kv_heads <= 0 || hd != kHD || page_shift_of(page_keys) < 0) return 0;
     return (size_t)num_pages * kv_heads * page_keys * kHD;
-}
-
-static bool fp8_log2_ok(int e) { return e >= kFp8ScaleLog2Min && e <= kFp8ScaleLog2Max; }
-static float host_pow2(int e) {
-    const unsigned bits = (unsigned)(127 + e) << 23;
-    float f;
-    __builtin_memcpy(&f, &bits, 4);
-    return f;
 }
 
 // pages.fp8: the pools are e4m3 bytes and the two exponents apply; everything else is one text for both
@@ -1045,8 +1025,7 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         return TCE_ERR_UNSUPPORTED_SHAPE;
     if (fp8 && !(fp8_log2_ok(pg.k_scale_log2) && fp8_log2_ok(pg.v_scale_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
     if (rows < 0 || rows > TCE_SPEC_MAX_ROWS || s.window < 0) return TCE_ERR_UNSUPPORTED_SHAPE;
-    PagedRowsAttnArgs a{};
-    a.rows_per_seq = rows;
+    PagedFp8AttnArgs a{};
     a.qkv = static_cast<const half_t *>(s.qkv);
     a.kc = static_cast<half_t *>(pg.k_pool);
     a.vc = static_cast<half_t *>(pg.v_pool);
@@ -1082,44 +1061,25 @@ int launch_attention_decode_paged(const KvPages &pg, const AttnStepArgs &s, int 
         a.k_inv = host_pow2(-pg.k_scale_log2);
         a.v_inv = host_pow2(-pg.v_scale_log2);
     }
-    if (s.window && rows) {
-        PagedRowsWindowAttnArgs w{};
-        static_cast<PagedRowsAttnArgs &>(w) = a;
-        w.window = s.window;
-        const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, rows, batch);  // (the windowed step's padded x, the rows step's y and z)
-        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, true, true>), grid, dim3(256), 0, stream, w);
-        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, true, true>), grid, dim3(256), 0, stream, w);
-    } else if (s.sinks) {
-        PagedSinkAttnArgs w{};
-        static_cast<PagedFp8AttnArgs &>(w) = a;
-        w.window = s.window;
-        w.sinks = s.sinks;
-        w.sink_row = (long long)s.sinks + s.window - 1 < (long long)pos_bound ? s.sinks + s.window - 1 : pos_bound;
-        const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, batch);  // (the windowed step's grid)
-        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, false, true, true>), grid, dim3(256), 0, stream, w);
-        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, false, true, true>), grid, dim3(256), 0, stream, w);
-    } else if (s.window) {
-        PagedWindowAttnArgs w{};
-        static_cast<PagedFp8AttnArgs &>(w) = a;
-        w.window = s.window;
-        const dim3 grid((kv_heads * a.chunks + 7) / 8 * 8 * a.rep, batch);  // (whole groups of 8 (key / value head, chunk slot) pairs x rep query heads: see the kernel)
-        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, false, true>), grid, dim3(256), 0, stream, w);
-        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, false, true>), grid, dim3(256), 0, stream, w);
-    } else if (rows) {
-        const dim3 grid(heads * a.chunks, rows, batch);
-        if (fp8) hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true, true>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, false, true>), grid, dim3(256), 0, stream, a);
-    } else if (fp8) {
-        hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, static_cast<const PagedFp8AttnArgs &>(a));
-    } else {
-        hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true>), dim3(heads * a.chunks, batch), dim3(256), 0, stream, static_cast<const PagedAttnArgs &>(a));
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    // the grid: x -- (query head, chunk slot) pairs; windowed: whole groups of 8 (key / value head, chunk slot) pairs x rep query heads (see the kernel) --, then the
+    // sequences, or (rows) the rows and the sequences
+    const dim3 grid(s.window ? (kv_heads * a.chunks + 7) / 8 * 8 * a.rep : heads * a.chunks, rows ? rows : batch, rows ? batch : 1);
+    with_bools([&](auto fp8_c, auto rows_c, auto window_c, auto sink_c) {
+        constexpr bool FP8 = decltype(fp8_c)::value, ROWS = decltype(rows_c)::value, WINDOW = decltype(window_c)::value, SINK = decltype(sink_c)::value;
+        if constexpr (!SINK || (WINDOW && !ROWS)) {  // (sinks exist beside a window on the one-row step: refused above)
+            using args_t = step_args_t<true, FP8, ROWS, WINDOW, SINK>;  // the form's arguments: `a` (the fp16 step: its PagedAttnArgs) and the form's own fields
+            args_t w{};
+            static_cast<std::conditional_t<std::is_base_of_v<PagedFp8AttnArgs, args_t>, PagedFp8AttnArgs, PagedAttnArgs> &>(w) = a;
+            if constexpr (ROWS) w.rows_per_seq = rows;
+            if constexpr (WINDOW) w.window = s.window;
+            if constexpr (SINK) {
+                w.sinks = s.sinks;
+                w.sink_row = (long long)s.sinks + s.window - 1 < (long long)pos_bound ? s.sinks + s.window - 1 : pos_bound;
+            }
+            hipLaunchKernelGGL((attn_decode_fast_kernel<false, 4, 1, true, true, FP8, ROWS, WINDOW, SINK>), grid, dim3(256), 0, stream, w);
+        }
+    }, fp8, rows != 0, s.window != 0, s.sinks != 0);
+    return launch_status(hip_err);
 }
 
 // rows [key0, key0 + nkeys) between the contiguous pair and the pages of the table row pages.table; pages.fp8: scatter quantises, gather dequantises
@@ -1136,12 +1096,7 @@ int launch_kv_pages_copy(const KvPages &pg, const KvLinear &lin, bool gather, in
     };
     if (!pg.fp8) gather ? go(kv_pages_copy_kernel<true>, h) : go(kv_pages_copy_kernel<false>, h);
     else gather ? go(kv_pages_copy_fp8_kernel<true>, b, k_log2, v_log2) : go(kv_pages_copy_fp8_kernel<false>, b, k_log2, v_log2);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    return launch_status(hip_err);
 }
 
 int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err, int window,
@@ -1151,12 +1106,7 @@ int launch_kv_block_table_check(const KvPages &pg, int batch, const int *pos_dev
     if (sinks > 0) hipLaunchKernelGGL((kv_block_table_check_kernel<true, true>), dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, window, sinks);
     else if (window > 0) hipLaunchKernelGGL(kv_block_table_check_kernel<true>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, window);
     else hipLaunchKernelGGL(kv_block_table_check_kernel<false>, dim3(1), dim3(1024), 0, stream, pg.table, pg.table_stride, shift, pg.num_pages, batch, pos_dev, pos_bound, violations, 0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    return launch_status(hip_err);
 }
 
 }  // namespace tce

@@ -41,6 +41,7 @@
 #include "tce_common.hpp"
 #include "w4a16_kernels.hpp"
 #include "fp8_kv.hpp"
+#include "attn_dispatch.hpp"
 
 namespace tce {
 
@@ -182,6 +183,22 @@ struct PagedPrefillArgs {
     PrefillSegment seg[kMaxSegments];
     unsigned order[kMaxListedBlocks / 2];
 };
+// the e4m3, windowed (fp16 and e4m3 pools: the two scales are unused on fp16 pools) and sink launches': each the one before and its own fields, so that a launcher
+// fills the last and hands any form its base.  paged_prefill_args_t names a form's
+struct PagedPrefillFp8Args : PagedPrefillArgs {
+    float k_scale, v_scale;
+};
+struct PagedPrefillWindowArgs : PagedPrefillFp8Args {
+    int window;
+};
+struct PagedPrefillSinkArgs : PagedPrefillWindowArgs {
+    int sinks;
+    const half_t *qkv;
+    int ld_qkv;
+    const half_t *cos_s, *sin_s;
+};
+template <bool FP8, bool WINDOW, bool SINK>
+using paged_prefill_args_t = std::conditional_t<SINK, PagedPrefillSinkArgs, std::conditional_t<WINDOW, PagedPrefillWindowArgs, std::conditional_t<FP8, PagedPrefillFp8Args, PagedPrefillArgs>>>;
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x) {
@@ -241,21 +258,12 @@ struct PagedBlockArgs {
     const int *trow;  // the segment's table row
     int ld_out, rep, kv_heads, total_rows, row0, pos, m, causal, page_shift;
     float alpha;
-};
-
-// the e4m3 form's block arguments: the pools hold bytes, a tile's rows are dequantised on their way into LDS
-struct PagedBlockFp8Args : PagedBlockArgs {
+    // FP8: the pools hold bytes, a tile's rows are dequantised on their way into LDS
     float k_scale, v_scale;  // 2^k_scale_log2, 2^v_scale_log2
-};
-
-// the windowed form's (causal only; the two scales are unused on fp16 pools): row i of the segment sits at p = pos + i and weighs keys max(0, p - window + 1) .. p
-struct PagedBlockWindowArgs : PagedBlockFp8Args {
+    // WINDOW (causal only): row i of the segment sits at p = pos + i and weighs keys max(0, p - window + 1) .. p
     int window;  // >= 1
-};
-
-// the sink form's (attention sinks beside the window): row i at p = pos + i BINDS iff p >= sinks + window and then weighs keys 0 .. sinks - 1, scored with its raw q rotated
-// by cos / sin row sinks + window - 1, beside keys p - window + 1 .. p; a row that does not bind weighs keys 0 .. p
-struct PagedBlockSinkArgs : PagedBlockWindowArgs {
+    // SINK (attention sinks beside the window): row i at p = pos + i BINDS iff p >= sinks + window and then weighs keys 0 .. sinks - 1, scored with its raw q rotated
+    // by cos / sin row sinks + window - 1, beside keys p - window + 1 .. p; a row that does not bind weighs keys 0 .. p
     int sinks;                    // 1 .. 16
     const half_t *qkv;            // the launch's raw rows [total_rows][ld_qkv]: the second rotation is made from them in registers
     int ld_qkv;
@@ -302,16 +310,16 @@ struct TileWords<true> {
 
 // FP8 (with PAGED): a row of the pools is 128 e4m3 bytes; fetch_tile requests 8-byte pieces and the write into LDS dequantises them (exactly: fp8_kv.hpp), so the K
 // and V tiles in LDS are the same fp16 images at the same strides and everything behind them is shared text.
-// WINDOW (with PAGED, causal launches only): sliding-window attention (PagedBlockWindowArgs).  The block walks key tiles from the tile of klo = lo(its first row) to the
+// WINDOW (with PAGED, causal launches only): sliding-window attention.  The block walks key tiles from the tile of klo = lo(its first row) to the
 // tile of its last row's position; tiles wholly below are neither requested nor computed, and keys below klo -- which may lie in pages that were given back -- are staged
 // as zeros like the keys at and beyond kend.  The lower bound is tested on the tiles that hold a key below the lo of one of the wave's rows: the causal diagonal's `edge`.
-// SINK (with WINDOW; PagedBlockSinkArgs): the window pass is the windowed block's with lo_r = 0 for a row that does not bind (klo: the lo of the block's FIRST row, 0 if that
+// SINK (with WINDOW): the window pass is the windowed block's with lo_r = 0 for a row that does not bind (klo: the lo of the block's FIRST row, 0 if that
 // row does not bind).  A block whose last row binds then makes one SINK PASS, the loop's last iteration (index ntiles): key tile 0 with keys >= sinks staged as zeros, scored
 // against Q_s -- the rows' raw q rotated with row sinks + window - 1, made in registers from qkv at the head of that iteration with the prepare kernel's binary16 statement
 // (a fragment's partner half qf[t][s ^ 2] is in the same lane) and put where Q was: no register is held for it through the window pass.  Keys >= sinks and rows that do not
 // bind are cut; a fully cut tile leaves a row's state as it was.  A block none of whose rows binds walks exactly the windowed block's tiles.
 template <bool MASK, int NW, int RT, bool PAGED = false, bool FP8 = false, bool WINDOW = false, bool SINK = false>
-__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<SINK, PagedBlockSinkArgs, std::conditional_t<WINDOW, PagedBlockWindowArgs, std::conditional_t<FP8, PagedBlockFp8Args, std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs>>>> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
+__device__ __forceinline__ void attn_prefill_block(const std::conditional_t<PAGED, PagedBlockArgs, PrefillArgs> &a, const int qb, const int head, unsigned char *ks, unsigned char *vs) {
     static_assert(!SINK || WINDOW, "sinks exist beside a window");
     static_assert(!PAGED || !MASK, "the paged form takes no additive mask");
     static_assert(!WINDOW || PAGED, "a window exists on pages only");
@@ -597,10 +605,11 @@ __global__ __launch_bounds__(64 * NW) void attn_prefill_kernel(const PrefillArgs
     }
 }
 
-// The paged launch: workgroup i takes entry i of the launch's block list (heaviest first) and, when `pair` is set, entry nblocks - 1 - i after it.  With one
-// segment the list is that segment's blocks nb - 1 .. 0: the contiguous launch's order and pairs.
-__device__ __forceinline__ PagedBlockArgs paged_block_args(const PagedPrefillArgs &a, const PrefillSegment sg) {
-    PagedBlockArgs b;
+// The paged launch, every form -- fp16 and e4m3 pools, windowed, with sinks --: workgroup i takes entry i of the launch's block list (heaviest first) and, when `pair` is
+// set, entry nblocks - 1 - i after it.  With one segment the list is that segment's blocks nb - 1 .. 0: the contiguous launch's order and pairs.
+template <bool FP8, bool WINDOW, bool SINK>
+__device__ __forceinline__ PagedBlockArgs paged_block_args(const paged_prefill_args_t<FP8, WINDOW, SINK> &a, const PrefillSegment sg) {
+    PagedBlockArgs b{};
     b.qrot = a.qrot;
     b.kc = a.kc;
     b.vc = a.vc;
@@ -616,128 +625,54 @@ __device__ __forceinline__ PagedBlockArgs paged_block_args(const PagedPrefillArg
     b.causal = a.causal;
     b.page_shift = a.page_shift;
     b.alpha = a.alpha;
+    if constexpr (FP8) {
+        b.k_scale = a.k_scale;
+        b.v_scale = a.v_scale;
+    }
+    if constexpr (WINDOW) b.window = a.window;
+    if constexpr (SINK) {
+        b.sinks = a.sinks;
+        b.qkv = a.qkv;
+        b.ld_qkv = a.ld_qkv;
+        b.cos_s = a.cos_s;
+        b.sin_s = a.sin_s;
+    }
     return b;
 }
 
-// (waves per SIMD: the paired 8-wave form is pinned to the 3 its contiguous counterpart has.  Left alone it fits 126 registers, the compiler then keeps the schedule
+// Waves per SIMD, the two bounds of amdgpu_waves_per_eu.
+// (fp16 pools, no window: the paired 8-wave form is pinned to the 3 its contiguous counterpart has.  Left alone it fits 126 registers, the compiler then keeps the schedule
 //  it made for a fourth wave -- two K fragments read ahead of the MFMAs instead of six -- and the launch at 2048 rows took 108 us against the contiguous 93, though a
 //  paired launch is one such workgroup per CU whatever its registers.  Every other form lands on its counterpart's occupancy by itself: 1 .. 8 leaves it alone.)
-template <int NW, int RT, bool PAIR>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((PAIR && NW == 8 && RT == 1) ? 3 : 1, (PAIR && NW == 8 && RT == 1) ? 3 : 8)))
-void attn_prefill_paged_kernel(const PagedPrefillArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile
-    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
-    const int i = (int)blockIdx.x;
-    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
-    attn_prefill_block<false, NW, RT, true>(paged_block_args(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
-    if constexpr (PAIR) {
-        const int j = a.nblocks - 1 - i;
-        if (i < j) {
-            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
-            attn_prefill_block<false, NW, RT, true>(paged_block_args(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
-        }
-    }
-}
-
-// The e4m3 launch: the same workgroups, block list and pairs on pools of bytes.  (waves per SIMD: every form is pinned to what its fp16 counterpart has -- FP8_WAVES
-// below, from profiles/fp8_kv/kernel_resources.txt: a tile's pieces are 8 registers fewer per lane and pass, which by itself would let some forms fit one more wave and
-// take the schedule the compiler makes for it, the effect the note above describes.)
-struct PagedPrefillFp8Args : PagedPrefillArgs {
-    float k_scale, v_scale;
+// (e4m3 pools, and every windowed and sink form: pinned to what the fp16 counterpart has, from profiles/fp8_kv/kernel_resources.txt: a tile's pieces are 8 registers fewer
+//  per lane and pass, which by itself would let some forms fit one more wave and take the schedule the compiler makes for it, the effect the note above describes.  The
+//  fp16 forms' registers -> waves per SIMD: 4 waves x 1 row tile 196 / 209 -> 2; 8 x 1 120 -> 4, paired 156 -> 3 (pinned); 8 x 2 221 / 232 -> 2; 4 x 2 301 / 314 -> 1)
+struct WavesPerSimd {
+    int lo, hi;
 };
-__device__ __forceinline__ PagedBlockFp8Args paged_block_args_fp8(const PagedPrefillFp8Args &a, const PrefillSegment sg) {
-    PagedBlockFp8Args b;
-    static_cast<PagedBlockArgs &>(b) = paged_block_args(a, sg);
-    b.k_scale = a.k_scale;
-    b.v_scale = a.v_scale;
-    return b;
+constexpr WavesPerSimd paged_prefill_waves(int NW, int RT, bool PAIR, bool FP8, bool WINDOW, bool SINK) {
+    if (!FP8 && !WINDOW && !SINK) return PAIR && NW == 8 && RT == 1 ? WavesPerSimd{3, 3} : WavesPerSimd{1, 8};
+    const int w = RT == 2 ? (NW == 8 ? 2 : 1) : (NW == 8 ? (PAIR ? 3 : 4) : 2);
+    return {w, w};
 }
-// (the fp16 forms' registers -> waves per SIMD: 4 waves x 1 row tile 196 / 209 -> 2; 8 x 1 120 -> 4, paired 156 -> 3 (pinned); 8 x 2 221 / 232 -> 2; 4 x 2 301 / 314 -> 1)
-#define FP8_WAVES(NW, RT, PAIR) ((RT) == 2 ? ((NW) == 8 ? 2 : 1) : ((NW) == 8 ? ((PAIR) ? 3 : 4) : 2))
-template <int NW, int RT, bool PAIR>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FP8_WAVES(NW, RT, PAIR), FP8_WAVES(NW, RT, PAIR))))
-void attn_prefill_paged_fp8_kernel(const PagedPrefillFp8Args a) {
-    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile (fp16: dequantised on the way in)
+
+template <int NW, int RT, bool PAIR, bool FP8, bool WINDOW, bool SINK>
+__global__ __launch_bounds__(64 * NW)
+__attribute__((amdgpu_waves_per_eu(paged_prefill_waves(NW, RT, PAIR, FP8, WINDOW, SINK).lo, paged_prefill_waves(NW, RT, PAIR, FP8, WINDOW, SINK).hi)))
+void attn_prefill_paged_kernel(const paged_prefill_args_t<FP8, WINDOW, SINK> a) {
+    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile (e4m3 pools: dequantised on the way in)
     __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
     const int i = (int)blockIdx.x;
     const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
-    attn_prefill_block<false, NW, RT, true, true>(paged_block_args_fp8(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
+    attn_prefill_block<false, NW, RT, true, FP8, WINDOW, SINK>(paged_block_args<FP8, WINDOW, SINK>(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
     if constexpr (PAIR) {
         const int j = a.nblocks - 1 - i;
         if (i < j) {
             const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
-            attn_prefill_block<false, NW, RT, true, true>(paged_block_args_fp8(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
+            attn_prefill_block<false, NW, RT, true, FP8, WINDOW, SINK>(paged_block_args<FP8, WINDOW, SINK>(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
         }
     }
 }
-
-
-// The windowed launch, fp16 and e4m3 pools: the same workgroups, block list and pairs.  (waves per SIMD: every form is pinned to its unwindowed counterpart's, as above.)
-struct PagedPrefillWindowArgs : PagedPrefillFp8Args {
-    int window;
-};
-template <bool FP8>
-__device__ __forceinline__ PagedBlockWindowArgs paged_block_args_window(const PagedPrefillWindowArgs &a, const PrefillSegment sg) {
-    PagedBlockWindowArgs b;
-    static_cast<PagedBlockArgs &>(b) = paged_block_args(a, sg);
-    b.k_scale = FP8 ? a.k_scale : 0.f;
-    b.v_scale = FP8 ? a.v_scale : 0.f;
-    b.window = a.window;
-    return b;
-}
-template <int NW, int RT, bool PAIR, bool FP8>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FP8_WAVES(NW, RT, PAIR), FP8_WAVES(NW, RT, PAIR))))
-void attn_prefill_paged_window_kernel(const PagedPrefillWindowArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile
-    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
-    const int i = (int)blockIdx.x;
-    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
-    attn_prefill_block<false, NW, RT, true, FP8, true>(paged_block_args_window<FP8>(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
-    if constexpr (PAIR) {
-        const int j = a.nblocks - 1 - i;
-        if (i < j) {
-            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
-            attn_prefill_block<false, NW, RT, true, FP8, true>(paged_block_args_window<FP8>(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
-        }
-    }
-}
-
-// The sink launch, fp16 and e4m3 pools: the same workgroups, block list and pairs.  (waves per SIMD: every form is pinned to its windowed counterpart's.)
-struct PagedPrefillSinkArgs : PagedPrefillWindowArgs {
-    int sinks;
-    const half_t *qkv;
-    int ld_qkv;
-    const half_t *cos_s, *sin_s;
-};
-template <bool FP8>
-__device__ __forceinline__ PagedBlockSinkArgs paged_block_args_sink(const PagedPrefillSinkArgs &a, const PrefillSegment sg) {
-    PagedBlockSinkArgs b;
-    static_cast<PagedBlockWindowArgs &>(b) = paged_block_args_window<FP8>(a, sg);
-    b.sinks = a.sinks;
-    b.qkv = a.qkv;
-    b.ld_qkv = a.ld_qkv;
-    b.cos_s = a.cos_s;
-    b.sin_s = a.sin_s;
-    return b;
-}
-template <int NW, int RT, bool PAIR, bool FP8>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FP8_WAVES(NW, RT, PAIR), FP8_WAVES(NW, RT, PAIR))))
-void attn_prefill_paged_sink_kernel(const PagedPrefillSinkArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char ks[kBK * kKStride];  // K tile
-    __shared__ __attribute__((aligned(16))) unsigned char vs[kBK * kVStride];  // V tile
-    const int i = (int)blockIdx.x;
-    const unsigned e = (a.order[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
-    attn_prefill_block<false, NW, RT, true, FP8, true, true>(paged_block_args_sink<FP8>(a, a.seg[e >> 12]), (int)(e & 4095u), blockIdx.y, ks, vs);
-    if constexpr (PAIR) {
-        const int j = a.nblocks - 1 - i;
-        if (i < j) {
-            const unsigned f = (a.order[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
-            attn_prefill_block<false, NW, RT, true, FP8, true, true>(paged_block_args_sink<FP8>(a, a.seg[f >> 12]), (int)(f & 4095u), blockIdx.y, ks, vs);
-        }
-    }
-}
-
-#undef FP8_WAVES
 
 thread_local int g_prefill_pair = 0;   // 0: by the rule; 1 / 2: pairing forced on / off
 thread_local int g_prefill_waves = 0;  // 0: by the rule in launch_attention_prefill; forced (tests, sweeps): 4 / 8 waves with one row tile per wave, 14 / 18: with two
@@ -770,6 +705,16 @@ void prefill_form_rule(F blocks, int causal, int *form_out, int *pair_out) {
 }
 
 int form_rows(int form) { return form == 18 ? 256 : (form == 8 || form == 14 ? 128 : 64); }
+
+// f(NW, RT) of a block form, as integral constants
+template <class F>
+void with_block_form(int form, F &&f) {
+    using std::integral_constant;
+    if (form == 18) f(integral_constant<int, 8>{}, integral_constant<int, 2>{});
+    else if (form == 14) f(integral_constant<int, 4>{}, integral_constant<int, 2>{});
+    else if (form == 8) f(integral_constant<int, 8>{}, integral_constant<int, 1>{});
+    else f(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+}
 
 }  // namespace
 
@@ -809,42 +754,18 @@ int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, co
     auto blocks = [&](int rows) { return (long long)((m + rows - 1) / rows) * heads; };
     int form = 0;
     prefill_form_rule(blocks, causal, &form, &a.pair);
-    auto go = [&](auto nw_c, auto rt_c) {
-        constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
-        const int nb = (m + 16 * RT * NW - 1) / (16 * RT * NW);
-        const dim3 grid(a.pair ? (nb + 1) / 2 : nb, heads);
-        if (a.pair) {
-            if (mask) hipLaunchKernelGGL((attn_prefill_kernel<true, NW, RT, true>), grid, dim3(64 * NW), 0, stream, a);
-            else hipLaunchKernelGGL((attn_prefill_kernel<false, NW, RT, true>), grid, dim3(64 * NW), 0, stream, a);
-        } else {
-            if (mask) hipLaunchKernelGGL((attn_prefill_kernel<true, NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
-            else hipLaunchKernelGGL((attn_prefill_kernel<false, NW, RT, false>), grid, dim3(64 * NW), 0, stream, a);
-        }
-    };
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I4 = std::integral_constant<int, 4>;
-    using I8 = std::integral_constant<int, 8>;
-    if (form == 18) go(I8{}, I2{});
-    else if (form == 14) go(I4{}, I2{});
-    else if (form == 8) go(I8{}, I1{});
-    else go(I4{}, I1{});
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    with_block_form(form, [&](auto nw_c, auto rt_c) {
+        with_bools([&](auto mask_c, auto pair_c) {
+            constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
+            const int nb = (m + 16 * RT * NW - 1) / (16 * RT * NW);
+            hipLaunchKernelGGL((attn_prefill_kernel<decltype(mask_c)::value, NW, RT, decltype(pair_c)::value>), dim3(a.pair ? (nb + 1) / 2 : nb, heads), dim3(64 * NW), 0, stream, a);
+        }, mask != nullptr, a.pair != 0);
+    });
+    return launch_status(hip_err);
 }
 
 // ---- the paged launch ----
 namespace {
-
-int prefill_page_shift(int page_keys) {  // log2 of a power of two in [16, 256], or -1
-    for (int s = 4; s <= 8; ++s)
-        if (page_keys == (1 << s)) return s;
-    return -1;
-}
 
 // form, pairing and the block list (heaviest first; ties: in segment order, a segment's later blocks first) of a paged launch; false: more blocks than the list holds
 // window >= 1 (causal): a block walks the tiles from the one of its first row's first visible key on -- those are what it is weighed by
@@ -904,24 +825,15 @@ int describe_attention_prefill_paged(int heads, int causal, const int *segments,
     return TCE_OK;
 }
 
-namespace {
-float host_pow2(int e) {
-    const unsigned bits = (unsigned)(127 + e) << 23;
-    float f;
-    __builtin_memcpy(&f, &bits, 4);
-    return f;
-}
-}  // namespace
-
 // pages.fp8: the pools are e4m3 bytes and the two exponents apply; the plan and both launches' shapes are one text
 int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, const PrefillRows &r, hipStream_t stream, hipError_t *hip_err) {
     const int heads = s.heads, kv_heads = s.kv_heads, nseg = r.nseg, total_rows = r.total_rows, causal = r.causal, table_stride = pg.table_stride;
     const int k_log2 = pg.k_scale_log2, v_log2 = pg.v_scale_log2;
     const bool fp8 = pg.fp8;
     const int *const table = pg.table;
-    const int shift = prefill_page_shift(pg.page_keys);
+    const int shift = page_shift_of(pg.page_keys);
     if (shift < 0 || nseg < 1 || nseg > kMaxSegments || !table || table_stride < 1 || kv_heads <= 0 || heads % kv_heads != 0 || total_rows < 1) return TCE_ERR_UNSUPPORTED_SHAPE;
-    if (fp8 && (k_log2 < kFp8ScaleLog2Min || k_log2 > kFp8ScaleLog2Max || v_log2 < kFp8ScaleLog2Min || v_log2 > kFp8ScaleLog2Max)) return TCE_ERR_UNSUPPORTED_SHAPE;
+    if (fp8 && !(fp8_log2_ok(k_log2) && fp8_log2_ok(v_log2))) return TCE_ERR_UNSUPPORTED_SHAPE;
     const int window = s.window;
     const int sinks = s.sinks;
     if (window < 0 || (window && !causal) || sinks < 0 || sinks > 16 || (sinks && !window)) return TCE_ERR_UNSUPPORTED_SHAPE;
@@ -981,48 +893,16 @@ int launch_attention_prefill_paged(const KvPages &pg, const AttnStepArgs &s, con
     half_t ah;
     __builtin_memcpy(&ah, &s.alpha_bits, 2);
     a.alpha = (float)ah;
-    auto go = [&](auto nw_c, auto rt_c) {
-        constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
-        const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
-        if (sinks) {
-            if (fp8) {
-                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, true, true>), grid, dim3(64 * NW), 0, stream, a);
-                else hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, false, true>), grid, dim3(64 * NW), 0, stream, a);
-            } else {
-                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, true, false>), grid, dim3(64 * NW), 0, stream, a);
-                else hipLaunchKernelGGL((attn_prefill_paged_sink_kernel<NW, RT, false, false>), grid, dim3(64 * NW), 0, stream, a);
-            }
-        } else if (window) {
-            const PagedPrefillWindowArgs &w = a;
-            if (fp8) {
-                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, true>), grid, dim3(64 * NW), 0, stream, w);
-                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, true>), grid, dim3(64 * NW), 0, stream, w);
-            } else {
-                if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, true, false>), grid, dim3(64 * NW), 0, stream, w);
-                else hipLaunchKernelGGL((attn_prefill_paged_window_kernel<NW, RT, false, false>), grid, dim3(64 * NW), 0, stream, w);
-            }
-        } else if (fp8) {
-            if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillFp8Args &>(a));
-            else hipLaunchKernelGGL((attn_prefill_paged_fp8_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillFp8Args &>(a));
-        } else {
-            if (a.pair) hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, true>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillArgs &>(a));
-            else hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, false>), grid, dim3(64 * NW), 0, stream, static_cast<const PagedPrefillArgs &>(a));
-        }
-    };
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I4 = std::integral_constant<int, 4>;
-    using I8 = std::integral_constant<int, 8>;
-    if (form == 18) go(I8{}, I2{});
-    else if (form == 14) go(I4{}, I2{});
-    else if (form == 8) go(I8{}, I1{});
-    else go(I4{}, I1{});
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = e;
-        return TCE_ERR_HIP;
-    }
-    return TCE_OK;
+    const dim3 grid(a.pair ? (a.nblocks + 1) / 2 : a.nblocks, heads);
+    with_block_form(form, [&](auto nw_c, auto rt_c) {
+        with_bools([&](auto pair_c, auto fp8_c, auto window_c, auto sink_c) {
+            constexpr int NW = decltype(nw_c)::value, RT = decltype(rt_c)::value;
+            constexpr bool PAIR = decltype(pair_c)::value, FP8 = decltype(fp8_c)::value, WINDOW = decltype(window_c)::value, SINK = decltype(sink_c)::value;
+            if constexpr (!SINK || WINDOW)  // (sinks exist beside a window: refused above)
+                hipLaunchKernelGGL((attn_prefill_paged_kernel<NW, RT, PAIR, FP8, WINDOW, SINK>), grid, dim3(64 * NW), 0, stream, static_cast<const paged_prefill_args_t<FP8, WINDOW, SINK> &>(a));
+        }, a.pair != 0, fp8, window != 0, sinks != 0);
+    });
+    return launch_status(hip_err);
 }
 
 }  // namespace tce

@@ -12,6 +12,21 @@ namespace tce {
 
 constexpr int kFp8ScaleLog2Min = -8, kFp8ScaleLog2Max = 7;
 
+// the host's side, what the paged launchers test and compute before a launch: a pool's exponent is in range; 2^e as a float; log2 of a page size that is a power of
+// two in [16, 256], or -1
+inline bool fp8_log2_ok(int e) { return e >= kFp8ScaleLog2Min && e <= kFp8ScaleLog2Max; }
+inline float host_pow2(int e) {
+    const unsigned bits = (unsigned)(127 + e) << 23;
+    float f;
+    __builtin_memcpy(&f, &bits, 4);
+    return f;
+}
+inline int page_shift_of(int page_keys) {
+    for (int s = 4; s <= 8; ++s)
+        if (page_keys == 1 << s) return s;
+    return -1;
+}
+
 __device__ __forceinline__ float fp8_pow2(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }  // 2^e, -126 <= e <= 127
 
 // 8 bytes -> 8 binary16, three instructions per pair: v_cvt_pk_f32_fp8 widens a pair exactly (NaN bytes to NaN), v_cvt_pkrtz_f16_f32 narrows it to binary16 -- every

@@ -1298,16 +1298,6 @@ int tce_attention_decode_step_batch_f16(const void *qkv, void *kc, void *vc, con
 size_t tce_kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes(num_pages, kv_heads, page_keys, hd); }
 size_t tce_kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd) { return tce::kv_pages_pool_bytes_fp8(num_pages, kv_heads, page_keys, hd); }
 
-int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int pos_bound, int page_keys, char *buf, int buf_len) {
-    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys))
-        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_paged: bad argument");
-    int chunk = 0, chunks = 0, waves = 0;
-    tce::describe_attention_decode_batch(heads, kv_heads, pos_bound, &chunk, &chunks, &waves);
-    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
-                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
-    return TCE_OK;
-}
-
 // rows_per_seq null: the step.  Else the multi-row form (speculative decoding), which has two rules of its own: the row count, and `out` 16-byte aligned (it stores
 // `out` in 16-byte pieces; the step never required it, and callers rely on that)
 // window null: every key.  Else the windowed step (sliding-window attention; with rows_per_seq: the windowed multi-row step, both rules), whose one rule of its own is window >= 1
@@ -1318,6 +1308,32 @@ static int check_window(const char *who, const int *window) {
 // sinks null: none.  Else the sink step (attention sinks beside the window): its one rule of its own, 1 <= sinks <= 16, is tested behind every rule of the windowed entry point
 static int check_sinks(const char *who, const int *sinks) {
     return sinks && (*sinks < 1 || *sinks > 16) ? fail(TCE_ERR_BAD_ARG, "%s: sinks %d (1 .. 16: the first keys of the sequence, all in the first page)", who, *sinks) : TCE_OK;
+}
+
+// the paged describe entry points: one guard, the form's cut, one text.  window null: every key; sinks null: none
+static int describe_paged(const char *who, int batch, int heads, int kv_heads, int pos_bound, int page_keys, const int *window, const int *sinks, char *buf, int buf_len) {
+    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys) || (window && *window < 1))
+        return fail(TCE_ERR_BAD_ARG, "%s: bad argument", who);
+    if (const int rc = check_sinks(who, sinks)) return rc;
+    int chunk = 0, chunks = 0, waves = 0;
+    if (sinks) tce::describe_attention_decode_sink(heads, kv_heads, pos_bound, *window, *sinks, &chunk, &chunks, &waves);
+    else if (window) tce::describe_attention_decode_window(heads, kv_heads, pos_bound, *window, &chunk, &chunks, &waves);
+    else tce::describe_attention_decode_batch(heads, kv_heads, pos_bound, &chunk, &chunks, &waves);
+    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
+                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
+    return TCE_OK;
+}
+
+int tce_attention_decode_describe_paged(int batch, int heads, int kv_heads, int pos_bound, int page_keys, char *buf, int buf_len) {
+    return describe_paged("tce_attention_decode_describe_paged", batch, heads, kv_heads, pos_bound, page_keys, nullptr, nullptr, buf, buf_len);
+}
+
+int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len) {
+    return describe_paged("tce_attention_decode_describe_paged_window", batch, heads, kv_heads, pos_bound, page_keys, &window, nullptr, buf, buf_len);
+}
+
+int tce_attention_decode_describe_paged_sink(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, int sinks, char *buf, int buf_len) {
+    return describe_paged("tce_attention_decode_describe_paged_sink", batch, heads, kv_heads, pos_bound, page_keys, &window, &sinks, buf, buf_len);
 }
 
 static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs s, const int *rows_per_seq, void *stream, const int *window = nullptr, const int *sinks = nullptr) {
@@ -1353,16 +1369,6 @@ int tce_attention_decode_step_paged_fp8(const void *qkv, void *k_pool, void *v_p
                       {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream);
 }
 
-int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len) {
-    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys) || window < 1)
-        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_paged_window: bad argument");
-    int chunk = 0, chunks = 0, waves = 0;
-    tce::describe_attention_decode_window(heads, kv_heads, pos_bound, window, &chunk, &chunks, &waves);
-    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
-                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
-    return TCE_OK;
-}
-
 int tce_attention_decode_step_paged_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                                const void *cosv, const void *sinv, void *out, void *workspace, int batch, int heads, int kv_heads, int hd,
                                                const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int window, void *stream) {
@@ -1376,17 +1382,6 @@ int tce_attention_decode_step_paged_window_fp8(const void *qkv, void *k_pool, vo
                                                void *stream) {
     return paged_step("tce_attention_decode_step_paged_window_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                       {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, nullptr, stream, &window);
-}
-
-int tce_attention_decode_describe_paged_sink(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, int sinks, char *buf, int buf_len) {
-    if (!buf || buf_len <= 0 || batch <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0 || pos_bound < 0 || !page_keys_ok(page_keys) || window < 1)
-        return fail(TCE_ERR_BAD_ARG, "tce_attention_decode_describe_paged_sink: bad argument");
-    if (const int rc = check_sinks("tce_attention_decode_describe_paged_sink", &sinks)) return rc;
-    int chunk = 0, chunks = 0, waves = 0;
-    tce::describe_attention_decode_sink(heads, kv_heads, pos_bound, window, sinks, &chunk, &chunks, &waves);
-    std::snprintf(buf, (size_t)buf_len, "chunks=%d keys-per-chunk=%d waves=%d workgroups=%lld combine=%s batch=%d page-keys=%d", chunks, chunk, waves,
-                  (long long)batch * heads * chunks, chunks > 1 ? "yes" : "no", batch, page_keys);
-    return TCE_OK;
 }
 
 int tce_attention_decode_step_paged_sink_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
