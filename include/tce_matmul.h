@@ -520,8 +520,9 @@ TCE_API int tce_kv_block_table_check_sink(const int32_t *block_table, int table_
  * no recapture.  A fresh row has generated = ring_pushed = 0 and ring = 64 zeros, as the reference's last_n_tokens starts (token 0 is penalised until 64 tokens have
  * passed); prompt tokens are pushed by the host at admission (ring[ring_pushed % 64], ring_pushed += 1).  A row's top_k outside [1, top_k_bound] is clamped (it lives
  * on the device: the host cannot refuse it at the call).
- * NOT BUILT: tfs_z, typical_p, mirostat (the call accepts only their disabled values 1.0, 1.0, 0), top_k <= 0 = "whole vocabulary", k > 256: TCE_ERR_UNSUPPORTED_SHAPE
- * before any launch.  (Token masks, automata and logit_bias ARE built: tce_sample_constrained_f16 below; this entry point applies none.)  Also refused there: vocab > ld (TCE_ERR_BAD_ARG), vocab > 2^20, logits not 16-byte aligned or ld % 8 != 0, and ceil(vocab / 4096) * top_k_bound
+ * NOT BUILT: mirostat, top_k <= 0 = "whole vocabulary", k > 256; and this entry point runs no tail-free or typical stage -- the CALL accepts only the disabled values
+ * tfs_z 1.0, typical_p 1.0, mirostat 0 --: TCE_ERR_UNSUPPORTED_SHAPE before any launch.  (The two stages ARE built, per slot: tce_sample_stages_f16 below.  Token masks,
+ * automata and logit_bias ARE built: tce_sample_constrained_f16 below; this entry point applies none.)  Also refused there: vocab > ld (TCE_ERR_BAD_ARG), vocab > 2^20, logits not 16-byte aligned or ld % 8 != 0, and ceil(vocab / 4096) * top_k_bound
  * > 8192 (the second launch holds the chunks' survivors in registers: 131072 entries at k = 256, 838k at k = 40).
  * workspace: tce_sample_workspace_bytes(batch, vocab) bytes (0 for a bad shape), zeroed once; word 0 counts the ids tce_embed_rows_f16 refused, the rest carries the
  * first launch's survivors to the second -- the kernel boundary is the only ordering, there is no counter to reset.  The logits are not modified.
@@ -586,7 +587,7 @@ TCE_API int tce_sample_f16(const tce_sample_call *call, void *stream);
  * LOSSLESS: the emitted tokens are those of tce_sample_f16 called once per token.  A row that is reached at all has had all its drafts accepted, so its window (the
  * ring plus drafts 1 .. t) is known in advance: the select launch runs for all B * T rows at once, the draw per row into a candidate array, and a last small launch
  * walks the chain and writes state.  Cache rows p + t + 1 .. of REJECTED drafts stay behind the position as garbage: the next step overwrites them or never weighs them.
- * Refusals: tce_sample_f16's (tfs, typical, mirostat, k > 256 and whole-vocabulary top-k stay unbuilt), rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS, batch *
+ * Refusals: tce_sample_f16's (mirostat, k > 256 and whole-vocabulary top-k stay unbuilt; tail-free and typical run behind tce_sample_verify_stages_f16), rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS, batch *
  * rows_per_seq > 65535, ngram outside 1 .. 4, hist_stride <= pos_bound. */
 typedef struct tce_sample_verify_call {
     tce_sample_call s;
@@ -680,6 +681,51 @@ typedef struct tce_constraint {
 } tce_constraint;
 TCE_API int tce_sample_constrained_f16(const tce_sample_call *call, const tce_constraint *c, const tce_logprob_out *lp /* may be NULL */, void *stream);
 TCE_API int tce_sample_verify_constrained_f16(const tce_sample_verify_call *call, const tce_constraint *c, const tce_logprob_out *lp /* may be NULL */, void *stream);
+/* Tail-free and locally typical sampling per slot (csrc/sampling.hip; additive within ABI 113, no existing struct or entry point changes): the two stages the reference
+ * runs between top-k and top-p in its temperature branch (LLaMA3Generate.cc:174-179: sample_top_k -> sample_tail_free(tfs_z) -> sample_typical(typical_p) -> sample_top_p
+ * -> sample_temperature -> sample_token; Generate.cc:203-302), with their two values PER SLOT in st->rows[b] -- two requests of one batch may differ, and a slot changes
+ * hands by one copy with no recapture.  tce_sample_stages_f16 is tce_sample_f16 (with lp: tce_sample_logprobs_f16; with c: tce_sample_constrained_f16) with, per ACTIVE
+ * row with temp > 0, behind the penalties (bias, mask) and top-k, on the kk candidates in the project's order (descending penalised logit, ascending id among equals),
+ * values l_i.  fp32, IEEE operations, no contraction; sums SEQUENTIAL in index order from 0.0f; expf and logf; comparisons as the reference writes them:
+ *   1. SOFTMAX(m candidates in their current order): e_i = expf(l_i - l_first), s = sum e_i, p_i = e_i / s, l_first = the value of the candidate that stands FIRST --
+ *      after rule 3 that need not be the maximum (the reference's `sorted` flag stays set and sample_softmax takes data[0].logit), so an argument may be positive.
+ *   2. TAIL-FREE.  Runs iff !(tfs_z >= 1.0f) and kk > 2, on p = softmax(kk): d1_i = p_i - p_{i+1} (i < kk - 1), d2_i = fabsf(d1_i - d1_{i+1}) (i < kk - 2), S = sum d2_i,
+ *      w_i = d2_i / S, cum the running sum of w; n1 = the first i >= 1 with cum_i > tfs_z, else kk.  S == 0 (equal candidates): NaN weights, no comparison holds, nothing
+ *      is cut.  tfs_z <= 0 keeps one candidate; a NaN tfs_z runs the stage and cuts nothing.
+ *   3. TYPICAL.  Runs iff !(typical_p >= 1.0f), on p = softmax(the first n1) (bit-identical to rule 2's when n1 == kk): H = sum (-p_i) * logf(p_i), one multiply and one
+ *      add per term; s_i = fabsf(-logf(p_i) - H); the candidates are ordered by ASCENDING s, the EARLIER candidate first among equal scores (std::sort leaves ties open:
+ *      the project's choice, like the id rule) -- rank_i = #{ j : s_j < s_i || (!(s_i < s_j) && j < i) }.  A p_i of 0 makes logf -inf, H NaN and every score NaN: the
+ *      order stays as it is.  With cum the running sum of p in that order, n2 = i + 1 at the first i >= 0 with cum > typical_p, else n1.  The candidates BECOME
+ *      order[0 .. n2) in that order.
+ *   4. TOP-P.  Runs iff top_p < 1.0f, as tce_sample_f16's, over softmax(the n2 in their current order): n = the first i >= 1 with cum_i > top_p, else n2.
+ *   5. l_i / temp, softmax(the n in their current order), the inverse-CDF draw in that order (the first i with u < cdf_i, else n - 1); the token is the id of the
+ *      candidate at that position.  Greedy rows, the generator's counter, the tail, stop ids, retirement and inactive rows are tce_sample_f16's.
+ *   6. IDENTITY.  A row whose two values are both >= 1.0f comes out bit for bit as the underlying entry point writes it: token, log, ring, counters, position, debug
+ *      record, logprob and constraint state.
+ * st->rows: DEVICE array [batch] of tce_stage_row; a captured graph keeps the pointer, the host rewrites a slot's pair stream-ordered.  st->debug (may be NULL): [batch]
+ * records for tests.  With it, tce_sample_debug keeps the meaning of ids, logit, p (the softmax over kk) and k -- the SORTED top-k candidates --; n, final_p and choice
+ * refer to the final order.
+ * tce_sample_verify_stages_f16: tce_sample_verify_f16 (with lp / c: its logprob / constrained form); st->rows is per SEQUENCE -- every virtual row of a sequence is
+ * sampled with its sequence's pair --, st->debug per VIRTUAL row.  LOSSLESS as the verifier is: the emitted tokens are those of tce_sample_stages_f16 called once per token.
+ * Launches: 2 and 3 as before; the first (the vocabulary pass) is the underlying form's own kernel.
+ * Refusals, before any launch: everything the underlying entry point refuses -- non-default tfs_z / typical_p / mirostat in the CALL included: the call's two fields stay
+ * refused, the values live in st->rows --, the constrained / logprob forms' for a non-NULL c / lp; TCE_ERR_BAD_ARG for a NULL st or st->rows; TCE_ERR_UNSUPPORTED_SHAPE for
+ * rows or debug not 4-byte aligned.
+ * NOT BUILT: mirostat, both versions (mirostat != 0 stays refused).  It replaces top-k with a softmax over the WHOLE sorted vocabulary, summed sequentially; its candidate
+ * count is not bounded by top_k_bound; its mu is a process-wide static in the reference; and a speculative row's cut would depend on the draw of the row in front of it,
+ * so the verifier's rows could not be sampled "known in advance".  A different design.  Also not built, as before: top_k <= 0 = "whole vocabulary", k > 256. */
+typedef struct tce_stage_row { float tfs_z, typical_p; } tce_stage_row;   /* per slot (8 bytes); 1.0 = off; changes hands by one copy */
+typedef struct tce_stage_debug {                                          /* tests; per row (per virtual row in the verifier); 2056 bytes.  A greedy row (temp <= 0) has ONE
+                                                                             candidate: n_tfs = n_typ = 1, order = {0}, p_top = 0.  An inactive or rule-6 row writes nothing */
+    int32_t n_tfs, n_typ;          /* candidates after tail-free, after typical */
+    int32_t order[256];            /* position i of the final order -> index into the sorted top-k candidates, i < n_typ (-1 behind) */
+    float p_top[256];              /* the softmax top-p walked (n_typ entries, final order) */
+} tce_stage_debug;
+typedef struct tce_sample_stages { tce_stage_row *rows; tce_stage_debug *debug /* may be NULL */; } tce_sample_stages;
+TCE_API int tce_sample_stages_f16(const tce_sample_call *call, const tce_sample_stages *st, const tce_constraint *c /* may be NULL */, const tce_logprob_out *lp /* may be NULL */,
+                                  void *stream);
+TCE_API int tce_sample_verify_stages_f16(const tce_sample_verify_call *call, const tce_sample_stages *st, const tce_constraint *c /* may be NULL */,
+                                         const tce_logprob_out *lp /* may be NULL */, void *stream);
 /* The next step's input rows, one launch: row token[b] of an fp16 table [vocab][hidden] into out[b] ([batch][hidden]) for every active row (pos_device / pos_bound as
  * above; inactive rows are left as they are).  The reference looks an fp32 table up and rounds with float2half (Int4llamaDecoder: Embedding + float2half); a table
  * rounded once to fp16 gives the same bits.  A token outside [0, vocab) is not followed: the row is written as zeros and word 0 of `workspace` (tce_sample_f16's, or

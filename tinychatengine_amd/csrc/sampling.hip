@@ -28,6 +28,11 @@
 // an invalid transition as one path (nothing emitted, the row retires, *violations += 1) and stores the next state in the tail; the verifier walks the drafts' transitions
 // to know each virtual row's state in advance.  fsm_next is the one edge lookup of all three.  The CON = false forms declare nothing new and compile to the instructions
 // they were (profiles/constrained/).
+//
+// TAIL-FREE AND TYPICAL SAMPLING (tce_sample_stages_f16, tce_sample_verify_stages_f16; the rules are in include/tce_matmul.h): the STG = true forms of the draw kernel
+// run the reference's sample_tail_free and sample_typical between the rank sort and top-p, on the candidates already in LDS, with the two values per slot in a
+// tce_stage_row.  The select and chain kernels are the underlying form's own.  The STG = false forms declare nothing new -- not even a local variable -- and compile to
+// the instructions they were (profiles/sampler_stages/).
 #include "tce_common.hpp"
 
 #include <type_traits>
@@ -417,11 +422,32 @@ struct VerifyArgs {
 // CON: no survivor at all (V == 0: an invalid or unreachable row, or a state that allows nothing inside the vocabulary) is rule 6 -- the row retires, *violations += 1,
 // nothing else is written (SPEC: cand = -1, the chain launch applies the rule).  Otherwise thread 0 looks the drawn token's transition up (fsm_next) BEFORE anything
 // is written: a next outside [-1, states) is rule 6 again; DONE retires the row behind the token like a stop id; any other next is stored as the state, in the tail.
+// STG (tce_sample_stages_f16, tce_sample_verify_stages_f16; the rules are in include/tce_matmul.h): sample_tail_free and sample_typical (Generate.cc:203-302) between
+// the rank sort and top-p, on the <= 256 sorted candidates in LDS and in the kernel's idiom -- per-element work on threads < kk, every thread walks the sequential sums
+// itself.  Tail-free cuts the sorted candidates to n1; typical ranks the n1 by |-logf(p) - H| (the 256 x 256 count that sorted the winners; equal scores keep their
+// order), cuts to n2 and PERMUTES lg / ids, so that top-p, temperature, the draw, the constraint lookup and the tail read the final order unchanged.  A row whose two
+// values are both >= 1.0 takes neither branch and recomputes nothing: its arithmetic is the STG = false form's.  The STG = false forms declare nothing new.
+struct StgLds {  // the STG = true forms' LDS (only they instantiate it): the sorted candidates, the softmax top-p walks, d2 / the scores, the order by score
+    float sv_lg[kMaxK], pq[kMaxK + 8], sc[kMaxK + 8];
+    int sv_id[kMaxK], ord[kMaxK];
+    int n1, n2, permuted, recomputed;  // thread 0's, for the debug record: a local variable, even an unused one, changes the STG = false forms' code
+};
+__device__ __forceinline__ StgLds &stg_lds() {
+    __shared__ StgLds s;
+    return s;
+}
+template <class Base>
+struct StgArgs : Base {  // the STG = true forms' arguments: the underlying form's, then the stage rows (the STG = false instantiations keep their argument layout)
+    const tce_stage_row *srows;  // [batch] (SPEC: per sequence)
+    tce_stage_debug *sdebug;     // [rows] or null
+};
 template <bool LSE, bool CON>
-using DrawArgsOf = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, DrawLseArgs, DrawArgs>>, std::conditional_t<LSE, DrawLseArgs, DrawArgs>>;
+using DrawArgsBase = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, DrawLseArgs, DrawArgs>>, std::conditional_t<LSE, DrawLseArgs, DrawArgs>>;
+template <bool LSE, bool CON, bool STG = false>
+using DrawArgsOf = std::conditional_t<STG, StgArgs<DrawArgsBase<LSE, CON>>, DrawArgsBase<LSE, CON>>;
 
-template <bool SPEC, bool LSE, bool CON>
-__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, CON> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
+template <bool SPEC, bool LSE, bool CON, bool STG = false>
+__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, CON, STG> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(a.pos, b, a.pos_bound)) return;
     [[maybe_unused]] float lse = 0.0f;
@@ -494,6 +520,18 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
     }
     __syncthreads();
 
+    if constexpr (STG) {  // the sorted candidates as the debug record shows them: typical permutes lg / ids
+        StgLds &S = stg_lds();
+        if (tid == 0) {
+            S.n1 = S.n2 = kk;
+            S.permuted = S.recomputed = 0;
+        }
+        if (tid < kk) {
+            S.sv_lg[tid] = lg[tid];
+            S.sv_id[tid] = ids[tid];
+        }
+    }
+
     const unsigned gen = SPEC ? r.generated + (unsigned)vt : r.generated;
     float u = 0.0f;
     int n = 1, choice = 0;
@@ -507,7 +545,106 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
         if (tid < kk) pr[tid] = ex[tid] / sum;
         __syncthreads();
         n = kk;
-        if (r.top_p < 1.0f) {  // sample_top_p (:304-327) with min_keep 1: the candidate that crosses the threshold is dropped
+        if constexpr (STG) {
+            StgLds &S = stg_lds();
+            float *const sc = S.sc, *const pq = S.pq;
+            int *const ord = S.ord;
+            int n1 = kk, n2;
+            bool permuted = false, recomputed = false;
+            const tce_stage_row &sr = a.srows[SPEC ? seq : b];
+            const float z = sr.tfs_z, typ = sr.typical_p;
+            if (!(z >= 1.0f) && kk > 2) {  // sample_tail_free (:203-246) with min_keep 1, on the softmax over the kk
+                if (tid < kk - 2) sc[tid] = fabsf((pr[tid] - pr[tid + 1]) - (pr[tid + 1] - pr[tid + 2]));
+                __syncthreads();
+                float d2sum = 0.0f;
+                for (int i = 0; i < kk - 2; ++i) d2sum += sc[i];
+                if (tid < kk - 2) pq[tid] = sc[tid] / d2sum;  // the weights, divided side by side: the walk below only adds (a sum of 0: NaN weights, no comparison holds, nothing is cut)
+                __syncthreads();
+                float cum = 0.0f;
+                for (int i = 0; i < kk - 2; ++i) {
+                    cum += pq[i];
+                    if (cum > z && i >= 1) {
+                        n1 = i;
+                        break;
+                    }
+                }
+                __syncthreads();  // (sc and pq are written again below)
+            }
+            n2 = n1;
+            if (!(typ >= 1.0f)) {  // sample_typical (:248-302) with min_keep 1, on the softmax over the n1
+                if (tid < n1) ex[tid] = expf(lg[tid] - l0);
+                __syncthreads();
+                float s1 = 0.0f;
+                for (int i = 0; i < n1; ++i) s1 += ex[i];
+                if (tid < n1) pq[tid] = ex[tid] / s1;
+                __syncthreads();
+                if (tid < n1) ex[tid] = logf(pq[tid]);
+                ord[tid] = tid;  // (a rank that NaNs leave unassigned stays an index of the row)
+                __syncthreads();
+                float H = 0.0f;
+                for (int i = 0; i < n1; ++i) H += -pq[i] * ex[i];
+                if (tid < n1) sc[tid] = fabsf(-ex[tid] - H);
+                __syncthreads();
+                if (tid < n1) {  // ascending score, the earlier candidate first among equals (every score NaN: the order stays)
+                    const float mine = sc[tid];
+                    int rank = 0;
+                    for (int j = 0; j < n1; ++j) rank += (sc[j] < mine || (!(mine < sc[j]) && j < tid)) ? 1 : 0;
+                    ord[rank] = tid;
+                }
+                __syncthreads();
+                if (tid < n1) sc[tid] = pq[ord[tid]];  // p in score order, gathered side by side: the walk below reads one word per step
+                __syncthreads();
+                float cum = 0.0f;
+                for (int i = 0; i < n1; ++i) {
+                    cum += sc[i];
+                    if (cum > typ) {
+                        n2 = i + 1;
+                        break;
+                    }
+                }
+                float lv = 0.0f;
+                int iv = 0;
+                if (tid < n2) {
+                    lv = lg[ord[tid]];
+                    iv = ids[ord[tid]];
+                }
+                __syncthreads();
+                if (tid < n2) {
+                    lg[tid] = lv;
+                    ids[tid] = iv;
+                }
+                permuted = true;
+                __syncthreads();
+            }
+            if (!(z >= 1.0f) || !(typ >= 1.0f)) {  // sample_top_p's softmax over the n2 in their current order: data[0] need not be the maximum any more
+                const float f0 = lg[0];
+                if (tid < n2) ex[tid] = expf(lg[tid] - f0);
+                __syncthreads();
+                float s2 = 0.0f;
+                for (int i = 0; i < n2; ++i) s2 += ex[i];
+                if (tid < n2) pq[tid] = ex[tid] / s2;
+                __syncthreads();
+                recomputed = true;
+            }
+            if (tid == 0) {  // (for the debug record, behind a barrier)
+                S.n1 = n1;
+                S.n2 = n2;
+                S.permuted = permuted;
+                S.recomputed = recomputed;
+            }
+            n = n2;
+            if (r.top_p < 1.0f) {  // sample_top_p over the n2, on the softmax above
+                const float *pt = recomputed ? pq : pr;
+                float cum = 0.0f;
+                for (int i = 0; i < n2; ++i) {
+                    cum += pt[i];
+                    if (cum > r.top_p && i >= 1) {
+                        n = i;
+                        break;
+                    }
+                }
+            }
+        } else if (r.top_p < 1.0f) {  // sample_top_p (:304-327) with min_keep 1: the candidate that crosses the threshold is dropped
             float cum = 0.0f;
             for (int i = 0; i < kk; ++i) {
                 cum += pr[i];
@@ -564,8 +701,13 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
         tce_sample_debug &d = a.debug[b];
         if (tid < kMaxK) {
             const bool in_k = tid < kk, in_n = tid < n && r.temp > 0.0f;
-            d.ids[tid] = in_k ? ids[tid] : -1;
-            d.logit[tid] = in_k ? lg[tid] : 0.0f;
+            if constexpr (STG) {  // the sorted top-k candidates, whatever typical made of lg / ids
+                d.ids[tid] = in_k ? stg_lds().sv_id[tid] : -1;
+                d.logit[tid] = in_k ? stg_lds().sv_lg[tid] : 0.0f;
+            } else {
+                d.ids[tid] = in_k ? ids[tid] : -1;
+                d.logit[tid] = in_k ? lg[tid] : 0.0f;
+            }
             d.p[tid] = in_k && r.temp > 0.0f ? pr[tid] : 0.0f;
             d.final_p[tid] = in_n ? fp[tid] : 0.0f;
         }
@@ -574,6 +716,22 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
             d.k = kk;
             d.u = u;
             d.choice = choice;
+        }
+    }
+    if constexpr (STG) {
+        if (a.sdebug) {
+            tce_stage_debug &sd = a.sdebug[b];
+            StgLds &S = stg_lds();
+            __syncthreads();  // (thread 0's words; a greedy row passes no other barrier behind them)
+            const float *pt = S.recomputed ? S.pq : pr;
+            if (tid < kMaxK) {
+                sd.order[tid] = tid < S.n2 ? (S.permuted ? S.ord[tid] : tid) : -1;
+                sd.p_top[tid] = tid < S.n2 && r.temp > 0.0f ? pt[tid] : 0.0f;
+            }
+            if (tid == 0) {
+                sd.n_tfs = S.n1;
+                sd.n_typ = S.n2;
+            }
         }
     }
     // ---- the tail: the token, the log, the ring, the counters, the position ----
@@ -837,8 +995,13 @@ static auto con_args(const Base &base, const tce_constraint *con) {
     }
 }
 
-// lp == null: tce_sample_f16, the launches they were
-int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err) {
+// tce_sample_stages_f16 / tce_sample_verify_stages_f16's draw launch: the STG = true form for `base` (DrawArgs or DrawLseArgs) with the stage rows behind the
+// underlying form's arguments.  Defined behind the two launchers, whose own launches stay as they were.
+template <bool SPEC, class Base>
+static void launch_draw_stages(const Base &base, const tce_constraint *con, const tce_sample_stages *stg, int rows, int RT, int32_t *cand, hipStream_t stream);
+
+// lp == null: tce_sample_f16, the launches they were.  stg (tce_sample_stages_f16): the select launch is the same, the draw launch is its STG = true form.
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err, const tce_sample_stages *stg) {
     const tce_constraint cv = con ? *con : tce_constraint{};
     const int nchunks = sample_chunks(c.vocab);
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
@@ -879,10 +1042,13 @@ int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const
             la.out_logprob = lp->out_logprob;
             la.last_lse = lp->last_lse;
             la.cand_logprob = la.cand_lse = nullptr;
-            with_con(con, [&](auto tag) {
+            if (stg) launch_draw_stages<false>(la, con, stg, c.batch, 1, nullptr, stream);
+            else with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
                 hipLaunchKernelGGL((sample_draw_kernel<false, true, CON>), dim3(c.batch), dim3(kThreads), 0, stream, con_args<CON>(la, con), 1, static_cast<int32_t *>(nullptr));
             });
+        } else if (stg) {
+            launch_draw_stages<false>(a, con, stg, c.batch, 1, nullptr, stream);
         } else {
             with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
@@ -906,7 +1072,8 @@ size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
     return verify_cand_offset(batch, rows_per_seq, vocab) + (((size_t)batch * rows_per_seq * 4 + 255) & ~(size_t)255);
 }
 
-int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err) {
+int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
+                             const tce_sample_stages *stg) {
     const tce_sample_call &c = v.s;
     const tce_constraint cv = con ? *con : tce_constraint{};
     const int nchunks = sample_chunks(c.vocab), T = v.rows_per_seq, vrows = c.batch * T;
@@ -965,10 +1132,13 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
     if (e == hipSuccess) {
         if (lp) {
             static_cast<DrawArgs &>(ld) = a.d;
-            with_con(con, [&](auto tag) {
+            if (stg) launch_draw_stages<true>(ld, con, stg, vrows, T, a.cand, stream);
+            else with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
                 hipLaunchKernelGGL((sample_draw_kernel<true, true, CON>), dim3(vrows), dim3(kThreads), 0, stream, con_args<CON>(ld, con), T, a.cand);
             });
+        } else if (stg) {
+            launch_draw_stages<true>(a.d, con, stg, vrows, T, a.cand, stream);
         } else {
             with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
@@ -998,6 +1168,19 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
         return TCE_ERR_HIP;
     }
     return TCE_OK;
+}
+
+template <bool SPEC, class Base>
+static void launch_draw_stages(const Base &base, const tce_constraint *con, const tce_sample_stages *stg, int rows, int RT, int32_t *cand, hipStream_t stream) {
+    constexpr bool LSE = std::is_same_v<Base, DrawLseArgs>;
+    with_con(con, [&](auto tag) {
+        constexpr bool CON = decltype(tag)::value;
+        StgArgs<DrawArgsBase<LSE, CON>> x;
+        static_cast<DrawArgsBase<LSE, CON> &>(x) = con_args<CON>(base, con);
+        x.srows = stg->rows;
+        x.sdebug = stg->debug;
+        hipLaunchKernelGGL((sample_draw_kernel<SPEC, LSE, CON, true>), dim3(rows), dim3(kThreads), 0, stream, x, RT, cand);
+    });
 }
 
 int launch_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, hipStream_t stream,

@@ -21,14 +21,16 @@ size_t w8a8_scratch_bytes();
 void set_w8a8_xsplit(int xs);
 int sample_chunks(int vocab);
 size_t sample_workspace_bytes(int batch, int vocab);
-int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err);
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
+                      const tce_sample_stages *stg = nullptr);
 size_t logprobs_workspace_bytes(int rows, int vocab);
 int launch_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, hipStream_t stream,
                         hipError_t *hip_err);
 int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *token, void *out, int batch, const int32_t *pos, int pos_bound, void *workspace,
                           hipStream_t stream, hipError_t *hip_err);
 size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
-int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err);
+int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
+                             const tce_sample_stages *stg = nullptr);
 int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
                        int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err);
 int launch_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, hipStream_t stream,
@@ -1627,6 +1629,41 @@ int tce_sample_verify_constrained_f16(const tce_sample_verify_call *v, const tce
         if (const int rc = check_logprob_out(who, lp)) return rc;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_sample_verify_f16(*v, lp, con, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
+}
+
+// the stages forms' own refusals (after the sampling call's)
+static int check_stages(const char *who, const tce_sample_stages *st) {
+    if (!st) return fail(TCE_ERR_BAD_ARG, "%s: null tce_sample_stages", who);
+    if (!st->rows) return fail(TCE_ERR_BAD_ARG, "%s: null pointer (rows)", who);
+    if ((reinterpret_cast<uintptr_t>(st->rows) | reinterpret_cast<uintptr_t>(st->debug)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: stage rows / debug 4-byte aligned", who);
+    return TCE_OK;
+}
+
+int tce_sample_stages_f16(const tce_sample_call *c, const tce_sample_stages *st, const tce_constraint *con, const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_stages_f16";
+    if (const int rc = check_sample_call(who, c, c ? c->batch : 0)) return rc;
+    if (const int rc = check_stages(who, st)) return rc;
+    if (con)
+        if (const int rc = check_constraint(who, con)) return rc;
+    if (lp)
+        if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_f16(*c, lp, con, static_cast<hipStream_t>(stream), &he, st);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+int tce_sample_verify_stages_f16(const tce_sample_verify_call *v, const tce_sample_stages *st, const tce_constraint *con, const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_verify_stages_f16";
+    if (const int rc = check_verify_call(who, v)) return rc;
+    if (const int rc = check_stages(who, st)) return rc;
+    if (con)
+        if (const int rc = check_constraint(who, con)) return rc;
+    if (lp)
+        if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_verify_f16(*v, lp, con, static_cast<hipStream_t>(stream), &he, st);
     return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
 }
 

@@ -7,6 +7,7 @@ The batched / paged decoders (batch_decode.py, paged_kv.py) run a "step" = the l
     1        tce_rmsnorm_half        the final norm, B rows
     1        tce_w4a16_forward       lm_head at M = B -> logits fp16 [B][vocab]
     2        tce_sample_f16          penalties, top-k, softmax, top-p, temperature, draw; token -> next_token, log, ring; pos += 1 or -1 (retired)
+                                     (stages=True: tce_sample_stages_f16, the same two launches with tail-free and typical sampling per slot between top-k and top-p)
                                      (logprobs=True: tce_sample_logprobs_f16, the same two launches, which also write the token's log-probability)
                                      (constraints=True: tce_sample_constrained_f16, the same two launches under a token automaton and a logit bias per slot:
                                      constrain.py)
@@ -83,8 +84,14 @@ class SamplingParams:
     typical_p: float = 1.0
     mirostat: int = 0
 
-    def check(self, top_k_bound: int = MAX_K) -> None:
-        if self.tfs_z != 1.0 or self.typical_p != 1.0 or self.mirostat != 0:
+    def check(self, top_k_bound: int = MAX_K, stages: bool = False) -> None:
+        """stages=False: what tce_sample_f16 can run (tfs_z 1.0, typical_p 1.0).  stages=True: what tce_sample_stages_f16 can run -- any tfs_z / typical_p but NaN."""
+        if stages:
+            if self.mirostat != 0:
+                raise ValueError("mirostat sampling is not built (mirostat 0 only)")
+            if self.tfs_z != self.tfs_z or self.typical_p != self.typical_p:
+                raise ValueError("tfs_z / typical_p: NaN")
+        elif self.tfs_z != 1.0 or self.typical_p != 1.0 or self.mirostat != 0:
             raise ValueError("tail-free, typical and mirostat sampling are not built (tfs_z 1.0, typical_p 1.0, mirostat 0 only)")
         if self.temp > 0 and not 1 <= self.top_k <= top_k_bound:
             raise ValueError(f"top_k {self.top_k}: 1 .. {top_k_bound} (top_k <= 0 = the whole vocabulary is not built)")
@@ -131,6 +138,49 @@ def top_p_cut(p: np.ndarray, top_p) -> int:
     return int(hit[0]) + 1 if hit.size else int(p.size)
 
 
+def _softmax_first(l: np.ndarray) -> np.ndarray:
+    """sample_softmax on candidates whose `sorted` flag is set (Generate.cc:91-100): subtract the value of the candidate that stands FIRST -- behind sample_typical not
+    the maximum --, expf, a SEQUENTIAL fp32 sum, divide.  On sorted candidates this is _softmax_sorted, operation for operation."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return _softmax_sorted(l)
+
+
+def tail_free_cut(p: np.ndarray, z) -> int:
+    """sample_tail_free with min_keep 1 (Generate.cc:203-246) on the softmax p of the sorted candidates: |second differences| of p, normalised by their SEQUENTIAL fp32
+    sum; the first i >= 1 whose running sum of weights exceeds z; candidates [0, i) stay.  z >= 1 or fewer than 3 candidates: nothing runs.  A zero sum gives NaN weights
+    and cuts nothing; so does a NaN z."""
+    z, k = np.float32(z), int(p.size)
+    if z >= np.float32(1.0) or k <= 2:
+        return k
+    d1 = (p[:-1] - p[1:]).astype(np.float32)
+    d2 = np.abs((d1[:-1] - d1[1:]).astype(np.float32))
+    S = np.cumsum(d2, dtype=np.float32)[-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cum = np.cumsum((d2 / S).astype(np.float32), dtype=np.float32)
+        hit = np.nonzero(cum[1:] > z)[0]
+    return int(hit[0]) + 1 if hit.size else k
+
+
+def typical_order(p: np.ndarray, typical_p) -> tuple[np.ndarray, int]:
+    """sample_typical with min_keep 1 (Generate.cc:248-302) on the softmax p of the candidates: H = sum (-p_i) * logf(p_i) (sequential, one multiply and one add per
+    term), scores |-logf(p_i) - H|, the candidates in ASCENDING score with the earlier one first among equals (the rank rule of include/tce_matmul.h: NaN scores leave
+    the order as it is), cut behind the first candidate whose running sum of p exceeds typical_p.  Returns (order, n2): order[i] = the index of the candidate that
+    stands at position i."""
+    k = int(p.size)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lp = np.log(p).astype(np.float32)
+        H = np.cumsum(((-p).astype(np.float32) * lp).astype(np.float32), dtype=np.float32)[-1]
+        s = np.abs(((-lp).astype(np.float32) - H).astype(np.float32))
+        less = s[None, :] < s[:, None]                        # [i][j]: s_j < s_i
+        tie = ~(s[:, None] < s[None, :]) & (np.arange(k)[None, :] < np.arange(k)[:, None])  # !(s_i < s_j) && j < i
+    rank = (less | tie).sum(axis=1)
+    order = np.arange(k)
+    order[rank] = np.arange(k)
+    cum = np.cumsum(p[order], dtype=np.float32)
+    hit = np.nonzero(cum > np.float32(typical_p))[0]
+    return order.astype(np.int32), (int(hit[0]) + 1 if hit.size else k)
+
+
 def draw_reference(final_p: np.ndarray, u) -> int:
     """Inverse CDF on the sequential fp32 running sum of final_p: the first i with u < cdf_i, the last candidate if rounding leaves none."""
     cdf = np.cumsum(final_p, dtype=np.float32)
@@ -154,7 +204,7 @@ def _chain(x: np.ndarray, among: np.ndarray, params: SamplingParams, u) -> dict:
     if params.temp <= 0:
         tok = int(among[int(np.argmax(xa))])  # the first maximum: std::max_element
         return {"ids": np.array([tok], np.int32), "logits": x[tok:tok + 1].copy(), "p": np.zeros(1, np.float32), "n": 1, "final_p": np.zeros(1, np.float32),
-                "choice": 0, "token": tok}
+                "choice": 0, "token": tok, "n_tfs": 1, "n_typ": 1, "order": np.zeros(1, np.int32), "p_top": np.zeros(1, np.float32), "final_ids": np.array([tok], np.int32)}
     k = min(max(int(params.top_k), 1), V)
     if k < V:
         kth = np.partition(xa, V - k)[V - k]
@@ -167,11 +217,21 @@ def _chain(x: np.ndarray, among: np.ndarray, params: SamplingParams, u) -> dict:
     ids = cand[order].astype(np.int32)
     l = (x[ids] + np.float32(0.0)).astype(np.float32)  # (-0 -> +0, as the device returns it)
     p = _softmax_sorted(l)
-    n = top_p_cut(p, params.top_p)
-    lt = (l[:n] / np.float32(params.temp)).astype(np.float32)
-    fp = _softmax_sorted(lt)
+    # the two stages of tce_sample_stages_f16 (rules 2 and 3 of include/tce_matmul.h); with tfs_z and typical_p both >= 1 nothing below differs from the chain without them
+    tfs_on, typ_on = not np.float32(params.tfs_z) >= np.float32(1.0), not np.float32(params.typical_p) >= np.float32(1.0)
+    n1 = tail_free_cut(p, params.tfs_z) if tfs_on else int(p.size)
+    order, n2 = np.arange(n1, dtype=np.int32), n1
+    if typ_on:
+        order, n2 = typical_order(_softmax_first(l[:n1]), params.typical_p)
+    order = order[:n2]
+    lf, final_ids = l[order], ids[order]
+    p_top = _softmax_first(lf) if (tfs_on or typ_on) else p
+    n = top_p_cut(p_top, params.top_p)
+    lt = (lf[:n] / np.float32(params.temp)).astype(np.float32)
+    fp = _softmax_first(lt)
     choice = draw_reference(fp, u)
-    return {"ids": ids, "logits": l, "p": p, "n": n, "final_p": fp, "choice": choice, "token": int(ids[choice])}
+    return {"ids": ids, "logits": l, "p": p, "n": n, "final_p": fp, "choice": choice, "token": int(final_ids[choice]), "n_tfs": n1, "n_typ": n2, "order": order,
+            "p_top": p_top, "final_ids": final_ids}
 
 
 def logprob_reference(logits_f16_row: np.ndarray, target: int) -> float:
@@ -228,10 +288,14 @@ class Sampler:
     [batch] the log-sum-exp of the row each slot's last token was drawn from.  logprobs=False: the call, the launches and a captured graph are what they were.
     constraints=True: the sampler owns the constraint rows [batch] (struct tce_constraint_row: automaton, state, logit bias), the automaton table (constrain.
     AutomatonTable) and the violations word, and step() calls tce_sample_constrained_f16 -- still two launches; set_row(..., automaton=, logit_bias=) gives a slot its
-    automaton (an index from table.register) and bias.  constraints=False: the existing entry points, untouched."""
+    automaton (an index from table.register) and bias.  constraints=False: the existing entry points, untouched.
+    stages=True: the sampler owns the stage rows [batch] (struct tce_stage_row: tfs_z, typical_p; (1.0, 1.0) until set_row writes a slot's pair from its SamplingParams)
+    and step() calls tce_sample_stages_f16 -- still two launches --, with the constraint and logprob blocks when those options are on; debug=True also keeps the
+    stage records (stage_debug_row).  stages=False: the call, the launches and a captured graph are what they were, and set_row refuses a SamplingParams whose
+    tfs_z / typical_p are not 1.0."""
 
     def __init__(self, batch: int, vocab: int, log_stride: int, device, top_k_bound: int = 40, stop_ids=(), debug: bool = False, tfs_z: float = 1.0,
-                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False, constraints: bool = False):
+                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False, constraints: bool = False, stages: bool = False):
         import torch
         if len(stop_ids) > 4:
             raise ValueError("at most 4 stop ids")
@@ -260,6 +324,16 @@ class Sampler:
             self.crows[:, 0] = -1  # every row unconstrained
             self.table = AutomatonTable(vocab, device)
             self.violations_word = torch.zeros(1, dtype=torch.int32, device=device)
+        self.stages = bool(stages)
+        self.srows = self.sdebug = None
+        if self.stages:
+            self.srows = torch.ones((batch, 2), dtype=torch.float32, device=device)  # every slot (1.0, 1.0): off
+            self.sdebug = torch.zeros((batch, C.sizeof(capi.StageDebug) // 4), dtype=torch.int32, device=device) if debug else None
+
+    def stage_block(self, debug=None) -> capi.SampleStages:
+        """struct tce_sample_stages over this sampler's stage rows (debug: another record array -- the verifier's, per virtual row)."""
+        debug = self.sdebug if debug is None else debug
+        return capi.SampleStages(rows=self.srows.data_ptr(), debug=debug.data_ptr() if debug is not None else None)
 
     def constraint(self) -> capi.Constraint:
         """struct tce_constraint over this sampler's table, rows and violations word (n_fsm is the table's size: a free entry has no states and is refused on the device)."""
@@ -288,7 +362,7 @@ class Sampler:
         """The slot changes hands: one stream-ordered copy of its row (parameters, a fresh ring with the prompt pushed, counters at zero) and, with constraints=True,
         one of its constraint row: automaton (an index of table.register, None: unconstrained) in its start state, logit_bias ({id: value} or [(id, value)], <= 16)."""
         import torch
-        params.check(self.top_k_bound)
+        params.check(self.top_k_bound, stages=self.stages)
         if not 1 <= max_new <= self.log_stride:
             raise ValueError(f"max_new {max_new}: 1 .. {self.log_stride}")
         bias = self.check_constraint(automaton, logit_bias)
@@ -302,6 +376,8 @@ class Sampler:
             self.table.users.pop(slot, None)
             if automaton is not None:
                 self.table.users[slot] = int(automaton)
+        if self.stages:
+            self.srows[slot].copy_(torch.tensor([params.tfs_z, params.typical_p], dtype=torch.float32))
 
     def step(self, logits, pos_device, pos_bound: int) -> None:
         """tce_sample_f16 on logits fp16 [batch][ld] (two launches on the current stream).  pos_device int32 [batch] is READ (activity) and WRITTEN (+1, or -1)."""
@@ -311,7 +387,9 @@ class Sampler:
         assert pos_device.dtype == torch.int32 and pos_device.is_contiguous() and pos_device.numel() == self.batch
         assert logits.is_cuda and pos_device.is_cuda
         c = self.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound)
-        if self.constraints:
+        if self.stages:
+            capi.check(capi.sample_stages_f16(c, self.stage_block(), self.constraint() if self.constraints else None, self.logprob_out() if self.logprobs else None, _stream()))
+        elif self.constraints:
             capi.check(capi.sample_constrained_f16(c, self.constraint(), self.logprob_out() if self.logprobs else None, _stream()))
         elif self.logprobs:
             capi.check(capi.sample_logprobs_f16(c, self.logprob_out(), _stream()))
@@ -337,6 +415,9 @@ class Sampler:
 
     def debug_row(self, slot: int) -> capi.SampleDebug:
         return capi.SampleDebug.from_buffer_copy(self.debug[slot].cpu().numpy().tobytes())
+
+    def stage_debug_row(self, slot: int) -> capi.StageDebug:
+        return capi.StageDebug.from_buffer_copy(self.sdebug[slot].cpu().numpy().tobytes())
 
     def generated(self) -> np.ndarray:
         return self.rows[:, 10].cpu().numpy().astype(np.int64)  # word 10: tce_sample_row.generated
@@ -576,7 +657,7 @@ class _GeneratorBase:
                 raise ValueError(f"slot {s} is live")
             if any(not 0 <= t < self.vocab for t in ids):
                 raise ValueError("a prompt token lies outside the vocabulary")
-            p.check(self.sampler.top_k_bound)
+            p.check(self.sampler.top_k_bound, stages=getattr(self.sampler, "stages", False))  # (a sampler stand-in without the attribute runs no stage)
             if any(c is not None for c in cons.get(s, ())):  # (the existing call forms read nothing new of the sampler)
                 self.sampler.check_constraint(*cons[s])
             if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
@@ -734,10 +815,10 @@ class BatchedGenerator(_GeneratorBase):
     inactive) and run() replays it: one replay is one token for every live slot."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
-                 debug: bool = False, logprobs: bool = False, constraints: bool = False, lora=None):
-        """lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  A
+                 debug: bool = False, logprobs: bool = False, constraints: bool = False, lora=None, stages: bool = False):
+        """stages=True: the sampler runs tce_sample_stages_f16 and every admission's SamplingParams may carry its own tfs_z / typical_p (Sampler).  lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  A
         gate_up=True pool adapts gate/up too (15 L + 5 launches per token instead of 13 L + 5).  lm_head and the embedding are not adapted."""
-        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints)
+        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints, stages=stages)
         self._take_pool(lora)
         self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
         self.score_logits: list = []

@@ -12,6 +12,7 @@ spread over up to T tokens of the SAME sequence: the linears run at M = B T and 
     1        tce_rmsnorm_half             the final norm
     1        tce_w4a16_forward            lm_head at M = B T
     3        tce_sample_verify_f16        select for all rows, draw per row, walk the chain: 1 .. T tokens per sequence
+                                          (stages=True: tce_sample_verify_stages_f16 -- the same three launches with the sequence's tail-free / typical pair on every row)
 
 LOSSLESS by construction: row t is sampled with the window and the Philox counter (seed, index of the token in its sequence) the plain loop would use, and a draft is
 kept only if it EQUALS the token sampled in front of it.  There is no draft distribution and no rejection sampling; draft models and tree drafts are not built.
@@ -233,6 +234,9 @@ class Verifier:
         self.uniform_override = None  # fp32 [batch * rows_per_seq] on the device (tests)
         self.debug = torch.zeros((sampler.batch * self.rows_per_seq, C.sizeof(capi.SampleDebug) // 4), dtype=torch.int32, device=dev) if debug else None
         self.partials = None
+        self.sdebug = None  # a Sampler built with stages=True: tce_sample_verify_stages_f16, the stage records per virtual row
+        if sampler.stages and debug:
+            self.sdebug = torch.zeros((sampler.batch * self.rows_per_seq, C.sizeof(capi.StageDebug) // 4), dtype=torch.int32, device=dev)
         if sampler.logprobs:
             self.partials = torch.empty(int(capi.lib().tce_logprobs_workspace_bytes(sampler.batch * self.rows_per_seq, sampler.vocab)), dtype=torch.uint8, device=dev)
 
@@ -250,7 +254,10 @@ class Verifier:
         c.debug = self.debug.data_ptr() if self.debug is not None else None
         v = capi.SampleVerifyCall(s=c, rows_per_seq=self.rows_per_seq, hist_stride=history.shape[1], row_token=row_token.data_ptr(), row_pos=row_pos.data_ptr(),
                                   history=history.data_ptr(), emitted=self.emitted.data_ptr())
-        if s.constraints:
+        if s.stages:
+            st = capi.SampleStages(rows=s.srows.data_ptr(), debug=self.sdebug.data_ptr() if self.sdebug is not None else None)
+            capi.check(capi.sample_verify_stages_f16(v, st, s.constraint() if s.constraints else None, s.logprob_out(self.partials) if s.logprobs else None, _stream()))
+        elif s.constraints:
             capi.check(capi.sample_verify_constrained_f16(v, s.constraint(), s.logprob_out(self.partials) if s.logprobs else None, _stream()))
         elif s.logprobs:
             capi.check(capi.sample_verify_logprobs_f16(v, s.logprob_out(self.partials), _stream()))
@@ -271,7 +278,7 @@ class SpeculativeGenerator(_GeneratorBase):
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False,
-                 constraints: bool = False, lora=None):
+                 constraints: bool = False, lora=None, stages: bool = False):
         if lora is not None:  # first: a pool that was not built for rows, or for another T, is refused before anything else of the constructor runs
             T = getattr(lora, "rows_per_seq", None)
             decoders = list(decoders) if T is not None and decoders is not None else None
@@ -290,7 +297,7 @@ class SpeculativeGenerator(_GeneratorBase):
         _check_rows(self.rows_per_seq, self.ngram)
         assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
         super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, rows_per_seq=self.rows_per_seq, logprobs=logprobs,
-                         constraints=constraints)
+                         constraints=constraints, stages=stages)
         self._take_pool(lora)
         B, T, dev = self.batch, self.rows_per_seq, self.device
         self.verifier = Verifier(self.sampler, T)
