@@ -520,8 +520,9 @@ TCE_API int tce_kv_block_table_check_sink(const int32_t *block_table, int table_
  * no recapture.  A fresh row has generated = ring_pushed = 0 and ring = 64 zeros, as the reference's last_n_tokens starts (token 0 is penalised until 64 tokens have
  * passed); prompt tokens are pushed by the host at admission (ring[ring_pushed % 64], ring_pushed += 1).  A row's top_k outside [1, top_k_bound] is clamped (it lives
  * on the device: the host cannot refuse it at the call).
- * NOT BUILT: mirostat, top_k <= 0 = "whole vocabulary", k > 256; and this entry point runs no tail-free or typical stage -- the CALL accepts only the disabled values
- * tfs_z 1.0, typical_p 1.0, mirostat 0 --: TCE_ERR_UNSUPPORTED_SHAPE before any launch.  (The two stages ARE built, per slot: tce_sample_stages_f16 below.  Token masks,
+ * NOT BUILT: top_k <= 0 = "whole vocabulary", k > 256; and this entry point runs no tail-free or typical stage and no mirostat -- the CALL accepts only the disabled values
+ * tfs_z 1.0, typical_p 1.0, mirostat 0 --: TCE_ERR_UNSUPPORTED_SHAPE before any launch.  (The two stages ARE built, per slot: tce_sample_stages_f16 below; so is mirostat,
+ * per slot over the top-k candidates: tce_sample_mirostat_f16 below.  Token masks,
  * automata and logit_bias ARE built: tce_sample_constrained_f16 below; this entry point applies none.)  Also refused there: vocab > ld (TCE_ERR_BAD_ARG), vocab > 2^20, logits not 16-byte aligned or ld % 8 != 0, and ceil(vocab / 4096) * top_k_bound
  * > 8192 (the second launch holds the chunks' survivors in registers: 131072 entries at k = 256, 838k at k = 40).
  * workspace: tce_sample_workspace_bytes(batch, vocab) bytes (0 for a bad shape), zeroed once; word 0 counts the ids tce_embed_rows_f16 refused, the rest carries the
@@ -587,7 +588,8 @@ TCE_API int tce_sample_f16(const tce_sample_call *call, void *stream);
  * LOSSLESS: the emitted tokens are those of tce_sample_f16 called once per token.  A row that is reached at all has had all its drafts accepted, so its window (the
  * ring plus drafts 1 .. t) is known in advance: the select launch runs for all B * T rows at once, the draw per row into a candidate array, and a last small launch
  * walks the chain and writes state.  Cache rows p + t + 1 .. of REJECTED drafts stay behind the position as garbage: the next step overwrites them or never weighs them.
- * Refusals: tce_sample_f16's (mirostat, k > 256 and whole-vocabulary top-k stay unbuilt; tail-free and typical run behind tce_sample_verify_stages_f16), rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS, batch *
+ * Refusals: tce_sample_f16's (k > 256 and whole-vocabulary top-k stay unbuilt; tail-free and typical run behind tce_sample_verify_stages_f16, mirostat behind
+ * tce_sample_verify_mirostat_f16), rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS, batch *
  * rows_per_seq > 65535, ngram outside 1 .. 4, hist_stride <= pos_bound. */
 typedef struct tce_sample_verify_call {
     tce_sample_call s;
@@ -711,9 +713,8 @@ TCE_API int tce_sample_verify_constrained_f16(const tce_sample_verify_call *call
  * Refusals, before any launch: everything the underlying entry point refuses -- non-default tfs_z / typical_p / mirostat in the CALL included: the call's two fields stay
  * refused, the values live in st->rows --, the constrained / logprob forms' for a non-NULL c / lp; TCE_ERR_BAD_ARG for a NULL st or st->rows; TCE_ERR_UNSUPPORTED_SHAPE for
  * rows or debug not 4-byte aligned.
- * NOT BUILT: mirostat, both versions (mirostat != 0 stays refused).  It replaces top-k with a softmax over the WHOLE sorted vocabulary, summed sequentially; its candidate
- * count is not bounded by top_k_bound; its mu is a process-wide static in the reference; and a speculative row's cut would depend on the draw of the row in front of it,
- * so the verifier's rows could not be sampled "known in advance".  A different design.  Also not built, as before: top_k <= 0 = "whole vocabulary", k > 256. */
+ * Mirostat is not run by these two entry points (mirostat != 0 in the CALL stays refused): it lives per slot behind tce_sample_mirostat_f16 below, over the row's top-k
+ * candidates, and behind tce_sample_verify_mirostat_f16, which needs one more launch (a speculative row's cut depends on the draw of the row in front of it).  Also not built, as before: top_k <= 0 = "whole vocabulary", k > 256. */
 typedef struct tce_stage_row { float tfs_z, typical_p; } tce_stage_row;   /* per slot (8 bytes); 1.0 = off; changes hands by one copy */
 typedef struct tce_stage_debug {                                          /* tests; per row (per virtual row in the verifier); 2056 bytes.  A greedy row (temp <= 0) has ONE
                                                                              candidate: n_tfs = n_typ = 1, order = {0}, p_top = 0.  An inactive or rule-6 row writes nothing */
@@ -726,6 +727,63 @@ TCE_API int tce_sample_stages_f16(const tce_sample_call *call, const tce_sample_
                                   void *stream);
 TCE_API int tce_sample_verify_stages_f16(const tce_sample_verify_call *call, const tce_sample_stages *st, const tce_constraint *c /* may be NULL */,
                                          const tce_logprob_out *lp /* may be NULL */, void *stream);
+/* Mirostat v1 and v2 per slot (csrc/sampling.hip; additive within ABI 113, no existing struct or entry point changes): the last branch of the reference's sampling
+ * configuration (Generate.h:69-71; LLaMA3Generate.cc:162-171: penalties -> sample_temperature -> sample_token_mirostat[_v2], Generate.cc:138-201), and the sampler's
+ * first STATEFUL rule: a running value mu per slot, read and written by the launch that emits the token, so a captured replay carries it with no host round trip.
+ * tce_sample_mirostat_f16 is tce_sample_stages_f16 with, per ACTIVE row b whose mi->rows[b].mode is 1 or 2 and whose temp > 0, INSTEAD of tail-free -> typical -> top-p
+ * -> temperature, on the row's kk candidates behind the penalties (bias, mask) and top-k in the project's order (descending penalised logit, ascending id among equals).
+ * fp32, IEEE operations, no contraction; sums SEQUENTIAL in index order from 0.0f; expf, logf, log2f, powf:
+ *   1. TEMPERATURE FIRST: l_i = logit_i / temp, a division per candidate (sample_temperature).  p = SOFTMAX(the kk) as rule 1 of the stages above.
+ *   2. MODE 1.  nt = min(m - 1, kk - 1) terms (m - 1 < 0: kk - 1, as the reference's size_t(m - 1)); t_i = logf(float(i + 2) / float(i + 1)), b_i = logf(p_i / p_{i+1});
+ *      A = sum t_i * b_i, B = sum t_i * t_i (one multiply and one add per term); s_hat = A / B; eps = s_hat - 1; N = float(call->vocab);
+ *      k_f = powf((eps * powf(2, mu)) / (1 - powf(N, -eps)), 1 / s_hat).  The first k' candidates are kept, where C leaves int(k_f) open the project's rule:
+ *      !(k_f >= 1) (NaN included) -> 1; k_f >= kk (+inf included) -> kk; otherwise int(k_f), truncated.  kk == 1 (or m == 1): no term, s_hat NaN, k' = 1.
+ *   3. MODE 2.  k' = the first i with -log2f(p_i) > mu, or kk where there is none.
+ *   4. final p = SOFTMAX(the first k'); the inverse-CDF draw on the row's uniform (Philox as tce_sample_f16's, or uniform_override): the first i with u < cdf_i, else k' - 1.
+ *   5. UPDATE, in the tail that stores the token: mu = mu - eta * ((-log2f(final p of the candidate drawn)) - tau).  mu is written whenever a token is emitted, a stop token
+ *      or the row's last token included; it is NOT touched where nothing is emitted: an inactive row, constraint rule 6.  A NaN mu stays NaN (mode 2 then keeps all kk).
+ *   6. temp <= 0: greedy as everywhere, mu untouched.  mode 0 (and any value but 1 and 2: the row lives on the device, the host cannot refuse it at the call): the row is
+ *      tce_sample_stages_f16's row bit for bit -- token, log, ring, counters, position, debug and stage records, logprob, constraint state --, mu untouched.  A mirostat
+ *      row ignores its tce_stage_row and top_p; its stage record shows kk candidates in sorted order.
+ * DEVIATIONS from the reference, all three deliberate:
+ *   a. CANDIDATES.  The reference's mirostat sees the WHOLE vocabulary and ignores top_k; here it sees the row's top_k <= 256 candidates, like every rule of this sampler
+ *      (N stays the vocabulary).  The two are the same chain whenever vocab <= top_k (tests/golden/mirostat_golden.npz holds such configurations).
+ *   b. EMPTY CUT.  Mode 2 with -log2f(p_0) > mu keeps ONE candidate; the reference would set size 0 and read an empty array.
+ *   c. mu IS PER SLOT and starts at 2 * tau, written by the host at admission; the reference's function-static mu, which leaks from one generate call into the next, is
+ *      not reproduced.
+ * mi->rows: DEVICE array [batch] of tce_mirostat_row (20 bytes): a slot changes hands by one stream-ordered copy, a captured graph keeps the pointer: no recapture.
+ * mi->debug (may be NULL): [batch] records for tests, written for every row that emits (mode 0 for a row that ran no mirostat: kept = n, mu_in = mu_out, the rest 0).
+ * With it, tce_sample_debug keeps its meaning: ids / logit the sorted penalised candidates (before the division), p the softmax of rule 1, n = k', final_p of rule 4.
+ * Launches: two; the first is the underlying form's own kernel, the second the MIRO = true form of the draw kernel, whose branch is uniform per workgroup.
+ * Refusals, before any launch: tce_sample_stages_f16's -- call->mirostat != 0 included: the mode lives per row --; TCE_ERR_BAD_ARG for a NULL mi or mi->rows;
+ * TCE_ERR_UNSUPPORTED_SHAPE for rows or debug not 4-byte aligned.
+ * powf: the device evaluates each of rule 2's three powers as the fp64 pow of the widened fp32 operands, rounded once to fp32 -- within one fp32 ulp of the exact
+ * value, with pow's special cases (the device library's fp32 powf compiles to an instruction form this library's build refuses).
+ * tce_sample_verify_mirostat_f16: tce_sample_verify_stages_f16 (with lp / c: its logprob / constrained form) with mi->rows per SEQUENCE and mi->debug per VIRTUAL row
+ * (written for the rows of sequences that run mirostat only; tce_sample_debug and the stage record are NOT written for those rows).  mu at virtual row t depends on the
+ * draws of rows < t, so the per-row draw launch cannot finish a mirostat sequence: it stops such a row behind the sort and leaves the sorted candidates in the
+ * workspace; ONE ADDED LAUNCH, one workgroup per sequence, walks the sequence's active rows t = 0, 1, ... with mu carried -- the same device function the plain entry
+ * point runs, on the uniform keyed (seed, generated + t) (uniform_override: per virtual row) -- and writes the row's token and the mu behind it; the chain launch emits
+ * as the verifier does and stores the mu behind the LAST token it emits.  FOUR launches, no host round trip.  LOSSLESS: the emitted tokens, generated, ring, position,
+ * constraint state, logprobs and the stored mu are those of tce_sample_mirostat_f16 called once per emitted token; a sequence that emits nothing keeps its mu.  Sequences
+ * in mode 0 and greedy sequences are tce_sample_verify_stages_f16's.  workspace: tce_sample_verify_mirostat_workspace_bytes(batch, rows_per_seq, vocab) bytes (the
+ * verifier's, then 2064 bytes per virtual row), zeroed once.  Refusals: tce_sample_verify_stages_f16's and tce_sample_mirostat_f16's.
+ * NOT BUILT, as before: top_k <= 0 = "whole vocabulary", k > 256. */
+typedef struct tce_mirostat_row { int32_t mode; int32_t m; float tau, eta, mu; } tce_mirostat_row;   /* per slot (20 bytes); the reference's defaults: m 100, tau 5, eta 0.1 */
+typedef struct tce_mirostat_debug {   /* tests; per row; 40 bytes.  An inactive or rule-6 row writes nothing */
+    int32_t mode, kk;                 /* the mode that RAN (0: none; a greedy row too); the candidates behind top-k */
+    float s_hat, k_f;                 /* mode 1 only (else 0) */
+    int32_t kept;                     /* k' */
+    float mu_in, mu_out, surprise;    /* surprise = -log2f(final p of the candidate drawn) (0 where no mirostat ran) */
+    int32_t choice;
+    float final_p;                    /* of the candidate drawn (0 for a greedy row) */
+} tce_mirostat_debug;
+typedef struct tce_sample_mirostat { tce_mirostat_row *rows; tce_mirostat_debug *debug /* may be NULL */; } tce_sample_mirostat;
+TCE_API int tce_sample_mirostat_f16(const tce_sample_call *call, const tce_sample_stages *st, const tce_sample_mirostat *mi, const tce_constraint *c /* may be NULL */,
+                                    const tce_logprob_out *lp /* may be NULL */, void *stream);
+TCE_API size_t tce_sample_verify_mirostat_workspace_bytes(int batch, int rows_per_seq, int vocab);
+TCE_API int tce_sample_verify_mirostat_f16(const tce_sample_verify_call *call, const tce_sample_stages *st, const tce_sample_mirostat *mi,
+                                           const tce_constraint *c /* may be NULL */, const tce_logprob_out *lp /* may be NULL */, void *stream);
 /* The next step's input rows, one launch: row token[b] of an fp16 table [vocab][hidden] into out[b] ([batch][hidden]) for every active row (pos_device / pos_bound as
  * above; inactive rows are left as they are).  The reference looks an fp32 table up and rounds with float2half (Int4llamaDecoder: Embedding + float2half); a table
  * rounded once to fp16 gives the same bits.  A token outside [0, vocab) is not followed: the row is written as zeros and word 0 of `workspace` (tce_sample_f16's, or

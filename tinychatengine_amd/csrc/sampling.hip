@@ -33,6 +33,11 @@
 // run the reference's sample_tail_free and sample_typical between the rank sort and top-p, on the candidates already in LDS, with the two values per slot in a
 // tce_stage_row.  The select and chain kernels are the underlying form's own.  The STG = false forms declare nothing new -- not even a local variable -- and compile to
 // the instructions they were (profiles/sampler_stages/).
+//
+// MIROSTAT (tce_sample_mirostat_f16; the rule and its three deviations from the reference are in include/tce_matmul.h): the MIRO = true forms of the draw kernel, on
+// top of the plain STG = true forms.  A row whose tce_mirostat_row says mode 1 or 2 runs temperature -> softmax -> sample_token_mirostat[_v2]'s cut -> softmax -> draw
+// on its sorted candidates and thread 0 stores the new mu beside the token; every other row takes the STG = true path.  The MIRO = false forms compile to the
+// instructions they were (profiles/mirostat/).  The verifier (tce_sample_verify_mirostat_f16) takes a fourth launch, sample_miro_walk_kernel: see MiroRowWs below.
 #include "tce_common.hpp"
 
 #include <type_traits>
@@ -443,11 +448,118 @@ struct StgArgs : Base {  // the STG = true forms' arguments: the underlying form
 };
 template <bool LSE, bool CON>
 using DrawArgsBase = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, DrawLseArgs, DrawArgs>>, std::conditional_t<LSE, DrawLseArgs, DrawArgs>>;
-template <bool LSE, bool CON, bool STG = false>
-using DrawArgsOf = std::conditional_t<STG, StgArgs<DrawArgsBase<LSE, CON>>, DrawArgsBase<LSE, CON>>;
-
-template <bool SPEC, bool LSE, bool CON, bool STG = false>
-__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, CON, STG> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
+// MIRO (tce_sample_mirostat_f16; the rule is in include/tce_matmul.h): on top of STG = true only, plain rows only.  A row whose mode is 1 or 2 (and temp > 0) skips the
+// whole top-p / stages / temperature block -- the branch is uniform per workgroup -- and runs sample_temperature, sample_softmax and sample_token_mirostat[_v2]
+// (Generate.cc:138-201) on the sorted candidates in LDS, in the kernel's idiom: per-element work on threads < kk, every thread walks the sequential sums itself.  ex[]
+// is computed ONCE: the reference's second softmax subtracts the same maximum from the same values, so only the sum over the kept and the divisions are redone.  The
+// row's mu is read here and written by thread 0 in the tail, beside the token.  Any other row takes the STG = true form's path unchanged.  The MIRO = false forms
+// declare nothing new: miro_mode folds to 0.
+struct MiroLds {  // the MIRO = true forms' LDS (only they instantiate it): thread 0's words from the rule to the tail
+    int mode, kept;
+    float s_hat, k_f;
+};
+__device__ __forceinline__ MiroLds &miro_lds() {
+    __shared__ MiroLds s;
+    return s;
+}
+// powf through the fp64 pow, rounded once to fp32: within one fp32 ulp of the exact value, with pow's special cases.  The fp32 powf of the device library inlines into
+// packed f32 multiplies whose low half picks a high register, the form the build refuses (isa_lint.py RULE 1); three calls per mode-1 row, uniform, off the mode-0 path.
+__device__ __forceinline__ float pow_f32(float x, float y) { return (float)pow((double)x, (double)y); }
+// SPEC + MIRO (tce_sample_verify_mirostat_f16): mu at virtual row t depends on the draws of rows < t, so the per-row draw launch cannot finish a mirostat sequence.  It
+// stops such a row behind the sort and leaves the sorted candidates in a MiroRowWs; sample_miro_walk_kernel (one workgroup per sequence) then walks rows 0 .. n - 1
+// with mu carried through miro_rule -- the SAME device function the plain form runs, so a row's arithmetic is the plain form's -- and writes cand[y] and mu_after;
+// the chain kernel's MIRO form stores mu_after of the last token it emits.
+struct MiroRowWs {  // per virtual row, behind the verifier's workspace
+    int kk;          // the candidates behind top-k; 0: no candidate (constraint rule 6)
+    float mu_after;  // mu behind this row's token, had rows 0 .. t all been emitted
+    int pad[2];
+    float lg[kMaxK];  // the sorted penalised logits (before the division)
+    int ids[kMaxK];
+};
+template <class Base>
+struct MiroArgs : Base {  // the MIRO = true forms' arguments: the STG = true form's, then the mirostat rows
+    tce_mirostat_row *mrows;      // [batch] (SPEC: per sequence)
+    tce_mirostat_debug *mdebug;   // [batch] or null (SPEC: written by the walk launch, per virtual row)
+    int mvocab;                   // N of mode 1
+    MiroRowWs *mws;               // SPEC: [batch * T]; else null
+};
+// The rule on the kk sorted candidates in lg[] (include/tce_matmul.h, rules 1 - 4), for the whole workgroup: lg is divided in place, pr holds the first softmax, fp the
+// final p of the `n` kept, `choice` the position drawn on u.  tb / bb: kMaxK words each.  Every thread returns the same values.
+__device__ __forceinline__ void miro_rule(int mode, int m, float mu, float temp, int vocab, int kk, float u, int tid, float *lg, float *ex, float *pr, float *fp, float *tb,
+                                          float *bb, int &n, int &choice, float &s_hat, float &k_f) {
+    if (tid < kk) lg[tid] = lg[tid] / temp;  // sample_temperature (:72-76)
+    __syncthreads();
+    const float l0 = lg[0];
+    if (tid < kk) ex[tid] = expf(lg[tid] - l0);
+    __syncthreads();
+    float sum = 0.0f;
+    for (int i = 0; i < kk; ++i) sum += ex[i];
+    if (tid < kk) pr[tid] = ex[tid] / sum;
+    __syncthreads();
+    int keep = kk;
+    s_hat = k_f = 0.0f;
+    if (mode == 1) {  // sample_token_mirostat (:138-160)
+        const int want = m - 1;
+        const int nt = want < 0 || want > kk - 1 ? kk - 1 : want;  // size_t(m - 1) && candidates->size - 1
+        if (tid < nt) {  // the products side by side (each rounded once, as the reference's uncontracted multiply): the walk below only adds
+            const float t = logf((float)(tid + 2) / (float)(tid + 1));
+            bb[tid] = t * logf(pr[tid] / pr[tid + 1]);
+            tb[tid] = t * t;
+        }
+        __syncthreads();
+        float sum_tb = 0.0f, sum_tt = 0.0f;
+        for (int i = 0; i < nt; ++i) {
+            sum_tb += bb[i];
+            sum_tt += tb[i];
+        }
+        s_hat = sum_tb / sum_tt;
+        const float eps = s_hat - 1.0f;
+        k_f = pow_f32((eps * pow_f32(2.0f, mu)) / (1.0f - pow_f32((float)vocab, -eps)), 1.0f / s_hat);
+        keep = !(k_f >= 1.0f) ? 1 : (k_f >= (float)kk ? kk : (int)k_f);  // the project's rule where C leaves int(k) open
+    } else {  // sample_token_mirostat_v2 (:176-185): the first candidate whose surprise exceeds mu, and everything behind it, go
+        if (tid < kk) tb[tid] = -log2f(pr[tid]);
+        __syncthreads();
+        for (int i = 0; i < kk; ++i) {
+            if (tb[i] > mu) {
+                keep = i;
+                break;
+            }
+        }
+        keep = keep < 1 ? 1 : keep;  // (the reference would read an empty array)
+    }
+    // sample_token's softmax over the kept: the same maximum, the same expf arguments -- ex[] stands --, a new sum
+    float sum2 = 0.0f;
+    for (int i = 0; i < keep; ++i) sum2 += ex[i];
+    if (tid < keep) fp[tid] = ex[tid] / sum2;
+    __syncthreads();
+    n = keep;
+    choice = n - 1;
+    float cdf = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        cdf += fp[i];
+        if (u < cdf) {
+            choice = i;
+            break;
+        }
+    }
+}
+// rule 5: the surprise of the candidate drawn and the mu behind it
+__device__ __forceinline__ float miro_surprise(float p) { return -log2f(p); }
+__device__ __forceinline__ float miro_update(float mu, float eta, float tau, float surprise) { return mu - eta * (surprise - tau); }
+template <bool LSE, bool CON, bool STG = false, bool MIRO = false>
+using DrawArgsOf = std::conditional_t<MIRO, MiroArgs<StgArgs<DrawArgsBase<LSE, CON>>>, std::conditional_t<STG, StgArgs<DrawArgsBase<LSE, CON>>, DrawArgsBase<LSE, CON>>>;
+template <bool MIRO, class A>
+__device__ __forceinline__ int miro_mode(const A &a, int b) {  // the mode that runs for row b: 1, 2, or 0
+    if constexpr (MIRO) {
+        const int m = a.mrows[b].mode;
+        return m == 1 || m == 2 ? m : 0;
+    } else {
+        return 0;
+    }
+}
+template <bool SPEC, bool LSE, bool CON, bool STG = false, bool MIRO = false>
+__global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, CON, STG, MIRO> a, [[maybe_unused]] int RT, [[maybe_unused]] int32_t *cand) {
+    static_assert(!MIRO || STG, "the mirostat forms stand on the STG = true forms");
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!row_active(a.pos, b, a.pos_bound)) return;
     [[maybe_unused]] float lse = 0.0f;
@@ -484,6 +596,7 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
             if (tid == 0) {
                 if constexpr (SPEC) {
                     cand[b] = -1;
+                    if constexpr (MIRO) a.mws[b].kk = 0;
                 } else {
                     a.pos[b] = -1;
                     atomicAdd(a.con.violations, 1u);
@@ -535,6 +648,39 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
     const unsigned gen = SPEC ? r.generated + (unsigned)vt : r.generated;
     float u = 0.0f;
     int n = 1, choice = 0;
+    if constexpr (MIRO) {
+        MiroLds &M = miro_lds();
+        const int mrow = SPEC ? seq : b;
+        const int mode = r.temp > 0.0f ? miro_mode<MIRO>(a, mrow) : 0;
+        if (tid == 0) {
+            M.mode = mode;
+            M.s_hat = M.k_f = 0.0f;
+        }
+        if (mode != 0) {  // (uniform)
+            if constexpr (SPEC) {  // the sorted candidates go to the walk launch; the log-sum-exp is this row's whatever token is drawn
+                MiroRowWs &w = a.mws[b];
+                if (tid < kk) {
+                    w.lg[tid] = lg[tid];
+                    w.ids[tid] = ids[tid];
+                }
+                if (tid == 0) {
+                    w.kk = kk;
+                    if constexpr (LSE) a.cand_lse[b] = lse;
+                }
+                return;
+            } else {
+                const tce_mirostat_row &mr = a.mrows[b];
+                u = a.uniform_override ? a.uniform_override[b] : (float)(philox4x32_10_first(gen, r.seed_lo, r.seed_hi) >> 8) * 0x1p-24f;
+                float s_hat, k_f;
+                miro_rule(mode, mr.m, mr.mu, r.temp, a.mvocab, kk, u, tid, lg, ex, pr, fp, stg_lds().sc, stg_lds().pq, n, choice, s_hat, k_f);
+                if (tid == 0) {
+                    M.s_hat = s_hat;
+                    M.k_f = k_f;
+                }
+                goto drawn;  // (uniform) past the top-p / stages / temperature block
+            }
+        }
+    }
     if (r.temp > 0.0f) {
         // sample_top_p's softmax over the k candidates (Generate.cc:81-100): every thread walks the sums itself (broadcast LDS reads), in sorted order
         const float l0 = lg[0];
@@ -673,6 +819,7 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
             }
         }
     }
+[[maybe_unused]] drawn:  // (only the MIRO = true forms jump here; as a second condition on the block above, the same test moved the MIRO = false forms' registers)
     if constexpr (CON && !SPEC) {  // the drawn token's next state, through one LDS word (0 for an unconstrained row: unused)
         int &con_next = con_next_word();
         if (tid == 0) {
@@ -774,6 +921,30 @@ __global__ __launch_bounds__(kThreads) void sample_draw_kernel(DrawArgsOf<LSE, C
             }
         }
         a.pos[b] = stop ? -1 : a.pos[b] + 1;
+        if constexpr (MIRO) {  // mu moves with every token a mirostat row emits; thread 0 wrote M itself
+            const MiroLds &M = miro_lds();
+            tce_mirostat_row &mr = a.mrows[b];
+            float surprise = 0.0f, mu_out = 0.0f;
+            if (M.mode != 0) {
+                surprise = miro_surprise(fp[choice]);
+                mu_out = miro_update(mr.mu, mr.eta, mr.tau, surprise);
+            }
+            if (a.mdebug) {
+                tce_mirostat_debug &md = a.mdebug[b];
+                const float mu_in = mr.mu;
+                md.mode = M.mode;
+                md.kk = kk;
+                md.s_hat = M.s_hat;
+                md.k_f = M.k_f;
+                md.kept = n;
+                md.mu_in = mu_in;
+                md.mu_out = M.mode != 0 ? mu_out : mu_in;
+                md.surprise = surprise;
+                md.choice = choice;
+                md.final_p = r.temp > 0.0f ? fp[choice] : 0.0f;
+            }
+            if (M.mode != 0) mr.mu = mu_out;
+        }
     }
 }
 
@@ -786,11 +957,82 @@ struct VerifyLseArgs : VerifyArgs {
 
 // CON: the sequence's state advances once per emitted token (fsm_next); DONE retires the sequence behind the token; a row that is invalid (rule 6: the base state, no
 // candidate -- cand < 0 --, or the token's next outside [-1, states)) emits nothing, retires the sequence behind the tokens already emitted and counts one violation.
+// MIRO: behind the tokens it emits the chain stores, for a sequence that runs mirostat, the mu the walk launch left behind the LAST of them.
+template <class Base>
+struct MiroChainArgs : Base {
+    tce_mirostat_row *mrows;  // [batch]
+    const MiroRowWs *mws;     // [batch * T]
+};
 template <bool LSE, bool CON>
-using VerifyArgsOf = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, VerifyLseArgs, VerifyArgs>>, std::conditional_t<LSE, VerifyLseArgs, VerifyArgs>>;
+using VerifyArgsBase = std::conditional_t<CON, ConArgs<std::conditional_t<LSE, VerifyLseArgs, VerifyArgs>>, std::conditional_t<LSE, VerifyLseArgs, VerifyArgs>>;
+template <bool LSE, bool CON, bool MIRO = false>
+using VerifyArgsOf = std::conditional_t<MIRO, MiroChainArgs<VerifyArgsBase<LSE, CON>>, VerifyArgsBase<LSE, CON>>;
 
-template <bool LSE, bool CON>
-__global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgsOf<LSE, CON> a) {
+// tce_sample_verify_mirostat_f16's third launch: workgroup = sequence.  For a sequence whose mode is 1 or 2 and whose temp > 0 it walks the active virtual rows in
+// order with mu carried: row t's sorted candidates (left by the SPEC draw form) through miro_rule on the uniform keyed (seed, generated + t), cand[y] = the token,
+// mu_after = the mu behind it, and with lp the token's log-probability on the row's own log-sum-exp.  A row without a candidate (rule 6: cand = -1 already) ends the
+// walk: the chain ends there too.  Rows behind a rejected draft are walked as well and never read.  Any other sequence: nothing.
+struct WalkArgs {
+    MiroRowWs *mws;
+    const tce_sample_row *rows;
+    const tce_mirostat_row *mrows;
+    tce_mirostat_debug *mdebug;  // [batch * T] or null
+    const int32_t *pos, *row_pos;
+    int pos_bound, T, vocab, ld;
+    const float *uniform_override;  // [batch * T] or null
+    int32_t *cand;
+    const half_t *logits;      // null without lp
+    float *cand_logprob;
+    const float *cand_lse;
+};
+__global__ __launch_bounds__(kThreads) void sample_miro_walk_kernel(WalkArgs a) {
+    const int seq = blockIdx.x, tid = threadIdx.x;
+    if (!row_active(a.pos, seq, a.pos_bound)) return;
+    const tce_sample_row &r = a.rows[seq];
+    const tce_mirostat_row &mr = a.mrows[seq];
+    const int mode = mr.mode == 1 || mr.mode == 2 ? mr.mode : 0;
+    if (!(r.temp > 0.0f) || mode == 0) return;
+    __shared__ float lg[kMaxK + 8], ex[kMaxK + 8], pr[kMaxK + 8], fp[kMaxK + 8], tb[kMaxK + 8], bb[kMaxK + 8];
+    float mu = mr.mu;
+    for (int t = 0; t < a.T; ++t) {
+        const int y = seq * a.T + t;
+        if (!row_active(a.row_pos, y, a.pos_bound)) break;  // the active rows are a prefix
+        MiroRowWs &w = a.mws[y];
+        const int kk = w.kk;
+        if (kk < 1 || kk > kMaxK) break;
+        if (tid < kk) lg[tid] = w.lg[tid];
+        __syncthreads();
+        const float u = a.uniform_override ? a.uniform_override[y] : (float)(philox4x32_10_first(r.generated + (unsigned)t, r.seed_lo, r.seed_hi) >> 8) * 0x1p-24f;
+        int n, choice;
+        float s_hat, k_f;
+        miro_rule(mode, mr.m, mu, r.temp, a.vocab, kk, u, tid, lg, ex, pr, fp, tb, bb, n, choice, s_hat, k_f);
+        const float p = fp[choice], surprise = miro_surprise(p), mu_out = miro_update(mu, mr.eta, mr.tau, surprise);
+        if (tid == 0) {
+            const int tok = w.ids[choice];
+            a.cand[y] = tok;
+            w.mu_after = mu_out;
+            if (a.logits) a.cand_logprob[y] = tok >= 0 && tok < a.vocab ? (float)a.logits[(size_t)y * a.ld + tok] - a.cand_lse[y] : __builtin_nanf("");
+            if (a.mdebug) {
+                tce_mirostat_debug &md = a.mdebug[y];
+                md.mode = mode;
+                md.kk = kk;
+                md.s_hat = s_hat;
+                md.k_f = k_f;
+                md.kept = n;
+                md.mu_in = mu;
+                md.mu_out = mu_out;
+                md.surprise = surprise;
+                md.choice = choice;
+                md.final_p = p;
+            }
+        }
+        mu = mu_out;
+        __syncthreads();  // (the next row writes lg / ex / fp again)
+    }
+}
+
+template <bool LSE, bool CON, bool MIRO = false>
+__global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgsOf<LSE, CON, MIRO> a) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.batch) return;
     if (!row_active(a.d.pos, b, a.d.pos_bound)) {
@@ -863,6 +1105,10 @@ __global__ __launch_bounds__(64) void sample_verify_chain_kernel(VerifyArgsOf<LS
         a.d.pos[b] = newpos;
         if constexpr (LSE) {
             if (a.last_lse) a.last_lse[b] = a.cand_lse[y0 + t - 1];
+        }
+        if constexpr (MIRO) {
+            tce_mirostat_row &mr = a.mrows[b];
+            if ((mr.mode == 1 || mr.mode == 2) && r.temp > 0.0f) mr.mu = a.mws[y0 + t - 1].mu_after;
         }
     }
     a.emitted[b] = t;
@@ -998,10 +1244,13 @@ static auto con_args(const Base &base, const tce_constraint *con) {
 // tce_sample_stages_f16 / tce_sample_verify_stages_f16's draw launch: the STG = true form for `base` (DrawArgs or DrawLseArgs) with the stage rows behind the
 // underlying form's arguments.  Defined behind the two launchers, whose own launches stay as they were.
 template <bool SPEC, class Base>
-static void launch_draw_stages(const Base &base, const tce_constraint *con, const tce_sample_stages *stg, int rows, int RT, int32_t *cand, hipStream_t stream);
+static void launch_draw_stages(const Base &base, const tce_constraint *con, const tce_sample_stages *stg, int rows, int RT, int32_t *cand, hipStream_t stream,
+                               const tce_sample_mirostat *mi = nullptr, int vocab = 0, MiroRowWs *mws = nullptr);
 
 // lp == null: tce_sample_f16, the launches they were.  stg (tce_sample_stages_f16): the select launch is the same, the draw launch is its STG = true form.
-int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err, const tce_sample_stages *stg) {
+// mi (tce_sample_mirostat_f16; with stg only): the draw launch is the MIRO = true form on top of it.
+int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err, const tce_sample_stages *stg,
+                      const tce_sample_mirostat *mi) {
     const tce_constraint cv = con ? *con : tce_constraint{};
     const int nchunks = sample_chunks(c.vocab);
     uint2_t *entries = reinterpret_cast<uint2_t *>(static_cast<char *>(c.workspace) + 256);
@@ -1042,13 +1291,13 @@ int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const
             la.out_logprob = lp->out_logprob;
             la.last_lse = lp->last_lse;
             la.cand_logprob = la.cand_lse = nullptr;
-            if (stg) launch_draw_stages<false>(la, con, stg, c.batch, 1, nullptr, stream);
+            if (stg) launch_draw_stages<false>(la, con, stg, c.batch, 1, nullptr, stream, mi, c.vocab);
             else with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
                 hipLaunchKernelGGL((sample_draw_kernel<false, true, CON>), dim3(c.batch), dim3(kThreads), 0, stream, con_args<CON>(la, con), 1, static_cast<int32_t *>(nullptr));
             });
         } else if (stg) {
-            launch_draw_stages<false>(a, con, stg, c.batch, 1, nullptr, stream);
+            launch_draw_stages<false>(a, con, stg, c.batch, 1, nullptr, stream, mi, c.vocab);
         } else {
             with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
@@ -1072,8 +1321,15 @@ size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab) {
     return verify_cand_offset(batch, rows_per_seq, vocab) + (((size_t)batch * rows_per_seq * 4 + 255) & ~(size_t)255);
 }
 
+// the mirostat verifier's workspace: the verifier's, then a MiroRowWs per virtual row
+size_t sample_verify_mirostat_workspace_bytes(int batch, int rows_per_seq, int vocab) {
+    const size_t base = sample_verify_workspace_bytes(batch, rows_per_seq, vocab);
+    return base ? base + (size_t)batch * rows_per_seq * sizeof(MiroRowWs) : 0;
+}
+
+// mi (tce_sample_verify_mirostat_f16; with stg only): the draw launch is the SPEC MIRO form, the walk launch follows it, the chain launch is its MIRO form: 4 launches.
 int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
-                             const tce_sample_stages *stg) {
+                             const tce_sample_stages *stg, const tce_sample_mirostat *mi) {
     const tce_sample_call &c = v.s;
     const tce_constraint cv = con ? *con : tce_constraint{};
     const int nchunks = sample_chunks(c.vocab), T = v.rows_per_seq, vrows = c.batch * T;
@@ -1100,6 +1356,7 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
     a.cand = reinterpret_cast<int32_t *>(static_cast<char *>(c.workspace) + verify_cand_offset(c.batch, T, c.vocab));
     a.history = v.history;
     a.emitted = v.emitted;
+    MiroRowWs *mws = mi ? reinterpret_cast<MiroRowWs *>(static_cast<char *>(c.workspace) + sample_verify_workspace_bytes(c.batch, T, c.vocab)) : nullptr;
     VerifyLseArgs la;
     DrawLseArgs ld;
     if (lp) {
@@ -1132,13 +1389,13 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
     if (e == hipSuccess) {
         if (lp) {
             static_cast<DrawArgs &>(ld) = a.d;
-            if (stg) launch_draw_stages<true>(ld, con, stg, vrows, T, a.cand, stream);
+            if (stg) launch_draw_stages<true>(ld, con, stg, vrows, T, a.cand, stream, mi, c.vocab, mws);
             else with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
                 hipLaunchKernelGGL((sample_draw_kernel<true, true, CON>), dim3(vrows), dim3(kThreads), 0, stream, con_args<CON>(ld, con), T, a.cand);
             });
         } else if (stg) {
-            launch_draw_stages<true>(a.d, con, stg, vrows, T, a.cand, stream);
+            launch_draw_stages<true>(a.d, con, stg, vrows, T, a.cand, stream, mi, c.vocab, mws);
         } else {
             with_con(con, [&](auto tag) {
                 constexpr bool CON = decltype(tag)::value;
@@ -1147,19 +1404,48 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
         }
         e = hipGetLastError();
     }
+    if (e == hipSuccess && mi) {
+        WalkArgs w;
+        w.mws = mws;
+        w.rows = c.rows;
+        w.mrows = mi->rows;
+        w.mdebug = mi->debug;
+        w.pos = c.pos_device;
+        w.row_pos = v.row_pos;
+        w.pos_bound = c.pos_bound;
+        w.T = T;
+        w.vocab = c.vocab;
+        w.ld = c.ld;
+        w.uniform_override = c.uniform_override;
+        w.cand = a.cand;
+        w.logits = lp ? static_cast<const half_t *>(c.logits) : nullptr;
+        w.cand_logprob = lp ? ld.cand_logprob : nullptr;
+        w.cand_lse = lp ? ld.cand_lse : nullptr;
+        hipLaunchKernelGGL(sample_miro_walk_kernel, dim3(c.batch), dim3(kThreads), 0, stream, w);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess) {
         a.d.pos = c.pos_device;
+        auto chain = [&](const auto &base, auto lse_tag) {
+            constexpr bool LSE = decltype(lse_tag)::value;
+            with_con(con, [&](auto tag) {
+                constexpr bool CON = decltype(tag)::value;
+                if (mi) {
+                    MiroChainArgs<VerifyArgsBase<LSE, CON>> x;
+                    static_cast<VerifyArgsBase<LSE, CON> &>(x) = con_args<CON>(base, con);
+                    x.mrows = mi->rows;
+                    x.mws = mws;
+                    hipLaunchKernelGGL((sample_verify_chain_kernel<LSE, CON, true>), dim3((c.batch + 63) / 64), dim3(64), 0, stream, x);
+                } else {
+                    hipLaunchKernelGGL((sample_verify_chain_kernel<LSE, CON>), dim3((c.batch + 63) / 64), dim3(64), 0, stream, con_args<CON>(base, con));
+                }
+            });
+        };
         if (lp) {
             static_cast<VerifyArgs &>(la) = a;
-            with_con(con, [&](auto tag) {
-                constexpr bool CON = decltype(tag)::value;
-                hipLaunchKernelGGL((sample_verify_chain_kernel<true, CON>), dim3((c.batch + 63) / 64), dim3(64), 0, stream, con_args<CON>(la, con));
-            });
+            chain(la, std::true_type{});
         } else {
-            with_con(con, [&](auto tag) {
-                constexpr bool CON = decltype(tag)::value;
-                hipLaunchKernelGGL((sample_verify_chain_kernel<false, CON>), dim3((c.batch + 63) / 64), dim3(64), 0, stream, con_args<CON>(a, con));
-            });
+            chain(a, std::false_type{});
         }
         e = hipGetLastError();
     }
@@ -1171,7 +1457,8 @@ int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_
 }
 
 template <bool SPEC, class Base>
-static void launch_draw_stages(const Base &base, const tce_constraint *con, const tce_sample_stages *stg, int rows, int RT, int32_t *cand, hipStream_t stream) {
+static void launch_draw_stages(const Base &base, const tce_constraint *con, const tce_sample_stages *stg, int rows, int RT, int32_t *cand, hipStream_t stream,
+                               const tce_sample_mirostat *mi, int vocab, MiroRowWs *mws) {
     constexpr bool LSE = std::is_same_v<Base, DrawLseArgs>;
     with_con(con, [&](auto tag) {
         constexpr bool CON = decltype(tag)::value;
@@ -1179,6 +1466,16 @@ static void launch_draw_stages(const Base &base, const tce_constraint *con, cons
         static_cast<DrawArgsBase<LSE, CON> &>(x) = con_args<CON>(base, con);
         x.srows = stg->rows;
         x.sdebug = stg->debug;
+        if (mi) {
+            MiroArgs<StgArgs<DrawArgsBase<LSE, CON>>> y;
+            static_cast<StgArgs<DrawArgsBase<LSE, CON>> &>(y) = x;
+            y.mrows = mi->rows;
+            y.mdebug = mi->debug;
+            y.mvocab = vocab;
+            y.mws = mws;
+            hipLaunchKernelGGL((sample_draw_kernel<SPEC, LSE, CON, true, true>), dim3(rows), dim3(kThreads), 0, stream, y, RT, cand);
+            return;
+        }
         hipLaunchKernelGGL((sample_draw_kernel<SPEC, LSE, CON, true>), dim3(rows), dim3(kThreads), 0, stream, x, RT, cand);
     });
 }

@@ -22,7 +22,7 @@ void set_w8a8_xsplit(int xs);
 int sample_chunks(int vocab);
 size_t sample_workspace_bytes(int batch, int vocab);
 int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
-                      const tce_sample_stages *stg = nullptr);
+                      const tce_sample_stages *stg = nullptr, const tce_sample_mirostat *mi = nullptr);
 size_t logprobs_workspace_bytes(int rows, int vocab);
 int launch_logprobs_f16(const void *logits, int ld, int vocab, int rows, const int32_t *target, float *out_logprob, float *out_lse, void *partials, hipStream_t stream,
                         hipError_t *hip_err);
@@ -30,7 +30,8 @@ int launch_embed_rows_f16(const void *table, int vocab, int hidden, const int32_
                           hipStream_t stream, hipError_t *hip_err);
 size_t sample_verify_workspace_bytes(int batch, int rows_per_seq, int vocab);
 int launch_sample_verify_f16(const tce_sample_verify_call &v, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
-                             const tce_sample_stages *stg = nullptr);
+                             const tce_sample_stages *stg = nullptr, const tce_sample_mirostat *mi = nullptr);
+size_t sample_verify_mirostat_workspace_bytes(int batch, int rows_per_seq, int vocab);
 int launch_draft_ngram(const int32_t *history, const int32_t *script, int hist_stride, const int32_t *pos, int pos_bound, int batch, int rows_per_seq, int ngram,
                        int32_t *row_token, int32_t *row_pos, hipStream_t stream, hipError_t *hip_err);
 int launch_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, hipStream_t stream,
@@ -1652,6 +1653,49 @@ int tce_sample_stages_f16(const tce_sample_call *c, const tce_sample_stages *st,
     hipError_t he = hipSuccess;
     const int rc = tce::launch_sample_f16(*c, lp, con, static_cast<hipStream_t>(stream), &he, st);
     return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+// the mirostat form's own refusals (after the stages form's)
+static int check_mirostat(const char *who, const tce_sample_mirostat *mi) {
+    if (!mi) return fail(TCE_ERR_BAD_ARG, "%s: null tce_sample_mirostat", who);
+    if (!mi->rows) return fail(TCE_ERR_BAD_ARG, "%s: null pointer (rows)", who);
+    if ((reinterpret_cast<uintptr_t>(mi->rows) | reinterpret_cast<uintptr_t>(mi->debug)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: mirostat rows / debug 4-byte aligned", who);
+    return TCE_OK;
+}
+
+int tce_sample_mirostat_f16(const tce_sample_call *c, const tce_sample_stages *st, const tce_sample_mirostat *mi, const tce_constraint *con, const tce_logprob_out *lp,
+                            void *stream) {
+    static const char *who = "tce_sample_mirostat_f16";
+    if (const int rc = check_sample_call(who, c, c ? c->batch : 0)) return rc;  // (call->mirostat != 0 stays refused: the mode lives per row)
+    if (const int rc = check_stages(who, st)) return rc;
+    if (const int rc = check_mirostat(who, mi)) return rc;
+    if (con)
+        if (const int rc = check_constraint(who, con)) return rc;
+    if (lp)
+        if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_f16(*c, lp, con, static_cast<hipStream_t>(stream), &he, st, mi);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "sampling launch") : rc;
+}
+
+size_t tce_sample_verify_mirostat_workspace_bytes(int batch, int rows_per_seq, int vocab) {
+    return tce_sample_verify_workspace_bytes(batch, rows_per_seq, vocab) ? tce::sample_verify_mirostat_workspace_bytes(batch, rows_per_seq, vocab) : 0;
+}
+
+int tce_sample_verify_mirostat_f16(const tce_sample_verify_call *v, const tce_sample_stages *st, const tce_sample_mirostat *mi, const tce_constraint *con,
+                                   const tce_logprob_out *lp, void *stream) {
+    static const char *who = "tce_sample_verify_mirostat_f16";
+    if (const int rc = check_verify_call(who, v)) return rc;
+    if (const int rc = check_stages(who, st)) return rc;
+    if (const int rc = check_mirostat(who, mi)) return rc;
+    if (con)
+        if (const int rc = check_constraint(who, con)) return rc;
+    if (lp)
+        if (const int rc = check_logprob_out(who, lp)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_sample_verify_f16(*v, lp, con, static_cast<hipStream_t>(stream), &he, st, mi);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "verify launch") : rc;
 }
 
 int tce_sample_verify_stages_f16(const tce_sample_verify_call *v, const tce_sample_stages *st, const tce_constraint *con, const tce_logprob_out *lp, void *stream) {

@@ -8,6 +8,7 @@ The batched / paged decoders (batch_decode.py, paged_kv.py) run a "step" = the l
     1        tce_w4a16_forward       lm_head at M = B -> logits fp16 [B][vocab]
     2        tce_sample_f16          penalties, top-k, softmax, top-p, temperature, draw; token -> next_token, log, ring; pos += 1 or -1 (retired)
                                      (stages=True: tce_sample_stages_f16, the same two launches with tail-free and typical sampling per slot between top-k and top-p)
+                                     (mirostat_rows=True: tce_sample_mirostat_f16, the same two launches with mirostat v1 / v2 per slot, mu kept on the device)
                                      (logprobs=True: tce_sample_logprobs_f16, the same two launches, which also write the token's log-probability)
                                      (constraints=True: tce_sample_constrained_f16, the same two launches under a token automaton and a logit bias per slot:
                                      constrain.py)
@@ -83,11 +84,20 @@ class SamplingParams:
     tfs_z: float = 1.0
     typical_p: float = 1.0
     mirostat: int = 0
+    mirostat_tau: float = 5.0
+    mirostat_eta: float = 0.1
 
-    def check(self, top_k_bound: int = MAX_K, stages: bool = False) -> None:
-        """stages=False: what tce_sample_f16 can run (tfs_z 1.0, typical_p 1.0).  stages=True: what tce_sample_stages_f16 can run -- any tfs_z / typical_p but NaN."""
+    def check(self, top_k_bound: int = MAX_K, stages: bool = False, mirostat_rows: bool = False) -> None:
+        """stages=False: what tce_sample_f16 can run (tfs_z 1.0, typical_p 1.0).  stages=True: what tce_sample_stages_f16 can run -- any tfs_z / typical_p but NaN.
+        mirostat_rows=True (implies stages=True, as in Sampler): what tce_sample_mirostat_f16 can run -- also mirostat 1 or 2 with finite tau and eta, eta >= 0."""
+        stages = stages or mirostat_rows
+        if mirostat_rows:
+            if self.mirostat not in (0, 1, 2):
+                raise ValueError(f"mirostat {self.mirostat}: 0, 1 or 2")
+            if not (np.isfinite(self.mirostat_tau) and np.isfinite(self.mirostat_eta)) or self.mirostat_eta < 0:
+                raise ValueError(f"mirostat_tau {self.mirostat_tau} / mirostat_eta {self.mirostat_eta}: finite, eta >= 0")
         if stages:
-            if self.mirostat != 0:
+            if self.mirostat != 0 and not mirostat_rows:
                 raise ValueError("mirostat sampling is not built (mirostat 0 only)")
             if self.tfs_z != self.tfs_z or self.typical_p != self.typical_p:
                 raise ValueError("tfs_z / typical_p: NaN")
@@ -181,6 +191,57 @@ def typical_order(p: np.ndarray, typical_p) -> tuple[np.ndarray, int]:
     return order.astype(np.int32), (int(hit[0]) + 1 if hit.size else k)
 
 
+MIROSTAT_M = 100  # the reference's mirostat_m (LLaMA3Generate.cc:164)
+
+
+def mirostat_keep(k_f, kk: int) -> int:
+    """The project's rule where C leaves int(k) open (include/tce_matmul.h, rule 2): NaN or k_f < 1 -> 1; k_f >= kk (+inf included) -> kk; otherwise int(k_f)."""
+    k_f = np.float32(k_f)
+    if not k_f >= np.float32(1.0):
+        return 1
+    return int(kk) if k_f >= np.float32(kk) else int(k_f)
+
+
+def mirostat_reference(sorted_logits: np.ndarray, params: "SamplingParams", mu, u, vocab: int, m: int = MIROSTAT_M) -> dict:
+    """tce_sample_mirostat_f16's rule for a row whose mode is 1 or 2 and whose temp > 0, restated in numpy fp32: sample_temperature, sample_softmax and
+    sample_token_mirostat[_v2] (Generate.cc:72-100, 138-201) on the row's kk sorted penalised candidates.  sorted_logits: fp32, descending.  Returns p (the softmax over
+    logit / temp), s_hat and k_f (mode 1; else 0), kept, final_p (kept entries), choice, surprise and mu_out."""
+    f32 = np.float32
+    l = np.asarray(sorted_logits, f32)
+    kk, mu = int(l.size), f32(mu)
+    with np.errstate(all="ignore"):
+        lt = (l / f32(params.temp)).astype(f32)
+        p = _softmax_sorted(lt)
+        s_hat = k_f = f32(0.0)
+        if int(params.mirostat) == 1:
+            nt = kk - 1 if (m - 1 < 0 or m - 1 > kk - 1) else m - 1
+            i = np.arange(nt)
+            t = np.log(((i + 2).astype(f32) / (i + 1).astype(f32)).astype(f32)).astype(f32)
+            bi = np.log((p[:nt] / p[1:nt + 1]).astype(f32)).astype(f32)
+            A = np.cumsum((t * bi).astype(f32), dtype=f32)[-1] if nt else f32(0.0)
+            B = np.cumsum((t * t).astype(f32), dtype=f32)[-1] if nt else f32(0.0)
+            s_hat = f32(A / B)
+            eps = f32(s_hat - f32(1.0))
+            num = f32(eps * _powf(2.0, mu))
+            den = f32(f32(1.0) - _powf(f32(vocab), f32(-eps)))
+            k_f = _powf(f32(num / den), f32(f32(1.0) / s_hat))
+            kept = mirostat_keep(k_f, kk)
+        else:
+            hit = np.nonzero((-np.log2(p).astype(f32)).astype(f32) > mu)[0]
+            kept = max(int(hit[0]) if hit.size else kk, 1)
+        fp = _softmax_sorted(lt[:kept])
+        choice = draw_reference(fp, u)
+        surprise = f32(-np.log2(fp[choice]).astype(f32))
+        mu_out = f32(mu - f32(f32(params.mirostat_eta) * f32(surprise - f32(params.mirostat_tau))))
+    return {"p": p, "s_hat": s_hat, "k_f": k_f, "kept": kept, "final_p": fp, "choice": choice, "surprise": surprise, "mu_out": mu_out}
+
+
+def _powf(x, y) -> np.float32:
+    """powf as one rounding of the float64 power (what the device computes); pow's special cases (a negative base with a fractional exponent: NaN)."""
+    with np.errstate(all="ignore"):
+        return np.float32(np.power(np.float64(np.float32(x)), np.float64(np.float32(y))))
+
+
 def draw_reference(final_p: np.ndarray, u) -> int:
     """Inverse CDF on the sequential fp32 running sum of final_p: the first i with u < cdf_i, the last candidate if rounding leaves none."""
     cdf = np.cumsum(final_p, dtype=np.float32)
@@ -188,15 +249,16 @@ def draw_reference(final_p: np.ndarray, u) -> int:
     return int(hit[0]) if hit.size else int(final_p.size) - 1
 
 
-def sample_reference(logits_f16_row: np.ndarray, recent, params: SamplingParams, u) -> dict:
+def sample_reference(logits_f16_row: np.ndarray, recent, params: SamplingParams, u, mu=None) -> dict:
     """One row through the chain tce_sample_f16 implements.  recent: the penalty window (the last repeat_last_n ids of the ring, initial zeros included).
     Ordering rule: descending penalised logit, ascending id among equals.  Returns ids / logits (the k sorted candidates), p (first softmax), n (kept by top-p),
-    final_p (after temperature, n entries), choice and token."""
+    final_p (after temperature, n entries), choice and token.  params.mirostat 1 or 2 with temp > 0 (tce_sample_mirostat_f16): mu is the row's running value (None:
+    2 * tau, a fresh slot's); the result also carries mirostat_reference's keys, mu_out among them."""
     x = penalised_logits(logits_f16_row, recent, params)
-    return _chain(x, np.arange(x.size), params, u)
+    return _chain(x, np.arange(x.size), params, u, mu)
 
 
-def _chain(x: np.ndarray, among: np.ndarray, params: SamplingParams, u) -> dict:
+def _chain(x: np.ndarray, among: np.ndarray, params: SamplingParams, u, mu=None) -> dict:
     """sample_reference behind the penalties, over the ids `among` (ascending) of the penalised fp32 row x: every id (sample_reference) or the allowed ones
     (constrain.constrained_reference).  The ids keep their values: ties go to the lowest id, and fewer than k ids make k their number."""
     xa = x[among]
@@ -216,6 +278,13 @@ def _chain(x: np.ndarray, among: np.ndarray, params: SamplingParams, u) -> dict:
     order = np.lexsort((cand, -x[cand].astype(np.float64)))
     ids = cand[order].astype(np.int32)
     l = (x[ids] + np.float32(0.0)).astype(np.float32)  # (-0 -> +0, as the device returns it)
+    if int(params.mirostat) in (1, 2):  # tce_sample_mirostat_f16: instead of the stages, top-p and temperature
+        mu = np.float32(2.0) * np.float32(params.mirostat_tau) if mu is None else mu
+        r = mirostat_reference(l, params, mu, u, x.size)
+        kept = r["kept"]
+        r.update({"ids": ids, "logits": l, "n": kept, "token": int(ids[r["choice"]]), "n_tfs": int(l.size), "n_typ": int(l.size), "order": np.arange(l.size, dtype=np.int32),
+                  "p_top": r["p"], "final_ids": ids, "mu_in": np.float32(mu)})
+        return r
     p = _softmax_sorted(l)
     # the two stages of tce_sample_stages_f16 (rules 2 and 3 of include/tce_matmul.h); with tfs_z and typical_p both >= 1 nothing below differs from the chain without them
     tfs_on, typ_on = not np.float32(params.tfs_z) >= np.float32(1.0), not np.float32(params.typical_p) >= np.float32(1.0)
@@ -267,6 +336,7 @@ def ring_window(ring: np.ndarray, pushed: int, repeat_last_n: int) -> np.ndarray
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 _ROW_WORDS = C.sizeof(capi.SampleRow) // 4
 _DEBUG_WORDS = C.sizeof(capi.SampleDebug) // 4
+_MIRO_WORDS = C.sizeof(capi.MirostatRow) // 4
 
 
 def make_row(params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> capi.SampleRow:
@@ -281,6 +351,12 @@ def make_row(params: SamplingParams, seed: int, max_new: int, prompt_ids=()) -> 
     return r
 
 
+def make_mirostat_row(params: SamplingParams, m: int = MIROSTAT_M) -> capi.MirostatRow:
+    """A fresh tce_mirostat_row: the request's mode, tau and eta, the reference's m, and mu = 2 * tau in fp32 (LLaMA3Generate.cc:163) -- per slot, at every admission."""
+    tau = np.float32(params.mirostat_tau)
+    return capi.MirostatRow(mode=int(params.mirostat), m=int(m), tau=float(tau), eta=float(np.float32(params.mirostat_eta)), mu=float(np.float32(2.0) * tau))
+
+
 class Sampler:
     """The per-row device state of tce_sample_f16 for `batch` rows: rows (parameters, ring, counters), next_token, the output log [batch][log_stride], the workspace
     (zeroed once).  debug=True keeps the sorted candidates of the last call (tests).  logprobs=True: step() calls tce_sample_logprobs_f16 -- the same two launches --
@@ -292,10 +368,14 @@ class Sampler:
     stages=True: the sampler owns the stage rows [batch] (struct tce_stage_row: tfs_z, typical_p; (1.0, 1.0) until set_row writes a slot's pair from its SamplingParams)
     and step() calls tce_sample_stages_f16 -- still two launches --, with the constraint and logprob blocks when those options are on; debug=True also keeps the
     stage records (stage_debug_row).  stages=False: the call, the launches and a captured graph are what they were, and set_row refuses a SamplingParams whose
-    tfs_z / typical_p are not 1.0."""
+    tfs_z / typical_p are not 1.0.
+    mirostat_rows=True (implies stages=True): the sampler also owns the mirostat rows [batch] (struct tce_mirostat_row: mode, m, tau, eta, mu; every slot mode 0 until
+    set_row writes a slot's row from its SamplingParams, with mu = 2 * tau) and step() calls tce_sample_mirostat_f16 -- still two launches; mu lives on the device and
+    moves with every token the slot emits, under a captured graph too.  debug=True also keeps the mirostat records (mirostat_debug_row).  The constructor's `mirostat`
+    argument is the CALL's field and stays refused when it is not 0."""
 
     def __init__(self, batch: int, vocab: int, log_stride: int, device, top_k_bound: int = 40, stop_ids=(), debug: bool = False, tfs_z: float = 1.0,
-                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False, constraints: bool = False, stages: bool = False):
+                 typical_p: float = 1.0, mirostat: int = 0, logprobs: bool = False, constraints: bool = False, stages: bool = False, mirostat_rows: bool = False):
         import torch
         if len(stop_ids) > 4:
             raise ValueError("at most 4 stop ids")
@@ -324,7 +404,12 @@ class Sampler:
             self.crows[:, 0] = -1  # every row unconstrained
             self.table = AutomatonTable(vocab, device)
             self.violations_word = torch.zeros(1, dtype=torch.int32, device=device)
-        self.stages = bool(stages)
+        self.mirostat_rows = bool(mirostat_rows)
+        self.stages = bool(stages) or self.mirostat_rows
+        self.mrows = self.mdebug = None
+        if self.mirostat_rows:
+            self.mrows = torch.zeros((batch, _MIRO_WORDS), dtype=torch.int32, device=device)  # every slot mode 0: off
+            self.mdebug = torch.zeros((batch, C.sizeof(capi.MirostatDebug) // 4), dtype=torch.int32, device=device) if debug else None
         self.srows = self.sdebug = None
         if self.stages:
             self.srows = torch.ones((batch, 2), dtype=torch.float32, device=device)  # every slot (1.0, 1.0): off
@@ -334,6 +419,10 @@ class Sampler:
         """struct tce_sample_stages over this sampler's stage rows (debug: another record array -- the verifier's, per virtual row)."""
         debug = self.sdebug if debug is None else debug
         return capi.SampleStages(rows=self.srows.data_ptr(), debug=debug.data_ptr() if debug is not None else None)
+
+    def mirostat_block(self) -> capi.SampleMirostat:
+        """struct tce_sample_mirostat over this sampler's mirostat rows"""
+        return capi.SampleMirostat(rows=self.mrows.data_ptr(), debug=self.mdebug.data_ptr() if self.mdebug is not None else None)
 
     def constraint(self) -> capi.Constraint:
         """struct tce_constraint over this sampler's table, rows and violations word (n_fsm is the table's size: a free entry has no states and is refused on the device)."""
@@ -362,7 +451,7 @@ class Sampler:
         """The slot changes hands: one stream-ordered copy of its row (parameters, a fresh ring with the prompt pushed, counters at zero) and, with constraints=True,
         one of its constraint row: automaton (an index of table.register, None: unconstrained) in its start state, logit_bias ({id: value} or [(id, value)], <= 16)."""
         import torch
-        params.check(self.top_k_bound, stages=self.stages)
+        params.check(self.top_k_bound, stages=self.stages, mirostat_rows=self.mirostat_rows)
         if not 1 <= max_new <= self.log_stride:
             raise ValueError(f"max_new {max_new}: 1 .. {self.log_stride}")
         bias = self.check_constraint(automaton, logit_bias)
@@ -378,6 +467,8 @@ class Sampler:
                 self.table.users[slot] = int(automaton)
         if self.stages:
             self.srows[slot].copy_(torch.tensor([params.tfs_z, params.typical_p], dtype=torch.float32))
+        if self.mirostat_rows:
+            self.mrows[slot].copy_(torch.from_numpy(np.frombuffer(bytes(make_mirostat_row(params)), dtype=np.int32).copy()))
 
     def step(self, logits, pos_device, pos_bound: int) -> None:
         """tce_sample_f16 on logits fp16 [batch][ld] (two launches on the current stream).  pos_device int32 [batch] is READ (activity) and WRITTEN (+1, or -1)."""
@@ -387,7 +478,10 @@ class Sampler:
         assert pos_device.dtype == torch.int32 and pos_device.is_contiguous() and pos_device.numel() == self.batch
         assert logits.is_cuda and pos_device.is_cuda
         c = self.call(logits.data_ptr(), logits.shape[1], pos_device.data_ptr(), pos_bound)
-        if self.stages:
+        if self.mirostat_rows:
+            capi.check(capi.sample_mirostat_f16(c, self.stage_block(), self.mirostat_block(), self.constraint() if self.constraints else None,
+                                                self.logprob_out() if self.logprobs else None, _stream()))
+        elif self.stages:
             capi.check(capi.sample_stages_f16(c, self.stage_block(), self.constraint() if self.constraints else None, self.logprob_out() if self.logprobs else None, _stream()))
         elif self.constraints:
             capi.check(capi.sample_constrained_f16(c, self.constraint(), self.logprob_out() if self.logprobs else None, _stream()))
@@ -418,6 +512,12 @@ class Sampler:
 
     def stage_debug_row(self, slot: int) -> capi.StageDebug:
         return capi.StageDebug.from_buffer_copy(self.sdebug[slot].cpu().numpy().tobytes())
+
+    def mirostat_row(self, slot: int) -> capi.MirostatRow:
+        return capi.MirostatRow.from_buffer_copy(self.mrows[slot].cpu().numpy().tobytes())
+
+    def mirostat_debug_row(self, slot: int) -> capi.MirostatDebug:
+        return capi.MirostatDebug.from_buffer_copy(self.mdebug[slot].cpu().numpy().tobytes())
 
     def generated(self) -> np.ndarray:
         return self.rows[:, 10].cpu().numpy().astype(np.int64)  # word 10: tce_sample_row.generated
@@ -657,7 +757,8 @@ class _GeneratorBase:
                 raise ValueError(f"slot {s} is live")
             if any(not 0 <= t < self.vocab for t in ids):
                 raise ValueError("a prompt token lies outside the vocabulary")
-            p.check(self.sampler.top_k_bound, stages=getattr(self.sampler, "stages", False))  # (a sampler stand-in without the attribute runs no stage)
+            p.check(self.sampler.top_k_bound, stages=getattr(self.sampler, "stages", False),  # (a sampler stand-in without the attribute runs no stage)
+                    mirostat_rows=getattr(self.sampler, "mirostat_rows", False))
             if any(c is not None for c in cons.get(s, ())):  # (the existing call forms read nothing new of the sampler)
                 self.sampler.check_constraint(*cons[s])
             if not 1 <= len(ids) < self.max_keys or not 1 <= mn <= self.sampler.log_stride:
@@ -815,10 +916,13 @@ class BatchedGenerator(_GeneratorBase):
     inactive) and run() replays it: one replay is one token for every live slot."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, eps: float | None = None, top_k_bound: int = 40, stop_ids=(), graph: bool = True,
-                 debug: bool = False, logprobs: bool = False, constraints: bool = False, lora=None, stages: bool = False):
-        """stages=True: the sampler runs tce_sample_stages_f16 and every admission's SamplingParams may carry its own tfs_z / typical_p (Sampler).  lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  A
+                 debug: bool = False, logprobs: bool = False, constraints: bool = False, lora=None, stages: bool = False, mirostat_rows: bool = False):
+        """stages=True: the sampler runs tce_sample_stages_f16 and every admission's SamplingParams may carry its own tfs_z / typical_p (Sampler).  mirostat_rows=True
+        (implies stages): the sampler runs tce_sample_mirostat_f16 and an admission's SamplingParams may carry mirostat 1 or 2 with its tau / eta; the slot's mu starts at
+        2 * tau and lives on the device, so a replay moves it with no host round trip and no admission captures again.  lora: the LoraPool whose layer views the decoders were built with (decoder i: lora=pool.layer(i)); None: the base model, every launch as before.  A
         gate_up=True pool adapts gate/up too (15 L + 5 launches per token instead of 13 L + 5).  lm_head and the embedding are not adapted."""
-        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints, stages=stages)
+        super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, debug=debug, logprobs=logprobs, constraints=constraints, stages=stages,
+                         mirostat_rows=mirostat_rows)
         self._take_pool(lora)
         self.score_keep_logits = False  # a debug hook (tests): score() keeps a copy of every chunk's logits in score_logits, the last chunk's last
         self.score_logits: list = []

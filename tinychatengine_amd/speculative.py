@@ -13,6 +13,7 @@ spread over up to T tokens of the SAME sequence: the linears run at M = B T and 
     1        tce_w4a16_forward            lm_head at M = B T
     3        tce_sample_verify_f16        select for all rows, draw per row, walk the chain: 1 .. T tokens per sequence
                                           (stages=True: tce_sample_verify_stages_f16 -- the same three launches with the sequence's tail-free / typical pair on every row)
+                                          (mirostat_rows=True: tce_sample_verify_mirostat_f16 -- FOUR launches: a mirostat sequence's rows are walked in order with mu carried)
 
 LOSSLESS by construction: row t is sampled with the window and the Philox counter (seed, index of the token in its sequence) the plain loop would use, and a draft is
 kept only if it EQUALS the token sampled in front of it.  There is no draft distribution and no rejection sampling; draft models and tree drafts are not built.
@@ -226,7 +227,8 @@ class Verifier:
         _check_rows(rows_per_seq)
         self.sampler, self.rows_per_seq = sampler, int(rows_per_seq)
         dev = sampler.rows.device
-        need = int(capi.lib().tce_sample_verify_workspace_bytes(sampler.batch, self.rows_per_seq, sampler.vocab))
+        size = capi.lib().tce_sample_verify_mirostat_workspace_bytes if getattr(sampler, "mirostat_rows", False) else capi.lib().tce_sample_verify_workspace_bytes
+        need = int(size(sampler.batch, self.rows_per_seq, sampler.vocab))
         if need == 0:
             raise ValueError("unsupported verify shape (batch * rows_per_seq <= 65535, vocab <= 2^20)")
         self.workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
@@ -237,6 +239,9 @@ class Verifier:
         self.sdebug = None  # a Sampler built with stages=True: tce_sample_verify_stages_f16, the stage records per virtual row
         if sampler.stages and debug:
             self.sdebug = torch.zeros((sampler.batch * self.rows_per_seq, C.sizeof(capi.StageDebug) // 4), dtype=torch.int32, device=dev)
+        self.mdebug = None  # a Sampler built with mirostat_rows=True: tce_sample_verify_mirostat_f16 (four launches), the mirostat records per virtual row
+        if getattr(sampler, "mirostat_rows", False) and debug:
+            self.mdebug = torch.zeros((sampler.batch * self.rows_per_seq, C.sizeof(capi.MirostatDebug) // 4), dtype=torch.int32, device=dev)
         if sampler.logprobs:
             self.partials = torch.empty(int(capi.lib().tce_logprobs_workspace_bytes(sampler.batch * self.rows_per_seq, sampler.vocab)), dtype=torch.uint8, device=dev)
 
@@ -254,7 +259,11 @@ class Verifier:
         c.debug = self.debug.data_ptr() if self.debug is not None else None
         v = capi.SampleVerifyCall(s=c, rows_per_seq=self.rows_per_seq, hist_stride=history.shape[1], row_token=row_token.data_ptr(), row_pos=row_pos.data_ptr(),
                                   history=history.data_ptr(), emitted=self.emitted.data_ptr())
-        if s.stages:
+        if getattr(s, "mirostat_rows", False):
+            st = capi.SampleStages(rows=s.srows.data_ptr(), debug=self.sdebug.data_ptr() if self.sdebug is not None else None)
+            mi = capi.SampleMirostat(rows=s.mrows.data_ptr(), debug=self.mdebug.data_ptr() if self.mdebug is not None else None)
+            capi.check(capi.sample_verify_mirostat_f16(v, st, mi, s.constraint() if s.constraints else None, s.logprob_out(self.partials) if s.logprobs else None, _stream()))
+        elif s.stages:
             st = capi.SampleStages(rows=s.srows.data_ptr(), debug=self.sdebug.data_ptr() if self.sdebug is not None else None)
             capi.check(capi.sample_verify_stages_f16(v, st, s.constraint() if s.constraints else None, s.logprob_out(self.partials) if s.logprobs else None, _stream()))
         elif s.constraints:
@@ -278,7 +287,7 @@ class SpeculativeGenerator(_GeneratorBase):
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False,
-                 constraints: bool = False, lora=None, stages: bool = False):
+                 constraints: bool = False, lora=None, stages: bool = False, mirostat_rows: bool = False):
         if lora is not None:  # first: a pool that was not built for rows, or for another T, is refused before anything else of the constructor runs
             T = getattr(lora, "rows_per_seq", None)
             decoders = list(decoders) if T is not None and decoders is not None else None
@@ -297,7 +306,7 @@ class SpeculativeGenerator(_GeneratorBase):
         _check_rows(self.rows_per_seq, self.ngram)
         assert all(d.rows_per_seq == self.rows_per_seq for d in decoders), "one T"
         super().__init__(decoders, final_gamma, lm_head, embed_table, max_new, eps, top_k_bound, stop_ids, rows_per_seq=self.rows_per_seq, logprobs=logprobs,
-                         constraints=constraints, stages=stages)
+                         constraints=constraints, stages=stages, mirostat_rows=mirostat_rows)
         self._take_pool(lora)
         B, T, dev = self.batch, self.rows_per_seq, self.device
         self.verifier = Verifier(self.sampler, T)
@@ -309,7 +318,7 @@ class SpeculativeGenerator(_GeneratorBase):
         self.script = z(B, self.hist_stride, fill=-1) if script else None
         self._emit_log = z(int(record_steps), B)
         self._steps, self._record = 0, True
-        self.launches_per_token = 1 + 1 + decoders[0].LAUNCHES * len(decoders) + 1 + 1 + 3
+        self.launches_per_token = 1 + 1 + decoders[0].LAUNCHES * len(decoders) + 1 + 1 + (4 if mirostat_rows else 3)  # (the mirostat verifier walks in a fourth launch)
         if graph:
             self._capture()
 
