@@ -999,7 +999,10 @@ __device__ __forceinline__ void w4a16_gemm_pk_body(const PkGemmArgs &g) {
         const int row = e / PPR, pc = e % PPR;
         const int m = m_base + row, n = nb0 + pc * 8;
         if (m >= g.M || n >= g.N) continue;
-        const half8_t v = *reinterpret_cast<const half8_t *>(lds_c + row * BN + pc * 8);
+        // (+ 0: an output that is exactly zero leaves the rescale chain with the sign of the scales it was multiplied by -- 0 * e, e < 0, is -0 -- where a sum of the
+        //  products themselves, started from +0, is +0, which is what every other W4A16 kernel stores and what SiLuMul_half below multiplies u by; x + (+0) is x for
+        //  every other x, inf and NaN included)
+        const half8_t v = *reinterpret_cast<const half8_t *>(lds_c + row * BN + pc * 8) + half8_t{0, 0, 0, 0, 0, 0, 0, 0};
         if (g.pairs) {  // interleaved gate / up columns: the fp16 values the two linears would have stored, then SiLuMul_half (Int4llamaDecoderLayer.cu:20-30, 96-102)
             half_t *c2 = g.C + (size_t)m * g.ldc + (n >> 1);
             if (n + 8 <= g.N && (g.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 7) == 0) {  // one 8-byte store for the piece's four outputs (round 6: four 2-byte stores until now)

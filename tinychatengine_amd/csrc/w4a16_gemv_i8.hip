@@ -364,12 +364,23 @@ __device__ __forceinline__ void w4a16_gemv_i8_body(const ARGS &args, unsigned ch
             half8_t y;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                // rmsnorm_out's arithmetic -- half(clamp((x * rs) * gamma)) -- with the clamp as ONE v_med3_f32 (the same value for every finite product; a NaN / inf
-                // activation poisons the row anyway): 3 vector instructions fewer per element, 48 per wave, in a kernel that is bound by issue
+                // rmsnorm_out's arithmetic -- half(clamp((x * rs) * gamma)) -- with the clamp as ONE v_med3_f32: the same value for every finite product, and for a NaN
+                // product too (v_med3_f32 returns the minimum of the other two, -64504, which is where rmsnorm_out's fmaxf sends it: a row that holds a NaN is
+                // normalised to FINITE values and is not poisoned below): 3 vector instructions fewer per element, 48 per wave, in a kernel that is bound by issue
                 const float f = ((float)v[e] * rs) * (e < 4 ? gm[c][0][e] : gm[c][1][e - 4]);
                 y[e] = (half_t)__builtin_amdgcn_fmed3f(f, -(65504.f - 1000.f), 65504.f - 1000.f);
             }
             xv[0][c] = __builtin_bit_cast(uint4_t, y);
+        }
+        // A ragged last wave (K no multiple of the wave's block): its chunks past K hold zeros and must STAY zero -- the weights they meet are the next tile's.  With a
+        // finite rs they do (0 * rs * 0); a row that holds a NaN has rs = NaN, and 0 * NaN is NaN, which the clamp above turns into -64504.  One scalar test for the
+        // launches that have no ragged wave (every K that is a multiple of 1024: the models' hidden sizes), a select per chunk for the others.
+        // (the lane against a scalar bound per chunk: no vector register beside the ones the prologue holds -- tests/test_decode_occupancy_isa.py)
+        if (K_ % (UW * 128) != 0) {
+            const int left = __builtin_amdgcn_readfirstlane(pieces - u0 * 16);  // the wave's pieces inside the row
+#pragma unroll
+            for (int c = 0; c < XC; ++c)
+                if (lane >= left - 64 * c) xv[0][c] = uint4_t{0u, 0u, 0u, 0u};
         }
     }
     int sh[MB];
