@@ -67,6 +67,64 @@ def test_cpp_adapter_selftest(oracle, tmp_path):
     assert r.stdout.count("Passed!") == 5 and "Fail!" not in r.stdout  # (round 6: + the GEMM scratch fault count)
 
 
+def _random_zero_points(rng, n, zw):
+    nib = rng.integers(0, 16, (n, zw * 8), dtype=np.uint32)
+    return (nib.reshape(n, -1, 8) << (np.arange(8, dtype=np.uint32) * 4)).sum(axis=2).astype(np.uint32)
+
+
+def test_adapter_call_sequences(oracle, tmp_path):
+    """Values that came THROUGH the adapter's cached state (adapter_selftest --sequences), every one against the oracle within case 1's tolerance
+    (1e-3 * max(|ref|, rms / 64)): the front-cache hit (call 1 with the zero-point verdict pending, synchronise, call 2, call 3 -- bit-identical), every M class
+    (4, 5, 128, 129, 200, 1) on the published linear, two tensors one after the other in the same buffers with tce_adapter_forget between, the same weights with
+    scales A / B / A / B, tce_adapter_prepare + one call, and the AWQ workspace cache across a forget.  N = 72 / 264, K = 512 / 4096, G = 128 / 64 / 32, zero points
+    all 8 and random: on random zero points a wrongly kept TCE_W4_ZERO_POINT_IS_8 misses the tolerance by orders of magnitude."""
+    from tinychatengine_amd import build as B
+    B.build_adapter()
+    rng = np.random.default_rng(46)
+    rows = 200
+    xs = {K: rng.standard_normal((rows, K)).astype(np.float16) for K in (512, 4096)}
+    blob = struct.pack("3i", 0x31514553, rows, len(xs))
+    for K, x in xs.items():
+        blob += struct.pack("i", K) + x.tobytes()
+
+    def record(N, K, G, random_zeros, m):
+        w = (rng.standard_normal((N, K)) * 0.02).astype(np.float32)
+        qw, sc, zp, _, _ = oracle.quantize_q4_6(w, G)
+        if random_zeros:
+            zp = _random_zero_points(rng, N, zp.shape[1])
+        ref32 = oracle.w4a16_gemv_q4_6_mt(xs[K][:m], qw, sc, zp, m, N, K, G, threads=8)
+        return struct.pack("5i", N, K, G, zp.shape[1], m) + qw.tobytes() + sc.tobytes() + zp.tobytes() + ref32.tobytes(), (qw, sc, zp)
+
+    linears = [(N, K, G, rz) for N in (72, 264) for K in (512, 4096) for G in (128, 64, 32) for rz in (False, True)]
+    blob += struct.pack("i", len(linears))
+    for N, K, G, rz in linears:
+        blob += record(N, K, G, rz, rows)[0]
+    # identity / forget: two tensors of one shape (the second with random zero points), and other scales for the first one's weights
+    N, K, G = 264, 512, 64
+    rec_a, (qw_a, sc_a, zp_a) = record(N, K, G, False, 1)
+    rec_c, _ = record(N, K, G, True, 1)
+    sc_b = (sc_a.astype(np.float32) * rng.uniform(0.5, 2.0, sc_a.shape)).astype(np.float16)
+    ref_b = oracle.w4a16_gemv_q4_6_mt(xs[K][:1], qw_a, sc_b, zp_a, 1, N, K, G, threads=8)
+    blob += rec_a + rec_c + sc_b.tobytes() + ref_b.tobytes()
+    # AWQ (q4_5): expected values from the q4_6 oracle on the same codes, as tests/test_gpu_w4a16.py::test_awq_layout_gemm
+    M, N, K, G = 4, 72, 512, 128
+    blob += struct.pack("4i", M, N, K, G)
+    for _ in range(2):
+        w = (rng.standard_normal((N, K)) * 0.02).astype(np.float32)
+        qw, sc, zp, codes, d = oracle.quantize_q4_6(w, G)
+        q5, s5, _ = oracle.pack_q4_5(codes, d.reshape(-1), N, K, G)
+        ref32, _ = oracle.w4a16_gemv_q4_6(xs[K][:M], qw, sc, zp, M, N, K, G)
+        blob += q5.tobytes() + s5.tobytes() + ref32.tobytes()
+    path = tmp_path / "sequences.bin"
+    path.write_bytes(blob)
+    env = {k: v for k, v in os.environ.items() if k != "TCE_ADAPTER_PACK"}
+    r = subprocess.run([B.ADAPTER_TEST_PATH, "--sequences", str(path)], capture_output=True, text=True, timeout=300, env=env)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.count("Passed!") == 7 and "Fail!" not in r.stdout
+    assert r.stdout.count("hit path: N=") == len(linears) and "DIFFER" not in r.stdout
+
+
 def test_adapter_bench_tiny_runs_every_leg():
     """adapter/adapter_bench.cc (the drop-in path on the clock: MatmulOperator::gemv_forward_cuda per linear, null stream, eager, the reference's glue order) on the
     tiny model: all three legs run, every launch is counted (11 per block + final norm + lm_head), the logits are finite, the adapter holds one packed copy per linear."""

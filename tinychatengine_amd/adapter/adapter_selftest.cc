@@ -7,6 +7,11 @@
 // compare.  Inputs and expected outputs come from a binary file written by tests/test_gpu_adapter.py (expected
 // values computed by oracle/); prints the reference's "-------- Test of X: Passed! --------" lines and returns
 // non-zero on any failure (the reference's tests do not propagate exit codes; this one does).
+//
+// `adapter_selftest --sequences <file>` (tests/test_gpu_adapter.py: test_adapter_call_sequences) runs CALL SEQUENCES instead of single calls: values that came through
+// the adapter's cached state -- the front-cache hit, every M class on a published linear, forget + rewrite, other scales on the same weights, tce_adapter_prepare, the AWQ
+// workspace cache -- each compared with the oracle within case 1's tolerance, and bit for bit with each other where the adapter promises the same bits (DESIGN.md 4.6;
+// tests/host/test_adapter_state.cc shows on a model of the C ABI which of these calls are hits).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -74,24 +79,309 @@ bool report(const char *name, bool ok) {
     return ok;
 }
 
+bool read_file(const char *path, Blob &b) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return false;
+    std::fseek(f, 0, SEEK_END);
+    const long n = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    b.bytes.resize(n);
+    const bool ok = std::fread(b.bytes.data(), 1, n, f) == (size_t)n;
+    std::fclose(f);
+    return ok;
+}
+
+// ---- --sequences ------------------------------------------------------------------------------------------------------------------------------------------------
+void sync_or_exit() {
+    if (tce_synchronize(nullptr) != TCE_OK) {  // the first failed HIP call ends the process: nothing more is started on the device
+        std::printf("tce_synchronize failed: %s\n", tce_last_error());
+        std::exit(3);
+    }
+}
+
+// one q4_6 linear of the file: managed copies of the three tensors, expected values for `rows` activation rows
+struct Q46 {
+    int N, K, G, zw, rows;
+    size_t qw_bytes, sc_bytes, zp_bytes;
+    const unsigned char *src_qw, *src_sc, *src_zp;
+    const float *expect;
+    int32_t *w = nullptr;
+    float16_t *sc = nullptr;
+    int *zp = nullptr;
+    void read(Blob &b) {
+        N = b.get<int>(), K = b.get<int>(), G = b.get<int>(), zw = b.get<int>(), rows = b.get<int>();
+        qw_bytes = (size_t)N * (K / 8) * 4, sc_bytes = (size_t)N * zw * 8 * 2, zp_bytes = (size_t)N * zw * 4;
+        src_qw = b.take(qw_bytes), src_sc = b.take(sc_bytes), src_zp = b.take(zp_bytes);
+        expect = reinterpret_cast<const float *>(b.take((size_t)rows * N * 4));
+    }
+    void upload() {
+        w = managed_copy<int32_t>(src_qw, qw_bytes / 4);
+        sc = managed_copy<float16_t>(src_sc, sc_bytes / 2);
+        zp = managed_copy<int>(src_zp, zp_bytes / 4);
+    }
+    void release() {  // what free_aligned_memory_gpu does in a QM_HIP build: forget, then free
+        tce_adapter_forget(w); tce_adapter_forget(sc); tce_adapter_forget(zp);
+        tce_free(w); tce_free(sc); tce_free(zp);
+        w = nullptr, sc = nullptr, zp = nullptr;
+    }
+};
+
+// case 1's tolerance, unchanged: |got - ref| <= 1e-3 * max(|ref|, rms(ref) / 64); returns the worst |err| / tol of the M x N block
+double worst_ratio(const float16_t *out, const float *expect, int M, int N) {
+    double rms = 0;
+    for (int i = 0; i < M * N; ++i) rms += (double)expect[i] * expect[i];
+    rms = std::sqrt(rms / (M * N));
+    double worst = 0;
+    for (int i = 0; i < M * N; ++i) {
+        const double got = half_to_float(out[i].bits), ref = expect[i];
+        const double r = std::fabs(got - ref) / (1e-3 * std::fmax(std::fabs(ref), rms / 64.0));
+        if (std::isnan(r)) return INFINITY;
+        if (r > worst) worst = r;
+    }
+    return worst;
+}
+
+void gemv_call(const Q46 &l, int M, const float16_t *x, float16_t *out, const float16_t *scales = nullptr) {
+    struct matmul_params params;
+    poison(params);  // everything the wrapper does not set is garbage
+    params.A.row = M;
+    params.A.column = l.K;
+    params.A.half_data_ptr = const_cast<float16_t *>(x);
+    params.B.row = l.K / 8;
+    params.B.column = l.N;
+    params.B.int32_data_ptr = l.w;
+    params.C.row = M;
+    params.C.column = l.N;
+    params.C.half_data_ptr = out;
+    params.opt_params.num_thread = 8;
+    params.half_scales = const_cast<float16_t *>(scales ? scales : l.sc);
+    params.int32_zero_point = l.zp;
+    params.block_size = l.G;
+    matmul::MatmulOperator op = matmul::MatmulOperator();
+    op.gemv_forward_cuda(&params);
+}
+
+int run_sequences(const char *path) {
+    Blob b;
+    if (!read_file(path, b) || b.get<int>() != 0x31514553) return 2;
+    const int max_rows = b.get<int>();
+    bool all_ok = true;
+    // activations: one [max_rows][K] block per K
+    const int n_x = b.get<int>();
+    std::vector<int> x_k(n_x);
+    std::vector<float16_t *> x_of(n_x);
+    for (int i = 0; i < n_x; ++i) {
+        x_k[i] = b.get<int>();
+        x_of[i] = managed_copy<float16_t>(b.take((size_t)max_rows * x_k[i] * 2), (size_t)max_rows * x_k[i]);
+    }
+    auto x_for = [&](int K) -> const float16_t * {
+        for (int i = 0; i < n_x; ++i)
+            if (x_k[i] == K) return x_of[i];
+        std::printf("no activations for K=%d\n", K);
+        std::exit(2);
+    };
+    int max_n = 0;
+    {
+        Blob peek = b;
+        for (int i = 0, n = peek.get<int>(); i < n; ++i) {
+            Q46 l;
+            l.read(peek);
+            if (l.N > max_n) max_n = l.N;
+        }
+    }
+    float16_t *out[3], *outm = managed_copy<float16_t>(nullptr, (size_t)max_rows * max_n);
+    for (auto &o : out) o = managed_copy<float16_t>(nullptr, (size_t)max_n);
+
+    // ---- hit path + M classes, per linear ----
+    {
+        const int n = b.get<int>();
+        bool ok_hit = true, ok_m = true;
+        double worst_hit = 0, worst_m = 0;
+        for (int i = 0; i < n; ++i) {
+            Q46 l;
+            l.read(b);
+            l.upload();
+            const float16_t *x = x_for(l.K);
+            for (auto &o : out) std::memset(o, 0xEE, (size_t)l.N * 2);
+            gemv_call(l, 1, x, out[0]);  // first sight: the zero-point verdict is pending, the packed copy is built in front of the call
+            sync_or_exit();
+            gemv_call(l, 1, x, out[1]);  // reads the verdict, publishes
+            gemv_call(l, 1, x, out[2]);  // the front-cache hit
+            sync_or_exit();
+            double w = 0;
+            for (auto &o : out) w = std::fmax(w, worst_ratio(o, l.expect, 1, l.N));
+            const bool same = std::memcmp(out[0], out[1], (size_t)l.N * 2) == 0 && std::memcmp(out[0], out[2], (size_t)l.N * 2) == 0;
+            const long want_entries = 1 + (l.K % 128 == 0 ? 1 : 0);
+            const bool entries_ok = tce_adapter_cache_entries() == want_entries;
+            std::printf("hit path: N=%d K=%d G=%d zeros=%s worst |err|/tol = %.3f, three calls %s, cache entries %ld\n", l.N, l.K, l.G,
+                        (unsigned)l.zp[0] == 0x88888888u ? "8" : "random", w, same ? "bit-identical" : "DIFFER", tce_adapter_cache_entries());
+            ok_hit &= w <= 1.0 && same && entries_ok;
+            worst_hit = std::fmax(worst_hit, w);
+            // every M class on the now-published linear
+            double wm = 0;
+            bool last_same = false;
+            for (int M : {4, 5, 128, 129, 200, 1}) {
+                if (M > l.rows) {  // the file must carry every class
+                    std::printf("M classes: N=%d K=%d G=%d M=%d: the file has only %d rows\n", l.N, l.K, l.G, M, l.rows);
+                    ok_m = false;
+                    continue;
+                }
+                std::memset(outm, 0xEE, (size_t)M * l.N * 2);
+                gemv_call(l, M, x, outm);
+                sync_or_exit();
+                const double r = worst_ratio(outm, l.expect, M, l.N);
+                if (!(r <= 1.0)) std::printf("M classes: N=%d K=%d G=%d M=%d worst |err|/tol = %.3f\n", l.N, l.K, l.G, M, r);
+                wm = std::fmax(wm, r);
+                if (M == 1) last_same = std::memcmp(outm, out[2], (size_t)l.N * 2) == 0;
+            }
+            std::printf("M classes: N=%d K=%d G=%d worst |err|/tol = %.3f over M = 4 5 128 129 200 1, the last M = 1 %s the hit\n", l.N, l.K, l.G, wm, last_same ? "bit-identical to" : "DIFFERS from");
+            ok_m &= wm <= 1.0 && last_same;
+            worst_m = std::fmax(worst_m, wm);
+            l.release();
+            ok_m &= tce_adapter_cache_entries() == 0;
+        }
+        std::printf("sequence hit path: %d linears, worst |err|/tol = %.3f\n", n, worst_hit);
+        all_ok &= report("adapter sequences: hit path (pending verdict, verdict read, front-cache hit)", ok_hit);
+        std::printf("sequence M classes: %d linears, worst |err|/tol = %.3f\n", n, worst_m);
+        all_ok &= report("adapter sequences: M classes on a published linear", ok_m);
+    }
+
+    // ---- identity and forget with real data ----
+    {
+        Q46 a, c;
+        a.read(b);  // zero points all 8
+        c.read(b);  // other weights, other scales, random zero points; same shape
+        const unsigned char *scales_b = b.take(a.sc_bytes);
+        const float *expect_b = reinterpret_cast<const float *>(b.take((size_t)a.N * 4));
+        const float16_t *x = x_for(a.K);
+        bool ok = a.N == c.N && a.K == c.K && a.G == c.G;
+        double worst = 0;
+        auto three_calls = [&](const Q46 &l, const float *expect, const char *what) {
+            for (auto &o : out) std::memset(o, 0xEE, (size_t)l.N * 2);
+            gemv_call(l, 1, x, out[0]);
+            sync_or_exit();
+            gemv_call(l, 1, x, out[1]);
+            gemv_call(l, 1, x, out[2]);
+            sync_or_exit();
+            for (auto &o : out) {
+                const double r = worst_ratio(o, expect, 1, l.N);
+                worst = std::fmax(worst, r);
+                ok &= r <= 1.0;
+            }
+            std::printf("forget + rewrite: %s worst |err|/tol so far = %.3f\n", what, worst);
+        };
+        // two tensors, one after the other, in the same managed buffers
+        a.upload();
+        three_calls(a, a.expect, "first tensor,");
+        tce_adapter_forget(a.w); tce_adapter_forget(a.sc); tce_adapter_forget(a.zp);
+        ok &= tce_adapter_cache_entries() == 0;
+        std::memcpy(a.w, c.src_qw, c.qw_bytes);
+        std::memcpy(a.sc, c.src_sc, c.sc_bytes);
+        std::memcpy(a.zp, c.src_zp, c.zp_bytes);
+        three_calls(a, c.expect, "second tensor in the same buffers,");
+        tce_adapter_forget_all();
+        std::memcpy(a.w, a.src_qw, a.qw_bytes);
+        std::memcpy(a.sc, a.src_sc, a.sc_bytes);
+        std::memcpy(a.zp, a.src_zp, a.zp_bytes);
+        three_calls(a, a.expect, "first tensor again after forget_all,");
+        std::printf("sequence forget + rewrite: worst |err|/tol = %.3f\n", worst);
+        all_ok &= report("adapter sequences: two tensors in one buffer, forget between", ok);
+        // the same weights with scales A / B / A / B
+        ok = true, worst = 0;
+        auto *sc_b = managed_copy<float16_t>(scales_b, a.sc_bytes / 2);
+        for (int i = 0; i < 4; ++i) {
+            std::memset(out[0], 0xEE, (size_t)a.N * 2);
+            gemv_call(a, 1, x, out[0], i % 2 ? sc_b : a.sc);
+            sync_or_exit();
+            const double r = worst_ratio(out[0], i % 2 ? expect_b : a.expect, 1, a.N);
+            worst = std::fmax(worst, r);
+            ok &= r <= 1.0;
+        }
+        std::printf("sequence scales A / B / A / B: worst |err|/tol = %.3f\n", worst);
+        all_ok &= report("adapter sequences: the same weights with scales A / B / A / B", ok);
+        tce_adapter_forget(sc_b);
+        tce_free(sc_b);
+        a.release();
+        // tce_adapter_prepare, then one call
+        c.upload();
+        const long long held = tce_adapter_prepare(c.w, c.sc, c.zp, c.N, c.K, c.G);
+        std::memset(out[0], 0xEE, (size_t)c.N * 2);
+        gemv_call(c, 1, x, out[0]);
+        sync_or_exit();
+        const double r = worst_ratio(out[0], c.expect, 1, c.N);
+        std::printf("sequence prepare + call: %lld bytes held, worst |err|/tol = %.3f\n", held, r);
+        all_ok &= report("adapter sequences: tce_adapter_prepare followed by one call", r <= 1.0 && held > 0 && held == tce_adapter_device_bytes() && tce_adapter_cache_entries() == 2);
+        c.release();
+    }
+
+    // ---- AWQ: gemm_forward_cuda twice on one tensor, then forget, rewrite and call ----
+    {
+        const int M = b.get<int>(), N = b.get<int>(), K = b.get<int>(), G = b.get<int>();
+        const size_t qw_bytes = (size_t)K * (N / 8) * 4, sc_bytes = (size_t)(K / G) * N * 2;
+        const unsigned char *q1 = b.take(qw_bytes), *s1 = b.take(sc_bytes);
+        const float *e1 = reinterpret_cast<const float *>(b.take((size_t)M * N * 4));
+        const unsigned char *q2 = b.take(qw_bytes), *s2 = b.take(sc_bytes);
+        const float *e2 = reinterpret_cast<const float *>(b.take((size_t)M * N * 4));
+        auto *w = managed_copy<int32_t>(q1, qw_bytes / 4);
+        auto *sc = managed_copy<float16_t>(s1, sc_bytes / 2);
+        const float16_t *x = x_for(K);
+        struct matmul_params params;
+        poison(params);
+        params.A.row = M;
+        params.A.column = K;
+        params.A.half_data_ptr = const_cast<float16_t *>(x);
+        params.B.row = K;
+        params.B.column = N / 8;
+        params.B.int32_data_ptr = w;
+        params.C.row = M;
+        params.C.column = N;
+        params.C.half_data_ptr = outm;
+        params.half_scales = sc;
+        params.block_size = G;
+        matmul::MatmulOperator op = matmul::MatmulOperator();
+        bool ok = true;
+        double worst = 0;
+        for (int call = 0; call < 3; ++call) {
+            if (call == 2) {
+                tce_adapter_forget(w);
+                ok &= tce_adapter_cache_entries() == 0;
+                std::memcpy(w, q2, qw_bytes);
+                std::memcpy(sc, s2, sc_bytes);
+            }
+            std::memset(outm, 0xEE, (size_t)M * N * 2);
+            if (call == 1) op.gemm_forward_cuda_half(&params, 4);
+            else op.gemm_forward_cuda(&params, 8);
+            sync_or_exit();
+            const double r = worst_ratio(outm, call == 2 ? e2 : e1, M, N);
+            worst = std::fmax(worst, r);
+            ok &= r <= 1.0 && tce_adapter_cache_entries() == 1;
+        }
+        std::printf("sequence AWQ: M=%d N=%d K=%d G=%d worst |err|/tol = %.3f\n", M, N, K, G, worst);
+        all_ok &= report("adapter sequences: gemm_forward_cuda twice, forget, rewrite, call", ok);
+        tce_adapter_forget(w);
+        tce_free(w); tce_free(sc);
+    }
+
+    // ---- the end ----
+    const long faults = tce_adapter_gemm_faults();
+    tce_adapter_forget_all();
+    all_ok &= report("adapter sequences: GEMM scratch faults == 0 and no cache entry after forget_all", faults == 0 && tce_adapter_cache_entries() == 0 && tce_adapter_device_bytes() == 0);
+    for (auto &o : out) tce_free(o);
+    tce_free(outm);
+    for (auto *p : x_of) tce_free(p);
+    return all_ok && b.pos == b.bytes.size() ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+    if (argc >= 3 && std::strcmp(argv[1], "--sequences") == 0) return run_sequences(argv[2]);
     if (argc < 2) {
-        std::printf("usage: %s <vectors.bin>\n", argv[0]);
+        std::printf("usage: %s <vectors.bin> | --sequences <sequences.bin>\n", argv[0]);
         return 2;
     }
     Blob b;
-    {
-        FILE *f = std::fopen(argv[1], "rb");
-        if (!f) return 2;
-        std::fseek(f, 0, SEEK_END);
-        const long n = std::ftell(f);
-        std::fseek(f, 0, SEEK_SET);
-        b.bytes.resize(n);
-        if (std::fread(b.bytes.data(), 1, n, f) != (size_t)n) return 2;
-        std::fclose(f);
-    }
+    if (!read_file(argv[1], b)) return 2;
     bool all_ok = true;
 
     // ---- case 1: Linear_half_int4::forward (linear.cu:5-40) ----

@@ -165,7 +165,9 @@ int zeros_are_8(const void *zeros, long long words, bool *final) {
 // A steady-state token calls gemv_forward_cuda 161-225 times with tensors the adapter has seen; everything it needs per call -- the packed copy, the zero-point
 // verdict, the scratch area -- is then a pure function of (qweight, scales, zeros, N, K, G).  Round 4 took g_mu two or three times per call for it; now one
 // acquire load of a direct-mapped table entry.  Entries are immutable once published; tce_adapter_forget* bump the generation, which un-publishes all of them
-// (they are rebuilt from the maps below on the next call).  Retired entries are kept until process exit: a few dozen bytes per weight tensor.
+// (they are rebuilt from the maps above on the next call).  An entry is only ever replaced when it is stale (or by a racing publication of another thread), and a
+// replaced entry is retired, not freed -- a reader may still hold it: 72 bytes per weight tensor per generation, i.e. per tce_adapter_forget* or re-pack, never per
+// token.  A tensor whose two probes both hold live entries of other tensors is not published and stays on the slow path (front_publish).
 struct FrontEntry {
     const void *qweight, *scales, *zeros;
     int N, K, G;
@@ -194,16 +196,24 @@ inline const FrontEntry *front_find(const tce_w4a16_desc &d) {
     return nullptr;
 }
 void front_publish(const tce_w4a16_desc &d, uint64_t gen) {
-    auto *e = new FrontEntry{d.qweight, d.scales, d.zeros, d.N, d.K, d.group_size, d.prepacked, d.scratch, d.flags, gen};
+    // `gen` was loaded before the call was resolved: a forget, or this call's own re-pack, since then makes the entry stale on arrival -- publish nothing, allocate
+    // nothing; the next call publishes
+    if (g_generation.load(std::memory_order_acquire) != gen) return;
     const size_t s0 = front_slot(d.qweight);
-    size_t slot = s0;
-    for (size_t i = 0; i < 2; ++i) {  // an empty or stale probe, else the first (newest wins)
+    size_t slot = kFrontSize;
+    for (size_t i = 0; i < 2; ++i) {  // an empty or stale probe, else nothing: a live entry of another tensor is never evicted
         const FrontEntry *cur = g_front[(s0 + i) & (kFrontSize - 1)].load(std::memory_order_acquire);
         if (!cur || cur->generation != gen) {
-            slot = (s0 + i) & (kFrontSize - 1);
-            break;
+            if (slot == kFrontSize) slot = (s0 + i) & (kFrontSize - 1);
+        } else if (cur->qweight == d.qweight && cur->scales == d.scales && cur->zeros == d.zeros && cur->N == d.N && cur->K == d.K && cur->G == d.group_size) {
+            return;  // another thread published this very call between our miss and now
         }
     }
+    // Both probes hold live entries of other tensors (three or more weight addresses on one window): this tensor stays on the slow path -- the mutex and two map
+    // lookups per call, no allocation.  Evicting instead ("newest wins") made the tensors of such a window evict each other on every token: two slow paths AND two
+    // retired entries per token, for the life of the process.
+    if (slot == kFrontSize) return;
+    auto *e = new FrontEntry{d.qweight, d.scales, d.zeros, d.N, d.K, d.group_size, d.prepacked, d.scratch, d.flags, gen};
     FrontEntry *old = g_front[slot].exchange(e, std::memory_order_acq_rel);
     if (old) {
         std::lock_guard<std::mutex> lk(g_mu);
@@ -375,6 +385,7 @@ void MatmulOperator::mat_mul_accelerator_int4_fast_no_offset(const struct matmul
 // Drops what the adapter remembers about a buffer (any tensor whose data starts at ptr): call it before freeing or
 // rewriting model memory.  tce_adapter_forget_all() drops everything (e.g. on model reload).
 extern "C" void tce_adapter_forget(const void *ptr) {
+    if (!ptr) return;  // names no buffer (and would match the null side-tensor fields of every AWQ entry below)
     std::lock_guard<std::mutex> lk(g_mu);
     g_generation.fetch_add(1, std::memory_order_acq_rel);  // every front-cache entry is stale from here on
     for (auto it = g_zero_state.begin(); it != g_zero_state.end();) it = it->first.ptr == ptr ? g_zero_state.erase(it) : std::next(it);

@@ -95,7 +95,7 @@ class MatmulOperator {
 #endif
 
 // Per-tensor caches of the adapter (zero-point-is-8 flags, AWQ re-layouts; see matmul_operator_hip.cc): forget one buffer
-// (call before freeing / rewriting it) or everything; number of live entries.
+// (call before freeing / rewriting it, from a host that has stopped calling the tensor; a null pointer names no buffer) or everything; number of live entries.
 extern "C" void tce_adapter_forget(const void *ptr);
 extern "C" void tce_adapter_forget_all(void);
 extern "C" long tce_adapter_cache_entries(void);
