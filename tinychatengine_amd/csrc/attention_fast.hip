@@ -722,7 +722,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SINK ? 
 }  // namespace
 
 // chunk of keys per workgroup: heads x chunks should cover the chip a couple of times; a multiple of 16 (4 waves x 4 keys per step)
-static thread_local int g_attn_target_wgs = 0;  // 0: the fitted rule below; tuning: tce_w4a16_set_debug_mode(3000 + workgroups)
+static thread_local int g_attn_target_wgs = 0;  // 0: the fitted rule below; tuning: tce_w4a16_set_debug_mode(3000 + workgroups) -- five rows of tuning_modes.hpp: other families' modes lie inside 3000 .. 11192; every count: tce_attention_set_tuning
 void set_attention_fast_target(int wgs) { g_attn_target_wgs = wgs >= 32 && wgs <= 8192 ? wgs : 0; }
 
 // Measured (scripts/attention_step_sweep.py, profiles/r2/attention_step_sweep.jsonl; 32 heads, caches rotating through > 256 MB so the

@@ -1,5 +1,5 @@
 // tce_capi.hip -- the C ABI of libtce_hip.so (include/tce_matmul.h): argument checking, dispatch, hipGraph plans.
-// No kernel lives here.  Nothing in this library falls back to a CPU path: if a kernel cannot run, the entry point
+// (include/tce_tuning.h is tce_tuning.hip; the settings it writes are read here as g_tuning.)  No kernel lives here.  Nothing in this library falls back to a CPU path: if a kernel cannot run, the entry point
 // returns a negative code and the caller fails loudly.
 #include <hip/hip_runtime.h>
 
@@ -12,13 +12,13 @@
 #include <vector>
 
 #include "tce_common.hpp"
+#include "tuning_state.hpp"
 #include "w4a16_kernels.hpp"
 #include "w4a16_mfma_layout.hpp"
 
 namespace tce {
 int launch_w8a8(const tce_w8a8_desc &d, hipStream_t stream, hipError_t *hip_err, void *scratch = nullptr, char *describe = nullptr, int describe_len = 0);
 size_t w8a8_scratch_bytes();
-void set_w8a8_xsplit(int xs);
 int sample_chunks(int vocab);
 size_t sample_workspace_bytes(int batch, int vocab);
 int launch_sample_f16(const tce_sample_call &c, const tce_logprob_out *lp, const tce_constraint *con, hipStream_t stream, hipError_t *hip_err,
@@ -40,17 +40,8 @@ int launch_lora_expand_add_f16(const float *t, const void *B, const float *scale
                                hipStream_t stream, hipError_t *hip_err);
 int launch_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C, int ldc,
                                     int rows, int N, int R, int n_adapters, hipStream_t stream, hipError_t *hip_err);
-}
-
-namespace {
 
 thread_local char g_err[512] = "";
-thread_local int g_gemv_rows = 0, g_gemv_wn = 0, g_gemv_wk = 0, g_gemv_depth = 0;
-thread_local int g_gemm_mt = 0, g_gemm_nt = 0;
-thread_local int g_debug_mode_capi = 0;
-void *g_dbg_buf_capi = nullptr;
-
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -58,6 +49,13 @@ int fail(int code, const char *fmt, ...) {
     va_end(ap);
     return code;
 }
+}
+
+using tce::fail;
+using tce::g_err;
+using tce::g_tuning;
+
+namespace {
 
 int hip_fail(hipError_t e, const char *what) {
     return fail(TCE_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -100,14 +98,13 @@ int64_t tce_w4a16_algorithmic_bytes(int M, int N, int K, int G) {
     return nk / 2 + 2 * nk / G + nk / (2 * (int64_t)G) + 2 * (int64_t)M * K + 2 * (int64_t)M * N;
 }
 
-thread_local int g_pk_mode = 0;  // 0 automatic, 1 / 2 / 3 forced form (taken whenever a packed copy is given), 9 off
 constexpr int kPkMinM = 129;  // below: the 64-row tiles / the small-batch kernel waste fewer rows (192 until round 4: from 129 rows on two 128-row tiles already beat the 64-row tiles on the wide linears -- 160 x 11008 x 4096: 42.4 -> 32.6 us -- and the cost models keep N = 4096 with the 64-row kernel)
 
 // the pre-packed 128-row GEMM takes the launch when a packed copy came with the descriptor and the batch is large enough
 static bool use_pk(const tce_w4a16_desc *d, bool want_gemm) {
-    if (!d->prepacked || g_pk_mode == 9 || !want_gemm || d->K % 128 != 0 || d->rmsnorm_gamma) return false;
-    if (g_pk_mode >= 1 && g_pk_mode <= 8) return true;
-    if (d->M < kPkMinM || g_gemm_mt != 0) return false;
+    if (!d->prepacked || g_tuning.pk_mode == 9 || !want_gemm || d->K % 128 != 0 || d->rmsnorm_gamma) return false;
+    if (g_tuning.pk_mode >= 1 && g_tuning.pk_mode <= 8) return true;
+    if (d->M < kPkMinM || g_tuning.gemm_mt != 0) return false;
     if (d->flags & TCE_W4_SILU_MUL_PAIRS) return true;  // the other GEMM kernels have no pair epilogue: the alternative is the GEMV kernel, M / 4 passes
     // both dispatchers' cost models, fitted to the same kind of sweep (the 64-row tiles win while the 128-row tiles are too few
     // to fill the chip: M = 512 at N = 4096); groups of 64 / 32: the pre-packed kernel needs no LDS re-deal, it takes them
@@ -122,302 +119,6 @@ static bool use_pk(const tce_w4a16_desc *d, bool want_gemm) {
 // RMSNorm prologue from 8k rows up, and is the body of the token kernel.
 constexpr long long kPersistentMinWeights = 1LL << 62;
 constexpr long long kFusedNormPersistentRows = 16384;  // fused RMSNorm prologue: rows from which the persistent kernel carries it
-thread_local int g_gemv_kernel = 0;  // 0 automatic, 1 workgroup-per-row-block kernel forced, 2 persistent stream kernel forced
-thread_local int g_skinny_enabled = 1;  // tuning: tce_w4a16_set_debug_mode(29) routes 3 <= M <= 16 to the GEMV / GEMM kernels again
-
-int tce_w4a16_set_gemv_config(int rows, int wn, int wk, int depth) {
-    if (rows == 0 && wn == 0 && wk == 0) {
-        g_gemv_rows = g_gemv_wn = g_gemv_wk = g_gemv_depth = 0;
-        g_gemv_kernel = 0;
-        tce::set_gemv_stream_config(0, 0, 0);
-        return TCE_OK;
-    }
-    if (wk == 0) {  // persistent stream kernel: rows per unit, waves per workgroup, units in flight
-        if ((rows % 10 != 0 && rows % 10 != 1 && rows % 10 != 2 && rows % 10 != 4) || rows < 0 || rows >= 90 || wn < 1 || wn > 16 || (depth != 0 && depth != 2 && depth != 3))
-            return fail(TCE_ERR_BAD_ARG, "stream GEMV config rows=%d waves=%d depth=%d is not available", rows, wn, depth);
-        tce::set_gemv_stream_config(rows, wn, depth);
-        g_gemv_kernel = 2;
-        return TCE_OK;
-    }
-    const int dd = depth ? depth : 2;
-    if (!tce::gemv_variant_exists(rows, wn, wk, dd))
-        return fail(TCE_ERR_BAD_ARG, "GEMV variant rows=%d wn=%d wk=%d depth=%d was not compiled", rows, wn, wk, dd);
-    g_gemv_rows = rows;
-    g_gemv_wn = wn;
-    g_gemv_wk = wk;
-    g_gemv_depth = dd;
-    g_gemv_kernel = 1;
-    return TCE_OK;
-}
-
-int tce_w4a16_set_gemv_i8(int mode, int rows) {
-    if (mode < 0 || mode > 1 || rows < 0 || rows > 2) return fail(TCE_ERR_BAD_ARG, "tce_w4a16_set_gemv_i8: mode %d rows %d", mode, rows);
-    tce::set_gemv_i8_mode(mode, rows);
-    return TCE_OK;
-}
-
-int tce_attention_set_tuning(int waves_per_workgroup, int workgroups, int heads_per_workgroup) {
-    const bool ok = (waves_per_workgroup == 0 || waves_per_workgroup == 4 || waves_per_workgroup == 8 || waves_per_workgroup == 16) &&
-                    (workgroups == 0 || (workgroups >= 32 && workgroups <= 8192)) &&
-                    (heads_per_workgroup == 0 || heads_per_workgroup == 1 || heads_per_workgroup == 2 || heads_per_workgroup == 4);
-    if (!ok) return fail(TCE_ERR_BAD_ARG, "tce_attention_set_tuning(%d, %d, %d)", waves_per_workgroup, workgroups, heads_per_workgroup);
-    tce::set_attention_fast_waves(waves_per_workgroup);
-    tce::set_attention_fast_target(workgroups);
-    tce::set_attention_fast_fuse(heads_per_workgroup);
-    return TCE_OK;
-}
-
-int tce_w8a8_set_tuning(int quartets_per_tile, int big_tiles, int deep_pipeline) {
-    const bool ok = (quartets_per_tile == 0 || quartets_per_tile == 1 || quartets_per_tile == 2 || quartets_per_tile == 4) &&
-                    ((big_tiles >= 0 && big_tiles <= 4) || big_tiles == 9) &&
-                    (deep_pipeline == 0 || deep_pipeline == 1 || deep_pipeline == 2 || deep_pipeline == 4 || deep_pipeline == 9);
-    if (!ok) return fail(TCE_ERR_BAD_ARG, "tce_w8a8_set_tuning(%d, %d, %d)", quartets_per_tile, big_tiles, deep_pipeline);
-    tce::set_w8a8_ksplit(quartets_per_tile);
-    tce::set_w8a8_big(big_tiles);
-    tce::set_w8a8_deep(deep_pipeline);
-    return TCE_OK;
-}
-
-static thread_local int g_plan_eager = 0;  // experiment (tce_w4a16_set_debug_mode(15001 / 15000)): stream-ordered plans issue their launches one by one instead of replaying the graph
-int tce_w4a16_set_debug_mode(int mode) {
-    if (mode >= 50000 && mode <= 50499) {  // overlapped plans: 50000 + 100 * graph branches (0 = 2) + ring slots per wave (0 = as many as fit, 2..4)
-        tce::set_gemv_ovl_config((mode - 50000) % 100, (mode - 50000) / 100);
-        return TCE_OK;
-    }
-    if (mode == 2930 || mode == 2931) {  // fast attention step, timing experiment: 2931 = partial states stored plainly, no combine, the output NOT written (2930: off)
-        tce::set_attention_fast_probe_no_combine(mode - 2930);
-        return TCE_OK;
-    }
-    if (mode >= 2920 && mode <= 2924) {  // fast attention step, grouped queries: query heads per workgroup (2920: the rule; 2921 / 2922 / 2924)
-        tce::set_attention_fast_fuse(mode - 2920);
-        return TCE_OK;
-    }
-    if (mode >= 2900 && mode <= 2916) {  // fast attention step: waves per workgroup (2900: by the chunk length, the default; 2904 / 2908 / 2916)
-        tce::set_attention_fast_waves(mode - 2900);
-        return TCE_OK;
-    }
-    // (round 6, ADVICE r5: the three GEMM mode families below sit INSIDE this range and were shadowed by it since they were added -- they are matched further down)
-    const bool pk_mode_in_attention_range = (mode >= 6950 && mode <= 6958) || (mode >= 6972 && mode <= 6974) || (mode >= 7700 && mode <= 7710 + 512) || mode == 6916 || mode == 6917;
-    if (mode >= 3000 && mode <= 3000 + 8192 && !pk_mode_in_attention_range) {  // fast attention step: workgroups the key range is cut for (3000: the fitted rule, the default)
-        tce::set_attention_fast_target(mode - 3000);
-        return TCE_OK;
-    }
-    if (mode >= 1000 && mode <= 1256) {  // small-batch kernel: largest M it takes
-        tce::set_skinny_max_m(mode - 1000);
-        return TCE_OK;
-    }
-    if (mode >= 2700 && mode <= 2899 && ((mode - 2700) % 100 == 0 || (mode - 2700) % 100 == 4 || (mode - 2700) % 100 == 8)) {  // prefill attention, block pairing forced: 27xx on, 28xx off; xx = 00 / 04 / 08 as 2950 / 2954 / 2958
-        tce::set_attention_prefill_waves((mode >= 2800 ? 200 : 100) + (mode % 100));
-        return TCE_OK;
-    }
-    if (mode == 2950 || mode == 2954 || mode == 2958 || mode == 2964 || mode == 2968) {  // prefill attention: 2950 automatic; 4 / 8 waves x 1 row tile; 2964 / 2968: x 2 row tiles
-        tce::set_attention_prefill_waves(mode - 2950);
-        return TCE_OK;
-    }
-    if ((mode >= 75 && mode <= 78) || mode == 176 || mode == 177) {  // W8A8, the 128-row tiles: 75 the rule, 76 / 77 forced with 128 / 64 columns, 176 / 177 the same with two quartets per tile, 78 off
-        tce::set_w8a8_big(mode == 78 ? 9 : (mode >= 176 ? mode - 173 : mode - 75));
-        return TCE_OK;
-    }
-    if (mode >= 7710 && mode <= 7710 + 512) {  // ... a stage with more than (mode - 7710) units per workgroup ends the prefix the kernel takes (7710: the default, 512)
-        tce::set_i8_token_max_units(mode - 7710);
-        return TCE_OK;
-    }
-    if (mode >= 7700 && mode <= 7703) {  // TCE_PLAN_TAGGED on packed copies (round 6): 7700 the int8-contraction token kernel where the list allows (default), 7701 never (round 2's kernel);
-                                         // 7702 / 7703: plans built from now on record per-stage wall-clock stamps in the debug buffer (tce_w4a16_set_debug_buffer) / stop
-        if (mode <= 7701) tce::set_i8_token_mode(mode - 7700);
-        else {
-#ifndef TCE_LAB
-            if (mode == 7702) return fail(TCE_ERR_BAD_ARG, "debug mode 7702 (per-stage stamps of the token kernel) needs the lab build (python -m tinychatengine_amd.build --lab, TCE_LIB_PATH)");
-#endif
-            tce::set_i8_token_stamps(mode == 7702 ? g_dbg_buf_capi : nullptr);
-        }
-        return TCE_OK;
-    }
-    if (mode == 7704 || mode == 7705) {  // the int8 decode kernel's time budget: plain launches from now on record wave 0's clock readings per workgroup in the debug buffer (7704) / stop (7705)
-#ifndef TCE_LAB
-        if (mode == 7704) return fail(TCE_ERR_BAD_ARG, "debug mode 7704 (stamps of the int8 decode kernel) needs the lab build (python -m tinychatengine_amd.build --lab, TCE_LIB_PATH)");
-#endif
-        tce::set_gemv_i8_stamps(mode == 7704 ? g_dbg_buf_capi : nullptr);
-        return TCE_OK;
-    }
-    if (mode >= 19000 && mode <= 19999) {  // W8A8, the whole tile in every wave (round 6): 19000 the rule, 19001 off, 19304 / 19404 / 19904 the 32 x 48 / 32 x 64 / 64 x 64 tile forced wherever the 64 x 64 kernel would run
-        tce::set_w8a8_kslice(mode - 19000);
-        return TCE_OK;
-    }
-    if (mode >= 190 && mode <= 192) {  // W8A8, 32 x 64 tiles (round 6): 190 the rule, 191 forced wherever the 64 x 64 kernel would run, 192 off
-        tce::set_w8a8_rows32(mode - 190);
-        return TCE_OK;
-    }
-    if (mode >= 180 && mode <= 188) {  // W8A8, a tile's k-steps cut across workgroups (needs tce_w8a8_desc_v2.scratch): 180 the rule, 181 off, 182 / 183 / 184 / 186 / 188 that many runs
-        tce::set_w8a8_xsplit(mode - 180);
-        return TCE_OK;
-    }
-    if (mode == 170 || mode == 171 || mode == 172 || mode == 174 || mode == 179) {  // W8A8, the 64 x 64 tile with 8 k-steps in flight: 170 the rule, 171 / 172 / 174 forced with 1 / 2 / 4 quartets, 179 off
-        tce::set_w8a8_deep(mode - 170);
-        return TCE_OK;
-    }
-    if (mode == 15000 || mode == 15001) {  // experiment: tce_plan_launch issues a stream-ordered plan's launches eagerly (15001) / replays its graph (15000)
-        g_plan_eager = mode - 15000;
-        return TCE_OK;
-    }
-    if (mode >= 70 && mode <= 74) {  // W8A8: wave quartets per tile (70 automatic; 73: automatic, without the decode-sized wave-per-column kernels)
-        tce::set_w8a8_ksplit(mode - 70);
-        return TCE_OK;
-    }
-    if (mode >= 640 && mode <= 644) {  // pre-packed GEMM, k range cut across workgroups: runs per cut tile forced (640: the cost model's choice)
-        g_pk_mode = 4;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_mode(4, 0);
-        tce::set_gemm_pk_split(mode - 640);
-        return TCE_OK;
-    }
-#ifndef TCE_LAB
-    // Round 6: the instantiations with parts of a loop switched off (600+a, 2600+a, 26000+a: outputs meaningless), the decode kernels' stream-only / timestamp /
-    // arithmetic-only forms (1, 2, 4) and the token kernel's stamps (7702) are compiled into libtce_hip_lab.so only (python -m tinychatengine_amd.build --lab;
-    // TCE_LIB_PATH selects it): the product library holds kernels the dispatcher can reach.
-    if ((mode > 2600 && mode <= 2664) || (mode > 600 && mode <= 664) || (mode > 26000 && mode <= 26256) || mode == 1 || mode == 2 || mode == 4 || mode == 7702)
-        return fail(TCE_ERR_BAD_ARG, "debug mode %d selects a diagnostic instantiation that only the lab build holds (python -m tinychatengine_amd.build --lab, TCE_LIB_PATH)", mode);
-#endif
-    if (mode >= 2600 && mode <= 2664) {  // the same switches on the 256-row form (round 5)
-        g_pk_mode = mode == 2600 ? 0 : 6;
-        tce::set_gemm_pk_mode(mode == 2600 ? 0 : 6, 0);
-        tce::set_gemm_pk_ablation(mode - 2600);
-        return TCE_OK;
-    }
-    if (mode >= 600 && mode <= 664) {  // pre-packed GEMM with parts of its loop switched off (timing experiments, one quartet)
-        g_pk_mode = mode == 600 ? 0 : 1;
-        tce::set_gemm_pk_mode(mode == 600 ? 0 : 1, 0);
-        tce::set_gemm_pk_ablation(mode - 600);
-        return TCE_OK;
-    }
-    if (mode == 2676) {  // (round 6) 128 x 128 tiles, two quartets alternating a run's k-blocks, every tile's k range handed off between two workgroups (form 16)
-        g_pk_mode = 8;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_split(0);
-        tce::set_gemm_pk_mode(16, 0);
-        return TCE_OK;
-    }
-    if (mode >= 51000 && mode <= 51016) {  // the mixed decode launch (tce_w4a16_forward_independent): waves per workgroup forced (51000: the rule)
-        tce::set_gemv_i8_mixed_waves(mode - 51000);
-        return TCE_OK;
-    }
-    if (mode == 6916 || mode == 6917) {  // form 16 offered to the dispatcher (6917, the default) or not (6916)
-        tce::set_gemm_pk_form16_auto(mode - 6916);
-        return TCE_OK;
-    }
-    if (mode == 2675) {  // the wide form on 128 x 512 tiles (two quartets side by side on one activation ring)
-        g_pk_mode = 8;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_split(0);
-        tce::set_gemm_pk_mode(15, 0);
-        return TCE_OK;
-    }
-    if (mode == 2673 || mode == 2674) {  // the wide form on 128 x 192 tiles (48 columns per wave): 2673 one quartet per tile, 2674 two quartets alternating its k-blocks
-        g_pk_mode = 8;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_split(0);
-        tce::set_gemm_pk_mode(mode - 2660, 0);
-        return TCE_OK;
-    }
-    if (mode >= 2670 && mode <= 2672) {  // pre-packed GEMM, the wide form (128 rows x 64 columns per wave): 2670 one quartet per 128 x 256 tile, 2671 two quartets alternating its k-blocks, 2672 every tile's k range cut across workgroups
-        g_pk_mode = 8;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_split(0);
-        tce::set_gemm_pk_mode(10 + mode - 2670, 0);
-        return TCE_OK;
-    }
-    if (mode >= 2682 && mode <= 2684) {  // the wide form with every tile's k range cut into 2 / 3 / 4 runs
-        g_pk_mode = 8;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_mode(12, 0);
-        tce::set_gemm_pk_split(mode - 2680);
-        return TCE_OK;
-    }
-    if (mode >= 6950 && mode <= 6958) {  // the hand-off's cut: run 0 shorter than run 1 by (mode - 6950) k-blocks (tuning)
-        tce::set_gemm_pk_handoff_delta(mode - 6950);
-        return TCE_OK;
-    }
-    if (mode == 696 || mode == 697 || mode == 698 || (mode >= 6972 && mode <= 6974)) {  // pre-packed GEMM: the two waves of a SIMD at different priorities
-        tce::set_gemm_pk_prio(mode == 698 ? -1 : mode >= 6970 ? mode - 6970 : mode - 696);  // 696 off, 697 on, 698 the launcher's rule (default);  // 6972: priority 3, 6973: priority 1, 6974: by slot parity instead of dispatch round
-        return TCE_OK;
-    }
-    if (mode == 694 || mode == 695) {  // pre-packed GEMM, k range cut in two: 695 = run 0 hands its tile to run 1 (the default), 694 = both runs meet at the counter (A/B)
-        tce::set_gemm_pk_handoff(mode - 694);
-        return TCE_OK;
-    }
-    if (mode == 692 || mode == 693) {  // pre-packed GEMM: 693 = the dispatcher may pick the wide forms, 692 = never
-        tce::set_gemm_pk_wide_auto(mode - 692);
-        return TCE_OK;
-    }
-    if (mode >= 26000 && mode <= 26256) {  // the wide form (one quartet) with parts of its loop switched off (timing experiments)
-        g_pk_mode = mode == 26000 ? 0 : 8;
-        tce::set_gemm_pk_mode(mode == 26000 ? 0 : 10, 0);
-        tce::set_gemm_pk_ablation(mode - 26000);
-        return TCE_OK;
-    }
-    if (mode == 2669) {  // pre-packed GEMM: 256 x 256 tiles, two quartets side by side (form 9)
-        g_pk_mode = 8;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_split(0);
-        tce::set_gemm_pk_mode(9, 0);
-        return TCE_OK;
-    }
-    if (mode >= 672 && mode <= 674) {  // pre-packed GEMM, 256-row wave tiles with every tile's k range cut into 2 / 3 / 4 runs
-        g_pk_mode = 7;
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_mode(7, 0);
-        tce::set_gemm_pk_split(mode - 670);
-        return TCE_OK;
-    }
-    if (mode == 690 || mode == 691) {  // pre-packed GEMM: 691 = the dispatcher may pick the 256-row forms (the default), 690 = never (A/B against the 128-row forms)
-        tce::set_gemm_pk256_auto(mode - 690);
-        return TCE_OK;
-    }
-    if (mode >= 60 && mode <= 69) {  // pre-packed GEMM: 60 automatic, 61 / 62 / 63 / 64 forced 128-row forms, 66 / 67 the 256-row wave tiles (whole tiles / k range cut), 68 the 256-row tile shared by two quartets, 69 off
-        g_pk_mode = mode - 60;
-        tce::set_gemm_pk_split(0);
-        tce::set_gemm_pk_ablation(0);
-        tce::set_gemm_pk_mode(g_pk_mode >= 1 && g_pk_mode <= 8 && g_pk_mode != 5 ? g_pk_mode : 0, 0);
-        return TCE_OK;
-    }
-    if (mode >= 50 && mode <= 52) {  // LDS-DMA GEMM: wave quartets per tile (50 automatic)
-        tce::set_gemm_dma_mode(mode - 50);
-        return TCE_OK;
-    }
-    if (mode == 40 || mode == 41 || mode == 42 || mode == 44 || mode == 48) {  // GEMM: XCD grid rows (40: automatic for the LDS-DMA kernel)
-        tce::set_gemm_xcd_rows(mode - 40);
-        tce::set_gemm_dma_xcd_rows(mode - 40);
-        return TCE_OK;
-    }
-    if (mode >= 80 && mode <= 87) {  // LayerNormQ + W8A8 group: 81 = the workgroup-per-8-rows form at every k; wide form: 83 no sums (wrong results), 84 no output rows, 85 phase times of workgroup 0 into the debug buffer, 86 the wide form from k = 256 on, 87 the 4-wave form's single row walked by one wave
-        tce::set_lnq_form(mode - 80);
-        return TCE_OK;
-    }
-    if (mode >= 20 && mode <= 30) {  // small-batch kernel tuning: 20 automatic, 21/22/24/28 = waves per tile, 30 = shared-x form, 29 = off
-        g_skinny_enabled = mode != 29;
-        tce::set_skinny_config(mode == 29 ? 0 : (mode == 30 ? 9 : mode - 20));
-        return TCE_OK;
-    }
-    if (mode >= 10 && mode <= 12) {  // row-block GEMV, M = 1: 10 the rule (x first when the grid is one generation), 11 x first always, 12 weights first always
-        tce::set_gemv_order(mode - 10);
-        return TCE_OK;
-    }
-    if (mode < 0 || mode > 4) return fail(TCE_ERR_BAD_ARG, "debug mode %d", mode);
-    tce::set_gemv_debug_mode(mode);
-    tce::set_gemv_stream_debug(mode, g_dbg_buf_capi);
-    tce::set_gemv_ovl_stamps(mode == 2 ? g_dbg_buf_capi : nullptr);
-    g_debug_mode_capi = mode;
-    return TCE_OK;
-}
-
-int tce_w4a16_set_debug_buffer(void *buf) {
-    tce::set_lnq_stamps(buf);
-    tce::set_gemv_debug_buffer(buf);
-    g_dbg_buf_capi = buf;
-    tce::set_gemv_stream_debug(g_debug_mode_capi, buf);
-    tce::set_gemv_ovl_stamps(g_debug_mode_capi == 2 ? buf : nullptr);
-    return TCE_OK;
-}
 
 int tce_reset_last_error(void) {
     int first = 0;
@@ -471,45 +172,6 @@ int tce_device_count(void) {
     return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 
-int tce_w4a16_gemv_variant(int idx, int *rows, int *wn, int *wk, int *depth) {
-    static const int table[][4] = {
-#define TCE_V(R, N_, K_, D_) {R, N_, K_, D_},
-        TCE_GEMV_VARIANTS(TCE_V)
-#undef TCE_V
-    };
-    const int n = (int)(sizeof(table) / sizeof(table[0]));
-    if (idx < 0 || idx >= n || !rows || !wn || !wk || !depth) return TCE_ERR_BAD_ARG;
-    *rows = table[idx][0];
-    *wn = table[idx][1];
-    *wk = table[idx][2];
-    *depth = table[idx][3];
-    return TCE_OK;
-}
-
-int tce_w4a16_gemm_variant(int idx, int *mt, int *nt) {
-    static const int table[][2] = {
-#define TCE_V(M_, N_) {M_, N_}, {100 + M_, N_}, {200 + M_, N_},
-        TCE_GEMM_VARIANTS(TCE_V)
-#undef TCE_V
-    };
-    const int n = (int)(sizeof(table) / sizeof(table[0]));
-    if (idx < 0 || idx >= n || !mt || !nt) return TCE_ERR_BAD_ARG;
-    *mt = table[idx][0];
-    *nt = table[idx][1];
-    return TCE_OK;
-}
-
-int tce_w4a16_set_gemm_config(int mt, int nt) {
-    if (mt == 0 && nt == 0) {
-        g_gemm_mt = g_gemm_nt = 0;
-        return TCE_OK;
-    }
-    if (!tce::gemm_variant_exists(mt >= 200 ? mt - 200 : mt, nt)) return fail(TCE_ERR_BAD_ARG, "GEMM variant %dx%d was not compiled", mt, nt);
-    g_gemm_mt = mt;
-    g_gemm_nt = nt;
-    return TCE_OK;
-}
-
 static int forward_group_norm(const tce_w4a16_desc *descs, int count, const float *gamma, float eps, void *stream) {
     if (!descs || count < 1 || count > TCE_MAX_GROUP) return fail(TCE_ERR_BAD_ARG, "group count %d not in 1..%d", count, TCE_MAX_GROUP);
     if (!gamma || reinterpret_cast<uintptr_t>(gamma) % 16 != 0) return fail(TCE_ERR_BAD_ARG, "gamma must be a 16-byte aligned fp32 [K] vector");
@@ -527,7 +189,7 @@ static int forward_group_norm(const tce_w4a16_desc *descs, int count, const floa
     // launches).  So the persistent kernel takes the fused form from ~16k rows up; the row-block kernel below that
     // (in-process A/B, scripts/fused_launch_ab.py, profiles/r2/fused_launch_ab.jsonl: norm + q/k/v 12288 rows 9.6 us row-block (4 rows,
     // 4 waves) vs 10.9 persistent; norm + gate/up 22016 rows 13.4 us persistent vs 15.8 row-block).
-    if (g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_supports(descs, count, /*with_norm=*/true)) {  // packed copies: the int8-contraction GEMV carries the prologue
+    if (g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && tce::gemv_i8_supports(descs, count, /*with_norm=*/true)) {  // packed copies: the int8-contraction GEMV carries the prologue
         const int rc = tce::launch_w4a16_gemv_i8(descs, count, static_cast<hipStream_t>(stream), &he, gamma, eps);
         if (rc == TCE_OK) return TCE_OK;
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemv (int8 contraction, rmsnorm prologue) launch");
@@ -535,14 +197,14 @@ static int forward_group_norm(const tce_w4a16_desc *descs, int count, const floa
     }
     long long rows = 0;
     for (int i = 0; i < count; ++i) rows += descs[i].N;
-    if (g_gemv_kernel == 2 || (g_gemv_kernel == 0 && rows >= kFusedNormPersistentRows)) {
+    if (g_tuning.gemv_kernel == 2 || (g_tuning.gemv_kernel == 0 && rows >= kFusedNormPersistentRows)) {
         const int rc = tce::launch_w4a16_gemv_stream(descs, count, static_cast<hipStream_t>(stream), &he, gamma, eps);
         if (rc == TCE_OK) return TCE_OK;
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 persistent gemv launch");
         if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 persistent gemv: unsupported configuration");
     }
-    const int rc = tce::launch_w4a16_gemv(descs, count, g_gemv_kernel == 1 ? g_gemv_rows : 0, g_gemv_kernel == 1 ? g_gemv_wn : 0,
-                                          g_gemv_kernel == 1 ? g_gemv_wk : 0, g_gemv_kernel == 1 ? g_gemv_depth : 0,
+    const int rc = tce::launch_w4a16_gemv(descs, count, g_tuning.gemv_kernel == 1 ? g_tuning.gemv_rows : 0, g_tuning.gemv_kernel == 1 ? g_tuning.gemv_wn : 0,
+                                          g_tuning.gemv_kernel == 1 ? g_tuning.gemv_wk : 0, g_tuning.gemv_kernel == 1 ? g_tuning.gemv_depth : 0,
                                           static_cast<hipStream_t>(stream), &he, gamma, eps);
     if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemv launch");
     if (rc != TCE_OK) return fail(rc, "w4a16 gemv (rmsnorm prologue): no kernel variant for this shape/config");
@@ -564,13 +226,13 @@ int tce_w4a16_forward_group(const tce_w4a16_desc *descs, int count, void *stream
     hipError_t he = hipSuccess;
     // decode batches on pre-packed copies: the int8-contraction GEMV (w4a16_gemv_i8.hip), one launch for the group (a forced geometry / a diagnostic mode of the
     // fp16 GEMV kernels keeps those kernels)
-    if (g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_supports(descs, count)) {
+    if (g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && tce::gemv_i8_supports(descs, count)) {
         const int rc = tce::launch_w4a16_gemv_i8(descs, count, static_cast<hipStream_t>(stream), &he);
         if (rc == TCE_OK) return TCE_OK;
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemv (int8 contraction) launch");
         if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 gemv (int8 contraction): unsupported configuration");
     }
-    if (g_skinny_enabled && descs[0].M >= 3) {  // small batches: one skinny launch per linear (they stream the weights once each)
+    if (g_tuning.skinny_enabled && descs[0].M >= 3) {  // small batches: one skinny launch per linear (they stream the weights once each)
         bool all = true;
         for (int i = 0; i < count; ++i) all = all && !(descs[i].flags & (TCE_W4_FORCE_GEMV | TCE_W4_FORCE_GEMM)) && tce::skinny_supports(descs[i]);
         if (all) {
@@ -588,7 +250,7 @@ int tce_w4a16_forward_group(const tce_w4a16_desc *descs, int count, void *stream
     // (the 128k-row lm_head: 47 vs 50.5 us) and loses 5-10 % on per-layer shapes, where a launch is 2-3 waves of work.
     long long weights = 0;
     for (int i = 0; i < count; ++i) weights += (long long)descs[i].N * descs[i].K;
-    const bool use_stream = g_gemv_kernel == 2 || (g_gemv_kernel == 0 && descs[0].M == 1 && weights >= kPersistentMinWeights && g_debug_mode_capi == 0);
+    const bool use_stream = g_tuning.gemv_kernel == 2 || (g_tuning.gemv_kernel == 0 && descs[0].M == 1 && weights >= kPersistentMinWeights && g_tuning.debug_mode == 0);
     if (use_stream) {
         const int rc = tce::launch_w4a16_gemv_stream(descs, count, static_cast<hipStream_t>(stream), &he);
         if (rc == TCE_OK) return TCE_OK;
@@ -596,7 +258,7 @@ int tce_w4a16_forward_group(const tce_w4a16_desc *descs, int count, void *stream
         if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 persistent gemv: unsupported configuration");
         // M > 1 or an over-long K: the workgroup-per-row-block kernel takes it
     }
-    const int rc = tce::launch_w4a16_gemv(descs, count, g_gemv_rows, g_gemv_wn, g_gemv_wk, g_gemv_depth,
+    const int rc = tce::launch_w4a16_gemv(descs, count, g_tuning.gemv_rows, g_tuning.gemv_wn, g_tuning.gemv_wk, g_tuning.gemv_depth,
                                           static_cast<hipStream_t>(stream), &he);
     if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemv launch");
     if (rc != TCE_OK) return fail(rc, "w4a16 gemv: no kernel variant for this shape/config");
@@ -611,7 +273,7 @@ int tce_w4a16_forward_independent(const tce_w4a16_desc *descs, int count, int *l
         if (rc != TCE_OK) return rc;
     }
     // one launch: decode rows on packed copies (csrc/w4a16_gemv_i8.hip, the mixed launch).  A forced GEMV geometry / a diagnostic mode keeps the kernels it names
-    if (count > 1 && g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_mixed_supports(descs, count)) {
+    if (count > 1 && g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && tce::gemv_i8_mixed_supports(descs, count)) {
         hipError_t he = hipSuccess;
         const int rc = tce::launch_w4a16_gemv_i8_mixed(descs, count, static_cast<hipStream_t>(stream), &he);
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemv (int8 contraction, mixed) launch");
@@ -635,7 +297,7 @@ int tce_w4a16_describe_independent(const tce_w4a16_desc *descs, int count, char 
         const int rc = check_w4a16(&descs[i]);
         if (rc != TCE_OK) return rc;
     }
-    if (count > 1 && g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_mixed_supports(descs, count)) {
+    if (count > 1 && g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && tce::gemv_i8_mixed_supports(descs, count)) {
         int waves = 0, wgs = 0;
         tce::gemv_i8_mixed_geometry(descs, count, &waves, &wgs);
         std::snprintf(buf, (size_t)buf_len, "gemv-i8-mixed waves=%d workgroups=%d", waves, wgs);
@@ -686,29 +348,29 @@ int tce_w4a16_forward(const tce_w4a16_desc *d, void *stream) {
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemm (pre-packed) launch");
         if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 gemm (pre-packed): unsupported configuration");
     }
-    if (g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_supports(d, 1)) return tce_w4a16_forward_group(d, 1, stream);  // M <= 4 on a packed copy
+    if (g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && tce::gemv_i8_supports(d, 1)) return tce_w4a16_forward_group(d, 1, stream);  // M <= 4 on a packed copy
     // small batches: weights streamed once, all M <= 16 rows on one MFMA tile (w4a16_skinny.hip)
-    if (g_skinny_enabled && !(d->flags & (TCE_W4_FORCE_GEMV | TCE_W4_FORCE_GEMM)) && tce::skinny_supports(*d)) {
+    if (g_tuning.skinny_enabled && !(d->flags & (TCE_W4_FORCE_GEMV | TCE_W4_FORCE_GEMM)) && tce::skinny_supports(*d)) {
         const int rc = tce::launch_w4a16_skinny(*d, static_cast<hipStream_t>(stream), &he);
         if (rc == TCE_OK) return TCE_OK;
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 skinny launch");
         if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 skinny: unsupported configuration");
     }
     if (d->rmsnorm_gamma && d->M != 1) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "the fused RMSNorm prologue is a decode (M = 1) path; use tce_rmsnorm_half for M = %d", d->M);
-    if (want_gemm && d->K % 128 == 0 && d->group_size != 128 && d->M > 16 && g_gemm_mt == 0) {  // groups of 64 / 32: LDS-DMA GEMM only
+    if (want_gemm && d->K % 128 == 0 && d->group_size != 128 && d->M > 16 && g_tuning.gemm_mt == 0) {  // groups of 64 / 32: LDS-DMA GEMM only
         const int rc = tce::launch_w4a16_gemm_dma(*d, 0, 0, static_cast<hipStream_t>(stream), &he);
         if (rc == TCE_OK) return TCE_OK;
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemm (dma) launch");
         if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 gemm (dma): no kernel variant for this config");
     }
     if (want_gemm && d->K % 128 == 0 && d->group_size == 128) {  // other group sizes without a GEMM form: GEMV kernel, 4 rows per pass
-        if (g_gemm_mt >= 200 || g_gemm_mt == 0) {  // the LDS-DMA kernel: the default (every M the GEMV / small-batch kernels leave), or forced by tile ids 200 + m_tiles  // the LDS-DMA kernel (w4a16_gemm_dma.hip): the default, or forced by tile ids 200 + m_tiles
-            const int rc = tce::launch_w4a16_gemm_dma(*d, g_gemm_mt ? g_gemm_mt - 200 : 0, g_gemm_mt ? g_gemm_nt : 0, static_cast<hipStream_t>(stream), &he);
+        if (g_tuning.gemm_mt >= 200 || g_tuning.gemm_mt == 0) {  // the LDS-DMA kernel: the default (every M the GEMV / small-batch kernels leave), or forced by tile ids 200 + m_tiles  // the LDS-DMA kernel (w4a16_gemm_dma.hip): the default, or forced by tile ids 200 + m_tiles
+            const int rc = tce::launch_w4a16_gemm_dma(*d, g_tuning.gemm_mt ? g_tuning.gemm_mt - 200 : 0, g_tuning.gemm_mt ? g_tuning.gemm_nt : 0, static_cast<hipStream_t>(stream), &he);
             if (rc == TCE_OK) return TCE_OK;
             if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemm (dma) launch");
             if (rc != TCE_ERR_UNSUPPORTED_SHAPE) return fail(rc, "w4a16 gemm (dma): no kernel variant for this config");
         }
-        const int rc = tce::launch_w4a16_gemm(*d, g_gemm_mt >= 200 ? g_gemm_mt - 200 : g_gemm_mt, g_gemm_nt, static_cast<hipStream_t>(stream), &he);
+        const int rc = tce::launch_w4a16_gemm(*d, g_tuning.gemm_mt >= 200 ? g_tuning.gemm_mt - 200 : g_tuning.gemm_mt, g_tuning.gemm_nt, static_cast<hipStream_t>(stream), &he);
         if (rc == TCE_ERR_HIP) return hip_fail(he, "w4a16 gemm launch");
         if (rc != TCE_OK) return fail(rc, "w4a16 gemm: no kernel variant for this shape/config");
         return TCE_OK;
@@ -743,30 +405,30 @@ int tce_w4a16_describe_dispatch(const tce_w4a16_desc *d, char *buf, int buf_len)
         else std::snprintf(buf, (size_t)buf_len, "gemm-pk tile=128x%d quartets=%d group=%d", form == 3 ? 256 : 128, form == 1 ? 1 : 2, d->group_size);
         return TCE_OK;
     }
-    if (g_gemv_kernel == 0 && g_debug_mode_capi == 0 && tce::gemv_i8_supports(d, 1)) {
+    if (g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && tce::gemv_i8_supports(d, 1)) {
         if (d->reserved2 > 0)  // a member of a group copy: launched with its neighbours (in order) the group is ONE linear on the shared copy
             std::snprintf(buf, (size_t)buf_len, "gemv-i8 rows-per-pass=%d group=%d group-copy first-tile=%d rows=%d", tce::gemv_i8_rows_per_pass(d->M, d->K, d->group_size), d->group_size, d->reserved, d->reserved2);
         else
         std::snprintf(buf, (size_t)buf_len, "gemv-i8 rows-per-pass=%d group=%d", tce::gemv_i8_rows_per_pass(d->M, d->K, d->group_size), d->group_size);
         return TCE_OK;
     }
-    if (g_skinny_enabled && !(d->flags & (TCE_W4_FORCE_GEMV | TCE_W4_FORCE_GEMM)) && tce::skinny_supports(*d)) {
+    if (g_tuning.skinny_enabled && !(d->flags & (TCE_W4_FORCE_GEMV | TCE_W4_FORCE_GEMM)) && tce::skinny_supports(*d)) {
         std::snprintf(buf, (size_t)buf_len, "small-batch slices=%d", (d->M + 15) / 16);
         return TCE_OK;
     }
-    if (want_gemm && d->K % 128 == 0 && (d->group_size == 128 || (d->M > 16 && g_gemm_mt == 0))) {
-        if (g_gemm_mt == 0 || g_gemm_mt >= 200) {
-            int mt = g_gemm_mt ? g_gemm_mt - 200 : 0, nt = g_gemm_nt, ks = 0;
+    if (want_gemm && d->K % 128 == 0 && (d->group_size == 128 || (d->M > 16 && g_tuning.gemm_mt == 0))) {
+        if (g_tuning.gemm_mt == 0 || g_tuning.gemm_mt >= 200) {
+            int mt = g_tuning.gemm_mt ? g_tuning.gemm_mt - 200 : 0, nt = g_tuning.gemm_nt, ks = 0;
             if (mt == 0) tce::gemm_dma_describe(d->M, d->N, d->group_size == 128, &mt, &nt, &ks);
             std::snprintf(buf, (size_t)buf_len, "gemm-dma tile=%dx%d quartets=%d group=%d", mt * 16, nt * 64, ks, d->group_size);
         } else {
-            std::snprintf(buf, (size_t)buf_len, "gemm tile=%dx%d", (g_gemm_mt % 100) * 16, g_gemm_nt * 64);
+            std::snprintf(buf, (size_t)buf_len, "gemm tile=%dx%d", (g_tuning.gemm_mt % 100) * 16, g_tuning.gemm_nt * 64);
         }
         return TCE_OK;
     }
     // which GEMV kernel: same rule as tce_w4a16_forward_group (one linear per launch here)
-    const bool persistent = g_gemv_kernel == 2 || (d->rmsnorm_gamma ? (g_gemv_kernel == 0 && d->N >= kFusedNormPersistentRows)
-                                                                     : (g_gemv_kernel == 0 && d->M == 1 && (long long)d->N * d->K >= kPersistentMinWeights && g_debug_mode_capi == 0));
+    const bool persistent = g_tuning.gemv_kernel == 2 || (d->rmsnorm_gamma ? (g_tuning.gemv_kernel == 0 && d->N >= kFusedNormPersistentRows)
+                                                                            : (g_tuning.gemv_kernel == 0 && d->M == 1 && (long long)d->N * d->K >= kPersistentMinWeights && g_tuning.debug_mode == 0));
     // (a launch the persistent kernel refuses -- M > 1, an over-long K -- goes to the row-block kernel: tce_w4a16_forward_group)
     std::snprintf(buf, (size_t)buf_len, "gemv passes=%d kernel=%s", (d->M + 3) / 4, persistent && tce::gemv_stream_supports(d, 1) ? "persistent" : "row-block");
     return TCE_OK;
@@ -1128,7 +790,7 @@ int tce_w4a16_forward_independent_gather(const tce_w4a16_desc *descs, int count,
     if (n_total > 0x7FFFFFFF) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_w4a16_forward_independent_gather: vector too long");
     // (ONE wave finishes the exchange inside the launch: vectors of up to 16384 halves -- a hidden state or an FFN row; longer ones, the logits, keep the gather kernel's
     //  1024 threads)
-    if (g_gemv_kernel == 0 && g_debug_mode_capi == 0 && n_total <= 16384 && tce::gemv_i8_mixed_supports(descs, count) && !(dg.flags & TCE_W4_SILU_MUL_PAIRS)) {
+    if (g_tuning.gemv_kernel == 0 && g_tuning.debug_mode == 0 && n_total <= 16384 && tce::gemv_i8_mixed_supports(descs, count) && !(dg.flags & TCE_W4_SILU_MUL_PAIRS)) {
         tce::PeerGatherEpi g{};
         const int rcg = tce::comm_peer_gather_epi(c, slot, dst_full, (int)n_total, &g);
         if (rcg == TCE_ERR_BAD_ARG) return fail(rcg, "tce_w4a16_forward_independent_gather: slot out of range or group not connected");
@@ -2238,7 +1900,7 @@ int tce_plan_create_ex(const tce_w4a16_desc *descs, const int32_t *group_sizes, 
 
     // Chained form: only if every launch is a valid GEMV group the persistent kernel takes (same checks as the
     // unchained entry points), and there is something to overlap.
-    bool chained = (flags & (TCE_PLAN_CHAINED | TCE_PLAN_TAGGED | TCE_PLAN_OVERLAPPED)) && n_launches > 1 && (g_gemv_kernel != 1 || (flags & TCE_PLAN_OVERLAPPED));
+    bool chained = (flags & (TCE_PLAN_CHAINED | TCE_PLAN_TAGGED | TCE_PLAN_OVERLAPPED)) && n_launches > 1 && (g_tuning.gemv_kernel != 1 || (flags & TCE_PLAN_OVERLAPPED));
     for (int i = 0, off = 0; i < n_launches && chained; off += p->groups[i], ++i)
         for (int j = 0; j < p->groups[i] && chained; ++j) {
             const tce_w4a16_desc &a = p->descs[off], &b = p->descs[off + j];
@@ -2268,7 +1930,7 @@ int tce_plan_create_ex(const tce_w4a16_desc *descs, const int32_t *group_sizes, 
         if (rc != TCE_OK) p->token = nullptr;  // a launch the token kernel does not take: stream-ordered plan
     }
 
-    if ((flags & TCE_PLAN_TUNED) && !p->token && !p->token_i8 && g_gemv_kernel == 0) (void)tune_plan_launches(p->descs, p->groups, p->tuned);
+    if ((flags & TCE_PLAN_TUNED) && !p->token && !p->token_i8 && g_tuning.gemv_kernel == 0) (void)tune_plan_launches(p->descs, p->groups, p->tuned);
     hipStream_t cap = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&cap, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -2365,7 +2027,7 @@ int tce_plan_status(tce_plan *plan) {
 
 int tce_plan_launch(tce_plan *plan, void *stream) {
     if (!plan || !plan->exec) return fail(TCE_ERR_BAD_ARG, "null plan");
-    if (g_plan_eager && !plan->token && !plan->token_i8) {
+    if (g_tuning.plan_eager && !plan->token && !plan->token_i8) {
         int rc = TCE_OK;
         const int n_launches = (int)plan->groups.size();
         for (int i = 0, off = 0; i < n_launches && rc == TCE_OK; off += plan->groups[i], ++i)

@@ -1070,7 +1070,7 @@ thread_local int g_pk_ks = 0;  // 0: choose per launch, 1 / 2: forced (tuning)
 thread_local int g_pk_xm = 0;
 thread_local int g_pk_abl = 0;  // timing experiments: parts of the loop switched off (one quartet, groups of 128 only)
 thread_local int g_pk_split_force = 0;  // tuning: the number of runs a cut tile's k range is divided into (0: the cost model's choice)
-thread_local int g_pk256_auto = 1;      // 0: the dispatcher never picks the 256-row forms by itself (A/B runs: tce_w4a16_set_debug_mode(650 / 651))
+thread_local int g_pk256_auto = 1;      // 0: the dispatcher never picks the 256-row forms by itself (A/B runs: tce_w4a16_set_debug_mode(690 / 691); 645 .. 664 are ablation modes -- the rows of tuning_modes.hpp)
 constexpr float kPk256wUsPerKBlock = 4.3f;  // eight waves of a 256 x 256 tile walking one k-block
 constexpr float kPk256x2UsPerPair = 3.45f;   // two quartets sharing a CU walking one 256-row k-block each
 thread_local int g_pk_handoff_delta = 2;   // k-blocks run 0 of a hand-off is shorter than run 1 (tce_w4a16_set_debug_mode(6950 + d))

@@ -1,6 +1,7 @@
 // w4a16_kernels.hpp -- host-visible declarations shared by the W4A16 translation units.
 #pragma once
 #include "tce_common.hpp"
+#include "tuning_setters.hpp"  // the set_* tuning setters of the units below
 
 namespace tce {
 
@@ -47,15 +48,6 @@ struct GemvArgs {
     X(1, 2, 4, 1)
 
 bool gemv_variant_exists(int rows, int wn, int wk, int depth);
-void set_gemv_debug_mode(int mode);
-void set_gemv_order(int force);
-void set_w8a8_deep(int d);          // W8A8 64 x 64 tile with 8 k-steps in flight: 0 the rule, 1 / 2 / 4 quartets forced, 9 off
-void set_w8a8_rows32(int r);        // W8A8 32 x 64 tiles (round 6): 0 the rule, 1 forced, 2 off
-void set_w8a8_kslice(int code);    // W8A8, the whole tile in every wave (round 6): 0 the rule, 1 off, else a forced form (w8a8_gemm.hip)
-void set_w8a8_big(int b);           // W8A8 128-row tiles: 0 the rule, 1 / 2 forced (128 / 64 columns), 9 off
-void set_lnq_stamps(void *p);
-void set_lnq_form(int f);           // 1: the workgroup-per-8-rows form of the LayerNormQ + W8A8 launch at every k
-void set_gemv_debug_buffer(void *p);
 
 // persistent form, w4a16_gemv_stream.hip
 // One GEMV launch (up to TCE_MAX_GROUP linears sharing the activation) as the persistent kernels read it.
@@ -73,8 +65,6 @@ struct StreamLaunch {
     const unsigned *A_tag;
     unsigned *C_tag[TCE_MAX_GROUP];
 };
-void set_gemv_stream_config(int rows, int nw, int depth);
-void set_gemv_stream_debug(int mode, void *buf);
 bool gemv_stream_supports(const tce_w4a16_desc *descs, int count);
 int launch_w4a16_gemv_stream(const tce_w4a16_desc *descs, int count, hipStream_t stream, hipError_t *hip_err,
                              const float *gamma = nullptr, float eps = 0.f);
@@ -93,8 +83,6 @@ struct OvlGeom {
 int ovl_chains();
 int ovl_geometry(const tce_w4a16_desc *descs, int count, int cus, int chains, OvlGeom *g, hipError_t *hip_err);
 hipError_t ovl_enqueue(const StreamLaunch *L, const OvlGeom &g, const unsigned *epoch, unsigned *status, int launch_index, hipStream_t stream);
-void set_gemv_ovl_config(int depth, int chains);
-void set_gemv_ovl_stamps(void *buf);
 int token_plan_enqueue(TokenPlan *tp, hipStream_t stream, hipError_t *hip_err);
 int token_plan_status(TokenPlan *tp, unsigned *status, hipError_t *hip_err);
 void token_plan_geometry(const TokenPlan *tp, int *rows, int *depth, int *waves, int *blocks);
@@ -106,7 +94,6 @@ int launch_w4a16_gemv(const tce_w4a16_desc *descs, int count, int forced_rows, i
 bool gemv_i8_supports(const tce_w4a16_desc *descs, int count, bool with_norm = false);
 int gemv_i8_group_copy_members(const tce_w4a16_desc *descs, int count);  // > 0: the group is launched as ONE linear on its shared copy
 int gemv_i8_rows_per_pass(int M, int K, int group_size);
-void set_gemv_i8_mode(int mode, int rows);  // mode 0 automatic (taken wherever a packed copy comes with the descriptors), 1 off; rows 0 the rule, 1 / 2 tiles per wave
 struct I8ResidualNorm {  // tce_w4a16_forward_residual_rmsnorm: the RMSNorm that follows the residual add, produced by the same launch
     const float *gamma;
     float eps;
@@ -121,7 +108,6 @@ int launch_w4a16_gemv_i8(const tce_w4a16_desc *descs, int count, hipStream_t str
 struct PeerGatherEpi;  // (below, with the communicator)
 bool gemv_i8_mixed_supports(const tce_w4a16_desc *descs, int count);
 void gemv_i8_mixed_geometry(const tce_w4a16_desc *descs, int count, int *waves, int *workgroups);
-void set_gemv_i8_mixed_waves(int w);  // tuning: 0 the rule
 int launch_w4a16_gemv_i8_mixed(const tce_w4a16_desc *descs, int count, hipStream_t stream, hipError_t *hip_err, const PeerGatherEpi *gather = nullptr, int gathered = -1);
 // w4a16_gemv_i8_token.hip (round 6): a prefix of a launch list as ONE persistent kernel on the int8-contraction body, the data flow ordered by tagged output words
 struct I8TokenPlan;
@@ -131,10 +117,6 @@ int i8_token_plan_status(I8TokenPlan *tp, unsigned *status, hipError_t *hip_err)
 int i8_token_plan_stages(const I8TokenPlan *tp);
 int i8_token_plan_blocks(const I8TokenPlan *tp);
 void i8_token_plan_destroy(I8TokenPlan *tp);
-void set_gemv_i8_stamps(void *buf);  // non-null (lab build): the plain decode launches record [workgroup][8] clock readings there (csrc/w4a16_gemv_i8.hip I8Stamps; scripts/decode_head_timeline.py)
-void set_i8_token_stamps(void *buf);  // non-null: plans built from now on record [workgroup][stage][8] wall-clock stamps there (scripts/token_timeline.py)
-void set_i8_token_max_units(int u);   // a stage with more units (16-row tile x 1024-k chunk) per workgroup ends the prefix the kernel takes (default 512)
-void set_i8_token_mode(int mode);     // 0: tagged plans take this kernel where the list allows (default), 1: never (round 2's token kernel on the fp16 body)
 
 // MFMA GEMM on the q4_6 layout (prefill).  m_tiles x n_tiles 16x16 MFMA tiles per wave, 4 waves along N.
 #define TCE_GEMM_VARIANTS(X) \
@@ -146,12 +128,8 @@ void set_i8_token_mode(int mode);     // 0: tagged plans take this kernel where 
     X(4, 4)                  \
     X(2, 4)
 bool gemm_variant_exists(int m_tiles, int n_tiles);
-void set_gemm_xcd_rows(int xm);
-void set_gemm_dma_xcd_rows(int xm);
 float gemm_dma_estimate_us(int M, int N, int K);
 void gemm_dma_describe(int M, int N, bool g128, int *mt, int *nt, int *ks);  // the tile and form launch_w4a16_gemm_dma would pick  // the GEMM dispatcher's cost model (rounds x k-blocks x us per k-block)
-void set_gemm_dma_mode(int mode);
-void set_w8a8_ksplit(int ks);  // w8a8_gemm.hip tuning: wave quartets per tile (0 = automatic)  // timing experiments, see w4a16_gemm_dma.hip
 // w4a16_gemm_dma.hip: same contract as launch_w4a16_gemm with an explicit tile; TCE_ERR_UNSUPPORTED_SHAPE when the shape
 // (alignment, table size) does not fit, so the caller can fall back
 int launch_w4a16_gemm_dma(const tce_w4a16_desc &d, int m_tiles, int n_tiles, hipStream_t stream, hipError_t *hip_err);  // tuning: XCD grid of xm x (8 / xm) over (row blocks x column blocks)
@@ -164,17 +142,8 @@ int launch_w4a16_prepack(const tce_w4a16_desc &d, void *out, hipStream_t stream,
 size_t prepack_group_bytes(const tce_w4a16_desc *descs, int count);
 int launch_w4a16_prepack_group(const tce_w4a16_desc *descs, int count, void *out, hipStream_t stream, hipError_t *hip_err);
 int launch_w4a16_gemm_pk(const tce_w4a16_desc &d, const void *packed, hipStream_t stream, hipError_t *hip_err);
-void set_gemm_pk256_auto(int on);  // 0: the dispatcher never picks the 256-row forms by itself
-void set_gemm_pk_wide_auto(int on);
-void set_gemm_pk_form16_auto(int on);
-void set_gemm_pk_handoff_delta(int d);
-void set_gemm_pk_prio(int on);
-void set_gemm_pk_handoff(int on);    // 0: a two-run k cut exchanges through the last arriver (A/B), 1: run 0 hands its tile to run 1  // 1: the dispatcher may pick the wide forms (128 rows x 64 columns per wave)
 float gemm_pk_estimate_us(int M, int N, int K, int *form_out, bool has_scratch = false, int *split_out = nullptr, int group_size = 128, bool zero_point_8 = false);
 size_t gemm_pk_scratch_bytes();
-void set_gemm_pk_split(int s);
-void set_gemm_pk_mode(int ks, int xm);
-void set_gemm_pk_ablation(int abl);  // timing experiments (results meaningless): see w4a16_gemm_pk_kernel  // tuning: forced wave quartets per tile / XCD rows (0 = automatic)
 
 int check_zero_point_8(const void *zeros, long long n_words, hipError_t *hip_err);
 int check_zero_point_8_async(const void *zeros, long long n_words, int *verdict, hipStream_t stream, hipError_t *hip_err);  // one launch, no synchronisation: *verdict (host-mapped) = 1 / 2
@@ -187,8 +156,6 @@ int launch_awq_repack(int N, int K, int G, const void *qweight, const void *scal
 
 // small batches, 2 <= M <= 16 (w4a16_skinny.hip)
 bool skinny_supports(const tce_w4a16_desc &d);
-void set_skinny_config(int ks);
-void set_skinny_max_m(int m);  // largest M the small-batch kernel takes (16-row slices of the batch on gridDim.y)  // tuning: waves per 16-row tile, 0 = automatic
 int launch_w4a16_skinny(const tce_w4a16_desc &d, hipStream_t stream, hipError_t *hip_err);
 
 // element-wise glue of the decoder layer (glue.hip)
@@ -238,10 +205,6 @@ int launch_allgather_rccl(Comm *c, const void *src_slice, void *dst_full, size_t
 size_t allgather_rows_workspace_bytes(int M, int n_total);
 int launch_allgather_rows_f16(Comm *c, int slot, const void *src, void *dst, int M, int n_total, int ldd, void *workspace, hipStream_t stream, hipError_t *he);
 // attention_fast.hip
-void set_attention_fast_target(int wgs);
-void set_attention_fast_waves(int nw);
-void set_attention_fast_fuse(int r);
-void set_attention_fast_probe_no_combine(int on);  // timing experiment: partial states stored, no combine, `out` not written
 void describe_attention_decode_fast(int heads, int keys, int *chunk, int *chunks, int *waves, int kv_heads = 0);
 size_t attention_decode_workspace_bytes(int heads, int max_keys, int hd);
 // attention_prefill.hip: m > 1 new rows (rotation + append + causal / masked attention over pos + m keys), two launches
@@ -249,7 +212,6 @@ size_t attention_decode_workspace_bytes(int heads, int max_keys, int hd);
 int launch_opt_attention_decode(const void *q, const void *kn, const void *vn, void *kc, void *vtc, const float *mask, void *out, int heads, int hd, int m, int pos,
                                 int max_keys, int ld, float a_qk, float a_pv, hipStream_t stream, hipError_t *hip_err);
 size_t attention_prefill_workspace_bytes(int heads, int m, int hd);
-void set_attention_prefill_waves(int w);  // 0 automatic, 4 / 8 forced
 int launch_attention_prefill(const void *qkv, int ld_qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, int ld_mask, int causal,
                              void *out, int ld_out, void *workspace, int heads, int kv_heads, int max_keys, int pos, int m, float alpha, hipStream_t stream,
                              hipError_t *hip_err);
