@@ -423,7 +423,7 @@ TCE_API int tce_attention_decode_step_paged_rows_fp8(const void *qkv, void *k_po
  *               tce_attention_decode_step_paged_window_f16 / _fp8 with the same pos_bound and window; no other pool byte changes; rows_per_seq = 1 is that step;
  *               window >= pos_bound + 1 is the unwindowed multi-row step.  Refusals: window < 1 TCE_ERR_BAD_ARG, rows_per_seq outside 1 .. TCE_SPEC_MAX_ROWS
  *               TCE_ERR_UNSUPPORTED_SHAPE, everything else the two parents' rules.
- * NOT BUILT: windows on contiguous caches and on the single-sequence step; attention sinks on the multi-row step (below: the one-row step and the prefill have them); a
+ * NOT BUILT: windows on contiguous caches and on the single-sequence step (attention sinks, below, exist wherever windows do: step, multi-row step, prefill); a
  * ring table for unbounded streams -- positions stay bounded by table_stride * page_keys. */
 TCE_API int tce_attention_decode_describe_paged_window(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, char *buf, int buf_len);
 TCE_API int tce_attention_decode_step_paged_window_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
@@ -479,7 +479,35 @@ TCE_API int tce_kv_block_table_check_window(const int32_t *block_table, int tabl
  *               point's.  2. COMPACTION: with cos = sin = NULL, S a multiple of 4 and lo % 4 == 0 the step at a binding pos equals the unwindowed step at position
  *               S + W - 1 under pos_bound S + W + 2 on a pool that holds keys [0, S) ++ [lo, pos) -- both launches use the same cut.  Elsewhere: the float64 evaluation
  *               of the definition (two binary16 rotations of q) within the steps' stated bound.
- *   refusals    the *_window entry point's, in its order, then sinks < 1 || sinks > 16: TCE_ERR_BAD_ARG.  Before any HIP call.  The prefill is causal only. */
+ *   refusals    the *_window entry point's, in its order, then sinks < 1 || sinks > 16: TCE_ERR_BAD_ARG.  Before any HIP call.  The prefill is causal only.
+ *   rows        tce_attention_decode_step_paged_rows_sink_f16 / _fp8: the multi-row step with sinks (speculative decoding on a sink layer; csrc/attention_rows_sink.hip)
+ *               -- the arguments of tce_attention_decode_step_paged_rows_window_f16 / _fp8 with `int sinks` behind `window`.  Virtual row y = b * T + t sits at
+ *               pos = p + t and BINDS iff pos >= S + W, by itself: one call may hold rows that do not bind in front of rows that do.  A binding row weighs keys
+ *               0 .. S - 1, scored with q rotated by cos / sin row min(S + W - 1, pos_bound), and keys pos - W + 1 .. pos, scored with q rotated by row pos, under one
+ *               softmax; a row that does not bind is the unwindowed row.  Keys in [pos - t, pos] come from the call's own q/k/v rows, never from the pool (the
+ *               multi-row rule); each row appends only its own key / value row, rotated with its own position: no pool byte depends on window or sinks.
+ *               SHAPE RULE: window >= rows_per_seq.  With pos >= S + W it gives p >= S + 1 for every sequence that has a binding row, so no key the call itself
+ *               appends is a sink key and every in-call key lies inside its row's window (the corner the windowed rows step carries for W <= t does not exist here;
+ *               sinks beside a window of fewer than 8 keys are not a use case).  The cut and the chunk slots are the one-row sink step's
+ *               (tce_attention_decode_describe_paged_sink describes them; there is no further describe entry point), the grid the windowed rows step's, the
+ *               workspace the multi-row step's (one slice per virtual row).  Of table row b an active binding row turns only word 0 and words
+ *               lo_t / page_keys .. pos / page_keys into addresses, a row that does not bind words 0 .. pos / page_keys: a sequence's rows p .. p + n - 1 are
+ *               covered by tce_kv_block_table_check_sink for position p + n - 1 with window W + n - 1 and sinks S -- exactly their words when p >= S + W, else
+ *               words 0 .. (p + n - 1) / page_keys, a superset (nothing behind page 0 can have been released before position S + W).
+ *               CONTRACT (no tolerance): row (b, t)'s `out` and the pool rows one call appends are bit-identical to t + 1 successive calls of
+ *               tce_attention_decode_step_paged_sink_f16 / _fp8 with the same pos_bound, window and sinks; no other pool byte changes; rows_per_seq = 1 is that step;
+ *               sinks + window >= pos_bound + 1 is the unwindowed multi-row step, bit for bit.  Refusals, before any HIP call, BAD_ARG rules before
+ *               UNSUPPORTED_SHAPE rules as everywhere in the paged family: the *_rows_window entry point's TCE_ERR_BAD_ARG rules in its order, then sinks < 1 ||
+ *               sinks > 16: TCE_ERR_BAD_ARG; then the *_rows_window entry point's TCE_ERR_UNSUPPORTED_SHAPE rules in its order, then window < rows_per_seq:
+ *               TCE_ERR_UNSUPPORTED_SHAPE (the message names both arguments). */
+TCE_API int tce_attention_decode_step_paged_rows_sink_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys,
+                                                          int num_pages, const void *cos_table, const void *sin_table, void *out, void *workspace, int batch,
+                                                          int rows_per_seq, int heads, int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound,
+                                                          unsigned short alpha_half_bits, int window, int sinks, void *stream);
+TCE_API int tce_attention_decode_step_paged_rows_sink_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys,
+                                                          int num_pages, const void *cos_table, const void *sin_table, void *out, void *workspace, int batch,
+                                                          int rows_per_seq, int heads, int kv_heads, int head_dim, const int32_t *pos_device, int pos_bound,
+                                                          unsigned short alpha_half_bits, int k_scale_log2, int v_scale_log2, int window, int sinks, void *stream);
 TCE_API int tce_attention_decode_describe_paged_sink(int batch, int heads, int kv_heads, int pos_bound, int page_keys, int window, int sinks, char *buf, int buf_len);
 TCE_API int tce_attention_decode_step_paged_sink_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
                                                      const void *cos_table, const void *sin_table, void *out, void *workspace, int batch, int heads, int kv_heads,

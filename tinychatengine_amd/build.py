@@ -22,7 +22,7 @@ TESTKIT_LIB_PATH = os.path.join(LIB_DIR, "libtce_testkit.so")
 ADAPTER_TEST_PATH = os.path.join(LIB_DIR, "adapter_selftest")
 ADAPTER_BENCH_PATH = os.path.join(LIB_DIR, "adapter_bench")
 
-HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip"]
+HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-ffp-contract=off",  # the int8 epilogue and the fp16-accumulate entry point need every rounding
@@ -54,6 +54,8 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1E", "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb1ELb1E",
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb1ELb1ELb1E", "kv_pages_copy_fp8_kernel",
                                                                "attn_decode_fast_kernelILb0ELi4ELi1ELb1ELb1ELb0ELb0ELb1ELb1E"],
+                                        # (attention_rows_sink.hip: its two kernels, the multi-row sink step on fp16 and e4m3 pools -- the same double buffer)
+                                        "attention_rows_sink.hip": ["attn_decode_fast_kernel"],
                                         # (attention_prefill.hip: one paged kernel, guarded by name -- the plain fp16 forms too, which spill nothing either:
                                         #  profiles/attn_forms/kernel_resources_parent.txt)
                                         "attention_prefill.hip": ["attn_prefill_paged_kernel", "attn_prefill_prepare_kernelILb1ELb1E"],

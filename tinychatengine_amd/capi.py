@@ -32,7 +32,7 @@ TCE_OUT_INT8, TCE_OUT_FP32 = 0, 1
 
 # every symbol include/tce_matmul.h declares (tests/test_boundary.py checks the .so exports exactly these)
 EXPORTS = [
-    "tce_w4a16_forward", "tce_w4a16_residual_rmsnorm_workspace_bytes", "tce_w4a16_forward_residual_rmsnorm", "tce_w4a16_prepack_bytes", "tce_w4a16_prepack", "tce_w4a16_prepack_group_bytes", "tce_w4a16_prepack_group", "tce_w4a16_gemm_scratch_bytes", "tce_w4a16_gemm_scratch_faults", "tce_w4a16_describe_dispatch", "tce_w8a8_describe_dispatch", "tce_reset_last_error", "tce_bmm_f16t", "tce_rope_half", "tce_softmax_half", "tce_attention_decode_f16", "tce_attention_decode_workspace_bytes", "tce_attention_decode_describe", "tce_attention_decode_step_f16", "tce_attention_decode_step_gqa_f16", "tce_attention_decode_describe_gqa", "tce_attention_decode_step_pos_f16", "tce_attention_decode_batch_workspace_bytes", "tce_attention_decode_describe_batch", "tce_attention_decode_step_batch_f16", "tce_kv_pages_pool_bytes", "tce_attention_decode_describe_paged", "tce_attention_decode_step_paged_f16", "tce_kv_pages_scatter_f16", "tce_kv_pages_gather_f16", "tce_kv_block_table_check", "tce_attention_prefill_f16", "tce_attention_prefill_workspace_bytes", "tce_attention_prefill_paged_workspace_bytes", "tce_attention_prefill_paged_f16", "tce_attention_prefill_describe_paged", "tce_kv_pages_pool_bytes_fp8", "tce_attention_decode_step_paged_fp8", "tce_attention_prefill_paged_fp8", "tce_kv_pages_scatter_fp8", "tce_kv_pages_gather_fp8", "tce_sample_workspace_bytes", "tce_sample_f16", "tce_embed_rows_f16", "tce_attention_decode_step_paged_rows_f16", "tce_attention_decode_step_paged_rows_fp8", "tce_attention_decode_describe_paged_window", "tce_attention_decode_step_paged_window_f16", "tce_attention_decode_step_paged_window_fp8", "tce_attention_prefill_paged_window_f16", "tce_attention_prefill_paged_window_fp8", "tce_kv_block_table_check_window", "tce_attention_decode_describe_paged_sink", "tce_attention_decode_step_paged_sink_f16", "tce_attention_decode_step_paged_sink_fp8", "tce_attention_prefill_paged_sink_f16", "tce_attention_prefill_paged_sink_fp8", "tce_kv_block_table_check_sink", "tce_attention_decode_step_paged_rows_window_f16", "tce_attention_decode_step_paged_rows_window_fp8", "tce_sample_verify_workspace_bytes", "tce_sample_verify_f16", "tce_draft_ngram", "tce_logprobs_workspace_bytes", "tce_sample_logprobs_f16", "tce_sample_verify_logprobs_f16", "tce_sample_constrained_f16", "tce_sample_verify_constrained_f16", "tce_sample_stages_f16", "tce_sample_verify_stages_f16", "tce_sample_mirostat_f16", "tce_sample_verify_mirostat_workspace_bytes", "tce_sample_verify_mirostat_f16", "tce_logprobs_f16", "tce_lora_shrink_f16", "tce_lora_expand_add_f16", "tce_lora_expand_silu_mul_f16", "tce_opt_attention_decode", "tce_prefetch", "tce_add_half", "tce_silu_mul_half", "tce_rmsnorm_half", "tce_w4a16_forward_group_rmsnorm", "tce_w4a16_forward_group", "tce_w4a16_forward_independent", "tce_w4a16_describe_independent", "tce_w4a16_forward_independent_gather", "tce_w4a16_check_zero_point_8", "tce_w4a16_awq_fp16acc", "tce_w4a16_awq_workspace_bytes",
+    "tce_w4a16_forward", "tce_w4a16_residual_rmsnorm_workspace_bytes", "tce_w4a16_forward_residual_rmsnorm", "tce_w4a16_prepack_bytes", "tce_w4a16_prepack", "tce_w4a16_prepack_group_bytes", "tce_w4a16_prepack_group", "tce_w4a16_gemm_scratch_bytes", "tce_w4a16_gemm_scratch_faults", "tce_w4a16_describe_dispatch", "tce_w8a8_describe_dispatch", "tce_reset_last_error", "tce_bmm_f16t", "tce_rope_half", "tce_softmax_half", "tce_attention_decode_f16", "tce_attention_decode_workspace_bytes", "tce_attention_decode_describe", "tce_attention_decode_step_f16", "tce_attention_decode_step_gqa_f16", "tce_attention_decode_describe_gqa", "tce_attention_decode_step_pos_f16", "tce_attention_decode_batch_workspace_bytes", "tce_attention_decode_describe_batch", "tce_attention_decode_step_batch_f16", "tce_kv_pages_pool_bytes", "tce_attention_decode_describe_paged", "tce_attention_decode_step_paged_f16", "tce_kv_pages_scatter_f16", "tce_kv_pages_gather_f16", "tce_kv_block_table_check", "tce_attention_prefill_f16", "tce_attention_prefill_workspace_bytes", "tce_attention_prefill_paged_workspace_bytes", "tce_attention_prefill_paged_f16", "tce_attention_prefill_describe_paged", "tce_kv_pages_pool_bytes_fp8", "tce_attention_decode_step_paged_fp8", "tce_attention_prefill_paged_fp8", "tce_kv_pages_scatter_fp8", "tce_kv_pages_gather_fp8", "tce_sample_workspace_bytes", "tce_sample_f16", "tce_embed_rows_f16", "tce_attention_decode_step_paged_rows_f16", "tce_attention_decode_step_paged_rows_fp8", "tce_attention_decode_describe_paged_window", "tce_attention_decode_step_paged_window_f16", "tce_attention_decode_step_paged_window_fp8", "tce_attention_prefill_paged_window_f16", "tce_attention_prefill_paged_window_fp8", "tce_kv_block_table_check_window", "tce_attention_decode_describe_paged_sink", "tce_attention_decode_step_paged_sink_f16", "tce_attention_decode_step_paged_sink_fp8", "tce_attention_prefill_paged_sink_f16", "tce_attention_prefill_paged_sink_fp8", "tce_kv_block_table_check_sink", "tce_attention_decode_step_paged_rows_window_f16", "tce_attention_decode_step_paged_rows_window_fp8", "tce_attention_decode_step_paged_rows_sink_f16", "tce_attention_decode_step_paged_rows_sink_fp8", "tce_sample_verify_workspace_bytes", "tce_sample_verify_f16", "tce_draft_ngram", "tce_logprobs_workspace_bytes", "tce_sample_logprobs_f16", "tce_sample_verify_logprobs_f16", "tce_sample_constrained_f16", "tce_sample_verify_constrained_f16", "tce_sample_stages_f16", "tce_sample_verify_stages_f16", "tce_sample_mirostat_f16", "tce_sample_verify_mirostat_workspace_bytes", "tce_sample_verify_mirostat_f16", "tce_logprobs_f16", "tce_lora_shrink_f16", "tce_lora_expand_add_f16", "tce_lora_expand_silu_mul_f16", "tce_opt_attention_decode", "tce_prefetch", "tce_add_half", "tce_silu_mul_half", "tce_rmsnorm_half", "tce_w4a16_forward_group_rmsnorm", "tce_w4a16_forward_group", "tce_w4a16_forward_independent", "tce_w4a16_describe_independent", "tce_w4a16_forward_independent_gather", "tce_w4a16_check_zero_point_8", "tce_w4a16_awq_fp16acc", "tce_w4a16_awq_workspace_bytes",
     "tce_w4a16_gemm_awq", "tce_w4a16_shard", "tce_comm_create", "tce_comm_export", "tce_comm_connect", "tce_comm_connect_local", "tce_allgather_f16", "tce_comm_rccl_unique_id", "tce_comm_rccl_init", "tce_allgather_rows_workspace_bytes", "tce_allgather_rows_f16", "tce_comm_status", "tce_comm_set_timeout_ms", "tce_comm_reset", "tce_comm_device", "tce_comm_destroy", "tce_w8a8_matmul", "tce_opt_softmax_q", "tce_opt_kv_append", "tce_layernorm_q", "tce_layernorm_q_w8a8_group", "tce_plan_create", "tce_plan_create_ex", "tce_plan_is_chained", "tce_plan_geometry", "tce_plan_status", "tce_plan_launch_geometry", "tce_plan_launch", "tce_plan_n_launches",
     "tce_w4a16_forward_v2", "tce_w8a8_matmul_v2", "tce_w8a8_scratch_bytes", "tce_attention_decode_step_deferred_f16", "tce_w4a16_forward_deferred_attention", "tce_plan_destroy", "tce_version", "tce_last_error", "tce_build_info", "tce_w4a16_set_gemv_config", "tce_w4a16_set_gemv_i8",
     "tce_w4a16_set_gemm_config", "tce_w4a16_algorithmic_bytes", "tce_w4a16_gemv_variant", "tce_w4a16_gemm_variant",
@@ -364,6 +364,9 @@ def lib() -> C.CDLL:
         L.tce_kv_block_table_check_sink.argtypes = L.tce_kv_block_table_check_window.argtypes[:-1] + [C.c_int, C.c_void_p]
         L.tce_attention_decode_step_paged_rows_window_f16.argtypes = L.tce_attention_decode_step_paged_rows_f16.argtypes[:-1] + [C.c_int, C.c_void_p]
         L.tce_attention_decode_step_paged_rows_window_fp8.argtypes = L.tce_attention_decode_step_paged_rows_fp8.argtypes[:-1] + [C.c_int, C.c_void_p]
+        # sinks on the multi-row step: the windowed rows argument lists with `sinks` behind `window`
+        L.tce_attention_decode_step_paged_rows_sink_f16.argtypes = L.tce_attention_decode_step_paged_rows_window_f16.argtypes[:-1] + [C.c_int, C.c_void_p]
+        L.tce_attention_decode_step_paged_rows_sink_fp8.argtypes = L.tce_attention_decode_step_paged_rows_window_fp8.argtypes[:-1] + [C.c_int, C.c_void_p]
         L.tce_sample_verify_workspace_bytes.restype = C.c_size_t
         L.tce_sample_verify_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.tce_sample_verify_f16.argtypes = [C.POINTER(SampleVerifyCall), C.c_void_p]

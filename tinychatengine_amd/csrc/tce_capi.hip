@@ -1005,7 +1005,13 @@ static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs
     if (const int rc = check_pages(who, pg)) return rc;
     if (const int rc = check_row_keys(who, pg)) return rc;
     if (const int rc = check_window(who, window)) return rc;
-    if (const int rc = check_step(who, s, row_keys(pg), "table_stride * page_keys")) return rc;
+    // (the rows form with sinks tests its sinks rule HERE, among the BAD_ARG rules and behind the windowed rows form's: check_step's BAD_ARG rules all stand in front
+    //  of its UNSUPPORTED_SHAPE rules, so a step that fails with the latter has passed the former.  The one-row sink step keeps its order: sinks last, below)
+    const int rc_step = check_step(who, s, row_keys(pg), "table_stride * page_keys");
+    if (rc_step == TCE_ERR_BAD_ARG) return rc_step;
+    if (rows_per_seq)
+        if (const int rc = check_sinks(who, sinks)) return rc;
+    if (rc_step) return rc_step;
     s.window = window ? *window : 0;
     if (rows_per_seq && (*rows_per_seq < 1 || *rows_per_seq > TCE_SPEC_MAX_ROWS))
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: rows_per_seq %d (1 .. %d; tree drafts and longer chains are not built)", who, *rows_per_seq, TCE_SPEC_MAX_ROWS);
@@ -1015,8 +1021,12 @@ static int paged_step(const char *who, const tce::KvPages &pg, tce::AttnStepArgs
     if (const int rc = check_aligned(who, 4, {{"pos_device", s.pos_device}, {"block_table", pg.table}})) return rc;
     if (const int rc = check_sinks(who, sinks)) return rc;
     s.sinks = sinks ? *sinks : 0;
+    // sinks on the multi-row step: the one rule of the pair -- with window >= rows_per_seq no key the call appends is a sink key and every one lies inside its row's window
+    if (sinks && rows_per_seq && *window < *rows_per_seq)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: window %d < rows_per_seq %d (sinks beside a window shorter than the call's rows are not built)", who, *window, *rows_per_seq);
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_attention_decode_paged(pg, s, rows_per_seq ? *rows_per_seq : 0, static_cast<hipStream_t>(stream), &he);
+    const int rc = sinks && rows_per_seq ? tce::launch_attention_decode_paged_rows_sink(pg, s, *rows_per_seq, static_cast<hipStream_t>(stream), &he)
+                                         : tce::launch_attention_decode_paged(pg, s, rows_per_seq ? *rows_per_seq : 0, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "paged attention decode step launch") : rc;
 }
 
@@ -1091,6 +1101,21 @@ int tce_attention_decode_step_paged_rows_window_fp8(const void *qkv, void *k_poo
                                                     int window, void *stream) {
     return paged_step("tce_attention_decode_step_paged_rows_window_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
                       {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream, &window);
+}
+
+int tce_attention_decode_step_paged_rows_sink_f16(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                  const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads,
+                                                  int hd, const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int window, int sinks, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_rows_sink_f16", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, false, 0, 0},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream, &window, &sinks);
+}
+
+int tce_attention_decode_step_paged_rows_sink_fp8(const void *qkv, void *k_pool, void *v_pool, const int32_t *block_table, int table_stride, int page_keys, int num_pages,
+                                                  const void *cosv, const void *sinv, void *out, void *workspace, int batch, int rows_per_seq, int heads, int kv_heads,
+                                                  int hd, const int32_t *pos_device, int pos_bound, unsigned short alpha_bits, int k_scale_log2, int v_scale_log2,
+                                                  int window, int sinks, void *stream) {
+    return paged_step("tce_attention_decode_step_paged_rows_sink_fp8", {k_pool, v_pool, block_table, 0, table_stride, page_keys, num_pages, true, k_scale_log2, v_scale_log2},
+                      {qkv, cosv, sinv, out, workspace, batch, heads, kv_heads, hd, pos_device, pos_bound, alpha_bits}, &rows_per_seq, stream, &window, &sinks);
 }
 
 // rows [key0, key0 + nkeys) between a contiguous pair and the pages of one table row (pg.table: that row)

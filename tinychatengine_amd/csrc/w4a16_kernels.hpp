@@ -271,6 +271,9 @@ int launch_attention_decode_batch(const AttnStepArgs &step, void *kc, void *vc, 
 size_t kv_pages_pool_bytes(int num_pages, int kv_heads, int page_keys, int hd);
 size_t kv_pages_pool_bytes_fp8(int num_pages, int kv_heads, int page_keys, int hd);
 int launch_attention_decode_paged(const KvPages &pages, const AttnStepArgs &step, int rows_per_seq, hipStream_t stream, hipError_t *hip_err);
+// the multi-row step with attention sinks (step.window >= rows_per_seq >= 1, step.sinks 1 .. 16): a unit of its own, attention_rows_sink.hip -- the one-row sink
+// step's cut, the windowed rows step's grid, the multi-row step's workspace
+int launch_attention_decode_paged_rows_sink(const KvPages &pages, const AttnStepArgs &step, int rows_per_seq, hipStream_t stream, hipError_t *hip_err);
 int launch_kv_pages_copy(const KvPages &pages, const KvLinear &lin, bool gather, int key0, int nkeys, hipStream_t stream, hipError_t *hip_err);
 int launch_kv_block_table_check(const KvPages &pages, int batch, const int *pos_dev, int pos_bound, unsigned *violations, hipStream_t stream, hipError_t *hip_err,
                                 int window = 0, int sinks = 0);  // window >= 1: only the words a windowed row follows; sinks >= 1: a sink row

@@ -352,7 +352,7 @@ class PagedBatchDecodeAttention:
 
     def _step(self, entry: str, rows_per_seq: int | None, qkv: torch.Tensor, pos_device: torch.Tensor, pos_bound: int, out: torch.Tensor | None) -> torch.Tensor:
         """The step's assertions and call, `entry`_f16 or _fp8, for batch * rows_per_seq rows (None: one row per sequence, and an entry point without that argument).
-        With a window the caller's `entry` already carries the suffix (_entry): ..._paged_window, ..._paged_rows_window."""
+        With a window the caller's `entry` already carries the suffix (_entry): ..._paged_window, ..._paged_rows_window; with sinks ..._paged_sink, ..._paged_rows_sink."""
         n = self.batch * (rows_per_seq or 1)
         rw = (self.heads + 2 * self.kv_heads) * self.hd
         assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and qkv.numel() == n * rw

@@ -129,16 +129,32 @@ class SpecSlotBook(SlotBook):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the layers at B T rows
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def rows_check_calls(n_active, last_pos, rows_per_seq: int, window: int | None) -> list[tuple[int | None, list[int]]]:
+def _check_rows_window(who: str, allocator, rows_per_seq: int, window, sinks) -> None:
+    """The two rules a rows attention object has beside PagedBatchDecodeAttention's: sinks need window >= rows_per_seq (the C entry point's rule: no key a call appends
+    is then a sink key), and with a window -- with or without sinks -- every path is a device path, so the allocator's block table must be on the device."""
+    if sinks is not None and window is not None and int(window) < int(rows_per_seq):
+        raise ValueError(f"{who}: window {window} < rows_per_seq {rows_per_seq} beside attention sinks (sinks={sinks}): the multi-row sink step needs window >= rows_per_seq")
+    if window is not None and not allocator.table.is_cuda:
+        # (the unwindowed form may be built over a host table for bookkeeping tests; with a window every path of the class -- step, table_violations -- is a
+        # device path, and a host table would only fail later, inside a launch wrapper)
+        raise ValueError(f"{who}: a window{'' if sinks is None else ' beside attention sinks (sinks=' + str(sinks) + ')'} needs the allocator's block table on the device")
+
+
+def rows_check_calls(n_active, last_pos, rows_per_seq: int, window: int | None, sinks: int | None = None) -> list[tuple[int | None, list[int]]]:
     """The table checks that cover a rows step: per sequence n_active[b] rows at consecutive positions that end at last_pos[b] (n_active 0: inactive).  Returns
     [(window argument, position words [batch])]: one tce_kv_block_table_check call each (window None: the unwindowed check), -1 for the sequences a call leaves out.
     Unwindowed rows follow words 0 .. last // page_keys: the check at the last position.  Windowed rows p .. p + n - 1 follow the union of
     [max(0, p + t - W + 1) // page_keys, (p + t) // page_keys], t < n -- contiguous, from row 0's first word to row n - 1's last --, which is what
-    tce_kv_block_table_check_window follows for position p + n - 1 with window W + n - 1: one call per distinct n."""
+    tce_kv_block_table_check_window follows for position p + n - 1 with window W + n - 1: one call per distinct n.
+    sinks = S (beside a window): the same calls, each a tce_kv_block_table_check_sink with sinks S.  At position p + n - 1 with window W + n - 1 that check binds iff
+    p >= S + W -- iff row 0 binds, hence iff every row does -- and then follows word 0 and words (p - W + 1) // page_keys .. (p + n - 1) // page_keys: exactly the union
+    the rows follow.  Otherwise it follows words 0 .. (p + n - 1) // page_keys, a SUPERSET of the rows' words where the later rows bind -- sound, because nothing behind
+    page 0 can have been given back before position S + W (tests/test_sink_rows_host.py holds both against an enumeration)."""
     _check_rows(rows_per_seq)
     n_active, last_pos = [int(n) for n in n_active], [int(p) for p in last_pos]
     assert len(n_active) == len(last_pos) and all(0 <= n <= rows_per_seq for n in n_active)
     if window is None:
+        assert sinks is None, "sinks exist beside a window"
         return [(None, [p if n else -1 for n, p in zip(n_active, last_pos)])]
     return [(int(window) + n - 1, [p if m == n else -1 for m, p in zip(n_active, last_pos)]) for n in sorted(set(n_active) - {0})]
 
@@ -148,16 +164,12 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
     row; prefill and the copies are the parent's.  window=W: tce_attention_decode_step_paged_rows_window_f16 / _fp8 -- row t of a sequence at position p weighs keys
     max(0, p + t - W + 1) .. p + t, the call's own rows among them from the call itself.  Rejected drafts leave pool rows beyond the accepted position: the next
     call's rows start AT that position and take every key from there on from their own q/k/v rows, and each appends its own row, so a stale row is overwritten
-    before any row weighs it -- with a window as without."""
+    before any row weighs it -- with a window as without.  window=W, sinks=S (W >= rows_per_seq): tce_attention_decode_step_paged_rows_sink_f16 / _fp8 -- each row
+    binds or not by its own position p + t >= S + W; a binding row weighs keys 0 .. S - 1 beside its window."""
 
     def __init__(self, allocator, heads, kv_heads, device, cos=None, sin=None, rows_per_seq: int = 1, **kw):
         _check_rows(rows_per_seq)
-        if kw.get("sinks") is not None:
-            raise ValueError("PagedRowsDecodeAttention: attention sinks are not built on the multi-row step (sinks=None)")
-        if kw.get("window") is not None and not allocator.table.is_cuda:
-            # (the unwindowed form may be built over a host table for bookkeeping tests; with a window every path of this class -- step, table_violations -- is a
-            # device path, and a host table would only fail later, inside a launch wrapper)
-            raise ValueError("PagedRowsDecodeAttention: a window needs the allocator's block table on the device")
+        _check_rows_window("PagedRowsDecodeAttention", allocator, rows_per_seq, kw.get("window"), kw.get("sinks"))
         super().__init__(allocator, heads, kv_heads, device, cos, sin, **kw)
         self.rows_per_seq = int(rows_per_seq)
         need = int(capi.lib().tce_attention_decode_batch_workspace_bytes(self.batch * self.rows_per_seq, heads, self.max_keys, self.hd))
@@ -180,11 +192,11 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
         last = np.where(active, rp, -1).max(axis=1)
         tab, stride, pk, n = self._table_args()
         bad = 0
-        for w, words in rows_check_calls(active.sum(axis=1), last, self.rows_per_seq, self.window):
+        for w, words in rows_check_calls(active.sum(axis=1), last, self.rows_per_seq, self.window, self.sinks):
             pos = torch.tensor(words, dtype=torch.int32, device=pos_device.device)
-            fn = capi.lib().tce_kv_block_table_check if w is None else capi.lib().tce_kv_block_table_check_window
+            fn = getattr(capi.lib(), self._entry("tce_kv_block_table_check"))
             capi.check(fn(tab, stride, pk, n, self.batch, C.c_void_p(pos.data_ptr()), int(pos_bound), C.c_void_p(self._violations.data_ptr()),
-                          *(() if w is None else (w,)), C.c_void_p(_stream())))
+                          *(() if w is None else ((w,) if self.sinks is None else (w, self.sinks))), C.c_void_p(_stream())))
             bad += int(self._violations.item())
         return bad
 
@@ -192,18 +204,18 @@ class PagedRowsDecodeAttention(PagedBatchDecodeAttention):
 class SpeculativeDecoder(PagedBatchedDecoder):
     """PagedBatchedDecoder whose step runs batch * rows_per_seq rows: the same seven launches (BatchedDecoder.step: hidden fp16 [batch * T][hidden], the position
     words tce_draft_ngram's row_pos int32 [batch * T]), the rows step as launch 3.  fp16 and fp8_e4m3 pages.  prefill / prefill_many are the parent's.  window: this
-    layer's sliding window (the windowed rows step and the windowed prefill), None for full attention."""
+    layer's sliding window (the windowed rows step and the windowed prefill), None for full attention.  sinks: this layer's attention sinks beside the window (the
+    rows-sink step and the sink prefill; window >= rows_per_seq), None for none; reported as .sinks."""
 
     def __init__(self, block, allocator, rows_per_seq: int, kv_dtype: str = "fp16", k_scale_log2: int = 0, v_scale_log2: int = 0, window: int | None = None, lora=None,
                  sinks: int | None = None):
         """lora: this layer's view of a LoraPool built with the same rows_per_seq (LoraPool(..., rows_per_seq=T).layer(i)): the T rows of a slot run on the slot's
-        adapter -- 7 + 6 launches, 7 + 8 with a gate_up=True pool.  sinks: refused (ValueError) unless None -- attention sinks exist on the one-row step only."""
-        if sinks is not None:
-            raise ValueError("SpeculativeDecoder: attention sinks are not built on the multi-row step (sinks=None)")
+        adapter -- 7 + 6 launches, 7 + 8 with a gate_up=True pool."""
         _check_rows(rows_per_seq)
+        _check_rows_window("SpeculativeDecoder", allocator, rows_per_seq, window, sinks)  # (before `block` is touched)
         self.rows_per_seq = int(rows_per_seq)
         attention = PagedRowsDecodeAttention(allocator, block.heads, block.kv_heads, block.gamma1.device, block.attention.cos, block.attention.sin,
-                                             rows_per_seq=rows_per_seq, kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window)
+                                             rows_per_seq=rows_per_seq, kv_dtype=kv_dtype, k_scale_log2=k_scale_log2, v_scale_log2=v_scale_log2, window=window, sinks=sinks)
         super().__init__(block, allocator, attention=attention, rows=allocator.batch * self.rows_per_seq, lora=lora)
 
 
@@ -283,7 +295,8 @@ class SpeculativeGenerator(_GeneratorBase):
     REPLACES the n-gram lookup: row t of a sequence at position p is fed script[b][p + t].  admit / tokens / logprobs / release are BatchedGenerator's.
     Decoders with sliding windows: as in BatchedGenerator, run() gives back the pages wholly behind every layer's window around each burst.  Row 0 of the next
     replay sits at the synced position p and needs keys from p - W + 1 on, later rows and later replays only later keys, so SpecSlotBook.wanted and _release_behind
-    are the plain loop's; a slot holds at most ceil((max W + n T) / page_keys) + 1 pages through run(n)."""
+    are the plain loop's; a slot holds at most ceil((max W + n T) / page_keys) + 1 + keep_pages pages through run(n).  Decoders with attention sinks (SpeculativeDecoder(...,
+    window=W, sinks=S)): the base class keeps the sinks' page (keep_pages = 1) beside the window's."""
 
     def __init__(self, decoders, final_gamma, lm_head, embed_table, max_new: int, ngram: int = 2, eps: float | None = None, top_k_bound: int = 40, stop_ids=(),
                  graph: bool = True, script: bool = False, record_steps: int = 4096, logprobs: bool = False,
@@ -295,9 +308,11 @@ class SpeculativeGenerator(_GeneratorBase):
                 raise ValueError(f"SpeculativeGenerator: lora= takes a pool built for its speculative rows, LoraPool(..., rows_per_seq=T) with the decoders' T "
                                  f"(this pool: rows_per_seq={T})")
         decoders = list(decoders)
-        for d in decoders:  # (attention sinks exist on the one-row step only)
-            if getattr(d, "sinks", None) is not None or getattr(getattr(d, "attention", None), "sinks", None) is not None:
-                raise ValueError("SpeculativeGenerator: a decoder has attention sinks, which are not built on the multi-row step")
+        for d in decoders:  # a layer with sinks must run the ROWS sink step: its attention object carries the count (SpeculativeDecoder(..., window=W, sinks=S) builds it so)
+            sk = getattr(d, "sinks", None)
+            if sk is not None and getattr(getattr(d, "attention", None), "sinks", None) != sk:
+                raise ValueError(f"SpeculativeGenerator: a decoder reports sinks {sk} but its attention object does not carry them (build the layer as "
+                                 f"SpeculativeDecoder(..., window=W, sinks=S))")
         for d in decoders:  # a windowed layer must run the windowed ROWS step: its attention object carries the window (SpeculativeDecoder(..., window=W) builds it so)
             w = getattr(d, "window", None)
             if w is not None and getattr(getattr(d, "attention", None), "window", None) != w:
