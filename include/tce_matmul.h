@@ -859,6 +859,45 @@ TCE_API int tce_lora_expand_add_f16(const float *t, const void *B, const float *
                                     void *stream);
 TCE_API int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C,
                                          int ldc, int rows, int N, int R, int n_adapters, void *stream);
+/* Mixture of experts: a sparse MoE FFN on W4A16 (csrc/w4a16_moe.hip; additive within ABI 113, no existing struct or entry point changes).  Which expert a row uses is
+ * decided per token ON THE DEVICE; nothing about the routing reaches the host, every launch has a fixed grid, and a captured graph follows a routing that changes.
+ * With E experts, k experts per row, P = rows * k pairs (pair p = i * k + s is slot s of row i):
+ *   router      Wr fp16 [E][hidden], not quantised.  l[e] = sum_k x[i][k] * Wr[e][k] in fp32 (one fmaf per element; the order depends on hidden alone).
+ *   selection   the k largest logits in descending order, ties to the lower expert index, -0 equal to +0, a NaN below every number: ids[i][s] in [0, E) whatever
+ *               the row holds.   weights  w[s] = exp(l[ids[s]] - max l) / sum_e exp(l[e] - max l) in fp32 (e ascending); renormalize != 0: divided by sum_s w[s]
+ *               (slot order).
+ *   experts     stacked q4_6 arrays with the default strides, group size 128: qweight u32 [E][N][K/8], scales fp16 [E][N][scales_stride], zeros u32 [E][N][zeros_stride].
+ *               Up stage: N = 2 * ffn, row 2n = gate n, row 2n + 1 = up n (the TCE_W4_SILU_MUL_PAIRS layout), K = hidden; down stage: N = hidden, K = ffn.
+ *               act[p] = silu_mul_half(fp16(gate_e . x_i), fp16(up_e . x_i)), e = ids[p], fp16 [P][ffn];   y[p] = down_e . act[p], fp32 [P][N], never rounded to fp16.
+ *   combine     acc = +0; for s ascending: acc = fmaf(w[i][s], y[i * k + s][n], acc); C[i][n] = fp16(float(C[i][n]) + acc), C the residual stream (TCE_W4_ADD_TO_C's place).
+ * WORKSPACE, tce_moe_workspace_bytes(rows, k, E, N_max) bytes (0 for arguments the entry points refuse), 256-byte aligned, N_max >= max(ffn, hidden): six sections, each
+ * rounded up to a multiple of 256 bytes, in this order: ids int32 [P]; weights fp32 [P]; count int32 [E]; list int32 [E][P]; act fp16 [P][ffn]; y fp32 [P][N].  Every
+ * entry point takes the SAME rows, k, E and N_max: they fix the offsets.
+ * tce_moe_route_f16        two launches: ids and weights per row; then the stable grouping -- count[e] = the pairs that name e, list[e][0 .. count[e]) = their indices ascending.
+ * tce_moe_gate_up_f16      one launch, grid (16-row tiles of N) x E (weights requested row-major: 16 lanes take four k-blocks = 256 contiguous bytes of a row): x fp16 [rows][ldx] -> act.   tce_moe_down_f16: one launch, act -> y.  A workgroup whose count[e] is 0
+ *                          leaves at once; up to 16 pairs of list[e] ride on one v_mfma_f32_16x16x32_f16 against the expert's unpacked tile, which is streamed once per
+ *                          launch for them; further pairs run further passes in list order.  The K sum: k-blocks of 128 ascending within a wave (one fp32 scale per row and
+ *                          group), 8 waves' partial sums added in wave order; the split depends on K alone.  No atomics; a pair's bits depend on its row's input, its
+ *                          expert's weights and K only -- not on the other rows, its place in a list, rows, or the grid.  A word of list / count outside the pairs (only a
+ *                          caller that writes them itself can produce one) is clamped, never followed.  flags: TCE_W4_ZERO_POINT_IS_8 (the promise it is elsewhere) or 0.
+ * tce_moe_combine_add_f16  one launch of 16-byte pieces over C fp16 [rows][ldc].  A slot whose ids word lies outside [0, E) is skipped: such a pair is in no list.
+ * All are asynchronous on `stream` and allocate nothing.  Refusals, before any HIP call and without reading through a pointer, arguments before shapes:
+ * TCE_ERR_BAD_ARG for a NULL pointer, rows / k / E / N_max / N / K / hidden < 1, k > E, ldx < K (hidden), ldc < N, flags other than TCE_W4_ZERO_POINT_IS_8, an N or K
+ * that does not fit N_max; TCE_ERR_UNSUPPORTED_GROUP for a group size other than 128; TCE_ERR_UNSUPPORTED_SHAPE for k > 8, E > 64, more than TCE_MOE_MAX_PAIRS pairs,
+ * a workspace not 256-byte aligned, K % 128 != 0 or K > 32768, an odd N of the up stage, hidden / N / ldx / ldc of route and combine not multiples of 8, misaligned
+ * pointers.
+ * NOT BUILT: a prefill-sized grouped GEMM on 128-row tiles, shared experts, expert parallelism, adapters on experts, a q4_mfma / int8 expert body, route fused into the
+ * preceding norm or combine into down. */
+#define TCE_MOE_MAX_TOP_K   8
+#define TCE_MOE_MAX_EXPERTS 64
+#define TCE_MOE_MAX_PAIRS   (1 << 16)   /* rows * k per call.  The kernels are built for decode-sized calls: the grouping is ONE wave whose lanes each walk all the pairs, and past 16 pairs of an expert a tile is re-read per pass of 16 with wave 0 alone in the reduction and the epilogue */
+TCE_API size_t tce_moe_workspace_bytes(int rows, int k, int E, int N_max);
+TCE_API int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream);
+TCE_API int tce_moe_gate_up_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size,
+                                int flags, int N_max, void *workspace, void *stream);
+TCE_API int tce_moe_down_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max,
+                             void *workspace, void *stream);
+TCE_API int tce_moe_combine_add_f16(void *C, int ldc, int rows, int k, int E, int N, int N_max, const void *workspace, void *stream);
 /* Reads [ptr, ptr + bytes) with at most `workgroups` workgroups (0 = as many as the range needs) and discards the data: the
  * range then sits in the memory-side cache (256 MiB) for the launch that needs it.  Meant for a side stream / graph branch
  * next to the launch BEFORE that one (no reference counterpart: cudaMallocManaged prefetching is the closest idea). */

@@ -98,6 +98,11 @@ class BatchedDecoder:
         pool's rows_per_seq must be the step's: None for rows == batch, T for rows == batch * T."""
         self.block, self.batch, self.rows = block, batch, batch if rows is None else rows
         self.lora, self._lora_t, self._gate_up_y = lora, None, None
+        moe = getattr(block, "moe", None)
+        if lora is not None and moe is not None:
+            raise ValueError("lora= together with a moe= block: adapters on experts are not built (DESIGN.md section 9)")
+        if moe is not None:
+            self.LAUNCHES = 5 + moe.LAUNCHES  # norm, q/k/v, attention, o_proj, norm + route (2), expert gate/up, expert down, combine
         if lora is not None:
             if self.rows != batch * (lora.pool.rows_per_seq or 1):
                 raise ValueError(f"lora: a step of {self.rows} rows for {batch} slots, but the pool was built with rows_per_seq={lora.pool.rows_per_seq} "

@@ -40,6 +40,13 @@ int launch_lora_expand_add_f16(const float *t, const void *B, const float *scale
                                hipStream_t stream, hipError_t *hip_err);
 int launch_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C, int ldc,
                                     int rows, int N, int R, int n_adapters, hipStream_t stream, hipError_t *hip_err);
+size_t moe_workspace_bytes(int rows, int k, int E, int n_max);
+size_t moe_lds_bytes(int K);
+int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
+                         hipError_t *hip_err);
+int launch_moe_stage(bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int scales_stride,
+                     int zeros_stride, bool z8, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err);
+int launch_moe_combine_add_f16(void *C, int ldc, int rows, int k, int E, int N, int n_max, const void *workspace, hipStream_t stream, hipError_t *hip_err);
 
 thread_local char g_err[512] = "";
 int fail(int code, const char *fmt, ...) {
@@ -1483,6 +1490,82 @@ int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu,
     hipError_t he = hipSuccess;
     const int rc = tce::launch_lora_expand_silu_mul_f16(t, Bg, Bu, scale, row_adapter, y, ldy, Cm, ldc, rows, N, R, n_adapters, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA gate/up expand launch") : rc;
+}
+
+// ---- mixture of experts (csrc/w4a16_moe.hip).  The rules the five entry points share, in the order they run: every argument refusal, then every shape refusal ----
+static int moe_bad_arg(const char *who, int rows, int k, int E, int n_max, const void *workspace) {
+    if (!workspace) return fail(TCE_ERR_BAD_ARG, "%s: null workspace", who);
+    if (rows < 1 || k < 1 || E < 1 || n_max < 1 || k > E) return fail(TCE_ERR_BAD_ARG, "%s: need rows, k, E, N_max >= 1 and k <= E (rows %d, k %d, E %d, N_max %d)", who, rows, k, E, n_max);
+    return TCE_OK;
+}
+static int moe_bad_shape(const char *who, int rows, int k, int E, const void *workspace) {
+    if (k > TCE_MOE_MAX_TOP_K || E > TCE_MOE_MAX_EXPERTS) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: k %d, E %d (at most %d of at most %d experts)", who, k, E, TCE_MOE_MAX_TOP_K, TCE_MOE_MAX_EXPERTS);
+    if ((long long)rows * k > TCE_MOE_MAX_PAIRS) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %lld pairs (at most %d per call)", who, (long long)rows * k, TCE_MOE_MAX_PAIRS);
+    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 256-byte aligned workspace", who);
+    return TCE_OK;
+}
+
+size_t tce_moe_workspace_bytes(int rows, int k, int E, int N_max) {
+    if (rows < 1 || k < 1 || E < 1 || N_max < 1 || k > E || k > TCE_MOE_MAX_TOP_K || E > TCE_MOE_MAX_EXPERTS || (long long)rows * k > TCE_MOE_MAX_PAIRS) return 0;
+    return tce::moe_workspace_bytes(rows, k, E, N_max);
+}
+
+int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream) {
+    const char *who = "tce_moe_route_f16";
+    if (!x || !Wr) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = moe_bad_arg(who, rows, k, E, N_max, workspace)) return rc;
+    if (hidden < 1 || ldx < hidden) return fail(TCE_ERR_BAD_ARG, "%s: need hidden >= 1 and ldx >= hidden", who);
+    if (const int rc = moe_bad_shape(who, rows, k, E, workspace)) return rc;
+    if (hidden % 8 != 0 || ldx % 8 != 0 || (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(Wr)) % 16 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: hidden %d, ldx %d (multiples of 8), 16-byte aligned x / Wr", who, hidden, ldx);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_moe_route_f16(x, ldx, Wr, rows, hidden, E, k, renormalize, N_max, workspace, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "MoE route launch") : rc;
+}
+
+// one contraction stage (up: x != nullptr is the caller's rows; down reads act from the workspace)
+static int moe_stage(const char *who, bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K,
+                     int group_size, int flags, int N_max, void *workspace, void *stream) {
+    if ((up && !x) || !qweight || !scales || !zeros) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = moe_bad_arg(who, rows, k, E, N_max, workspace)) return rc;
+    if (N < 1 || K < 1 || (up && ldx < K)) return fail(TCE_ERR_BAD_ARG, "%s: need N, K >= 1%s", who, up ? " and ldx >= K" : "");
+    if (flags & ~TCE_W4_ZERO_POINT_IS_8) return fail(TCE_ERR_BAD_ARG, "%s: flags 0x%x (TCE_W4_ZERO_POINT_IS_8 only)", who, flags);
+    if ((up ? N / 2 : (N > K ? N : K)) > N_max) return fail(TCE_ERR_BAD_ARG, "%s: N %d, K %d do not fit a workspace of N_max %d", who, N, K, N_max);
+    if (group_size != 128) return fail(TCE_ERR_UNSUPPORTED_GROUP, "%s: group size %d (128 only)", who, group_size);
+    if (const int rc = moe_bad_shape(who, rows, k, E, workspace)) return rc;
+    if (K % 128 != 0 || K > 32768 || tce::moe_lds_bytes(K) > 160 * 1024) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: K %d (a multiple of 128, at most 32768)", who, K);
+    if (up && N % 2 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d (interleaved gate / up rows: even)", who, N);
+    if ((long long)E * N * (K / 8) >= (1LL << 40)) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: E * N * K too large", who);
+    if ((up && (ldx % 8 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0)) || reinterpret_cast<uintptr_t>(qweight) % 16 != 0 || reinterpret_cast<uintptr_t>(scales) % 2 != 0 ||
+        reinterpret_cast<uintptr_t>(zeros) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned x (ldx %% 8 == 0) / qweight, aligned scales / zeros", who);
+    const int zw = tce::zeros_width(K, group_size);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_moe_stage(up, x, ldx, qweight, scales, zeros, rows, k, E, N, K, zw * 8, zw, (flags & TCE_W4_ZERO_POINT_IS_8) != 0, N_max, workspace,
+                                         static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "MoE contraction launch") : rc;
+}
+
+int tce_moe_gate_up_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags,
+                        int N_max, void *workspace, void *stream) {
+    return moe_stage("tce_moe_gate_up_f16", true, x, ldx, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
+}
+
+int tce_moe_down_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max, void *workspace,
+                     void *stream) {
+    return moe_stage("tce_moe_down_f16", false, nullptr, 0, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
+}
+
+int tce_moe_combine_add_f16(void *Cm, int ldc, int rows, int k, int E, int N, int N_max, const void *workspace, void *stream) {
+    const char *who = "tce_moe_combine_add_f16";
+    if (!Cm) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (const int rc = moe_bad_arg(who, rows, k, E, N_max, workspace)) return rc;
+    if (N < 1 || ldc < N || N > N_max) return fail(TCE_ERR_BAD_ARG, "%s: need 1 <= N <= N_max and ldc >= N", who);
+    if (const int rc = moe_bad_shape(who, rows, k, E, workspace)) return rc;
+    if (N % 8 != 0 || ldc % 8 != 0 || reinterpret_cast<uintptr_t>(Cm) % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d, ldc %d (multiples of 8), 16-byte aligned C", who, N, ldc);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_moe_combine_add_f16(Cm, ldc, rows, k, E, N, N_max, workspace, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "MoE combine launch") : rc;
 }
 
 int tce_attention_decode_step_deferred_f16(const void *qkv, void *kc, void *vc, const void *cosv, const void *sinv, const void *mask, void *out, void *workspace, int heads,

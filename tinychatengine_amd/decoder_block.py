@@ -28,10 +28,14 @@ from .linear import Linear_half_int4, _stream, rmsnorm_half
 
 
 class DecoderBlock:
+    moe = None  # the layer's MoeFFN (moe.py) where the FFN is a sparse mixture of experts; None: the dense gate/up and down
+
     def __init__(self, hidden: int, heads: int, ffn: int, max_keys: int, device, cos: torch.Tensor, sin: torch.Tensor, seed: int = 0,
-                 group_size: int = 128, eps: float = 1e-6, kv_heads: int | None = None, prepack: bool = True, defer_combine: bool | None = None):
+                 group_size: int = 128, eps: float = 1e-6, kv_heads: int | None = None, prepack: bool = True, defer_combine: bool | None = None, moe=None):
         """kv_heads < heads: grouped-query attention (Llama-3-8B: 32 / 8, llm/include/model.h:83) -- the fused projection is
-        (heads + 2 * kv_heads) * 128 rows wide and the caches hold kv_heads heads."""
+        (heads + 2 * kv_heads) * 128 rows wide and the caches hold kv_heads heads.
+        moe: a MoeFFN (moe.py) of this hidden and ffn, or {"experts": E, "top_k": k[, "renormalize": ...]} to build one -- the layer's FFN is then the sparse
+        mixture of experts (layer_body: blk.moe.forward in place of gate/up and down) and no dense gate / up / down linear is made.  None: the dense layer, unchanged."""
         assert hidden % heads == 0 and hidden // heads == 128, "the attention step is built for head_dim 128 (Llama)"
         self.hidden, self.heads, self.ffn, self.eps = hidden, heads, ffn, eps
         self.kv_heads = heads if kv_heads is None else kv_heads
@@ -42,10 +46,17 @@ class DecoderBlock:
         rnd = lambda n, k: torch.empty(n, k, device=device).normal_(0.0, k ** -0.5, generator=g)
         self.qkv = Linear_half_int4.from_float(rnd((heads + 2 * self.kv_heads) * 128, hidden), group_size)   # rows: q | k | v, head-major (llama_qkv_merger.py:27-48)
         self.o = Linear_half_int4.from_float(rnd(hidden, hidden), group_size)
-        self.gate = Linear_half_int4.from_float(rnd(ffn, hidden), group_size)
-        self.up = Linear_half_int4.from_float(rnd(ffn, hidden), group_size)
-        self.gate_up = Linear_half_int4.interleave(self.gate, self.up)                  # row 2n = gate n, row 2n + 1 = up n
-        self.down = Linear_half_int4.from_float(rnd(hidden, ffn), group_size)
+        if moe is not None:
+            from .moe import MoeFFN
+            self.moe = moe if isinstance(moe, MoeFFN) else MoeFFN(hidden, ffn, moe["experts"], moe["top_k"], device, renormalize=moe.get("renormalize", True), seed=seed + 1)
+            if (self.moe.hidden, self.moe.ffn) != (hidden, ffn) or group_size != 128:
+                raise ValueError(f"moe: experts of hidden {self.moe.hidden} / ffn {self.moe.ffn} in a block of hidden {hidden} / ffn {ffn} (group size 128 only)")
+            self.gate = self.up = self.gate_up = self.down = None
+        else:
+            self.gate = Linear_half_int4.from_float(rnd(ffn, hidden), group_size)
+            self.up = Linear_half_int4.from_float(rnd(ffn, hidden), group_size)
+            self.gate_up = Linear_half_int4.interleave(self.gate, self.up)                  # row 2n = gate n, row 2n + 1 = up n
+            self.down = Linear_half_int4.from_float(rnd(hidden, ffn), group_size)
         self.gamma1 = (1.0 + 0.1 * torch.empty(hidden, device=device).normal_(0, 1, generator=g)).float()
         self.gamma2 = (1.0 + 0.1 * torch.empty(hidden, device=device).normal_(0, 1, generator=g)).float()
         if prepack:  # load-time re-layout: the four launches of a decode step then run on the packed copies (csrc/w4a16_gemv_i8.hip, fused prologue / epilogues included)
@@ -58,6 +69,7 @@ class DecoderBlock:
     def step(self, hidden_state: torch.Tensor, pos: int, pos_device: torch.Tensor | None = None) -> None:
         """hidden_state fp16 [1][hidden], updated in place (it is the residual stream).  pos_device: the position on the device (`pos` then
         bounds it): the five launches can be captured once and replayed token after token."""
+        self._no_moe("step")
         st = _stream()
         capi.check(capi.w4a16_forward(self.qkv.desc(hidden_state, self.qkv_out, gamma=self.gamma1, eps=self.eps), st))
         if self.defer_combine:  # round 5: the attention step ends at its per-chunk partial states, o_proj's prologue combines them (same row, bit for bit; one launch boundary instead of a cross-workgroup exchange)
@@ -76,6 +88,7 @@ class DecoderBlock:
         formed by the launch that produced hidden_state (the previous layer's down_proj; tce_rmsnorm_half for the first layer); o_proj's residual epilogue forms
         post_attention_layernorm, down_proj's forms the NEXT layer's input_layernorm (`next_gamma`) into `xn_out`.  q/k/v and gate/up are plain launches.
         Same bits as step(): every piece has the arithmetic of the separate kernels."""
+        self._no_moe("step_chained")
         st = _stream()
         capi.check(capi.w4a16_forward(self.qkv.desc(xn_in, self.qkv_out), st))
         self.attention.step(self.qkv_out.view(-1), pos, out=self.attn_out.view(self.heads, 128), pos_device=pos_device)
@@ -87,11 +100,17 @@ class DecoderBlock:
 
     LAUNCHES = 5
 
+    def _no_moe(self, what: str) -> None:
+        if self.moe is not None:
+            raise ValueError(f"DecoderBlock.{what}: the M = 1 five-launch form has no moe= FFN (its gate/up and down are dense launches); an MoE block runs through "
+                             "prefill, BatchedDecoder and the generators")
+
     # ---- m > 1 rows: a prompt, or a chunk of one (the same reference code path with sqlen > 1) ----
     def prepare_prefill(self) -> "DecoderBlock":
         """Load-time work for the prefill path: the q4_mfma copies the 128-row GEMM reads (tce_w4a16_prepack)."""
         for l in (self.qkv, self.o, self.gate_up, self.down):
-            l.prepack()
+            if l is not None:  # (an MoE block has no dense FFN linears; the experts are read as q4_6: no second copy)
+                l.prepack()
         return self
 
     def prefill(self, hidden_rows: torch.Tensor, pos: int) -> None:
@@ -111,7 +130,7 @@ class DecoderBlock:
     PREFILL_LAUNCHES = 8  # with pre-packed weights and m > 128 (otherwise 10: gate, up and SiLU*mul as three launches)
 
     def linear_bytes(self) -> int:
-        return sum(capi.algorithmic_bytes(1, l.out_features, l.in_features, l.group_size) for l in (self.qkv, self.o, self.gate_up, self.down))
+        return sum(capi.algorithmic_bytes(1, l.out_features, l.in_features, l.group_size) for l in (self.qkv, self.o, self.gate_up, self.down) if l is not None)
 
 
 # ---- the layer over m rows: ONE body for DecoderBlock.prefill, BatchedDecoder.step and BatchedDecoder._prefill_rows (step / step_chained above are other launches) ----
@@ -122,7 +141,11 @@ def layer_body(blk: DecoderBlock, rows: torch.Tensor, xn, qkv, attn, act, attend
     (BatchedDecoder._gate_up, or gate_up_by_rule).
     lora: the layer's LoraLayer, with t = lora.workspace(m) and row_words int32 [m] (None: the pool's own row_adapter).  q/k/v, o_proj and down_proj are then adapted
     linears.  A view of a gate_up=True pool adapts gate/up too, the one linear that does not follow the rule: the delta belongs in front of the nonlinearity, so the base
-    gate_up linear runs WITHOUT the pair flag into y [m][2 * ffn] and tce_lora_expand_silu_mul_f16 adds both deltas and applies SiLU * mul; the policy is not asked."""
+    gate_up linear runs WITHOUT the pair flag into y [m][2 * ffn] and tce_lora_expand_silu_mul_f16 adds both deltas and applies SiLU * mul; the policy is not asked.
+    blk.moe (DecoderBlock(..., moe=)): the last two stages are blk.moe.forward(xn, rows) -- route, expert gate/up, expert down, combine + residual; the first five are
+    the dense layer's, call for call."""
+    if lora is not None and blk.moe is not None:
+        raise ValueError("lora= together with a moe= block: adapters on experts are not built (DESIGN.md section 9)")
     st = _stream()
 
     def linear(target, lin, x, out, flags=0):
@@ -138,6 +161,9 @@ def layer_body(blk: DecoderBlock, rows: torch.Tensor, xn, qkv, attn, act, attend
     attend(qkv, attn)
     linear("o", blk.o, attn, rows, capi.TCE_W4_ADD_TO_C)
     rmsnorm_half(rows, blk.gamma2, blk.eps, out=xn)
+    if blk.moe is not None:
+        blk.moe.forward(xn, rows)
+        return
     if lora is not None and lora.gate_up:
         lora.shrink("gate_up", xn, t["gate_up"], row_words)
         capi.check(capi.w4a16_forward(blk.gate_up.desc(xn, y), st))
