@@ -886,17 +886,31 @@ TCE_API int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const v
  * that does not fit N_max; TCE_ERR_UNSUPPORTED_GROUP for a group size other than 128; TCE_ERR_UNSUPPORTED_SHAPE for k > 8, E > 64, more than TCE_MOE_MAX_PAIRS pairs,
  * a workspace not 256-byte aligned, K % 128 != 0 or K > 32768, an odd N of the up stage, hidden / N / ldx / ldc of route and combine not multiples of 8, misaligned
  * pointers.
- * NOT BUILT: a prefill-sized grouped GEMM on 128-row tiles, shared experts, expert parallelism, adapters on experts, a q4_mfma / int8 expert body, route fused into the
- * preceding norm or combine into down. */
+ * THE TILED FORM, tce_moe_gate_up_tiled_f16 / tce_moe_down_tiled_f16 (csrc/w4a16_moe_tiled.hip): the same arguments, operands, workspace and refusals (in the same order;
+ * the same K <= 32768: the form's LDS, 81 KiB, does not depend on K) as tce_moe_gate_up_f16 / tce_moe_down_f16, for prompt-sized pair counts.  One launch, grid
+ * ceil(N / TCE_MOE_TILE_ROWS) x (P / TCE_MOE_TILE_PAIRS + min(E, P)) -- the second number is the host-known bound on sum_e ceil(count[e] / TCE_MOE_TILE_PAIRS); a
+ * workgroup reads count[0 .. E) (clamped to [0, P]), finds the (expert, first pair) of its slot by a prefix sum and leaves when the slot is past the total, so a captured
+ * graph follows a routing that changes.  A workgroup owns TCE_MOE_TILE_ROWS weight rows x TCE_MOE_TILE_PAIRS pairs of one expert's list over the whole K (weights and
+ * gathered rows double-buffered in LDS per k-block of 128); no split of K across workgroups, no atomics.  PROMISE: every word of act and y is BIT-IDENTICAL to what
+ * tce_moe_gate_up_f16 / tce_moe_down_f16 write on the same workspace contents (the same MFMA on the same operands per k-block, the same eight K slices added in the same
+ * order), and words those leave unwritten stay unwritten: the choice between the forms is a question of time only.
+ * NOT BUILT: a parallel stable grouping (the grouping is one wave that walks every pair), shared experts, expert parallelism, adapters on experts, a q4_mfma / int8 expert
+ * body, route fused into the preceding norm or combine into down. */
 #define TCE_MOE_MAX_TOP_K   8
 #define TCE_MOE_MAX_EXPERTS 64
-#define TCE_MOE_MAX_PAIRS   (1 << 16)   /* rows * k per call.  The kernels are built for decode-sized calls: the grouping is ONE wave whose lanes each walk all the pairs, and past 16 pairs of an expert a tile is re-read per pass of 16 with wave 0 alone in the reduction and the epilogue */
+#define TCE_MOE_MAX_PAIRS   (1 << 16)   /* rows * k per call.  The grouping is ONE wave whose lanes each walk all the pairs; tce_moe_gate_up_f16 / tce_moe_down_f16 re-read a tile per pass of 16 pairs of an expert with wave 0 alone in the reduction and the epilogue (decode-sized calls); the _tiled_ forms are the ones for prompt-sized calls */
+#define TCE_MOE_TILE_ROWS   128         /* the tiled form's tile: weight rows ... */
+#define TCE_MOE_TILE_PAIRS  128         /* ... x pairs of one expert's list (a multiple of 16) */
 TCE_API size_t tce_moe_workspace_bytes(int rows, int k, int E, int N_max);
 TCE_API int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream);
 TCE_API int tce_moe_gate_up_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size,
                                 int flags, int N_max, void *workspace, void *stream);
 TCE_API int tce_moe_down_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max,
                              void *workspace, void *stream);
+TCE_API int tce_moe_gate_up_tiled_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size,
+                                      int flags, int N_max, void *workspace, void *stream);
+TCE_API int tce_moe_down_tiled_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max,
+                                   void *workspace, void *stream);
 TCE_API int tce_moe_combine_add_f16(void *C, int ldc, int rows, int k, int E, int N, int N_max, const void *workspace, void *stream);
 /* Reads [ptr, ptr + bytes) with at most `workgroups` workgroups (0 = as many as the range needs) and discards the data: the
  * range then sits in the memory-side cache (256 MiB) for the launch that needs it.  Meant for a side stream / graph branch

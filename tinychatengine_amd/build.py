@@ -22,7 +22,7 @@ TESTKIT_LIB_PATH = os.path.join(LIB_DIR, "libtce_testkit.so")
 ADAPTER_TEST_PATH = os.path.join(LIB_DIR, "adapter_selftest")
 ADAPTER_BENCH_PATH = os.path.join(LIB_DIR, "adapter_bench")
 
-HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip", "w4a16_moe.hip"]
+HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip", "w4a16_moe.hip", "w4a16_moe_tiled.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-ffp-contract=off",  # the int8 epilogue and the fp16-accumulate entry point need every rounding
@@ -35,8 +35,10 @@ HIPCC_FLAGS = [
 # lora.hip: no SLP vectorisation -- paired, the expand's fmafs become v_pk_fma_f32 whose shared t[i][j] sits in the high half of a scalar pair (op_sel:[1,0,0]): the form
 # isa_lint.py RULE 1 refuses
 # w4a16_moe.hip: no packed fp32 arithmetic at all (the route's and the combine's fmaf chains and the K sum are plain v_fma_f32 / v_add_f32)
+# w4a16_moe_tiled.hip: the same, and for a second reason: its K sum has to give w4a16_moe.hip's bits
 EXTRA_FLAGS: dict[str, list[str]] = {"w4a16_gemv_i8.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"], "lora.hip": ["-fno-slp-vectorize"],
-                                     "w4a16_moe.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                                     "w4a16_moe.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                                     "w4a16_moe_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # Kernels that must not spill a vector register: lnq_w8a8_wide_kernel keeps 16 requested weight pieces per lane in flight through its sums; ONE spilled register
 # makes the compiler wait for all of them at the spill (measured: the OPT-6.7B layer 94 -> 103 us, found only by accident).  The build fails instead.
 NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_kernel"],
@@ -47,6 +49,9 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         # the expert-grouped contraction keeps four k-blocks of weights and two gathered activation blocks in flight per wave: a spilled one
                                         # would be waited for at the spill; the route holds a row's k selections in registers through the selection rounds
                                         "w4a16_moe.hip": ["w4a16_moe_kernel", "moe_route_kernel", "moe_group_kernel", "moe_combine_add_kernel"],
+                                        # the tiled form holds 2 x 4 MFMA tiles twice (the K slice and the total) beside the next k-block's requests: 64 accumulators in scratch
+                                        # would be re-read per k-block
+                                        "w4a16_moe_tiled.hip": ["w4a16_moe_tiled_kernel"],
                                         # the sampler's two kernels keep 16 / 32 64-bit numbers per thread in registers through ~50 counting rounds: in scratch every round would re-read them
                                         # (every instantiation, the logprob forms included; the two scoring kernels hold the same 16 logits per thread)
                                         "sampling.hip": ["sample_select_kernel", "sample_draw_kernel", "logprobs_partials_kernel", "logprobs_merge_kernel"],

@@ -46,6 +46,8 @@ int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int h
                          hipError_t *hip_err);
 int launch_moe_stage(bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int scales_stride,
                      int zeros_stride, bool z8, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err);
+int launch_moe_stage_tiled(bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int scales_stride,
+                           int zeros_stride, bool z8, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err);
 int launch_moe_combine_add_f16(void *C, int ldc, int rows, int k, int E, int N, int n_max, const void *workspace, hipStream_t stream, hipError_t *hip_err);
 
 thread_local char g_err[512] = "";
@@ -1523,8 +1525,9 @@ int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidd
     return rc == TCE_ERR_HIP ? hip_fail(he, "MoE route launch") : rc;
 }
 
-// one contraction stage (up: x != nullptr is the caller's rows; down reads act from the workspace)
-static int moe_stage(const char *who, bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K,
+// one contraction stage (up: x != nullptr is the caller's rows; down reads act from the workspace), in either form: the refusals are the same ones in the same order
+// (the tiled form's LDS does not depend on K, so it needs no lower cap on K)
+static int moe_stage(const char *who, bool up, bool tiled, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K,
                      int group_size, int flags, int N_max, void *workspace, void *stream) {
     if ((up && !x) || !qweight || !scales || !zeros) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
     if (const int rc = moe_bad_arg(who, rows, k, E, N_max, workspace)) return rc;
@@ -1541,19 +1544,29 @@ static int moe_stage(const char *who, bool up, const void *x, int ldx, const voi
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned x (ldx %% 8 == 0) / qweight, aligned scales / zeros", who);
     const int zw = tce::zeros_width(K, group_size);
     hipError_t he = hipSuccess;
-    const int rc = tce::launch_moe_stage(up, x, ldx, qweight, scales, zeros, rows, k, E, N, K, zw * 8, zw, (flags & TCE_W4_ZERO_POINT_IS_8) != 0, N_max, workspace,
-                                         static_cast<hipStream_t>(stream), &he);
+    const int rc = (tiled ? tce::launch_moe_stage_tiled : tce::launch_moe_stage)(up, x, ldx, qweight, scales, zeros, rows, k, E, N, K, zw * 8, zw,
+                                                                                 (flags & TCE_W4_ZERO_POINT_IS_8) != 0, N_max, workspace, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "MoE contraction launch") : rc;
 }
 
 int tce_moe_gate_up_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags,
                         int N_max, void *workspace, void *stream) {
-    return moe_stage("tce_moe_gate_up_f16", true, x, ldx, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
+    return moe_stage("tce_moe_gate_up_f16", true, false, x, ldx, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
 }
 
 int tce_moe_down_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max, void *workspace,
                      void *stream) {
-    return moe_stage("tce_moe_down_f16", false, nullptr, 0, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
+    return moe_stage("tce_moe_down_f16", false, false, nullptr, 0, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
+}
+
+int tce_moe_gate_up_tiled_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags,
+                              int N_max, void *workspace, void *stream) {
+    return moe_stage("tce_moe_gate_up_tiled_f16", true, true, x, ldx, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
+}
+
+int tce_moe_down_tiled_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max, void *workspace,
+                           void *stream) {
+    return moe_stage("tce_moe_down_tiled_f16", false, true, nullptr, 0, qweight, scales, zeros, rows, k, E, N, K, group_size, flags, N_max, workspace, stream);
 }
 
 int tce_moe_combine_add_f16(void *Cm, int ldc, int rows, int k, int E, int N, int N_max, const void *workspace, void *stream) {

@@ -29,37 +29,18 @@
 // row in one piece.  The q4_6 row pitch (K / 2 bytes) keeps the tile's rows apart, so 1 KiB in one piece would be 16 k-blocks of one row: 16 KiB of staged weights
 // per wave for the tile, which the workgroup's LDS does not hold beside the gathered rows.  The wave's LDS slot takes the group in fragment order, so the request
 // order and the MFMA order are decoupled.
-#include "tce_common.hpp"
+#include "w4a16_moe.hpp"
 #include "w4a16_unpack16.hpp"
 
 namespace tce {
 namespace {
 
-constexpr int kMoeWaves = 8;        // waves of a contraction workgroup: the K split
 constexpr int kWSub = 68;           // 16-byte slots between the k-blocks of a staged group: 64 + 4, so the 16 lanes that write one row's 256 bytes fall on 16 different bank groups
 constexpr int kWBuf = 4 * kWSub * 16;  // packed weight group of one wave: 4 k-blocks x 16 rows x 64 bytes
 constexpr int kXBuf = 256 * 16;     // gathered activation block of one wave: 16 pairs x 256 bytes
 constexpr int kRedBytes = kMoeWaves * 64 * 16;
 constexpr int kRouteThreads = 256;  // 4 waves: wave w forms the logits of experts w, w + 4, ...
 constexpr int kGroupChunk = 1024;
-
-struct MoeLayout {
-    size_t ids, weights, count, list, act, y, total;
-};
-// the caller's workspace: six sections, each a multiple of 256 bytes (tinychatengine_amd/moe.py mirrors it; include/tce_matmul.h states it)
-MoeLayout moe_layout(int rows, int k, int E, int n_max) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t P = (size_t)rows * k;
-    MoeLayout L;
-    L.ids = 0;
-    L.weights = L.ids + up(P * 4);
-    L.count = L.weights + up(P * 4);
-    L.list = L.count + up((size_t)E * 4);
-    L.act = L.list + up((size_t)E * P * 4);
-    L.y = L.act + up(P * (size_t)n_max * 2);
-    L.total = L.y + up(P * (size_t)n_max * 4);
-    return L;
-}
 
 // fp32 -> a word whose unsigned order is the numbers' order (-0 was made +0 by the caller); every number maps to >= 0x007FFFFF, so 0 ("taken" / no such expert) and
 // 1 (NaN) sit below all of them
@@ -150,17 +131,6 @@ __global__ __launch_bounds__(64) void moe_group_kernel(const int32_t *__restrict
     }
     if (e < E) count[e] = c;
 }
-
-struct MoeArgs {
-    const half_t *X;  // the rows the pairs read: x fp16 [rows][ldx] (up stage, row p / k) or act fp16 [rows * k][ldx] (down stage, row p)
-    const uint4_t *qweight;
-    const half_t *scales;
-    const unsigned *zeros;
-    const int32_t *count, *list;
-    void *out;  // up: act fp16 [P][ld_out]; down: y fp32 [P][ld_out]
-    long long ldx;
-    int P, k, N, K, ld_out, scales_stride, zeros_stride, gpw;
-};
 
 template <bool UP, bool Z8>
 __global__ __launch_bounds__(64 * kMoeWaves) void w4a16_moe_kernel(const MoeArgs a) {
@@ -354,7 +324,6 @@ int launched(hipError_t *hip_err) {
 
 size_t moe_workspace_bytes(int rows, int k, int E, int n_max) { return moe_layout(rows, k, E, n_max).total; }
 
-int moe_gpw(int K) { return ((K >> 7) + kMoeWaves - 1) / kMoeWaves; }
 size_t moe_lds_bytes(int K) { return (size_t)kMoeWaves * (kWBuf + kXBuf + (size_t)moe_gpw(K) * 64) + kRedBytes; }
 
 int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
@@ -372,25 +341,7 @@ int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int h
 // one contraction stage: up (x fp16 [rows][ldx] -> act fp16 [P][N / 2]) or down (act fp16 [P][K] -> y fp32 [P][N])
 int launch_moe_stage(bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int scales_stride,
                      int zeros_stride, bool z8, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err) {
-    const MoeLayout L = moe_layout(rows, k, E, n_max);
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    MoeArgs a{};
-    a.X = up ? static_cast<const half_t *>(x) : reinterpret_cast<const half_t *>(ws + L.act);
-    a.ldx = up ? ldx : K;
-    a.qweight = static_cast<const uint4_t *>(qweight);
-    a.scales = static_cast<const half_t *>(scales);
-    a.zeros = static_cast<const unsigned *>(zeros);
-    a.count = reinterpret_cast<const int32_t *>(ws + L.count);
-    a.list = reinterpret_cast<const int32_t *>(ws + L.list);
-    a.out = up ? static_cast<void *>(ws + L.act) : static_cast<void *>(ws + L.y);
-    a.P = rows * k;
-    a.k = k;
-    a.N = N;
-    a.K = K;
-    a.ld_out = up ? N / 2 : N;
-    a.scales_stride = scales_stride;
-    a.zeros_stride = zeros_stride;
-    a.gpw = moe_gpw(K);
+    const MoeArgs a = moe_stage_args(up, x, ldx, qweight, scales, zeros, rows, k, E, N, K, scales_stride, zeros_stride, n_max, workspace);
     const size_t lds = moe_lds_bytes(K);
     auto kfn = up ? (z8 ? w4a16_moe_kernel<true, true> : w4a16_moe_kernel<true, false>) : (z8 ? w4a16_moe_kernel<false, true> : w4a16_moe_kernel<false, false>);
     // every K needs more than the 64 KiB a kernel gets by default: the limit is raised ONCE per instantiation, to what the largest accepted K (32768) needs, not per launch

@@ -11,7 +11,8 @@ back, and a captured graph follows a routing that changes from replay to replay:
     moe_reference     the definition in numpy float64 on the stored values: the yardstick of the tests
     group_reference   the stable grouping (count, lists) of ids
     MoeWorkspace      the caller workspace of the five entry points and typed views of its six sections
-    route / gate_up / down / combine_add    one entry point each, on torch tensors, on the current stream
+    route / gate_up / down / combine_add    one entry point each, on torch tensors, on the current stream; gate_up / down(tiled=True): the tiled form for prompt-sized
+                      pair counts (csrc/w4a16_moe_tiled.hip: TILE_ROWS weight rows x TILE_PAIRS pairs per workgroup), bit-identical per pair to the other
     MoeFFN            the stacked expert tensors of one layer (synthetic weights, quantize_q4_6 per expert) and forward(xn, rows_inout): DecoderBlock(..., moe=)
 """
 from __future__ import annotations
@@ -24,6 +25,7 @@ import numpy as np
 from . import capi, quantize
 
 GROUP = 128
+TILE_ROWS, TILE_PAIRS = capi.TCE_MOE_TILE_ROWS, capi.TCE_MOE_TILE_PAIRS  # the tiled form's tile (include/tce_matmul.h)
 
 
 def _unpack_nibbles(words: np.ndarray) -> np.ndarray:
@@ -196,18 +198,19 @@ def _stacked(arrays, E: int):
     return N, K
 
 
-def gate_up(x, arrays, ws: MoeWorkspace, flags: int = 0) -> None:
-    """tce_moe_gate_up_f16: x fp16 [rows][K], arrays (qweight int32 [E][N][K/8], scales fp16, zeros int32) with gate / up rows interleaved -> ws.act(N / 2)"""
+def gate_up(x, arrays, ws: MoeWorkspace, flags: int = 0, tiled: bool = False) -> None:
+    """tce_moe_gate_up_f16 (tiled: tce_moe_gate_up_tiled_f16, the same bits): x fp16 [rows][K], arrays (qweight int32 [E][N][K/8], scales fp16, zeros int32) with gate /
+    up rows interleaved -> ws.act(N / 2)"""
     import torch
     N, K = _stacked(arrays, ws.E)
     assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1 and tuple(x.shape) == (ws.rows, K)
-    capi.check(capi.lib().tce_moe_gate_up_f16(_ptr(x), x.stride(0), *(_ptr(a) for a in arrays), ws.rows, ws.k, ws.E, N, K, GROUP, flags, ws.n_max, _ptr(ws.buf), _st()))
+    capi.check((capi.lib().tce_moe_gate_up_tiled_f16 if tiled else capi.lib().tce_moe_gate_up_f16)(_ptr(x), x.stride(0), *(_ptr(a) for a in arrays), ws.rows, ws.k, ws.E, N, K, GROUP, flags, ws.n_max, _ptr(ws.buf), _st()))
 
 
-def down(arrays, ws: MoeWorkspace, flags: int = 0) -> None:
-    """tce_moe_down_f16: ws.act(K) -> ws.y(N)"""
+def down(arrays, ws: MoeWorkspace, flags: int = 0, tiled: bool = False) -> None:
+    """tce_moe_down_f16 (tiled: tce_moe_down_tiled_f16, the same bits): ws.act(K) -> ws.y(N)"""
     N, K = _stacked(arrays, ws.E)
-    capi.check(capi.lib().tce_moe_down_f16(*(_ptr(a) for a in arrays), ws.rows, ws.k, ws.E, N, K, GROUP, flags, ws.n_max, _ptr(ws.buf), _st()))
+    capi.check((capi.lib().tce_moe_down_tiled_f16 if tiled else capi.lib().tce_moe_down_f16)(*(_ptr(a) for a in arrays), ws.rows, ws.k, ws.E, N, K, GROUP, flags, ws.n_max, _ptr(ws.buf), _st()))
 
 
 def combine_add(Cm, ws: MoeWorkspace) -> None:
@@ -222,9 +225,16 @@ class MoeFFN:
     down = (qweight int32 [E][hidden][ffn / 8], scales, zeros).  Synthetic weights, quantize_q4_6 per expert, as DecoderBlock's; nothing loads a checkpoint."""
 
     LAUNCHES = 5  # route (logits + selection, grouping), gate_up, down, combine
+    # forward runs the two contractions in the tiled form from this many pairs (rows * top_k) on; None: never.  From profiles/moe_tiled/moe_tiled_time.jsonl: the smallest
+    # measured P from which the tiled pair of launches beats the pass pair at every larger measured point by more than the repeats' spreads (slower at P = 32 and 128)
+    TILED_FROM_PAIRS = 256
 
-    def __init__(self, hidden: int, ffn: int, experts: int, top_k: int, device, renormalize: bool = True, seed: int = 0):
+    def __init__(self, hidden: int, ffn: int, experts: int, top_k: int, device, renormalize: bool = True, seed: int = 0, tiled_from=None):
+        """tiled_from: the pair count from which forward uses the tiled form (0: always); None: the class default TILED_FROM_PAIRS.  Both forms give the same bits."""
         import torch
+        if tiled_from is not None and int(tiled_from) < 0:
+            raise ValueError(f"tiled_from {tiled_from}: a pair count >= 0, or None for the default")
+        self.tiled_from = None if tiled_from is None else int(tiled_from)
         if not 1 <= int(top_k) <= capi.TCE_MOE_MAX_TOP_K or not int(top_k) <= int(experts) <= capi.TCE_MOE_MAX_EXPERTS:
             raise ValueError(f"top_k {top_k} of {experts} experts: 1 <= top_k <= {capi.TCE_MOE_MAX_TOP_K}, top_k <= experts <= {capi.TCE_MOE_MAX_EXPERTS}")
         if hidden % GROUP or ffn % GROUP:
@@ -263,7 +273,9 @@ class MoeFFN:
     def forward(self, xn, rows_inout) -> None:
         """xn fp16 [m][hidden], the normalised rows; rows_inout fp16 [m][hidden], the residual stream, updated in place.  Five launches on the current stream."""
         ws = self.workspace(xn.shape[0])
+        frm = self.TILED_FROM_PAIRS if self.tiled_from is None else self.tiled_from
+        tiled = frm is not None and ws.P >= frm
         route(xn, self.Wr, ws, self.renormalize)
-        gate_up(xn, self.gate_up, ws, self.flags)
-        down(self.down, ws, self.flags)
+        gate_up(xn, self.gate_up, ws, self.flags, tiled)
+        down(self.down, ws, self.flags, tiled)
         combine_add(rows_inout, ws)
