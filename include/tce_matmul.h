@@ -850,15 +850,39 @@ TCE_API int tce_embed_rows_f16(const void *table, int vocab, int hidden, const i
  *                          TCE_ERR_UNSUPPORTED_SHAPE for N, ldy or ldc not a multiple of 8, R not a multiple of 8, 2 R above TCE_LORA_MAX_RANK, n_adapters above
  *                          TCE_LORA_MAX_ADAPTERS, more than 262140 rows, Bg / Bu / y / C not 16-byte aligned, t / scale / row_adapter not 4-byte aligned.
  * Speculative rows need nothing here: the T rows of a slot carry the slot's word (row_adapter int32 [batch * T], written by the host).
- * NOT BUILT: a segmented expand for a fused q/k/v (its B is block-structured with zeros off the blocks), an MFMA shrink for long prefills, quantised adapters, adapters on
- * lm_head and the embedding. */
+ * THE TILED FORM, tce_lora_shrink_tiled_f16 / tce_lora_expand_add_tiled_f16 (csrc/lora_tiled.hip): the same operands and the same definition on matrix instructions,
+ * for calls with many rows (a prompt).  Workgroups own tiles of TCE_LORA_TILE_ROWS rows and walk the DISTINCT adapters among a tile's words, so the rows of a prompt
+ * share one read of their adapter per tile; there is no adapter dimension in the grid.
+ *   tce_lora_tiled_slices(K)   S(K), 1 .. TCE_LORA_TILED_MAX_SLICES: the shrink cuts K into S runs (1024 k each, longer where that would give more than 16); a function
+ *                              of K ALONE.  0 for K < 1.
+ *   tce_lora_tiled_workspace_bytes(rows, K, R)   S(K) * rows * R * 4: `partial`, fp32 [S][rows][R]; slice s holds a row's sum over the s-th run of K.  0 for an argument < 1.
+ *   tce_lora_shrink_tiled_f16       writes partial[s][i][0 .. R) for every slice s and every row i whose word names an adapter (v_mfma_f32_16x16x32_f16: exact products,
+ *                              fp32 sums); the partials of other rows are neither written nor read.
+ *   tce_lora_expand_add_tiled_f16   t[i][j] = ((p[0] + p[1]) + ...) + p[S - 1] in slice order in fp32 -- never stored, never rounded to fp16 --, then
+ *                              C[i][n] = fp16(fmaf(scale[a], sum_j t[i][j] * float(B[a][j][n]), float(C[i][n]))), the sum on v_mfma_f32_16x16x4_f32 with j ascending.  It
+ *                              takes K only to find S.
+ * The summation orders are not tce_lora_shrink_f16's / tce_lora_expand_add_f16's, so the results are NOT their bits (the same bound against the definition holds).  What
+ * the form keeps: no floating-point atomics; a row's bits depend only on that row's x, that row's C, its adapter's contents, K and R -- not on its index, `rows`, the
+ * other rows' words or data, or the grid; a row whose word lies outside [0, n_adapters) keeps C's bits and nothing of the pool is read for it.
+ * Refusals as for the pair above, in the same order, before any HIP call (`partial` in t's place; the expand also TCE_ERR_BAD_ARG for K < 1 and
+ * TCE_ERR_UNSUPPORTED_SHAPE for K not a multiple of 8).
+ * NOT BUILT: a segmented expand for a fused q/k/v (its B is block-structured with zeros off the blocks), a tiled gate/up expand (tce_lora_expand_silu_mul_f16 serves every
+ * row count), quantised adapters, adapters on lm_head and the embedding. */
 #define TCE_LORA_MAX_RANK     192   /* padded rank R of a pool: 8 .. 192 in steps of 8 (a fused q/k/v at r = 64) */
 #define TCE_LORA_MAX_ADAPTERS 64    /* adapters resident in one pool */
+#define TCE_LORA_TILE_ROWS    32    /* rows of a workgroup's tile in the tiled form */
+#define TCE_LORA_TILED_MAX_SLICES 16  /* the most K slices of the tiled shrink */
 TCE_API int tce_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, void *stream);
 TCE_API int tce_lora_expand_add_f16(const float *t, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int R, int n_adapters,
                                     void *stream);
 TCE_API int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C,
                                          int ldc, int rows, int N, int R, int n_adapters, void *stream);
+TCE_API int tce_lora_tiled_slices(int K);
+TCE_API size_t tce_lora_tiled_workspace_bytes(int rows, int K, int R);
+TCE_API int tce_lora_shrink_tiled_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *partial, int rows, int K, int R, int n_adapters,
+                                      void *stream);
+TCE_API int tce_lora_expand_add_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int K,
+                                          int R, int n_adapters, void *stream);
 /* Mixture of experts: a sparse MoE FFN on W4A16 (csrc/w4a16_moe.hip; additive within ABI 113, no existing struct or entry point changes).  Which expert a row uses is
  * decided per token ON THE DEVICE; nothing about the routing reaches the host, every launch has a fixed grid, and a captured graph follows a routing that changes.
  * With E experts, k experts per row, P = rows * k pairs (pair p = i * k + s is slot s of row i):

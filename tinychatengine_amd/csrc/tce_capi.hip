@@ -40,6 +40,11 @@ int launch_lora_expand_add_f16(const float *t, const void *B, const float *scale
                                hipStream_t stream, hipError_t *hip_err);
 int launch_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C, int ldc,
                                     int rows, int N, int R, int n_adapters, hipStream_t stream, hipError_t *hip_err);
+int lora_tiled_slices(int K);
+int launch_lora_shrink_tiled_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *partial, int rows, int K, int R, int n_adapters, hipStream_t stream,
+                                 hipError_t *hip_err);
+int launch_lora_expand_add_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int K, int R,
+                                     int n_adapters, hipStream_t stream, hipError_t *hip_err);
 size_t moe_workspace_bytes(int rows, int k, int E, int n_max);
 size_t moe_lds_bytes(int K);
 int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
@@ -1445,13 +1450,32 @@ static int check_lora_shape(const char *who, int rows, int R, int n_adapters) {
     return TCE_OK;
 }
 
-int tce_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, void *stream) {
-    if (!x || !A || !row_adapter || !t) return fail(TCE_ERR_BAD_ARG, "tce_lora_shrink_f16: null pointer");
-    if (rows < 1 || K < 1 || R < 1 || n_adapters < 1 || ldx < K) return fail(TCE_ERR_BAD_ARG, "tce_lora_shrink_f16: need rows, K, R, n_adapters >= 1 and ldx >= K");
-    if (K % 8 != 0 || ldx % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_shrink_f16: K %d, ldx %d (multiples of 8)", K, ldx);
-    if (const int rc = check_lora_shape("tce_lora_shrink_f16", rows, R, n_adapters)) return rc;
+// every refusal of a shrink (the 4-row form and the tiled one: `t` is the tiled form's `partial`), arguments before shapes
+static int check_lora_shrink(const char *who, const void *x, int ldx, const void *A, const int32_t *row_adapter, const float *t, int rows, int K, int R, int n_adapters) {
+    if (!x || !A || !row_adapter || !t) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (rows < 1 || K < 1 || R < 1 || n_adapters < 1 || ldx < K) return fail(TCE_ERR_BAD_ARG, "%s: need rows, K, R, n_adapters >= 1 and ldx >= K", who);
+    if (K % 8 != 0 || ldx % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: K %d, ldx %d (multiples of 8)", who, K, ldx);
+    if (const int rc = check_lora_shape(who, rows, R, n_adapters)) return rc;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(A)) % 16 != 0 || (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t)) % 4 != 0)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_shrink_f16: 16-byte aligned x / A, 4-byte aligned row_adapter / t");
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned x / A, 4-byte aligned row_adapter / t", who);
+    return TCE_OK;
+}
+
+// ... and of an expand; K: the tiled form's (it finds its slices from it), 8 for the 4-row form
+static int check_lora_expand(const char *who, const float *t, const void *B, const float *scale, const int32_t *row_adapter, const void *Cm, int ldc, int rows, int N, int K,
+                             int R, int n_adapters) {
+    if (!t || !B || !scale || !row_adapter || !Cm) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (rows < 1 || N < 1 || K < 1 || R < 1 || n_adapters < 1 || ldc < N) return fail(TCE_ERR_BAD_ARG, "%s: need rows, N, R, n_adapters (the tiled form: K) >= 1 and ldc >= N", who);
+    if (N % 8 != 0 || K % 8 != 0 || ldc % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d, ldc %d (the tiled form: K %d) (multiples of 8)", who, N, ldc, K);
+    if (const int rc = check_lora_shape(who, rows, R, n_adapters)) return rc;
+    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(Cm)) % 16 != 0 ||
+        (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(scale)) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned B / C, 4-byte aligned row_adapter / t / scale", who);
+    return TCE_OK;
+}
+
+int tce_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *t, int rows, int K, int R, int n_adapters, void *stream) {
+    if (const int rc = check_lora_shrink("tce_lora_shrink_f16", x, ldx, A, row_adapter, t, rows, K, R, n_adapters)) return rc;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_lora_shrink_f16(x, ldx, A, row_adapter, t, rows, K, R, n_adapters, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA shrink launch") : rc;
@@ -1459,16 +1483,33 @@ int tce_lora_shrink_f16(const void *x, int ldx, const void *A, const int32_t *ro
 
 int tce_lora_expand_add_f16(const float *t, const void *B, const float *scale, const int32_t *row_adapter, void *Cm, int ldc, int rows, int N, int R, int n_adapters,
                             void *stream) {
-    if (!t || !B || !scale || !row_adapter || !Cm) return fail(TCE_ERR_BAD_ARG, "tce_lora_expand_add_f16: null pointer");
-    if (rows < 1 || N < 1 || R < 1 || n_adapters < 1 || ldc < N) return fail(TCE_ERR_BAD_ARG, "tce_lora_expand_add_f16: need rows, N, R, n_adapters >= 1 and ldc >= N");
-    if (N % 8 != 0 || ldc % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_expand_add_f16: N %d, ldc %d (multiples of 8)", N, ldc);
-    if (const int rc = check_lora_shape("tce_lora_expand_add_f16", rows, R, n_adapters)) return rc;
-    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(Cm)) % 16 != 0 ||
-        (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(scale)) % 4 != 0)
-        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "tce_lora_expand_add_f16: 16-byte aligned B / C, 4-byte aligned row_adapter / t / scale");
+    if (const int rc = check_lora_expand("tce_lora_expand_add_f16", t, B, scale, row_adapter, Cm, ldc, rows, N, 8, R, n_adapters)) return rc;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_lora_expand_add_f16(t, B, scale, row_adapter, Cm, ldc, rows, N, R, n_adapters, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA expand launch") : rc;
+}
+
+// the tiled form (csrc/lora_tiled.hip): the pair's refusals, in the pair's order
+int tce_lora_tiled_slices(int K) { return K < 1 ? 0 : tce::lora_tiled_slices(K); }
+
+size_t tce_lora_tiled_workspace_bytes(int rows, int K, int R) {
+    if (rows < 1 || K < 1 || R < 1) return 0;
+    return (size_t)tce::lora_tiled_slices(K) * (size_t)rows * (size_t)R * sizeof(float);
+}
+
+int tce_lora_shrink_tiled_f16(const void *x, int ldx, const void *A, const int32_t *row_adapter, float *partial, int rows, int K, int R, int n_adapters, void *stream) {
+    if (const int rc = check_lora_shrink("tce_lora_shrink_tiled_f16", x, ldx, A, row_adapter, partial, rows, K, R, n_adapters)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_shrink_tiled_f16(x, ldx, A, row_adapter, partial, rows, K, R, n_adapters, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "tiled LoRA shrink launch") : rc;
+}
+
+int tce_lora_expand_add_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *Cm, int ldc, int rows, int N, int K, int R,
+                                  int n_adapters, void *stream) {
+    if (const int rc = check_lora_expand("tce_lora_expand_add_tiled_f16", partial, B, scale, row_adapter, Cm, ldc, rows, N, K, R, n_adapters)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_expand_add_tiled_f16(partial, B, scale, row_adapter, Cm, ldc, rows, N, K, R, n_adapters, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "tiled LoRA expand launch") : rc;
 }
 
 int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *Cm, int ldc,

@@ -26,6 +26,12 @@ column 2n + 1 = up n) and tce_lora_expand_silu_mul_f16, which adds both deltas i
     expand_silu_mul          the launch on torch tensors
     lora_gate_up_reference   its definition in float64, the two roundings to fp16, then the oracle's SiLU * mul (silu_mul_reference restates it)
 
+LoraPool(..., tiled_from=M) runs the adapted "qkv", "o" and "down" in the TILED form (csrc/lora_tiled.hip: 32-row tiles on matrix instructions, an adapter read once
+per tile) for calls of at least M rows -- a prompt; below M, and in every pool built without it, today's launches run.  The tiled sums have another order: the results
+meet the same bound against lora_reference but are not the 4-row kernels' bits, which is why it is opt-in.
+
+    shrink_tiled, expand_add_tiled   the two launches on torch tensors; partial fp32 [S][rows][R] between them (tiled_workspace), S = tiled_slices(K)
+
 LoraPool(..., rows_per_seq=T) serves the speculative step: row_adapter is int32 [batch * T], the T rows of a slot carry the slot's word (set_slot writes it T times;
 no launch is added: the host writes the word anyway).
 """
@@ -120,6 +126,44 @@ def expand_add(t, B, scale, row_adapter, Cm, rows: int | None = None) -> None:
                                                   C.c_void_p(_stream())))
 
 
+def tiled_slices(K: int) -> int:
+    """tce_lora_tiled_slices: the K slices of the tiled shrink, 1 .. capi.TCE_LORA_TILED_MAX_SLICES, a function of K alone"""
+    return int(capi.lib().tce_lora_tiled_slices(int(K)))
+
+
+def tiled_workspace(rows: int, K: int, R: int, device):
+    """partial fp32 [S(K)][rows][R] (tce_lora_tiled_workspace_bytes; need not be zeroed): what shrink_tiled writes and expand_add_tiled sums"""
+    import torch
+    S = tiled_slices(K)
+    assert S >= 1 and capi.lib().tce_lora_tiled_workspace_bytes(int(rows), int(K), int(R)) == S * rows * R * 4
+    return torch.empty((S, rows, R), dtype=torch.float32, device=device)
+
+
+def shrink_tiled(x, A, row_adapter, partial, rows: int | None = None) -> None:
+    """tce_lora_shrink_tiled_f16: x fp16 [rows][K] (row stride x.stride(0)), A fp16 [n][R][K], row_adapter int32 [rows], partial fp32 [S(K)][rows][R]."""
+    import torch
+    from .linear import _stream
+    assert x.dtype == A.dtype == torch.float16 and partial.dtype == torch.float32 and row_adapter.dtype == torch.int32
+    assert x.dim() == 2 and x.stride(1) == 1 and A.is_contiguous() and A.dim() == 3 and partial.is_contiguous() and row_adapter.is_contiguous()
+    rows = x.shape[0] if rows is None else rows
+    assert row_adapter.numel() >= rows and x.shape[1] == A.shape[2] and tuple(partial.shape) == (tiled_slices(A.shape[2]), rows, A.shape[1])
+    capi.check(capi.lib().tce_lora_shrink_tiled_f16(_ptr(x), x.stride(0), _ptr(A), _ptr(row_adapter), _ptr(partial), rows, A.shape[2], A.shape[1], A.shape[0],
+                                                    C.c_void_p(_stream())))
+
+
+def expand_add_tiled(partial, B, scale, row_adapter, Cm, K: int, rows: int | None = None) -> None:
+    """tce_lora_expand_add_tiled_f16: partial fp32 [S(K)][rows][R] (the shrink's K), B fp16 [n][R][N], scale fp32 [n], row_adapter int32 [rows], Cm fp16 [rows][N] (row
+    stride Cm.stride(0)), in place."""
+    import torch
+    from .linear import _stream
+    assert Cm.dtype == B.dtype == torch.float16 and partial.dtype == scale.dtype == torch.float32 and row_adapter.dtype == torch.int32
+    assert Cm.dim() == 2 and Cm.stride(1) == 1 and B.is_contiguous() and B.dim() == 3 and partial.is_contiguous() and row_adapter.is_contiguous() and scale.is_contiguous()
+    rows = Cm.shape[0] if rows is None else rows
+    assert row_adapter.numel() >= rows and Cm.shape[1] == B.shape[2] and scale.numel() == B.shape[0] and tuple(partial.shape) == (tiled_slices(K), rows, B.shape[1])
+    capi.check(capi.lib().tce_lora_expand_add_tiled_f16(_ptr(partial), _ptr(B), _ptr(scale), _ptr(row_adapter), _ptr(Cm), Cm.stride(0), rows, B.shape[2], int(K), B.shape[1],
+                                                        B.shape[0], C.c_void_p(_stream())))
+
+
 def expand_silu_mul(t, Bg, Bu, scale, row_adapter, y, Cm, rows: int | None = None) -> None:
     """tce_lora_expand_silu_mul_f16: t fp32 [rows][2R], Bg / Bu fp16 [n][R][N], scale fp32 [n], row_adapter int32 [rows], y fp16 [rows][2N] (row stride y.stride(0), only
     read), Cm fp16 [rows][N] (row stride Cm.stride(0)): SiLU(g) * u of every row, g and u with the row's deltas added."""
@@ -204,16 +248,26 @@ class LoraLayer:
     def row_adapter(self):
         return self.pool.row_adapter
 
+    def tiled(self, target: str, rows: int) -> bool:
+        """does a call of `rows` rows run `target` in the tiled form?  (a pool built with tiled_from=, qkv / o / down, at least that many rows)"""
+        return self.pool.tiled_from is not None and target in TARGETS and rows >= self.pool.tiled_from
+
     def workspace(self, rows: int) -> dict:
-        """{target: t fp32 [rows][R]} for `rows` rows (the shrink's output; need not be zeroed); "gate_up": [rows][2 * rank]"""
+        """{target: t fp32 [rows][R]} for `rows` rows (the shrink's output; need not be zeroed); "gate_up": [rows][2 * rank].  Where the tiled form will run:
+        its partial sums, fp32 [S(K)][rows][R]."""
         import torch
-        return {t: torch.empty((rows, self.A[t].shape[1]), dtype=torch.float32, device=self.pool.device) for t in self.A}
+        return {t: tiled_workspace(rows, self.A[t].shape[2], self.A[t].shape[1], self.pool.device) if self.tiled(t, rows) else
+                torch.empty((rows, self.A[t].shape[1]), dtype=torch.float32, device=self.pool.device) for t in self.A}
 
     def shrink(self, target: str, x, t, row_adapter=None) -> None:
-        shrink(x, self.A[target], self.row_adapter if row_adapter is None else row_adapter, t)
+        (shrink_tiled if self.tiled(target, x.shape[0]) else shrink)(x, self.A[target], self.row_adapter if row_adapter is None else row_adapter, t)
 
     def expand_add(self, target: str, t, Cm, row_adapter=None) -> None:
-        expand_add(t, self.B[target], self.scale, self.row_adapter if row_adapter is None else row_adapter, Cm)
+        words = self.row_adapter if row_adapter is None else row_adapter
+        if self.tiled(target, Cm.shape[0]):
+            expand_add_tiled(t, self.B[target], self.scale, words, Cm, self.A[target].shape[2])
+        else:
+            expand_add(t, self.B[target], self.scale, words, Cm)
 
     def expand_silu_mul(self, t, y, Cm, row_adapter=None) -> None:
         """gate_up=True pools: t = the shrink of "gate_up", y the base gate_up linear's [rows][2 * ffn], Cm [rows][ffn]"""
@@ -231,9 +285,12 @@ class LoraPool:
     gate_up=True: the fourth target (A["gate_up"] [layers][max_adapters][2 * rank][hidden], Bg and Bu [layers][max_adapters][rank][ffn]); load accepts gate_proj and
     up_proj, and the decoders run gate/up as shrink + base linear + tce_lora_expand_silu_mul_f16.  False (the default): gate_proj / up_proj are refused, as before.
     rows_per_seq=T: a pool for the speculative step -- row_adapter is int32 [batch * T] and a slot's word stands T times (set_slot).  None (the default): one word per
-    slot; such a pool is not built for rows."""
+    slot; such a pool is not built for rows.
+    tiled_from=M (an integer >= 1): calls of at least M rows run qkv / o / down in the tiled form (csrc/lora_tiled.hip); None (the default): never -- every row count
+    runs the 4-row kernels, bit for bit as before.  "gate_up" keeps tce_lora_expand_silu_mul_f16 at every row count."""
 
-    def __init__(self, block_shapes, layers: int, max_adapters: int, rank: int, device, gate_up: bool = False, rows_per_seq: int | None = None):
+    def __init__(self, block_shapes, layers: int, max_adapters: int, rank: int, device, gate_up: bool = False, rows_per_seq: int | None = None,
+                 tiled_from: int | None = None):
         import torch
         if int(rank) != rank or rank < 8 or rank % 8 != 0 or 3 * rank > capi.TCE_LORA_MAX_RANK:
             raise ValueError(f"rank {rank}: a multiple of 8 from 8 to {capi.TCE_LORA_MAX_RANK // 3} (the fused q/k/v runs at 3 * rank <= {capi.TCE_LORA_MAX_RANK})")
@@ -243,6 +300,9 @@ class LoraPool:
             raise ValueError("layers >= 1")
         if rows_per_seq is not None and (int(rows_per_seq) != rows_per_seq or not 1 <= int(rows_per_seq) <= capi.TCE_SPEC_MAX_ROWS):
             raise ValueError(f"rows_per_seq {rows_per_seq}: None or 1 .. {capi.TCE_SPEC_MAX_ROWS} (the speculative step's rows per sequence)")
+        if tiled_from is not None and (isinstance(tiled_from, bool) or not isinstance(tiled_from, int) or tiled_from < 1):
+            raise ValueError(f"tiled_from {tiled_from!r}: None (never the tiled form) or an integer >= 1 (the row count from which a call runs it)")
+        self.tiled_from = tiled_from
         self.shapes, self.layers, self.max_adapters, self.rank, self.device = _shapes(block_shapes), int(layers), int(max_adapters), int(rank), torch.device(device)
         self.gate_up, self.rows_per_seq = bool(gate_up), None if rows_per_seq is None else int(rows_per_seq)
         self.target_shapes = target_shapes(self.shapes, self.rank, self.gate_up)
