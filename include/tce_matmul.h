@@ -866,8 +866,23 @@ TCE_API int tce_embed_rows_f16(const void *table, int vocab, int hidden, const i
  * other rows' words or data, or the grid; a row whose word lies outside [0, n_adapters) keeps C's bits and nothing of the pool is read for it.
  * Refusals as for the pair above, in the same order, before any HIP call (`partial` in t's place; the expand also TCE_ERR_BAD_ARG for K < 1 and
  * TCE_ERR_UNSUPPORTED_SHAPE for K not a multiple of 8).
- * NOT BUILT: a segmented expand for a fused q/k/v (its B is block-structured with zeros off the blocks), a tiled gate/up expand (tce_lora_expand_silu_mul_f16 serves every
- * row count), quantised adapters, adapters on lm_head and the embedding. */
+ * THE SEGMENTED TILED EXPANDS, tce_lora_expand_silu_mul_tiled_f16 / tce_lora_expand_add_segmented_tiled_f16 (csrc/lora_tiled_seg.hip): two more expands behind
+ * tce_lora_shrink_tiled_f16, the tiled expand with a column tile that walks only ITS block of B and of t -- no zero of a block-structured B is loaded, converted or multiplied.
+ *   tce_lora_expand_silu_mul_tiled_f16   the tiled form of tce_lora_expand_silu_mul_f16: partial fp32 [S(K)][rows][2R] (the tiled shrink on the stacked A [2R][K]); Bg, Bu,
+ *                              y, C as there.  t as in the tiled expand (slice order, never stored or rounded); for a row whose word a names an adapter
+ *                              g = fp16(fmaf(scale[a], sum_{j<R} t[i][j] * float(Bg[a][j][n]), float(y[i][2n]))), u likewise from t[i][R+j], Bu and y[i][2n+1], the sums on
+ *                              v_mfma_f32_16x16x4_f32 from +0 with j ascending (tce_lora_expand_add_tiled_f16's order); any other word: g = y[i][2n], u = y[i][2n+1], and
+ *                              nothing of the pool, of scale or of partial is read for the row.  EVERY row below `rows` gets C[i][n] = SiLuMul_half(g, u).  For finite t
+ *                              bit-identical to tce_lora_expand_add_tiled_f16 on a copy of y with the block-structured B' [2R][2N], de-interleaved, then tce_silu_mul_half.
+ *   tce_lora_expand_add_segmented_tiled_f16   tce_lora_expand_add_tiled_f16's operands plus seg_cols, a HOST array of segments + 1 ascending column bounds read at the call
+ *                              (seg_cols[0] = 0, seg_cols[segments] = N, 1 <= segments <= 4): columns [seg_cols[s], seg_cols[s+1]) sum j over
+ *                              [s R / segments, (s + 1) R / segments) only, and nothing of B or t outside that block is read.  Bit-identical to tce_lora_expand_add_tiled_f16
+ *                              whenever t is finite and B is zero off its blocks (a fused q/k/v: segments = 3).
+ * Refusals before any HIP call, every TCE_ERR_BAD_ARG rule before the first TCE_ERR_UNSUPPORTED_SHAPE rule: those of tce_lora_expand_silu_mul_f16 (C overlapping y among
+ * them) resp. tce_lora_expand_add_tiled_f16, `partial` in t's place, plus K (< 1: TCE_ERR_BAD_ARG; not a multiple of 8: TCE_ERR_UNSUPPORTED_SHAPE); the segmented one also
+ * TCE_ERR_BAD_ARG for a null seg_cols, segments outside 1 .. 4, seg_cols[0] != 0, seg_cols[segments] != N or bounds that do not strictly ascend, and
+ * TCE_ERR_UNSUPPORTED_SHAPE for R not a multiple of 8 * segments or an inner bound that is not a multiple of 128 (a workgroup's 128-column tile lies in one segment).
+ * NOT BUILT: quantised adapters, adapters on lm_head and the embedding. */
 #define TCE_LORA_MAX_RANK     192   /* padded rank R of a pool: 8 .. 192 in steps of 8 (a fused q/k/v at r = 64) */
 #define TCE_LORA_MAX_ADAPTERS 64    /* adapters resident in one pool */
 #define TCE_LORA_TILE_ROWS    32    /* rows of a workgroup's tile in the tiled form */
@@ -883,6 +898,10 @@ TCE_API int tce_lora_shrink_tiled_f16(const void *x, int ldx, const void *A, con
                                       void *stream);
 TCE_API int tce_lora_expand_add_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int K,
                                           int R, int n_adapters, void *stream);
+TCE_API int tce_lora_expand_silu_mul_tiled_f16(const float *partial, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy,
+                                               void *C, int ldc, int rows, int N, int K, int R, int n_adapters, void *stream);
+TCE_API int tce_lora_expand_add_segmented_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N,
+                                                    int K, int R, int n_adapters, const int *seg_cols, int segments, void *stream);
 /* Mixture of experts: a sparse MoE FFN on W4A16 (csrc/w4a16_moe.hip; additive within ABI 113, no existing struct or entry point changes).  Which expert a row uses is
  * decided per token ON THE DEVICE; nothing about the routing reaches the host, every launch has a fixed grid, and a captured graph follows a routing that changes.
  * With E experts, k experts per row, P = rows * k pairs (pair p = i * k + s is slot s of row i):

@@ -27,20 +27,13 @@
 //   of 8 = two v_mfma_f32_16x16x4_f32 (lane group kq on j0 + 2 kq, then j0 + 2 kq + 1), B's columns on the M side and the rows on the N side: a lane ends with 4
 //   adjacent columns of one row.  Epilogue fmaf(scale[a], acc, float(C)) and ONE rounding to fp16, stored for the pass's rows only.
 // The unit is built without packed fp32 arithmetic (build.py) and with -ffp-contract=off: the sums beside the MFMAs are plain v_add_f32.
-#include "tce_common.hpp"
+#include "lora_tiled.hpp"  // the tile, the staged chunk, walk_adapters: shared with lora_tiled_seg.hip
 
 namespace tce {
 namespace {
 
-constexpr int kTileRows = TCE_LORA_TILE_ROWS;
-constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kRun = 1024;         // k of a slice, unless K would need more than TCE_LORA_TILED_MAX_SLICES of them
 constexpr int kSuper = 128;        // k of one wave iteration of the shrink: four MFMA steps
-constexpr int kExpandCols = 128;   // columns of an expand workgroup: 32 per wave
-constexpr int kChunkJ = 64;        // rows of B staged at once
-constexpr int kLdB = kExpandCols + 8;  // fp32 row stride of the staged chunk: the four lane groups' rows (2 kq + s) fall on different banks
-static_assert(kTileRows == 32, "lane i and lane 32 + i read word i; two MFMA row blocks");
-static_assert(kChunkJ * (kExpandCols / 8) == 4 * kThreads && kExpandCols == kWaves * 32, "the expand's request view: four 16-byte pieces per thread; two column blocks per wave");
 
 __host__ __device__ inline int tiled_run(int K) {
     if ((K + kRun - 1) / kRun <= TCE_LORA_TILED_MAX_SLICES) return kRun;
@@ -52,21 +45,6 @@ __device__ __forceinline__ half8_t load8_or_zero(const half_t *p, bool ok) {
     uint4_t v = {0u, 0u, 0u, 0u};
     if (ok) v = *reinterpret_cast<const uint4_t *>(p);
     return __builtin_bit_cast(half8_t, v);
-}
-
-// the tile's distinct valid adapters, every wave for itself and all waves alike: body(adapter, the 32-bit set of the tile's rows on it)
-template <class Body>
-__device__ __forceinline__ void walk_adapters(const int32_t *__restrict__ row_adapter, int row0, int rows, int n_adapters, Body body) {
-    const int i = row0 + (threadIdx.x & 31);
-    const int w = i < rows ? row_adapter[i] : -1;
-    const bool valid = w >= 0 && w < n_adapters;
-    unsigned pending = (unsigned)__ballot(valid);
-    while (pending) {
-        const int a = __builtin_amdgcn_readlane(w, __builtin_amdgcn_readfirstlane(__builtin_ctz(pending)));
-        const unsigned same = (unsigned)__ballot(valid && w == a);
-        pending &= ~same;
-        body(a, same);
-    }
 }
 
 template <int NJB>

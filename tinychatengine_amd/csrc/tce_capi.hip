@@ -45,6 +45,10 @@ int launch_lora_shrink_tiled_f16(const void *x, int ldx, const void *A, const in
                                  hipError_t *hip_err);
 int launch_lora_expand_add_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int K, int R,
                                      int n_adapters, hipStream_t stream, hipError_t *hip_err);
+int launch_lora_expand_silu_mul_tiled_f16(const float *partial, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *C,
+                                          int ldc, int rows, int N, int K, int R, int n_adapters, hipStream_t stream, hipError_t *hip_err);
+int launch_lora_expand_add_segmented_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *C, int ldc, int rows, int N, int K,
+                                               int R, int n_adapters, const int *seg_cols, int segments, hipStream_t stream, hipError_t *hip_err);
 size_t moe_workspace_bytes(int rows, int k, int E, int n_max);
 size_t moe_lds_bytes(int K);
 int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
@@ -1512,27 +1516,61 @@ int tce_lora_expand_add_tiled_f16(const float *partial, const void *B, const flo
     return rc == TCE_ERR_HIP ? hip_fail(he, "tiled LoRA expand launch") : rc;
 }
 
-int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *Cm, int ldc,
-                                 int rows, int N, int R, int n_adapters, void *stream) {
-    const char *who = "tce_lora_expand_silu_mul_f16";
+// every refusal of a gate/up expand (the 4-row form and the tiled one: `t` is the tiled form's `partial`; K: the tiled form's, 8 for the 4-row form), arguments before shapes
+static int check_lora_expand_silu_mul(const char *who, const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy,
+                                      const void *Cm, int ldc, int rows, int N, int K, int R, int n_adapters) {
     if (!t || !Bg || !Bu || !scale || !row_adapter || !y || !Cm) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
-    if (rows < 1 || N < 1 || R < 1 || n_adapters < 1 || ldy < 2 * (long long)N || ldc < N)
-        return fail(TCE_ERR_BAD_ARG, "%s: need rows, N, R, n_adapters >= 1, ldy >= 2 N and ldc >= N", who);
+    if (rows < 1 || N < 1 || K < 1 || R < 1 || n_adapters < 1 || ldy < 2 * (long long)N || ldc < N)
+        return fail(TCE_ERR_BAD_ARG, "%s: need rows, N, R, n_adapters (the tiled form: K) >= 1, ldy >= 2 N and ldc >= N", who);
     {  // y is only read and C is written by other lanes than those that read the pair: the two ranges must not meet
         const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), c0 = reinterpret_cast<uintptr_t>(Cm);
         const uintptr_t y1 = y0 + ((uintptr_t)(rows - 1) * (uintptr_t)ldy + 2 * (uintptr_t)N) * 2, c1 = c0 + ((uintptr_t)(rows - 1) * (uintptr_t)ldc + (uintptr_t)N) * 2;
         if (y0 < c1 && c0 < y1) return fail(TCE_ERR_BAD_ARG, "%s: C overlaps y", who);
     }
-    if (N % 8 != 0 || ldy % 8 != 0 || ldc % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d, ldy %d, ldc %d (multiples of 8)", who, N, ldy, ldc);
+    if (N % 8 != 0 || K % 8 != 0 || ldy % 8 != 0 || ldc % 8 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d, ldy %d, ldc %d (the tiled form: K %d) (multiples of 8)", who, N, ldy, ldc, K);
     if (R % 8 != 0 || R > TCE_LORA_MAX_RANK / 2)  // (t carries gate's and up's sums: 2 R <= TCE_LORA_MAX_RANK, the shrink's bound)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: R %d (a multiple of 8, 8 .. %d: gate's and up's rows share the shrink's %d)", who, R, TCE_LORA_MAX_RANK / 2, TCE_LORA_MAX_RANK);
     if (const int rc = check_lora_shape(who, rows, 2 * R, n_adapters)) return rc;
     if ((reinterpret_cast<uintptr_t>(Bg) | reinterpret_cast<uintptr_t>(Bu) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(Cm)) % 16 != 0 ||
         (reinterpret_cast<uintptr_t>(row_adapter) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(scale)) % 4 != 0)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned Bg / Bu / y / C, 4-byte aligned row_adapter / t / scale", who);
+    return TCE_OK;
+}
+
+int tce_lora_expand_silu_mul_f16(const float *t, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *Cm, int ldc,
+                                 int rows, int N, int R, int n_adapters, void *stream) {
+    if (const int rc = check_lora_expand_silu_mul("tce_lora_expand_silu_mul_f16", t, Bg, Bu, scale, row_adapter, y, ldy, Cm, ldc, rows, N, 8, R, n_adapters)) return rc;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_lora_expand_silu_mul_f16(t, Bg, Bu, scale, row_adapter, y, ldy, Cm, ldc, rows, N, R, n_adapters, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "LoRA gate/up expand launch") : rc;
+}
+
+// the segmented tiled expands (csrc/lora_tiled_seg.hip), both behind tce_lora_shrink_tiled_f16: the refusals of the forms they stand beside, in their order
+int tce_lora_expand_silu_mul_tiled_f16(const float *partial, const void *Bg, const void *Bu, const float *scale, const int32_t *row_adapter, const void *y, int ldy, void *Cm,
+                                       int ldc, int rows, int N, int K, int R, int n_adapters, void *stream) {
+    if (const int rc = check_lora_expand_silu_mul("tce_lora_expand_silu_mul_tiled_f16", partial, Bg, Bu, scale, row_adapter, y, ldy, Cm, ldc, rows, N, K, R, n_adapters)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_expand_silu_mul_tiled_f16(partial, Bg, Bu, scale, row_adapter, y, ldy, Cm, ldc, rows, N, K, R, n_adapters, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "tiled LoRA gate/up expand launch") : rc;
+}
+
+int tce_lora_expand_add_segmented_tiled_f16(const float *partial, const void *B, const float *scale, const int32_t *row_adapter, void *Cm, int ldc, int rows, int N, int K, int R,
+                                            int n_adapters, const int *seg_cols, int segments, void *stream) {
+    const char *who = "tce_lora_expand_add_segmented_tiled_f16";
+    // the segment list's argument rules first (they decide what of seg_cols may be read), then the expand's, arguments before shapes; then the list's shape rules
+    if (!seg_cols || segments < 1 || segments > 4) return fail(TCE_ERR_BAD_ARG, "%s: need seg_cols and 1 .. 4 segments (got %d)", who, segments);
+    if (seg_cols[0] != 0 || seg_cols[segments] != N) return fail(TCE_ERR_BAD_ARG, "%s: seg_cols must begin at 0 and end at N %d (got %d .. %d)", who, N, seg_cols[0], seg_cols[segments]);
+    for (int s = 0; s < segments; ++s)
+        if (seg_cols[s] >= seg_cols[s + 1]) return fail(TCE_ERR_BAD_ARG, "%s: seg_cols must ascend (bound %d: %d, then %d)", who, s, seg_cols[s], seg_cols[s + 1]);
+    if (const int rc = check_lora_expand(who, partial, B, scale, row_adapter, Cm, ldc, rows, N, K, R, n_adapters)) return rc;
+    if (R % (8 * segments) != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: R %d in %d segments (every segment's block of B a multiple of 8 rows)", who, R, segments);
+    for (int s = 1; s < segments; ++s)  // (the last bound is N: a tile that ends there is cut like tce_lora_expand_add_tiled_f16's)
+        if (seg_cols[s] % 128 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: segment bound %d (a multiple of 128: a workgroup's column tile lies in one segment)", who, seg_cols[s]);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_lora_expand_add_segmented_tiled_f16(partial, B, scale, row_adapter, Cm, ldc, rows, N, K, R, n_adapters, seg_cols, segments,
+                                                                   static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "segmented tiled LoRA expand launch") : rc;
 }
 
 // ---- mixture of experts (csrc/w4a16_moe.hip).  The rules the five entry points share, in the order they run: every argument refusal, then every shape refusal ----

@@ -32,6 +32,11 @@ meet the same bound against lora_reference but are not the 4-row kernels' bits, 
 
     shrink_tiled, expand_add_tiled   the two launches on torch tensors; partial fp32 [S][rows][R] between them (tiled_workspace), S = tiled_slices(K)
 
+LoraPool(..., tiled_from=M, segmented=True) runs, from M rows on, the SEGMENTED tiled expands (csrc/lora_tiled_seg.hip): qkv's expand walks each of q's, k's and v's own
+block of B alone (the tiled expand's bits without reading the zeros), and a gate_up=True pool runs "gate_up" tiled as well -- shrink_tiled on the stacked A, then
+
+    expand_silu_mul_tiled, expand_add_segmented_tiled   the two launches on torch tensors
+
 LoraPool(..., rows_per_seq=T) serves the speculative step: row_adapter is int32 [batch * T], the T rows of a slot carry the slot's word (set_slot writes it T times;
 no launch is added: the host writes the word anyway).
 """
@@ -179,6 +184,35 @@ def expand_silu_mul(t, Bg, Bu, scale, row_adapter, y, Cm, rows: int | None = Non
                                                        C.c_void_p(_stream())))
 
 
+def expand_silu_mul_tiled(partial, Bg, Bu, scale, row_adapter, y, Cm, K: int, rows: int | None = None) -> None:
+    """tce_lora_expand_silu_mul_tiled_f16: partial fp32 [S(K)][rows][2R] (shrink_tiled on the stacked A), the other operands as expand_silu_mul's."""
+    import torch
+    from .linear import _stream
+    assert Cm.dtype == y.dtype == Bg.dtype == Bu.dtype == torch.float16 and partial.dtype == scale.dtype == torch.float32 and row_adapter.dtype == torch.int32
+    assert Cm.dim() == y.dim() == 2 and Cm.stride(1) == y.stride(1) == 1 and Bg.is_contiguous() and Bu.is_contiguous() and Bg.dim() == 3 and Bg.shape == Bu.shape
+    assert partial.is_contiguous() and row_adapter.is_contiguous() and scale.is_contiguous()
+    rows = Cm.shape[0] if rows is None else rows
+    n, R, N = Bg.shape
+    assert row_adapter.numel() >= rows and tuple(partial.shape) == (tiled_slices(K), rows, 2 * R) and y.shape[0] >= rows and Cm.shape[1] == N and y.shape[1] == 2 * N
+    assert scale.numel() == n
+    capi.check(capi.lib().tce_lora_expand_silu_mul_tiled_f16(_ptr(partial), _ptr(Bg), _ptr(Bu), _ptr(scale), _ptr(row_adapter), _ptr(y), y.stride(0), _ptr(Cm), Cm.stride(0), rows,
+                                                             N, int(K), R, n, C.c_void_p(_stream())))
+
+
+def expand_add_segmented_tiled(partial, B, scale, row_adapter, Cm, K: int, seg_cols, rows: int | None = None) -> None:
+    """tce_lora_expand_add_segmented_tiled_f16: expand_add_tiled's operands and seg_cols, len(seg_cols) - 1 segments' ascending column bounds (host integers, 0 first, N
+    last): segment s sums block s of B's rows alone."""
+    import torch
+    from .linear import _stream
+    assert Cm.dtype == B.dtype == torch.float16 and partial.dtype == scale.dtype == torch.float32 and row_adapter.dtype == torch.int32
+    assert Cm.dim() == 2 and Cm.stride(1) == 1 and B.is_contiguous() and B.dim() == 3 and partial.is_contiguous() and row_adapter.is_contiguous() and scale.is_contiguous()
+    rows = Cm.shape[0] if rows is None else rows
+    assert row_adapter.numel() >= rows and Cm.shape[1] == B.shape[2] and scale.numel() == B.shape[0] and tuple(partial.shape) == (tiled_slices(K), rows, B.shape[1])
+    bounds = (C.c_int * len(seg_cols))(*(int(v) for v in seg_cols))
+    capi.check(capi.lib().tce_lora_expand_add_segmented_tiled_f16(_ptr(partial), _ptr(B), _ptr(scale), _ptr(row_adapter), _ptr(Cm), Cm.stride(0), rows, B.shape[2], int(K),
+                                                                  B.shape[1], B.shape[0], bounds, len(seg_cols) - 1, C.c_void_p(_stream())))
+
+
 def _shapes(block_shapes) -> dict:
     """hidden / heads / kv_heads / ffn from a dict or from anything with these attributes (a DecoderBlock); head_dim is 128."""
     get = (lambda k: block_shapes[k]) if isinstance(block_shapes, dict) else (lambda k: getattr(block_shapes, k))
@@ -249,12 +283,13 @@ class LoraLayer:
         return self.pool.row_adapter
 
     def tiled(self, target: str, rows: int) -> bool:
-        """does a call of `rows` rows run `target` in the tiled form?  (a pool built with tiled_from=, qkv / o / down, at least that many rows)"""
-        return self.pool.tiled_from is not None and target in TARGETS and rows >= self.pool.tiled_from
+        """does a call of `rows` rows run `target` in the tiled form?  (a pool built with tiled_from=, qkv / o / down -- segmented=True: gate_up too --, at least that
+        many rows)"""
+        return self.pool.tiled_from is not None and (target in TARGETS or (target == GATE_UP and self.pool.gate_up and self.pool.segmented)) and rows >= self.pool.tiled_from
 
     def workspace(self, rows: int) -> dict:
         """{target: t fp32 [rows][R]} for `rows` rows (the shrink's output; need not be zeroed); "gate_up": [rows][2 * rank].  Where the tiled form will run:
-        its partial sums, fp32 [S(K)][rows][R]."""
+        its partial sums, fp32 [S(K)][rows][R] ("gate_up" in a segmented=True pool: [S(hidden)][rows][2 * rank])."""
         import torch
         return {t: tiled_workspace(rows, self.A[t].shape[2], self.A[t].shape[1], self.pool.device) if self.tiled(t, rows) else
                 torch.empty((rows, self.A[t].shape[1]), dtype=torch.float32, device=self.pool.device) for t in self.A}
@@ -264,14 +299,20 @@ class LoraLayer:
 
     def expand_add(self, target: str, t, Cm, row_adapter=None) -> None:
         words = self.row_adapter if row_adapter is None else row_adapter
-        if self.tiled(target, Cm.shape[0]):
+        if self.tiled(target, Cm.shape[0]) and target == "qkv" and self.pool.segmented:
+            expand_add_segmented_tiled(t, self.B[target], self.scale, words, Cm, self.A[target].shape[2], self.pool.qkv_seg_cols)
+        elif self.tiled(target, Cm.shape[0]):
             expand_add_tiled(t, self.B[target], self.scale, words, Cm, self.A[target].shape[2])
         else:
             expand_add(t, self.B[target], self.scale, words, Cm)
 
     def expand_silu_mul(self, t, y, Cm, row_adapter=None) -> None:
         """gate_up=True pools: t = the shrink of "gate_up", y the base gate_up linear's [rows][2 * ffn], Cm [rows][ffn]"""
-        expand_silu_mul(t, self.Bg, self.Bu, self.scale, self.row_adapter if row_adapter is None else row_adapter, y, Cm)
+        words = self.row_adapter if row_adapter is None else row_adapter
+        if self.tiled(GATE_UP, Cm.shape[0]):
+            expand_silu_mul_tiled(t, self.Bg, self.Bu, self.scale, words, y, Cm, self.A[GATE_UP].shape[2])
+        else:
+            expand_silu_mul(t, self.Bg, self.Bu, self.scale, words, y, Cm)
 
 
 class LoraPool:
@@ -287,10 +328,13 @@ class LoraPool:
     rows_per_seq=T: a pool for the speculative step -- row_adapter is int32 [batch * T] and a slot's word stands T times (set_slot).  None (the default): one word per
     slot; such a pool is not built for rows.
     tiled_from=M (an integer >= 1): calls of at least M rows run qkv / o / down in the tiled form (csrc/lora_tiled.hip); None (the default): never -- every row count
-    runs the 4-row kernels, bit for bit as before.  "gate_up" keeps tce_lora_expand_silu_mul_f16 at every row count."""
+    runs the 4-row kernels, bit for bit as before.  "gate_up" keeps tce_lora_expand_silu_mul_f16 at every row count.
+    segmented=True (needs tiled_from=): calls of at least tiled_from rows run the SEGMENTED tiled expands (csrc/lora_tiled_seg.hip) -- qkv's expand walks only each of
+    q's, k's and v's own block of B (the same bits as the tiled expand: the blocks it skips are zeros), and in a gate_up=True pool "gate_up" runs tiled too (its workspace:
+    the partial sums [S(hidden)][rows][2 * rank]).  False (the default): exactly the above, workspace shapes included."""
 
     def __init__(self, block_shapes, layers: int, max_adapters: int, rank: int, device, gate_up: bool = False, rows_per_seq: int | None = None,
-                 tiled_from: int | None = None):
+                 tiled_from: int | None = None, segmented: bool = False):
         import torch
         if int(rank) != rank or rank < 8 or rank % 8 != 0 or 3 * rank > capi.TCE_LORA_MAX_RANK:
             raise ValueError(f"rank {rank}: a multiple of 8 from 8 to {capi.TCE_LORA_MAX_RANK // 3} (the fused q/k/v runs at 3 * rank <= {capi.TCE_LORA_MAX_RANK})")
@@ -302,10 +346,14 @@ class LoraPool:
             raise ValueError(f"rows_per_seq {rows_per_seq}: None or 1 .. {capi.TCE_SPEC_MAX_ROWS} (the speculative step's rows per sequence)")
         if tiled_from is not None and (isinstance(tiled_from, bool) or not isinstance(tiled_from, int) or tiled_from < 1):
             raise ValueError(f"tiled_from {tiled_from!r}: None (never the tiled form) or an integer >= 1 (the row count from which a call runs it)")
-        self.tiled_from = tiled_from
+        if segmented and tiled_from is None:
+            raise ValueError("segmented=True: the segmented expands are tiled forms -- set tiled_from= (the row count from which a call runs them)")
+        self.tiled_from, self.segmented = tiled_from, bool(segmented)
         self.shapes, self.layers, self.max_adapters, self.rank, self.device = _shapes(block_shapes), int(layers), int(max_adapters), int(rank), torch.device(device)
         self.gate_up, self.rows_per_seq = bool(gate_up), None if rows_per_seq is None else int(rows_per_seq)
         self.target_shapes = target_shapes(self.shapes, self.rank, self.gate_up)
+        q, kv = self.shapes["q"], self.shapes["kv"]
+        self.qkv_seg_cols = (0, q, q + kv, q + 2 * kv)  # pack_adapter's blocks: q's rank rows of B, then k's, then v's (head_dim 128: multiples of 128)
         z = lambda *shape, dtype=torch.float16: torch.zeros(shape, dtype=dtype, device=self.device)
         self.A = {t: z(self.layers, self.max_adapters, R, K) for t, (R, K, N) in self.target_shapes.items()}
         self.B = {t: z(self.layers, self.max_adapters, R, N) for t, (R, K, N) in self.target_shapes.items() if t != GATE_UP}
