@@ -937,15 +937,27 @@ TCE_API int tce_lora_expand_add_segmented_tiled_f16(const float *partial, const 
  * gathered rows double-buffered in LDS per k-block of 128); no split of K across workgroups, no atomics.  PROMISE: every word of act and y is BIT-IDENTICAL to what
  * tce_moe_gate_up_f16 / tce_moe_down_f16 write on the same workspace contents (the same MFMA on the same operands per k-block, the same eight K slices added in the same
  * order), and words those leave unwritten stay unwritten: the choice between the forms is a question of time only.
- * NOT BUILT: a parallel stable grouping (the grouping is one wave that walks every pair), shared experts, expert parallelism, adapters on experts, a q4_mfma / int8 expert
+ * THE PARALLEL GROUPING, tce_moe_group_parallel / tce_moe_route_parallel_f16 (csrc/w4a16_moe_group.hip), for prompt-sized pair counts: tce_moe_route_f16's grouping is
+ * ONE wave whose lane e walks every pair.  tce_moe_group_parallel(rows, k, E, N_max, workspace, stream) groups the ids ALREADY in the workspace (tce_moe_route_f16's, or
+ * words the caller wrote) in two launches of ceil(P / 1024) workgroups of 16 waves, one pair per lane: per-chunk per-expert counts, then every pair's place = the counts
+ * of its expert in the chunks in front + in the waves in front inside its chunk + among the lower lanes of its wave (a loop over the distinct ids of the wave: read one
+ * lane's id, ballot the equal lanes, popcount below the lane).  No atomics, no arrival counters: count and list[e][0 .. count[e]) are tce_moe_route_f16's BIT FOR BIT
+ * (functions of ids, P and E alone), a word of ids outside [0, E) is in no list, words of list[e] at and beyond count[e] are not written, and a captured graph follows
+ * a routing that changes.  SCRATCH: the per-chunk counts, int32 [ceil(P / 1024)][E], are written into the HEAD OF THE y SECTION, which holds nothing between the route
+ * and tce_moe_down_f16.  tce_moe_route_parallel_f16: tce_moe_route_f16's arguments; its first launch (ids, weights), then this grouping: three launches.  Refusals:
+ * tce_moe_route_f16's, in its order (tce_moe_group_parallel: those of rows, k, E, N_max and workspace), then TCE_ERR_UNSUPPORTED_SHAPE when the counts do not fit the
+ * y section (P * N_max < ceil(P / 1024) * E: calls of a few pairs with a small N_max; tce_moe_route_f16 serves them).
+ * NOT BUILT: a one-launch grouping for calls of one chunk, shared experts, expert parallelism, adapters on experts, a q4_mfma / int8 expert
  * body, route fused into the preceding norm or combine into down. */
 #define TCE_MOE_MAX_TOP_K   8
 #define TCE_MOE_MAX_EXPERTS 64
-#define TCE_MOE_MAX_PAIRS   (1 << 16)   /* rows * k per call.  The grouping is ONE wave whose lanes each walk all the pairs; tce_moe_gate_up_f16 / tce_moe_down_f16 re-read a tile per pass of 16 pairs of an expert with wave 0 alone in the reduction and the epilogue (decode-sized calls); the _tiled_ forms are the ones for prompt-sized calls */
+#define TCE_MOE_MAX_PAIRS   (1 << 16)   /* rows * k per call.  tce_moe_route_f16's grouping is ONE wave whose lanes each walk all the pairs (tce_moe_route_parallel_f16: the one for prompt-sized calls, whose per-chunk sums are 64 terms at this cap); tce_moe_gate_up_f16 / tce_moe_down_f16 re-read a tile per pass of 16 pairs of an expert with wave 0 alone in the reduction and the epilogue (decode-sized calls); the _tiled_ forms are the ones for prompt-sized calls */
 #define TCE_MOE_TILE_ROWS   128         /* the tiled form's tile: weight rows ... */
 #define TCE_MOE_TILE_PAIRS  128         /* ... x pairs of one expert's list (a multiple of 16) */
 TCE_API size_t tce_moe_workspace_bytes(int rows, int k, int E, int N_max);
 TCE_API int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream);
+TCE_API int tce_moe_group_parallel(int rows, int k, int E, int N_max, void *workspace, void *stream);
+TCE_API int tce_moe_route_parallel_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream);
 TCE_API int tce_moe_gate_up_f16(const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size,
                                 int flags, int N_max, void *workspace, void *stream);
 TCE_API int tce_moe_down_f16(const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int group_size, int flags, int N_max,

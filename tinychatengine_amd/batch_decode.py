@@ -102,7 +102,7 @@ class BatchedDecoder:
         if lora is not None and moe is not None:
             raise ValueError("lora= together with a moe= block: adapters on experts are not built (DESIGN.md section 9)")
         if moe is not None:
-            self.LAUNCHES = 5 + moe.LAUNCHES  # norm, q/k/v, attention, o_proj, norm + route (2), expert gate/up, expert down, combine
+            self.LAUNCHES = 5 + moe.LAUNCHES  # norm, q/k/v, attention, o_proj, norm + route (2), expert gate/up, expert down, combine (a step of MoeFFN.PARALLEL_GROUP_FROM_PAIRS pairs or more: one more)
         if lora is not None:
             if self.rows != batch * (lora.pool.rows_per_seq or 1):
                 raise ValueError(f"lora: a step of {self.rows} rows for {batch} slots, but the pool was built with rows_per_seq={lora.pool.rows_per_seq} "

@@ -22,7 +22,7 @@ TESTKIT_LIB_PATH = os.path.join(LIB_DIR, "libtce_testkit.so")
 ADAPTER_TEST_PATH = os.path.join(LIB_DIR, "adapter_selftest")
 ADAPTER_BENCH_PATH = os.path.join(LIB_DIR, "adapter_bench")
 
-HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip", "w4a16_moe.hip", "w4a16_moe_tiled.hip", "lora_tiled.hip", "lora_tiled_seg.hip"]
+HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip", "w4a16_moe.hip", "w4a16_moe_tiled.hip", "w4a16_moe_group.hip", "lora_tiled.hip", "lora_tiled_seg.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-ffp-contract=off",  # the int8 epilogue and the fp16-accumulate entry point need every rounding
@@ -56,6 +56,8 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         # the tiled form holds 2 x 4 MFMA tiles twice (the K slice and the total) beside the next k-block's requests: 64 accumulators in scratch
                                         # would be re-read per k-block
                                         "w4a16_moe_tiled.hip": ["w4a16_moe_tiled_kernel"],
+                                        # the parallel grouping is all latency (a few workgroups, a scalar loop per wave): a scratch round trip inside that loop is time
+                                        "w4a16_moe_group.hip": ["moe_group_hist_kernel", "moe_group_place_kernel"],
                                         # the tiled shrink holds 2 x ceil(R / 16) MFMA tiles (96 accumulators at R = 192) beside a super-step's fragments in flight
                                         "lora_tiled.hip": ["lora_shrink_tiled_kernel", "lora_expand_add_tiled_kernel"],
                                         # the segmented expands hold 2 x 2 MFMA tiles beside the next chunk's four requested pieces (both instantiations)

@@ -58,6 +58,10 @@ int launch_moe_stage(bool up, const void *x, int ldx, const void *qweight, const
 int launch_moe_stage_tiled(bool up, const void *x, int ldx, const void *qweight, const void *scales, const void *zeros, int rows, int k, int E, int N, int K, int scales_stride,
                            int zeros_stride, bool z8, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err);
 int launch_moe_combine_add_f16(void *C, int ldc, int rows, int k, int E, int N, int n_max, const void *workspace, hipStream_t stream, hipError_t *hip_err);
+int launch_moe_route_select_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
+                                hipError_t *hip_err);
+size_t moe_group_hist_bytes(int rows, int k, int E);
+int launch_moe_group_parallel(int rows, int k, int E, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err);
 
 thread_local char g_err[512] = "";
 int fail(int code, const char *fmt, ...) {
@@ -1591,16 +1595,47 @@ size_t tce_moe_workspace_bytes(int rows, int k, int E, int N_max) {
     return tce::moe_workspace_bytes(rows, k, E, N_max);
 }
 
-int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream) {
-    const char *who = "tce_moe_route_f16";
+// the route's refusals, for both groupings behind it
+static int moe_route_refusal(const char *who, const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int N_max, const void *workspace) {
     if (!x || !Wr) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
     if (const int rc = moe_bad_arg(who, rows, k, E, N_max, workspace)) return rc;
     if (hidden < 1 || ldx < hidden) return fail(TCE_ERR_BAD_ARG, "%s: need hidden >= 1 and ldx >= hidden", who);
     if (const int rc = moe_bad_shape(who, rows, k, E, workspace)) return rc;
     if (hidden % 8 != 0 || ldx % 8 != 0 || (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(Wr)) % 16 != 0)
         return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: hidden %d, ldx %d (multiples of 8), 16-byte aligned x / Wr", who, hidden, ldx);
+    return TCE_OK;
+}
+// the parallel grouping keeps its per-chunk counts in the head of the y section (csrc/w4a16_moe_group.hip): a call of a few pairs and a small N_max has no room for them
+static int moe_group_no_room(const char *who, int rows, int k, int E, int N_max) {
+    const size_t need = tce::moe_group_hist_bytes(rows, k, E), have = (size_t)rows * k * (size_t)N_max * 4;
+    if (need > have) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: the grouping's %zu bytes of counts do not fit the y section (%zu bytes): use tce_moe_route_f16", who, need, have);
+    return TCE_OK;
+}
+
+int tce_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream) {
+    if (const int rc = moe_route_refusal("tce_moe_route_f16", x, ldx, Wr, rows, hidden, E, k, N_max, workspace)) return rc;
     hipError_t he = hipSuccess;
     const int rc = tce::launch_moe_route_f16(x, ldx, Wr, rows, hidden, E, k, renormalize, N_max, workspace, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "MoE route launch") : rc;
+}
+
+int tce_moe_group_parallel(int rows, int k, int E, int N_max, void *workspace, void *stream) {
+    const char *who = "tce_moe_group_parallel";
+    if (const int rc = moe_bad_arg(who, rows, k, E, N_max, workspace)) return rc;
+    if (const int rc = moe_bad_shape(who, rows, k, E, workspace)) return rc;
+    if (const int rc = moe_group_no_room(who, rows, k, E, N_max)) return rc;
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_moe_group_parallel(rows, k, E, N_max, workspace, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "MoE grouping launch") : rc;
+}
+
+int tce_moe_route_parallel_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int N_max, void *workspace, void *stream) {
+    const char *who = "tce_moe_route_parallel_f16";
+    if (const int rc = moe_route_refusal(who, x, ldx, Wr, rows, hidden, E, k, N_max, workspace)) return rc;
+    if (const int rc = moe_group_no_room(who, rows, k, E, N_max)) return rc;
+    hipError_t he = hipSuccess;
+    int rc = tce::launch_moe_route_select_f16(x, ldx, Wr, rows, hidden, E, k, renormalize, N_max, workspace, static_cast<hipStream_t>(stream), &he);
+    if (rc == TCE_OK) rc = tce::launch_moe_group_parallel(rows, k, E, N_max, workspace, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "MoE route launch") : rc;
 }
 

@@ -326,15 +326,23 @@ size_t moe_workspace_bytes(int rows, int k, int E, int n_max) { return moe_layou
 
 size_t moe_lds_bytes(int K) { return (size_t)kMoeWaves * (kWBuf + kXBuf + (size_t)moe_gpw(K) * 64) + kRedBytes; }
 
-int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
-                         hipError_t *hip_err) {
+// the route's first launch alone: ids and weights (the grouping behind it is moe_group_kernel below, or w4a16_moe_group.hip's pair of launches)
+int launch_moe_route_select_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
+                                hipError_t *hip_err) {
     const MoeLayout L = moe_layout(rows, k, E, n_max);
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    int32_t *ids = reinterpret_cast<int32_t *>(ws + L.ids);
-    hipLaunchKernelGGL(moe_route_kernel, dim3(rows), dim3(kRouteThreads), 0, stream, static_cast<const half_t *>(x), (long long)ldx, static_cast<const half_t *>(Wr), ids,
-                       reinterpret_cast<float *>(ws + L.weights), hidden, E, k, renormalize);
-    if (const int rc = launched(hip_err)) return rc;
-    hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(64), 0, stream, ids, reinterpret_cast<int32_t *>(ws + L.count), reinterpret_cast<int32_t *>(ws + L.list), rows * k, E);
+    hipLaunchKernelGGL(moe_route_kernel, dim3(rows), dim3(kRouteThreads), 0, stream, static_cast<const half_t *>(x), (long long)ldx, static_cast<const half_t *>(Wr),
+                       reinterpret_cast<int32_t *>(ws + L.ids), reinterpret_cast<float *>(ws + L.weights), hidden, E, k, renormalize);
+    return launched(hip_err);
+}
+
+int launch_moe_route_f16(const void *x, int ldx, const void *Wr, int rows, int hidden, int E, int k, int renormalize, int n_max, void *workspace, hipStream_t stream,
+                         hipError_t *hip_err) {
+    if (const int rc = launch_moe_route_select_f16(x, ldx, Wr, rows, hidden, E, k, renormalize, n_max, workspace, stream, hip_err)) return rc;
+    const MoeLayout L = moe_layout(rows, k, E, n_max);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<const int32_t *>(ws + L.ids), reinterpret_cast<int32_t *>(ws + L.count),
+                       reinterpret_cast<int32_t *>(ws + L.list), rows * k, E);
     return launched(hip_err);
 }
 

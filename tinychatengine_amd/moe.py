@@ -11,8 +11,9 @@ back, and a captured graph follows a routing that changes from replay to replay:
     moe_reference     the definition in numpy float64 on the stored values: the yardstick of the tests
     group_reference   the stable grouping (count, lists) of ids
     MoeWorkspace      the caller workspace of the five entry points and typed views of its six sections
-    route / gate_up / down / combine_add    one entry point each, on torch tensors, on the current stream; gate_up / down(tiled=True): the tiled form for prompt-sized
-                      pair counts (csrc/w4a16_moe_tiled.hip: TILE_ROWS weight rows x TILE_PAIRS pairs per workgroup), bit-identical per pair to the other
+    route / gate_up / down / combine_add    one entry point each, on torch tensors, on the current stream; route(parallel=True) / group_parallel: the grouping for
+                      prompt-sized pair counts (csrc/w4a16_moe_group.hip: chunks of 1024 pairs, a workgroup each), the same count and lists; gate_up /
+                      down(tiled=True): the tiled form for prompt-sized pair counts (csrc/w4a16_moe_tiled.hip: TILE_ROWS weight rows x TILE_PAIRS pairs per workgroup), bit-identical per pair to the other
     MoeFFN            the stacked expert tensors of one layer (synthetic weights, quantize_q4_6 per expert) and forward(xn, rows_inout): DecoderBlock(..., moe=)
 """
 from __future__ import annotations
@@ -181,11 +182,18 @@ def _st() -> C.c_void_p:
     return C.c_void_p(_stream())
 
 
-def route(x, Wr, ws: MoeWorkspace, renormalize: bool = True) -> None:
-    """tce_moe_route_f16: x fp16 [rows][hidden] (row stride x.stride(0)), Wr fp16 [E][hidden] -> ws.ids, ws.weights, ws.count, ws.list"""
+def route(x, Wr, ws: MoeWorkspace, renormalize: bool = True, parallel: bool = False) -> None:
+    """tce_moe_route_f16 (parallel: tce_moe_route_parallel_f16, the same bits in three launches, the grouping's two of ceil(P / 1024) workgroups each): x fp16
+    [rows][hidden] (row stride x.stride(0)), Wr fp16 [E][hidden] -> ws.ids, ws.weights, ws.count, ws.list"""
     import torch
     assert x.dtype == Wr.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1 and Wr.is_contiguous() and x.shape == (ws.rows, Wr.shape[1]) and Wr.shape[0] == ws.E
-    capi.check(capi.lib().tce_moe_route_f16(_ptr(x), x.stride(0), _ptr(Wr), ws.rows, Wr.shape[1], ws.E, ws.k, int(bool(renormalize)), ws.n_max, _ptr(ws.buf), _st()))
+    fn = capi.lib().tce_moe_route_parallel_f16 if parallel else capi.lib().tce_moe_route_f16
+    capi.check(fn(_ptr(x), x.stride(0), _ptr(Wr), ws.rows, Wr.shape[1], ws.E, ws.k, int(bool(renormalize)), ws.n_max, _ptr(ws.buf), _st()))
+
+
+def group_parallel(ws: MoeWorkspace) -> None:
+    """tce_moe_group_parallel: ws.ids -> ws.count, ws.list (group_reference's grouping; the head of ws.y is its scratch)"""
+    capi.check(capi.lib().tce_moe_group_parallel(ws.rows, ws.k, ws.E, ws.n_max, _ptr(ws.buf), _st()))
 
 
 def _stacked(arrays, E: int):
@@ -224,17 +232,24 @@ class MoeFFN:
     """One layer's experts: Wr fp16 [E][hidden]; gate_up = (qweight int32 [E][2 ffn][hidden / 8], scales, zeros) with row 2n = gate n, row 2n + 1 = up n;
     down = (qweight int32 [E][hidden][ffn / 8], scales, zeros).  Synthetic weights, quantize_q4_6 per expert, as DecoderBlock's; nothing loads a checkpoint."""
 
-    LAUNCHES = 5  # route (logits + selection, grouping), gate_up, down, combine
+    LAUNCHES = 5  # route (logits + selection, grouping), gate_up, down, combine; a forward of PARALLEL_GROUP_FROM_PAIRS pairs or more: 6 (the grouping is two launches)
     # forward runs the two contractions in the tiled form from this many pairs (rows * top_k) on; None: never.  From profiles/moe_tiled/moe_tiled_time.jsonl: the smallest
     # measured P from which the tiled pair of launches beats the pass pair at every larger measured point by more than the repeats' spreads (slower at P = 32 and 128)
     TILED_FROM_PAIRS = 256
+    # forward routes with the parallel grouping (route(parallel=True): one launch more than LAUNCHES) from this many pairs on; None: never.  The same rule on
+    # profiles/moe_group/moe_group_time.jsonl, over both measured routers (E = 8, k = 2 and E = 64, k = 8): slower at P = 32 (8.8 -> 9.4, 20.6 -> 23.9 us), level at
+    # P = 128 with 64 experts (26.8 -> 26.4 us) and 1.6x faster with 8, then faster everywhere: 295 -> 16 us at 4096 pairs
+    PARALLEL_GROUP_FROM_PAIRS = 128
 
-    def __init__(self, hidden: int, ffn: int, experts: int, top_k: int, device, renormalize: bool = True, seed: int = 0, tiled_from=None):
-        """tiled_from: the pair count from which forward uses the tiled form (0: always); None: the class default TILED_FROM_PAIRS.  Both forms give the same bits."""
+    def __init__(self, hidden: int, ffn: int, experts: int, top_k: int, device, renormalize: bool = True, seed: int = 0, tiled_from=None, parallel_group_from=None):
+        """tiled_from: the pair count from which forward uses the tiled form (0: always); None: the class default TILED_FROM_PAIRS.  Both forms give the same bits.
+        parallel_group_from: the same for the parallel grouping of the route (class default PARALLEL_GROUP_FROM_PAIRS); the same bits again."""
         import torch
-        if tiled_from is not None and int(tiled_from) < 0:
-            raise ValueError(f"tiled_from {tiled_from}: a pair count >= 0, or None for the default")
+        for name, v in (("tiled_from", tiled_from), ("parallel_group_from", parallel_group_from)):
+            if v is not None and int(v) < 0:
+                raise ValueError(f"{name} {v}: a pair count >= 0, or None for the default")
         self.tiled_from = None if tiled_from is None else int(tiled_from)
+        self.parallel_group_from = None if parallel_group_from is None else int(parallel_group_from)
         if not 1 <= int(top_k) <= capi.TCE_MOE_MAX_TOP_K or not int(top_k) <= int(experts) <= capi.TCE_MOE_MAX_EXPERTS:
             raise ValueError(f"top_k {top_k} of {experts} experts: 1 <= top_k <= {capi.TCE_MOE_MAX_TOP_K}, top_k <= experts <= {capi.TCE_MOE_MAX_EXPERTS}")
         if hidden % GROUP or ffn % GROUP:
@@ -271,11 +286,13 @@ class MoeFFN:
         return MoeWorkspace(m, self.top_k, self.experts, n_max, self.device, buf=self._buf)
 
     def forward(self, xn, rows_inout) -> None:
-        """xn fp16 [m][hidden], the normalised rows; rows_inout fp16 [m][hidden], the residual stream, updated in place.  Five launches on the current stream."""
+        """xn fp16 [m][hidden], the normalised rows; rows_inout fp16 [m][hidden], the residual stream, updated in place.  Five launches on the current stream; six from
+        parallel_group_from pairs on (the parallel grouping is two launches)."""
         ws = self.workspace(xn.shape[0])
         frm = self.TILED_FROM_PAIRS if self.tiled_from is None else self.tiled_from
         tiled = frm is not None and ws.P >= frm
-        route(xn, self.Wr, ws, self.renormalize)
+        frm = self.PARALLEL_GROUP_FROM_PAIRS if self.parallel_group_from is None else self.parallel_group_from
+        route(xn, self.Wr, ws, self.renormalize, parallel=frm is not None and ws.P >= frm)
         gate_up(xn, self.gate_up, ws, self.flags, tiled)
         down(self.down, ws, self.flags, tiled)
         combine_add(rows_inout, ws)
