@@ -1100,6 +1100,33 @@ typedef struct tce_w8a8_desc_v2 {
 TCE_API int tce_w8a8_matmul_v2(const tce_w8a8_desc_v2 *d, void *stream);
 TCE_API size_t tce_w8a8_scratch_bytes(void);
 
+/* FP8 linears: W8A8 in OCP e4m3fn with one fp32 scale per output channel and one per token (csrc/fp8_linear.hip; additive within ABI 113, no existing struct or
+ * entry point changes) -- what FP8_DYNAMIC / "PTPC-FP8" checkpoints hold.  The element format is the FP8 pages': 1 sign, 4 exponent (bias 7), 3 mantissa bits,
+ * subnormals m * 2^-9, 0x7f / 0xff NaN, no infinities; e4m3_rne_sat(f) = nearest with ties to the even mantissa, saturating at +-448, -0 stays 0x80, NaN -> 0x7f.
+ *   weights     wq e4m3 bytes [N][K] row-major, sw fp32 [N].  The caller promises that no weight byte is 0x7f / 0xff.
+ *   activations per row m of x (fp16 [M][ldx]):  amax = max_k |float(x[m][k])|, a maximum that a NaN element does not enter;
+ *                 amax == 0:  sx[m] = 1.0f, every byte the byte of its (signed) zero;
+ *                 otherwise   sx[m] = amax / 448.0f and inv = 448.0f / amax, each ONE correctly rounded fp32 division;
+ *                             xq[m][k] = e4m3_rne_sat(float(x[m][k]) * inv), one fp32 multiply.
+ *               A row that holds +-inf: sx[m] = +inf, inv = 0, its finite elements become signed zeros and its infinities (inf * 0) the NaN byte 0x7f.  A NaN element
+ *               becomes 0x7f whatever the rest of its row holds (a row of nothing but NaN and zeros has amax == 0, sx[m] = 1).  Either way only that row of xq, sx --
+ *               and of a product formed from them -- is affected: a row is quantised by a workgroup of its own and an output row reads no other row's bytes.
+ *   product     acc[m][n] = sum_k e4m3(xq[m][k]) * e4m3(wq[n][k]) in fp32 by v_mfma_f32_16x16x128_f8f6f4, 128-byte K steps ascending;
+ *               v = (acc * sx[m]) * sw[n], two fp32 multiplies in this order;  C[m][n] = fp16(v), with TCE_W4_ADD_TO_C  C[m][n] = fp16(float(C[m][n]) + v).
+ *               No atomics and no cut of K across workgroups: an output's bits depend on its own row of xq, sx, its own row of wq, sw, and K -- not on M, the rows
+ *               beside it or the grid.  Two forms, each deterministic; they cut K differently and need not agree bit for bit:
+ *                 skinny (M <= 16)  eight waves share a band of 16 weight rows, wave w takes K steps [w S / 8, (w + 1) S / 8) of S = K / 128, sums added in wave order;
+ *                 tiled  (any M)    128 x 128 outputs per workgroup, one chain over all K steps.
+ *               flags: 0 | TCE_W4_ADD_TO_C | at most one of TCE_FP8_FORM_SKINNY / TCE_FP8_FORM_TILED (neither: M <= 16 runs the skinny form, more rows the tiled one).
+ * Shapes: K % 128 == 0, K <= 32768, N % 16 == 0, rows / M <= 8388480; x, xq, wq, sw, C 16-byte aligned, sx 4-byte; ldx % 8 == 0, ldq % 16 == 0, ldc % 8 == 0.
+ * Refusals, before any HIP call and without reading through a pointer, arguments before shapes: TCE_ERR_BAD_ARG for a NULL pointer, rows / M / N / K < 1, ldx < K,
+ * ldq < K, ldc < N, a flag bit other than the three above, both form bits; TCE_ERR_UNSUPPORTED_SHAPE for the shape rules above and TCE_FP8_FORM_SKINNY with M > 16. */
+#define TCE_FP8_FORM_SKINNY 256
+#define TCE_FP8_FORM_TILED 512
+TCE_API int tce_fp8_quantize_rows_f16(const void *x, int ldx, void *xq, int ldq, float *sx, int rows, int K, void *stream);
+TCE_API int tce_w8a8_fp8_forward_f16(const void *xq, int ldq, const float *sx, const void *wq, const float *sw, void *C, int ldc, int M, int N, int K, int flags,
+                                     void *stream);
+
 /* The element-wise steps between the two int8 BMMs of the reference's OPT attention (llm/src/nn_modules/Int8OPTAttention.cc:254-268), as ONE launch:
  *   batch_Add (llm/src/ops/batch_add.cc:3-24): s[h][j][k] + mask[j][k];  softmax over k (llm/src/ops/softmax.cc:5-40: the running maximum starts
  *   from `m_data[0]` -- element [0][0][0] of the tensor the reference normalises IN PLACE, i.e. the masked score for row (0, 0) and that row's first

@@ -22,7 +22,7 @@ TESTKIT_LIB_PATH = os.path.join(LIB_DIR, "libtce_testkit.so")
 ADAPTER_TEST_PATH = os.path.join(LIB_DIR, "adapter_selftest")
 ADAPTER_BENCH_PATH = os.path.join(LIB_DIR, "adapter_bench")
 
-HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip", "w4a16_moe.hip", "w4a16_moe_tiled.hip", "w4a16_moe_group.hip", "lora_tiled.hip", "lora_tiled_seg.hip"]
+HIP_SOURCES = ["tce_capi.hip", "tce_tuning.hip", "w4a16_gemv.hip", "w4a16_gemv_i8.hip", "w4a16_gemv_i8_token.hip", "w4a16_gemv_stream.hip", "w4a16_gemv_ovl.hip", "w4a16_gemm.hip", "w4a16_gemm_dma.hip", "w4a16_gemm_pk.hip", "w4a16_skinny.hip", "w4a16_awq.hip", "w8a8_gemm.hip", "w8a8_lnq_fused.hip", "glue.hip", "attention_ops.hip", "attention_fast.hip", "attention_rows_sink.hip", "attention_prefill.hip", "opt_attention.hip", "comm.hip", "sampling.hip", "lora.hip", "w4a16_moe.hip", "w4a16_moe_tiled.hip", "w4a16_moe_group.hip", "lora_tiled.hip", "lora_tiled_seg.hip", "fp8_linear.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-ffp-contract=off",  # the int8 epilogue and the fp16-accumulate entry point need every rounding
@@ -38,11 +38,13 @@ HIPCC_FLAGS = [
 # w4a16_moe_tiled.hip: the same, and for a second reason: its K sum has to give w4a16_moe.hip's bits
 # lora_tiled.hip: the same -- the sums beside its MFMAs (the waves' tiles, the K slices) are plain v_add_f32
 # lora_tiled_seg.hip: the same -- its K-slice sums have to give lora_tiled.hip's bits
+# fp8_linear.hip: the same -- the two scale multiplies of its epilogues and the skinny form's wave-order sum are plain v_mul_f32 / v_add_f32
 EXTRA_FLAGS: dict[str, list[str]] = {"w4a16_gemv_i8.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"], "lora.hip": ["-fno-slp-vectorize"],
                                      "w4a16_moe.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                                      "w4a16_moe_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                                      "lora_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-                                     "lora_tiled_seg.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                                     "lora_tiled_seg.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                                     "fp8_linear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # Kernels that must not spill a vector register: lnq_w8a8_wide_kernel keeps 16 requested weight pieces per lane in flight through its sums; ONE spilled register
 # makes the compiler wait for all of them at the spill (measured: the OPT-6.7B layer 94 -> 103 us, found only by accident).  The build fails instead.
 NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_kernel"],
@@ -62,6 +64,9 @@ NO_VGPR_SPILL: dict[str, list[str]] = {"w8a8_lnq_fused.hip": ["lnq_w8a8_wide_ker
                                         "lora_tiled.hip": ["lora_shrink_tiled_kernel", "lora_expand_add_tiled_kernel"],
                                         # the segmented expands hold 2 x 2 MFMA tiles beside the next chunk's four requested pieces (both instantiations)
                                         "lora_tiled_seg.hip": ["lora_expand_seg_tiled_kernel"],
+                                        # the FP8 linears: the tiled form holds 4 x 4 accumulator tiles beside four operand fragments and the next K step's eight requested pieces;
+                                        # the skinny form four K steps of both operands in flight; the quantiser its whole row share (16 pieces at K = 32768)
+                                        "fp8_linear.hip": ["w8a8_fp8_tiled_kernel", "w8a8_fp8_skinny_kernel", "fp8_quantize_rows_kernel"],
                                         # the sampler's two kernels keep 16 / 32 64-bit numbers per thread in registers through ~50 counting rounds: in scratch every round would re-read them
                                         # (every instantiation, the logprob forms included; the two scoring kernels hold the same 16 logits per thread)
                                         "sampling.hip": ["sample_select_kernel", "sample_draw_kernel", "logprobs_partials_kernel", "logprobs_merge_kernel"],

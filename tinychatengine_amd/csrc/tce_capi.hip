@@ -62,6 +62,9 @@ int launch_moe_route_select_f16(const void *x, int ldx, const void *Wr, int rows
                                 hipError_t *hip_err);
 size_t moe_group_hist_bytes(int rows, int k, int E);
 int launch_moe_group_parallel(int rows, int k, int E, int n_max, void *workspace, hipStream_t stream, hipError_t *hip_err);
+int launch_fp8_quantize_rows_f16(const void *x, int ldx, void *xq, int ldq, float *sx, int rows, int K, hipStream_t stream, hipError_t *hip_err);
+int launch_w8a8_fp8_forward_f16(const void *xq, int ldq, const float *sx, const void *wq, const float *sw, void *C, int ldc, int M, int N, int K, int flags, hipStream_t stream,
+                                hipError_t *hip_err);
 
 thread_local char g_err[512] = "";
 int fail(int code, const char *fmt, ...) {
@@ -1448,6 +1451,44 @@ int tce_embed_rows_f16(const void *table, int vocab, int hidden, const int32_t *
     hipError_t he = hipSuccess;
     const int rc = tce::launch_embed_rows_f16(table, vocab, hidden, token, out, batch, pos_device, pos_bound, workspace, static_cast<hipStream_t>(stream), &he);
     return rc == TCE_ERR_HIP ? hip_fail(he, "embedding launch") : rc;
+}
+
+// FP8 linears (csrc/fp8_linear.hip): every refusal before any HIP call, arguments before shapes
+static int check_fp8_shape(const char *who, int rows, int K) {
+    if (K % 128 != 0 || K > 32768) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: K %d (a multiple of 128, at most 32768)", who, K);
+    if (rows > 65535 * 128) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: %d rows (at most %d per call)", who, rows, 65535 * 128);
+    return TCE_OK;
+}
+
+int tce_fp8_quantize_rows_f16(const void *x, int ldx, void *xq, int ldq, float *sx, int rows, int K, void *stream) {
+    const char *who = "tce_fp8_quantize_rows_f16";
+    if (!x || !xq || !sx) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (rows < 1 || K < 1 || ldx < K || ldq < K) return fail(TCE_ERR_BAD_ARG, "%s: need rows, K >= 1, ldx >= K and ldq >= K", who);
+    if (const int rc = check_fp8_shape(who, rows, K)) return rc;
+    if (ldx % 8 != 0 || ldq % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ldx %d (a multiple of 8), ldq %d (a multiple of 16)", who, ldx, ldq);
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xq)) % 16 != 0 || reinterpret_cast<uintptr_t>(sx) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned x / xq, 4-byte aligned sx", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_fp8_quantize_rows_f16(x, ldx, xq, ldq, sx, rows, K, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "FP8 row quantiser launch") : rc;
+}
+
+int tce_w8a8_fp8_forward_f16(const void *xq, int ldq, const float *sx, const void *wq, const float *sw, void *Cm, int ldc, int M, int N, int K, int flags, void *stream) {
+    const char *who = "tce_w8a8_fp8_forward_f16";
+    if (!xq || !sx || !wq || !sw || !Cm) return fail(TCE_ERR_BAD_ARG, "%s: null pointer", who);
+    if (M < 1 || N < 1 || K < 1 || ldq < K || ldc < N) return fail(TCE_ERR_BAD_ARG, "%s: need M, N, K >= 1, ldq >= K and ldc >= N", who);
+    if (flags & ~(TCE_W4_ADD_TO_C | TCE_FP8_FORM_SKINNY | TCE_FP8_FORM_TILED)) return fail(TCE_ERR_BAD_ARG, "%s: flags 0x%x (TCE_W4_ADD_TO_C and one form bit at most)", who, flags);
+    if ((flags & TCE_FP8_FORM_SKINNY) && (flags & TCE_FP8_FORM_TILED)) return fail(TCE_ERR_BAD_ARG, "%s: TCE_FP8_FORM_SKINNY and TCE_FP8_FORM_TILED exclude each other", who);
+    if (const int rc = check_fp8_shape(who, M, K)) return rc;
+    if (N % 16 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: N %d (a multiple of 16)", who, N);
+    if ((flags & TCE_FP8_FORM_SKINNY) && M > 16) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: the skinny form takes M <= 16, got %d", who, M);
+    if (ldq % 16 != 0 || ldc % 8 != 0) return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: ldq %d (a multiple of 16), ldc %d (a multiple of 8)", who, ldq, ldc);
+    if ((reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(wq) | reinterpret_cast<uintptr_t>(sw) | reinterpret_cast<uintptr_t>(Cm)) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(sx) % 4 != 0)
+        return fail(TCE_ERR_UNSUPPORTED_SHAPE, "%s: 16-byte aligned xq / wq / sw / C, 4-byte aligned sx", who);
+    hipError_t he = hipSuccess;
+    const int rc = tce::launch_w8a8_fp8_forward_f16(xq, ldq, sx, wq, sw, Cm, ldc, M, N, K, flags, static_cast<hipStream_t>(stream), &he);
+    return rc == TCE_ERR_HIP ? hip_fail(he, "FP8 linear launch") : rc;
 }
 
 // the shape rules both LoRA entry points share (csrc/lora.hip): after every argument refusal

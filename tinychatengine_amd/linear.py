@@ -204,6 +204,62 @@ def forward_group_rmsnorm(linears: list[Linear_half_int4], x: torch.Tensor, outs
     capi.check(capi.lib().tce_w4a16_forward_group_rmsnorm(arr, len(descs), _ptr(gamma), float(eps), C.c_void_p(_stream() or 0)))
 
 
+class Linear_half_fp8:
+    """W8A8 linear in e4m3 with one fp32 scale per output channel and one per token (include/tce_matmul.h, "FP8 linears"): fp16 in, fp16 out.  The activation rows are
+    quantised at run time (quantize_rows); linears that read the same activation (q/k/v, gate and up) share one quantisation through forward_quantized."""
+
+    def __init__(self, wq: torch.Tensor, sw: torch.Tensor):
+        self.out_features, self.in_features = wq.shape
+        if wq.dtype != torch.uint8 or sw.dtype != torch.float32 or tuple(sw.shape) != (self.out_features,):
+            raise ValueError("Linear_half_fp8: wq uint8 [N][K] (e4m3 bytes), sw fp32 [N]")
+        if self.in_features % 128 or self.in_features > 32768 or self.out_features % 16:
+            raise ValueError("Linear_half_fp8: K a multiple of 128 up to 32768, N a multiple of 16")
+        self.weight, self.scale = wq.contiguous(), sw.contiguous()
+
+    @classmethod
+    def from_float(cls, w: torch.Tensor) -> "Linear_half_fp8":
+        return cls(*quantize.quantize_fp8_channel(w))
+
+    def quantize_rows(self, x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """x fp16 [..., K] -> (xq uint8 [M][K], sx fp32 [M]): tce_fp8_quantize_rows_f16."""
+        k = self.in_features
+        if x.dtype != torch.float16 or x.shape[-1] != k:
+            raise ValueError("Linear_half_fp8: x is fp16 [..., in_features]")
+        m = x.numel() // k
+        xq = torch.empty((m, k), dtype=torch.uint8, device=x.device)
+        sx = torch.empty(m, dtype=torch.float32, device=x.device)
+        capi.check(capi.lib().tce_fp8_quantize_rows_f16(_ptr(x), k, _ptr(xq), k, _ptr(sx), m, k, _stream()))
+        return xq, sx
+
+    def forward_quantized(self, xq: torch.Tensor, sx: torch.Tensor, out: torch.Tensor | None = None, flags: int = 0) -> torch.Tensor:
+        """out [M][N] = the product of already quantised rows; flags: TCE_W4_ADD_TO_C (out is added into) and / or one of capi.TCE_FP8_FORM_*."""
+        m, n = xq.shape[0], self.out_features
+        if out is None:
+            if flags & capi.TCE_W4_ADD_TO_C:
+                raise ValueError("Linear_half_fp8: TCE_W4_ADD_TO_C needs the tensor to add into")
+            out = torch.empty((m, n), dtype=torch.float16, device=xq.device)
+        if xq.dtype != torch.uint8 or tuple(xq.shape) != (m, self.in_features) or sx.dtype != torch.float32 or sx.numel() != m or out.dtype != torch.float16 or out.numel() != m * n:
+            raise ValueError("Linear_half_fp8: xq uint8 [M][K], sx fp32 [M], out fp16 [M][N]")
+        capi.check(capi.lib().tce_w8a8_fp8_forward_f16(_ptr(xq), self.in_features, _ptr(sx), _ptr(self.weight), _ptr(self.scale), _ptr(out), n, m, n, self.in_features,
+                                                       flags, _stream()))
+        return out
+
+    def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        if out is None:
+            out = torch.empty((*x.shape[:-1], self.out_features), dtype=torch.float16, device=x.device)
+        self.forward_quantized(*self.quantize_rows(x), out=out)
+        return out
+
+    __call__ = forward
+
+    def forward_add(self, x: torch.Tensor, residual_inout: torch.Tensor) -> torch.Tensor:
+        """residual_inout = fp16(float(residual_inout) + self(x)) as one launch behind the quantisation (o_proj / down_proj with the residual add)."""
+        return self.forward_quantized(*self.quantize_rows(x), out=residual_inout, flags=capi.TCE_W4_ADD_TO_C)
+
+    def weight_bytes(self) -> int:
+        return self.out_features * self.in_features + 4 * self.out_features
+
+
 class W8A8B8O8Linear:
     """int8 -> int8 linear, alpha/beta epilogue (llm/src/ops/W8A8B8O8Linear.cc:15-78); relu=True is W8A8B8O8LinearReLU
     (q_min = 0, W8A8B8O8LinearReLU.cc:32)."""

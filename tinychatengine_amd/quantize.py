@@ -130,3 +130,29 @@ def load_linear_q4_6(dirname: str, out_features: int, in_features: int, group_si
 def merge_qkv_q4_6(q, k, v):
     """llm/tools/llama_qkv_merger.py:27-48: the fused qkv linear is the row-wise concatenation of the three."""
     return tuple(torch.cat([a, b, c], dim=0).contiguous() for a, b, c in zip(q, k, v))
+
+
+def e4m3_rne_sat(f: torch.Tensor) -> torch.Tensor:
+    """fp32 -> OCP e4m3fn bytes (uint8), the definition of include/tce_matmul.h ("FP8 linears") in the integer arithmetic of csrc/fp8_kv.hpp's fp8_quant1: nearest with
+    ties to the even mantissa, saturating at +-448, -0 stays 0x80, NaN -> 0x7f."""
+    assert f.dtype == torch.float32
+    sign = (f.view(torch.int32) >> 24) & 0x80
+    a = f.abs().clamp(max=448.0)
+    b = a.view(torch.int32)
+    normal = ((b + 0x7FFFF + ((b >> 20) & 1)) >> 20) - (120 << 3)  # the fp32 mantissa rounded to 3 bits; the carry runs into the exponent
+    sub = (a + 16384.0).view(torch.int32) - 0x46800000             # below 2^-6 the spacing is 2^-9, the ulp of 2^14: the adder rounds
+    r = torch.where(a >= 0.015625, normal, sub) | sign
+    return torch.where(torch.isnan(f), torch.full_like(r, 0x7F), r).to(torch.uint8)
+
+
+def quantize_fp8_channel(w: torch.Tensor):
+    """FP8_DYNAMIC weights at load time: w float [N][K] -> (wq uint8 [N][K] e4m3 bytes, sw fp32 [N]) with sw[n] = amax_n / 448 (1.0 for an all-zero row) and
+    wq[n][k] = e4m3_rne_sat(w[n][k] * (448 / amax_n)) -- the activation rule of tce_fp8_quantize_rows_f16 applied to a weight row."""
+    w = w.to(torch.float32)
+    assert w.dim() == 2 and bool(torch.isfinite(w).all())
+    amax = w.abs().amax(dim=1)
+    zero = amax == 0
+    c448 = torch.full_like(amax, 448.0)
+    sw = torch.where(zero, torch.ones_like(amax), amax / c448)
+    inv = torch.where(zero, torch.ones_like(amax), c448 / amax)
+    return e4m3_rne_sat(w * inv[:, None]).contiguous(), sw.contiguous()
